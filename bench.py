@@ -43,6 +43,11 @@ Extra objects on the JSON line:
                 1D:256-268) — Newton iterations / s, the roofline of its direct solve (block cyclic reduction, k_bcr_*), and the
                 C oracle timed on the same 100 steps.  `--case edl50` makes that the headline line instead.
 
+--dump-outputs DIR writes what the headline's last timed step computed, for comparing two builds output for output:
+vertex_values.npy (the state after the last timed step, (n_vertices, fields) as PoreRun / EDLRun history holds it) and
+newton_iterations.npy (one entry per timed step); the 3D line at N = 1 adds edl50_vertex_values.npy and
+edl50_newton_iterations.npy of its secondary 1D measurement.  The inputs are deterministic: same arguments, same inputs.
+
 Exit codes: 0 = a line was printed and every phase finished; 3 = the partitioned phase hung and the watchdog printed the line
 (with what was measured before) — the driver sees the hang.
 """
@@ -58,11 +63,14 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=50)
+    p.add_argument("--steps", type=int, default=None, help="timed steps (default: 50 for pore50, the 1D script's 100 for edl50)")
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy (float64, at most "
+                        "64 MB in all; see dump_outputs)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--mesh", type=str, default="L_50_R_5", help="L_<nm>_R_<nm> pore mesh (default: the north-star mesh)")
     p.add_argument("--refine", type=int, default=0, help="uniform refinements of the mesh (0 = the reference mesh itself)")
@@ -79,7 +87,32 @@ def parse():
                         "same Newton iterates, 8x fewer BiCGStab iterations at R = 2.  On by itself from R = 2 on at N = 1 (where it is 3.7x faster); "
                         "--no-multilevel keeps the two-level scheme")
     p.add_argument("--no-multilevel", action="store_true")
-    return p.parse_args()
+    a = p.parse_args(argv)
+    if a.steps is None:
+        a.steps = 100 if a.case == "edl50" else 50
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_LIMIT = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT, seed=0):
+    """Write each array as <path>/<name>.npy in float64, `limit` bytes at most in all.  Every array gets an equal share of
+    `limit`; one larger than its share (a state of `--refine 3`) is cut to a fixed sample of its rows, drawn with `seed` and
+    kept in order, whose row numbers go to <path>/<name>_rows.npy.  Same shapes in, same rows out: two builds of the project
+    can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(1, len(arrays)) - 2 * 4096    # room for the .npy headers
+    for name, v in arrays.items():
+        v = np.asarray(v, dtype=np.float64)
+        if v.nbytes > share:
+            row_bytes = v[0].nbytes + 8                   # a row and its row number
+            rows = np.sort(np.random.default_rng(seed).choice(v.shape[0], share // row_bytes, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def usable_cpus():
@@ -227,10 +260,11 @@ def banded_leg(O, prob, u0, un):
     return out
 
 
-def edl50_case(device_id, steps=100, warmup=3, cpu=True, repeats=1):
+def edl50_case(device_id, steps=100, warmup=3, cpu=True, repeats=1, outputs=None):
     """BASELINE configs[1]: reference 1D/MPNP_CO2ER_EDL.py with its defaults (K+, 0.1 M KHCO3, MPNP, V = -1, 50 um mesh of 5,991
     vertices, 7 fields = 41,937 dofs), the 100 dry-run steps of 1D:256-268.  A step = one Newton solve on the device (element
-    pass, gathers, block-cyclic-reduction direct solve, update) + the step glue (vertex values back, u_n.assign(u))."""
+    pass, gathers, block-cyclic-reduction direct solve, update) + the step glue (vertex values back, u_n.assign(u)).
+    `outputs` (a dict) receives what the last timed step computed: the vertex values and the Newton iterations per step."""
     import torch
     from gmpnp_amd.edl1d import EDLRun
     run = EDLRun(device_kwargs={"device_id": device_id})
@@ -259,6 +293,8 @@ def edl50_case(device_id, steps=100, warmup=3, cpu=True, repeats=1):
             windows.append(time.perf_counter() - t0)
         dt = sorted(windows)[len(windows) // 2]
         its = int(sum(run.newton_its))
+        if outputs is not None:
+            outputs.update(vertex_values=run.history[-1].copy(), newton_iterations=np.asarray(run.newton_its, dtype=np.float64))
         dev = run.sys.dev
         nf = dev.nf
         nd = dev.ndof
@@ -344,7 +380,10 @@ def main():
     if a.case == "edl50":   # BASELINE configs[1] as the headline line: N independent replicas of the 1D run (the 1D path does not shard)
         if dist is not None:
             dist.barrier()
-        o = edl50_case(local, steps=a.steps if a.steps != 50 else 100, warmup=a.warmup, cpu=(rank == 0 and not a.no_cpu_baseline))
+        outputs = {}
+        o = edl50_case(local, steps=a.steps, warmup=a.warmup, cpu=(rank == 0 and not a.no_cpu_baseline), outputs=outputs)
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, outputs)
         val, ms = o["value"], o["ms_per_step"]
         if dist is not None:
             t = torch.tensor([ms], dtype=torch.float64, device=red_dev)
@@ -420,11 +459,16 @@ def main():
     # The complete line is built BEFORE the partitioned phase (roofline sampling, event overhead, CPU baseline, 1D case): from
     # here on the only thing that can still change is `partitioned`, so the watchdog has nothing to compute on a GPU that may hang.
     out = make_output(a, run, run.sys.dev, prof, nv, world, dt, its, kry) if rank == 0 else None
+    # --dump-outputs: what the last timed step computed; at N > 1 the partitioned run's replaces it when that run is the headline
+    outputs = {"vertex_values": final_replica, "newton_iterations": np.asarray(run.newton_its, dtype=np.float64)}
+    part_outputs = {}
     if rank == 0 and world == 1 and not a.no_edl50 and a.refine == 0:
+        edl_outputs = {}
         try:
-            out["edl50"] = edl50_case(local, cpu=not a.no_cpu_baseline, repeats=3)
+            out["edl50"] = edl50_case(local, cpu=not a.no_cpu_baseline, repeats=3, outputs=edl_outputs)
         except Exception as e:  # noqa: BLE001
             out["edl50"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+        outputs.update({"edl50_" + k: v for k, v in edl_outputs.items()})
     import threading
     emit_lock = threading.Lock()
     emitted = {"done": False}
@@ -435,6 +479,9 @@ def main():
             if emitted["done"] or rank != 0:
                 return
             emitted["done"] = True
+            if a.dump_outputs:
+                partitioned_headline = world > 1 and part_result is not None and "value" in part_result
+                dump_outputs(a.dump_outputs, dict(outputs, **(part_outputs if partitioned_headline else {})))
             print(json.dumps(attach_partitioned(out, a, world, part_result)), flush=True)
 
     # ---- N > 1: the north-star quantity — ONE problem, mesh-partitioned over the N GPUs -------------------------------------
@@ -532,6 +579,7 @@ def main():
                 tried.append({"transport": transport, "value": res["value"], "krylov_iterations": pkry})
                 if state["best"] is None or res["value"] > state["best"]["value"]:   # identical on every rank (all-reduced time)
                     state["best"] = res
+                    part_outputs.update(vertex_values=prun.history[-1].copy(), newton_iterations=np.asarray(prun.newton_its, dtype=np.float64))
             except Exception as e:  # noqa: BLE001
                 msg = "%s transport: %s: %s" % (transport, type(e).__name__, str(e)[:300])
                 errors.append(msg)

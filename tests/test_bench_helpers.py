@@ -88,3 +88,37 @@ def test_block_band_lu_is_thread_count_independent_and_reports_singular_blocks()
 def test_usable_cpus_is_within_the_machine():
     n = bench.usable_cpus()
     assert 1 <= n <= (os.cpu_count() or 1)
+
+
+def test_steps_sets_the_number_of_timed_steps():
+    assert bench.parse([]).steps == 50 and bench.parse(["--case", "edl50"]).steps == 100      # the defaults of the two cases
+    assert bench.parse(["--case", "edl50", "--steps", "50"]).steps == 50
+    assert bench.parse(["--steps", "7", "--warmup", "0", "--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse(bad)
+            raise AssertionError("accepted %s" % bad)
+        except SystemExit:
+            pass
+
+
+def test_dump_outputs_writes_float64_within_the_limit(tmp_path):
+    rng = np.random.default_rng(2)
+    state = rng.standard_normal((3000, 9))
+    its = np.array([5, 4, 4])
+    bench.dump_outputs(str(tmp_path / "all"), {"vertex_values": state, "newton_iterations": its})
+    got = np.load(str(tmp_path / "all" / "vertex_values.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, state)
+    assert np.array_equal(np.load(str(tmp_path / "all" / "newton_iterations.npy")), its.astype(np.float64))
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["newton_iterations.npy", "vertex_values.npy"]
+    # over the limit: the same seeded rows every time, in order, and the files stay within the limit
+    limit = 100_000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"vertex_values": state, "newton_iterations": its}, limit=limit)
+    rows = np.load(str(tmp_path / "s1" / "vertex_values_rows.npy"))
+    sample = np.load(str(tmp_path / "s1" / "vertex_values.npy"))
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 0 < len(rows) < len(state)
+    assert np.array_equal(sample, state[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(str(tmp_path / "s2" / "vertex_values_rows.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "newton_iterations.npy")), its.astype(np.float64))
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))) <= limit

@@ -1005,6 +1005,36 @@ def test_bench_partitioned_code_path_at_world_size_one(gpu_lib):
     assert out["n_gpus"] == 1 and out["scaling"] == "weak"
 
 
+def test_bench_dumps_what_its_last_timed_step_computed(gpu_lib, tmp_path):
+    """`bench.py --steps K --dump-outputs DIR`, both cases: exactly K timed steps (after warm-up and reset to t = 0), and the state
+    after the last one is the oracle's state after step K (tests/golden/pore50_window.npz, edl50_default_steps.npz)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    lines = {}
+    for case, steps in (("pore50", 3), ("edl50", 3)):
+        d = str(tmp_path / case)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--case", case, "--steps", str(steps), "--warmup", "1",
+                            "--no-cpu-baseline", "--no-edl50", "--dump-outputs", d], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        its = np.load(os.path.join(d, "newton_iterations.npy"))
+        assert line["steps"] == steps and len(its) == steps and its.sum() == line["config"]["newton_iterations"]
+        assert line["ms_per_step"] > 0 and np.isclose(line["value"], its.sum() / (line["ms_per_step"] * 1e-3 * steps), rtol=1e-9)
+        lines[case] = (np.load(os.path.join(d, "vertex_values.npy")), its)
+    u, its = lines["pore50"]
+    g = np.load(os.path.join(GOLDEN, "pore50_window.npz"))
+    assert u.dtype == np.float64 and u.shape == (g["full_states"].shape[1] // 9, 9)
+    assert list(its) == list(g["newton_its"][:3])
+    assert relerr(u[g["probes"]].ravel(), g["probe_values"][2].ravel()) < 1e-8
+    assert np.allclose(np.sqrt((u ** 2).sum(axis=0)), g["field_norms"][2], rtol=1e-8)
+    u, its = lines["edl50"]
+    g = np.load(os.path.join(GOLDEN, "edl50_default_steps.npz"))
+    assert u.shape == (5991, 7) and list(its) == list(g["newton_its"][:3])
+    assert relerr(u.ravel(), g["states"][2]) < 1e-8
+
+
 @pytest.mark.parametrize("nparts", [4, 8])
 def test_partitioned_time_loop_survives_krylov_breakdowns(gpu_lib, nparts):
     """Twelve time steps of the bench problem on 4 / 8 partitions (all ranks in one process): 88 linear solves, some of which
