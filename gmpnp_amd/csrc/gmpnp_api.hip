@@ -667,7 +667,7 @@ template <int NF>
 int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, int maxit, gmpnp_linear_stats_t* st,
                     int verify_above = 0, double warm_scale = 0.0, double warm_prev = 0.0, const double* rhs_src = nullptr,
                     bool rhs_ready = false, bool x0_ready = false, const NewtonUpdate* upd = nullptr, bool* upd_done = nullptr,
-                    bool dots_in_flight = false) {
+                    bool dots_in_flight = false, bool refine = false) {
   const int n = s->ndof;
   if (!std::isfinite(bnorm)) return fail(GMPNP_ERR_LINEAR, "right-hand side of the linear system is not finite");
   const double tol = std::max(rtol * bnorm, atol);
@@ -713,6 +713,7 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
   constexpr int restart_every = 1000;
   bool have_x = warm;      // kx holds a partial solution
   bool random_shadow = false;
+  double pass_start = rhs_norm;   // true residual the current pass started from
   int bad_passes = 0;
   for (int pass = 0;; ++pass) {
     gmpnp_linear_stats_t ls{};
@@ -768,7 +769,12 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
     // A non-finite true residual is a failed solve whatever the recurrence reported: the caller's direct fallback takes
     // over (3D) and nothing of this x reaches u.
     const bool finite = std::isfinite(rn);
-    if (s->last_done == 1 && finite && rn <= 1e3 * tol) break;
+    // `refine` (gmpnp_linear_solve): a pass that converged by its recurrence but left a true residual above the target is
+    // followed by another pass on b - J x while passes still halve it; the 1000x acceptance then only covers stagnation at the
+    // attainable accuracy.  (Without it, the generated 14 ... 370-vertex cylinders ended at 1.6e-9 ... 1.7e-8 of a 1e-10
+    // target with 1e-13 attainable, and the solve said converged.)  Inside Newton the rule is unchanged.
+    if (s->last_done == 1 && finite && rn <= tol) break;
+    if (s->last_done == 1 && finite && rn <= 1e3 * tol && !(refine && rn < 0.5 * pass_start)) break;
     if (total.iterations >= maxit || bad_passes > 8 || !finite) {
       if (st) { total.converged = 0; *st = total; }
       char buf[200];
@@ -777,6 +783,7 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
       return fail(GMPNP_ERR_LINEAR, buf);
     }
     rhs_norm = rn;  // next pass solves J ddx = r (already in kr)
+    pass_start = rn;
   }
   if (st) *st = total;
   return GMPNP_OK;
@@ -1603,7 +1610,8 @@ int gmpnp_linear_solve(gmpnp_solver* s, const double* b, double* x, int32_t mode
   GMPNP_DISPATCH(s, rc = (setup_preconditioner<DIM, NF>(s, mode)));
   if (rc) return rc;
   gmpnp_linear_stats_t ls{};
-  GMPNP_DISPATCH(s, rc = (krylov_verified<NF>(s, mode, bn, rtol, atol, maxit, &ls)));
+  GMPNP_DISPATCH(s, rc = (krylov_verified<NF>(s, mode, bn, rtol, atol, maxit, &ls, 0, 0.0, 0.0, nullptr, false, false, nullptr,
+                                               nullptr, false, /*refine=*/true)));
   if (stats) *stats = ls;
   HIP_TRY(hipMemcpy(s->h_status, s->status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
   HIP_TRY(hipStreamSynchronize(s->stream));
