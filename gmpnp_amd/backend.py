@@ -33,6 +33,8 @@ EXPORTS = [
     "gmpnp_group_peer_begin", "gmpnp_group_peer_connect",
     "gmpnp_group_destroy", "gmpnp_group_newton_solve", "gmpnp_group_assign_previous", "gmpnp_group_selftest", "gmpnp_group_set_exchange_form", "gmpnp_group_exchange_form", "gmpnp_attach_coarse_level",
     "gmpnp_project_gradient", "gmpnp_project_cellwise",
+    "gmpnp_ensemble_create", "gmpnp_ensemble_destroy", "gmpnp_ensemble_size", "gmpnp_ensemble_newton_solve",
+    "gmpnp_ensemble_member_error", "gmpnp_ensemble_assign_previous", "gmpnp_ensemble_get_state",
 ]
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
@@ -166,6 +168,16 @@ def load_library(path: str = None):
     lib.gmpnp_attach_coarse_level.argtypes = [c_void_p, c_void_p, POINTER(c_int32), c_double, c_int32]
     lib.gmpnp_project_gradient.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(CLinearStats)]
     lib.gmpnp_project_cellwise.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double), POINTER(CLinearStats)]
+    lib.gmpnp_ensemble_create.argtypes = [c_int32, POINTER(c_void_p), POINTER(c_void_p)]
+    lib.gmpnp_ensemble_destroy.argtypes = [c_void_p]
+    lib.gmpnp_ensemble_destroy.restype = None
+    lib.gmpnp_ensemble_size.argtypes = [c_void_p]
+    lib.gmpnp_ensemble_size.restype = c_int32
+    lib.gmpnp_ensemble_newton_solve.argtypes = [c_void_p, POINTER(CNewtonOptions), POINTER(CNewtonStats), POINTER(c_int32)]
+    lib.gmpnp_ensemble_member_error.argtypes = [c_void_p, c_int32]
+    lib.gmpnp_ensemble_member_error.restype = ctypes.c_char_p
+    lib.gmpnp_ensemble_assign_previous.argtypes = [c_void_p]
+    lib.gmpnp_ensemble_get_state.argtypes = [c_void_p, POINTER(c_double)]
     if path is None:
         _lib = lib
     return lib
@@ -508,3 +520,68 @@ class DeviceSolver:
         n, mean, launched = c_int64(), c_double(), c_int64()
         self._check(self.lib.gmpnp_spmv_profile(self._h, byref(n), byref(mean), byref(launched)))
         return {"sampled": n.value, "mean_us": mean.value, "launched": launched.value}
+
+
+MAX_ENSEMBLE = 64   # gmpnp_ensemble_create refuses more members
+
+
+class DeviceEnsemble:
+    """``gmpnp_ensemble``: the Newton solves of several 1D ``DeviceSolver`` handles on ONE mesh in one launch chain per iteration
+    (include/gmpnp.h).  The members stay owned by the caller and keep their own surface (set_model, set_state, get_state,
+    project_gradient, ...); every call here is complete when it returns."""
+
+    def __init__(self, devices, lib=None):
+        self.lib = lib or load_library()
+        self.devices = list(devices)
+        self._h = None
+        arr = (c_void_p * max(1, len(self.devices)))(*[d._h for d in self.devices])
+        h = c_void_p()
+        self._check(self.lib.gmpnp_ensemble_create(len(self.devices), arr, byref(h)))
+        self._h = h
+        self.ndof = self.devices[0].ndof
+
+    def _check(self, code):
+        if code != OK:
+            raise GmpnpError(code, self.lib.gmpnp_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.gmpnp_ensemble_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return len(self.devices)
+
+    def newton_solve(self, options: CNewtonOptions):
+        """One Newton solve of every member.  Returns (stats, codes, messages): per member the statistics dict of
+        ``DeviceSolver.newton_solve``, its gmpnp_status and the library's message of its failure ("" if none)."""
+        n = len(self.devices)
+        st = (CNewtonStats * n)()
+        codes = (c_int32 * n)()
+        rc = self.lib.gmpnp_ensemble_newton_solve(self._h, byref(options), st, codes)
+        if rc != OK and not any(codes):   # refused before any member ran
+            self._check(rc)
+        stats = [DeviceSolver.stats_dict(st[k]) for k in range(n)]
+        msgs = [self.lib.gmpnp_ensemble_member_error(self._h, k).decode() for k in range(n)]
+        return stats, [int(c) for c in codes], msgs
+
+    def assign_previous(self):
+        self._check(self.lib.gmpnp_ensemble_assign_previous(self._h))
+
+    def get_state(self):
+        """u of every member, (n, n_dofs) in file order (one device-to-host copy)."""
+        out = np.empty((len(self.devices), self.ndof))
+        self._check(self.lib.gmpnp_ensemble_get_state(self._h, _dptr(out)))
+        return out

@@ -1791,3 +1791,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 
 #include "gmpnp_group.h"
 #include "gmpnp_project.h"
+#include "gmpnp_ensemble.h"

@@ -63,6 +63,16 @@ class EDLRun:
         self.newton_its = []
 
     def step(self, verbose=True):
+        self.advance_clock(verbose)
+        st = self.sys.solve(self.solver_parameters)
+        self.accept_solution(st, self.sys.vertex_values(), verbose)
+        self.sys.assign_previous()
+        self.newton_its.append(st["iterations"])
+        self.n += 1
+        return st
+
+    def advance_clock(self, verbose=True):
+        """Host glue of a step before its Newton solve: the clock (Q2 stage switch) and the SUPG parameters."""
         ep = self.ep
         if verbose:
             if ep.dry_run:
@@ -84,8 +94,11 @@ class EDLRun:
             w = np.arange(6, dtype=np.int32)
             w[ep.species.index("OH")] = ep.species.index("H")
             self.sys.dev.set_supg(rho, w)
-        st = self.sys.solve(self.solver_parameters)
-        vals = self.sys.vertex_values()
+
+    def accept_solution(self, st, vals, verbose=True):
+        """Host glue of a step after its Newton solve: the state joins the history and the H_OHP controller (reference
+        1D:770-793) re-uploads the OHP fluxes.  u_n.assign(u) and the step count stay with the caller."""
+        ep = self.ep
         self.history.append(vals)
         H_OHP_frac = vals[0, 0]
         H_OHP = ep.H_OHP
@@ -109,10 +122,6 @@ class EDLRun:
             self.model.point_flux[ep.species.index("H")] = JH
             self.model.point_flux[ep.species.index("OH")] = JOH
             self.sys.set_model(self.model)
-        self.sys.assign_previous()
-        self.newton_its.append(st["iterations"])
-        self.n += 1
-        return st
 
     def run(self, verbose=True):
         for _ in range(self.n, self.tot_num_steps):
@@ -135,8 +144,7 @@ class EDLRun:
         ep, mesh, k = self.ep, self.mesh, self.kwargs
         stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         end_time = datetime.now().strftime("%y-%m-%d-%H-%M-%S")
-        identifier = ("voltage_" + str(ep.voltage_scaled) + "_H2_FE_" + str(k.get("H2_FE", 0.2)) + "_current_"
-                      + str(ep.current_OHP_ss) + "_H_OHP_" + str(ep.H_OHP) + "_cation_" + ep.cation)
+        identifier = run_identifier(ep, k)
         newpath = os.path.join(output_root(), ep.model_name, stamp + "_experiment", identifier)
         os.makedirs(newpath, exist_ok=True)
         hist = np.stack(self.history)
@@ -187,6 +195,12 @@ class EDLRun:
         with open(newpath + "/metadata.json", "w") as fh:
             fh.write(json.dumps(metadata_dict, indent=0))
         return newpath
+
+
+def run_identifier(ep, kwargs):
+    """Name of a run's output directory below ``<model>/<stamp>_experiment`` (reference 1D:862-866)."""
+    return ("voltage_" + str(ep.voltage_scaled) + "_H2_FE_" + str(kwargs.get("H2_FE", 0.2)) + "_current_"
+            + str(ep.current_OHP_ss) + "_H_OHP_" + str(ep.H_OHP) + "_cation_" + ep.cation)
 
 
 def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=-1.0, H2_FE=0.2, mesh_structure="variable",

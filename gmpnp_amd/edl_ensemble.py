@@ -1,0 +1,195 @@
+"""Many 1D EDL runs on one mesh in lock-step: the members' Newton solves run as ONE ensemble on the device
+(``gmpnp_ensemble_newton_solve``: one launch chain per Newton iteration for all members, include/gmpnp.h).
+
+Each member is an ordinary ``EDLRun`` (its own handle, model tables, Dirichlet values, state, clock and H_OHP controller);
+per step the ensemble applies exactly the host glue of ``EDLRun.step`` to every member (``advance_clock`` before the solve,
+``accept_solution`` after it, then ``u_n.assign(u)``), reads the state of all members with one copy, and freezes a member
+whose solve fails with the error text the serial driver would raise, while the others carry on.  Outputs are the members'
+own ``EDLRun.write_outputs`` / ``ohp_summary``."""
+from __future__ import annotations
+
+import itertools
+
+from . import backend
+from .edl1d import EDLRun, run_identifier
+from .params import edl_parameters
+
+# keyword surface of solve_EDL / EDLRun (reference 1D:66-79) and its defaults
+MEMBER_DEFAULTS = {"concentration_elec": 0.1, "model": "MPNP", "voltage_multiplier": -1.0, "H2_FE": 0.2,
+                   "mesh_structure": "variable", "current_OHP_ss": 10.0, "L_n": 50.0e-6, "stabilization": "N",
+                   "H_OHP": None, "cation": "K", "params_file": "parameters", "dry_run": True}
+# what every member of one ensemble must share: the mesh and the step schedule
+SHARED_FIELDS = ("L_n", "mesh_structure", "params_file", "dry_run", "num_steps")
+
+
+def sweep_members(voltages, cations=("K",), concentrations=(0.1,), **common):
+    """Member keyword dicts of the Cartesian product, voltage outermost, then cation, then concentration."""
+    return [dict(common, voltage_multiplier=float(v), cation=c, concentration_elec=float(x))
+            for v, c, x in itertools.product(voltages, cations, concentrations)]
+
+
+def plan_members(members, num_steps=None):
+    """Validate the members of one ensemble before anything touches the device.  Returns (member kwargs with defaults
+    filled in, their EDLParameters, the number of steps).  ValueError names the field that differs."""
+    members = list(members)
+    if not 1 <= len(members) <= backend.MAX_ENSEMBLE:
+        raise ValueError("an ensemble holds 1 ... %d members, not %d" % (backend.MAX_ENSEMBLE, len(members)))
+    full = []
+    for k, m in enumerate(members):
+        unknown = set(m) - set(MEMBER_DEFAULTS) - {"num_steps"}
+        if unknown:
+            raise TypeError("member %d: unknown keyword(s) %s" % (k, sorted(unknown)))
+        d = dict(MEMBER_DEFAULTS)
+        d.update(m)
+        d.setdefault("num_steps", num_steps)
+        if num_steps is not None and d["num_steps"] is None:
+            d["num_steps"] = num_steps
+        if d["stabilization"] == "Y" and d["model"] == "PNP":
+            raise ValueError("member %d: stabilization='Y' with PNP (SUPG terms) is not supported in an ensemble" % k)
+        full.append(d)
+    eps = [edl_parameters(**{f: d[f] for f in MEMBER_DEFAULTS}) for d in full]
+    for f in SHARED_FIELDS:
+        vals = [bool(d[f]) if f == "dry_run" else d[f] for d in full]
+        if f == "num_steps":
+            vals = [ep.tot_num_steps if v is None else int(v) for v, ep in zip(vals, eps)]
+        if any(v != vals[0] for v in vals):
+            k = next(i for i, v in enumerate(vals) if v != vals[0])
+            raise ValueError("ensemble members differ in %s: member 0 has %r, member %d has %r" % (f, vals[0], k, vals[k]))
+    # (the scaled time steps themselves are per member: they follow the concentration through the Debye length)
+    sched = [(ep.mesh_name, tuple(ep.stage_steps)) for ep in eps]
+    if any(s != sched[0] for s in sched):
+        raise ValueError("ensemble members differ in mesh or in the steps per stage of their schedule")
+    steps = eps[0].tot_num_steps if full[0]["num_steps"] is None else int(full[0]["num_steps"])
+    for d in full:
+        d.pop("num_steps")
+    return full, eps, steps
+
+
+def member_identifier(kwargs):
+    """The output directory name ``EDLRun.write_outputs`` gives a run with these keyword arguments."""
+    d = dict(MEMBER_DEFAULTS)
+    d.update(kwargs)
+    d.pop("num_steps", None)
+    return run_identifier(edl_parameters(**d), d)
+
+
+def error_text(code, message):
+    """The RuntimeError text ``GMPNPSystem.solve`` raises for a failed solve with this status."""
+    if code == backend.ERR_NOT_CONVERGED:
+        return "Newton solver did not converge because maximum number of iterations reached"
+    return str(backend.GmpnpError(code, message))
+
+
+class EDLEnsemble:
+    """``members``: keyword dicts of ``EDLRun`` (voltage, cation, concentration, H2_FE, current_OHP_ss, H_OHP, model may
+    differ; mesh and schedule may not).  ``keep_history=False`` keeps only the latest state of each member (long runs)."""
+
+    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True):
+        self.kwargs, self.eps, self.tot_num_steps = plan_members(members, num_steps)
+        self.keep_history = keep_history
+        self.runs = []
+        self._ens, self._ens_members = None, None
+        try:
+            for kw in self.kwargs:
+                self.runs.append(EDLRun(num_steps=self.tot_num_steps, device_kwargs=device_kwargs, **kw))
+        except BaseException:
+            self.close()
+            raise
+        self.opts = backend.newton_options(self.runs[0].solver_parameters, dim=1)
+        n = len(self.runs)
+        self.errors = [None] * n        # RuntimeError text of a failed member
+        self.status = [0] * n           # its gmpnp_status
+        self.failed_step = [None] * n   # the step it failed at (frozen there)
+        self.n = 0
+
+    def __len__(self):
+        return len(self.runs)
+
+    def _ensemble(self, live):
+        if self._ens_members != live:
+            if self._ens is not None:
+                self._ens.close()
+            self._ens = backend.DeviceEnsemble([self.runs[k].sys.dev for k in live])
+            self._ens_members = list(live)
+        return self._ens
+
+    def live(self):
+        return [k for k in range(len(self.runs)) if self.errors[k] is None]
+
+    def step(self):
+        live = self.live()
+        if not live:
+            self.n += 1
+            return
+        ens = self._ensemble(live)
+        for k in live:
+            self.runs[k].advance_clock(verbose=False)
+        stats, codes, msgs = ens.newton_solve(self.opts)
+        U = ens.get_state()
+        ok = []
+        for i, k in enumerate(live):
+            r = self.runs[k]
+            if codes[i] != backend.OK:
+                self.errors[k], self.status[k], self.failed_step[k] = error_text(codes[i], msgs[i]), codes[i], r.n
+                continue
+            r.sys.record(stats[i])
+            r.accept_solution(stats[i], U[i].reshape(r.sys.nv, r.sys.nf), verbose=False)
+            ok.append((k, stats[i]))
+        # u_n.assign(u) of the members whose solve succeeded (a failed one stays as its failed solve left it)
+        if ok:
+            self._ensemble([k for k, _ in ok]).assign_previous()
+        for k, st in ok:
+            r = self.runs[k]
+            r.newton_its.append(st["iterations"])
+            r.n += 1
+            if not self.keep_history:
+                r.history = r.history[-1:]
+        self.n += 1
+
+    def run(self):
+        while self.n < self.tot_num_steps:
+            self.step()
+        return self
+
+    def ohp_summary(self, k):
+        return self.runs[k].ohp_summary()
+
+    def identifiers(self):
+        return [member_identifier(kw) for kw in self.kwargs]
+
+    def write_outputs(self, stamp=None):
+        """``EDLRun.write_outputs`` of every member that did not fail.  Members that would share a directory (they differ
+        only in fields the reference leaves out of the name, e.g. the concentration) get the concentration appended to
+        the stamp, then their index.  Returns per member the path, or the exception the member's write raised (the
+        staged schedule ends with the reference's NameError)."""
+        from datetime import datetime
+        stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
+        names = [(kw["model"], i) for kw, i in zip(self.kwargs, self.identifiers())]
+        stamps = [stamp] * len(self.runs)
+        if len(set(names)) < len(names):
+            stamps = [stamp + "_c" + str(kw["concentration_elec"]) for kw in self.kwargs]
+            if len(set(zip(names, stamps))) < len(names):
+                stamps = [s + "_m%d" % k for k, s in enumerate(stamps)]
+        out = []
+        for k, r in enumerate(self.runs):
+            if self.errors[k] is not None:
+                out.append(None)
+                continue
+            try:
+                out.append(r.write_outputs(stamps[k]))
+            except NameError as e:
+                out.append(e)
+        return out
+
+    def close(self):
+        if self._ens is not None:
+            self._ens.close()
+            self._ens = None
+        for r in self.runs:
+            r.sys.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -44,10 +44,14 @@ class GMPNPSystem:
             if e.code == backend.ERR_NOT_CONVERGED:
                 raise RuntimeError("Newton solver did not converge because maximum number of iterations reached") from e
             raise
+        self.record(st)
+        return st
+
+    def record(self, st):
+        """Account one Newton solve's statistics (also for solves an ensemble ran on this system's handle)."""
         self.newton_iterations += st["iterations"]
         self.krylov_iterations += st["krylov_iterations"]
         self.last_stats = st
-        return st
 
     def vertex_values(self):
         """(nv, nf) array = compute_vertex_values() of every sub-function, file vertex order."""

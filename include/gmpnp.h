@@ -355,6 +355,32 @@ int gmpnp_group_assign_previous(gmpnp_group* g);
  * any more.  BiCGStab then runs in the materialised vector form.  3D, unpartitioned handles on one device. */
 int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const int32_t* parents, double theta, int32_t sweeps);
 
+/* ---- ensemble of 1D problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
+ * concentration sweep of 1D/MPNP_CO2ER_EDL.py is many separate runs) ------------------------------------------------------------
+ * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME 1D mesh (same vertices, cells and vertex order) and device.
+ * Each member keeps its whole per-handle surface (gmpnp_set_model, gmpnp_set_dirichlet, gmpnp_set_state / gmpnp_get_state,
+ * gmpnp_project_gradient / gmpnp_project_cellwise) and its own model tables, Dirichlet values and state; the ensemble only runs
+ * the Newton iterations of all members in one launch chain per iteration (one host synchronisation per iteration for the
+ * whole ensemble).  Refused (GMPNP_ERR_INVALID): 3D handles (3D ensembles are not supported), partitioned handles, members on
+ * other devices or with another topology, SUPG terms set on a member (checked again at every solve), n outside 1 ... 64.
+ * The members stay owned by the caller and must outlive the ensemble.  Every ensemble call is complete when it returns: a
+ * member call made afterwards on the member's own stream sees the ensemble's results. */
+typedef struct gmpnp_ensemble gmpnp_ensemble;
+int gmpnp_ensemble_create(int32_t n, gmpnp_solver* const* members, gmpnp_ensemble** out);
+void gmpnp_ensemble_destroy(gmpnp_ensemble* e);
+int32_t gmpnp_ensemble_size(const gmpnp_ensemble* e);
+/* solve(F == 0, u, bcs, solver_parameters) on every member at once; opts.linear_solver must be GMPNP_LINEAR_BLOCK_TRIDIAGONAL.
+ * stats[n] and status[n] (a gmpnp_status per member) are what gmpnp_newton_solve on that handle alone returns, timing fields
+ * excepted; a member that has converged or failed gets no further updates while the others go on.  Returns 0 when every member
+ * succeeded, else the first non-zero member status (gmpnp_last_error names the member). */
+int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t* opts, gmpnp_newton_stats_t* stats, int32_t* status);
+/* Message of member k's failure in the last gmpnp_ensemble_newton_solve ("" = none). */
+const char* gmpnp_ensemble_member_error(const gmpnp_ensemble* e, int32_t k);
+/* u_n.assign(u) on every member (blocking). */
+int gmpnp_ensemble_assign_previous(gmpnp_ensemble* e);
+/* u of every member, u_out[n][n_dofs] in file order, with one device-to-host copy for the whole ensemble. */
+int gmpnp_ensemble_get_state(gmpnp_ensemble* e, double* u_out);
+
 /* Benchmark hooks: time `launches` back-to-back launches of one kernel on the handle's stream with HIP
  * events; kernel: 0 = plain Jacobian SpMV, 1 = element kernel (F+J), 2 = Jacobian gather, 3 = residual gather,
  * 4/5 = fused BiCGStab half-iterations A/B, 6/7 = their scalar+coarse kernels, 8 = one-wave copy, 9-11 = streaming
