@@ -22,6 +22,10 @@ parameter-sweep mapping of BASELINE configs[4], no collective, weak scaling) and
 partitioned phase fail or hang on the node (its RCCL path cannot be rehearsed on a one-GPU box), the replica figure is
 what `value` falls back to, with the reason under `partitioned`.
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds every
+measurement that runs after the timed steps (the CPU baselines, the secondary 1D case, kernels timed by themselves for the
+roofline, the empty event pair): about 50 s outside the steps on one MI355X, against 3 s for a plain run.
+
 Extra objects on the JSON line:
   roofline      dominant kernels = the two fused BiCGStab half-iterations (k_half_a / k_half_b on meshes whose workgroups are
                 all resident at once, else k_bicg_a / k_bicg_b after a separate coarse launch): one SELL block SpMV each
@@ -30,8 +34,10 @@ Extra objects on the JSON line:
                 during the timed region: the first burst of every 4th linear solve — 40-odd back-to-back half-iterations,
                 all of them live — sits between ONE pair of HIP events on the solver's stream; elapsed time / number of
                 half-iterations = the launch plus the gap to the next one (in the forms with a separate coarse launch, that
-                launch too).  rocprofv3's kernel durations of the same command (profiles/) are the check.
-  cpu_baseline  the CPU oracle (NumPy assembly + SciPy SuperLU) timed on rank 0 / N = 1 over the first 3 Newton iterations
+                launch too).  rocprofv3's kernel durations of the same command (profiles/) are the check.  Where the live
+                sample cannot give the figure (no linear solve sampled; the multilevel form, whose tile kernels are timed by
+                themselves) it takes launches of its own: --full only, a plain line says so under `skipped`.
+  cpu_baseline  (--full) the CPU oracle (NumPy assembly + SciPy SuperLU) timed on rank 0 / N = 1 over the first 3 Newton iterations
                 of the same window, on 1 thread and on all cores (about 35 s together); kind = "port" (FEniCS itself
                 cannot be installed).  `full_window_recorded` = the committed timing of the whole 50-step window.
                 `banded_all_cores`: the same Jacobian in the library's slab order is a band of ~1,650 scalars; one LAPACK
@@ -39,14 +45,16 @@ Extra objects on the JSON line:
                 same band as 9x9 node blocks factored by oracle/band_lu_omp.c with OpenMP (the leg that does scale with
                 cores) — the stand-ins for the reference's MUMPS (3D:792) that use the box.  `value` is the FASTEST of the
                 legs (`cores` = the threads it used).
-  edl50         (N = 1) BASELINE configs[1]: the 1D script's 100 dry-run steps (50 um mesh, 7 fields, 41,937 dofs; reference
-                1D:256-268) — Newton iterations / s, the roofline of its direct solve (block cyclic reduction, k_bcr_*), and the
-                C oracle timed on the same 100 steps.  `--case edl50` makes that the headline line instead.
+  edl50         (--full, N = 1) BASELINE configs[1]: the 1D script's 100 dry-run steps (50 um mesh, 7 fields, 41,937 dofs;
+                reference 1D:256-268) — Newton iterations / s, the roofline of its direct solve (block cyclic reduction,
+                k_bcr_*), and the C oracle timed on the same 100 steps.  `--case edl50` makes that the headline line instead
+                (its roofline and C oracle: --full).
 
 --dump-outputs DIR writes what the headline's last timed step computed, for comparing two builds output for output:
 vertex_values.npy (the state after the last timed step, (n_vertices, fields) as PoreRun / EDLRun history holds it) and
 newton_iterations.npy (one entry per timed step); the 3D line at N = 1 adds edl50_vertex_values.npy and
-edl50_newton_iterations.npy of its secondary 1D measurement.  The inputs are deterministic: same arguments, same inputs.
+edl50_newton_iterations.npy of its secondary 1D measurement (a plain run steps the 1D case once, untimed, for them).  The
+inputs are deterministic: same arguments, same inputs.
 
 Exit codes: 0 = a line was printed and every phase finished; 3 = the partitioned phase hung and the watchdog printed the line
 (with what was measured before) — the driver sees the hang.
@@ -71,7 +79,10 @@ def parse(argv=None):
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy (float64, at most "
                         "64 MB in all; see dump_outputs)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: CPU baselines, the secondary 1D case (N = 1), kernels timed by "
+                        "themselves for the roofline figures")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     p.add_argument("--mesh", type=str, default="L_50_R_5", help="L_<nm>_R_<nm> pore mesh (default: the north-star mesh)")
     p.add_argument("--refine", type=int, default=0, help="uniform refinements of the mesh (0 = the reference mesh itself)")
     p.add_argument("--replicas-only", action="store_true", help="N > 1: time only the N independent replicas (no partitioned solve)")
@@ -81,7 +92,7 @@ def parse(argv=None):
     p.add_argument("--partition-timeout", type=int, default=240, help="seconds the partitioned phase may take before the replica result is reported alone")
     p.add_argument("--case", choices=["pore50", "edl50"], default="pore50",
                    help="pore50 = BASELINE configs[2] (the headline); edl50 = BASELINE configs[1], the 1D script's 100 dry-run steps")
-    p.add_argument("--no-edl50", action="store_true", help="N = 1: skip the secondary 1D measurement")
+    p.add_argument("--no-edl50", action="store_true", help="N = 1: skip the secondary 1D measurement (and its --dump-outputs arrays)")
     p.add_argument("--multilevel", action="store_true",
                    help="with --refine R > 0: the geometric multilevel term of the preconditioner over the nested meshes (gmpnp_attach_coarse_level); "
                         "same Newton iterates, 8x fewer BiCGStab iterations at R = 2.  On by itself from R = 2 on at N = 1 (where it is 3.7x faster); "
@@ -260,11 +271,12 @@ def banded_leg(O, prob, u0, un):
     return out
 
 
-def edl50_case(device_id, steps=100, warmup=3, cpu=True, repeats=1, outputs=None):
+def edl50_case(device_id, steps=100, warmup=3, full=False, cpu=True, repeats=1, outputs=None):
     """BASELINE configs[1]: reference 1D/MPNP_CO2ER_EDL.py with its defaults (K+, 0.1 M KHCO3, MPNP, V = -1, 50 um mesh of 5,991
     vertices, 7 fields = 41,937 dofs), the 100 dry-run steps of 1D:256-268.  A step = one Newton solve on the device (element
     pass, gathers, block-cyclic-reduction direct solve, update) + the step glue (vertex values back, u_n.assign(u)).
-    `outputs` (a dict) receives what the last timed step computed: the vertex values and the Newton iterations per step."""
+    `outputs` (a dict) receives what the last timed step computed: the vertex values and the Newton iterations per step.
+    `full`: also the roofline of the direct solve (launches of its own) and, with `cpu`, the C oracle on the same steps."""
     import torch
     from gmpnp_amd.edl1d import EDLRun
     run = EDLRun(device_kwargs={"device_id": device_id})
@@ -298,26 +310,27 @@ def edl50_case(device_id, steps=100, warmup=3, cpu=True, repeats=1, outputs=None
         dev = run.sys.dev
         nf = dev.nf
         nd = dev.ndof
-        # direct solve of the block-tridiagonal Jacobian: every matrix block read once, right-hand side in, solution out
-        alg_bytes = (3 * nv - 2) * nf * nf * 8 + 2 * 8 * nd
-        solve_us = dev.time_kernel(18, 50)
-        levels = int(np.ceil(np.log2(nv))) + 1
         out = {"metric": "newton_iterations_per_sec", "value": its / dt, "unit": "Newton-iterations/s", "steps": steps, "warmup": warmup,
                "ms_per_step": 1e3 * dt / steps, "dtype": "f64",
                "config": {"workload": "1D MPNP_CO2ER_EDL, 1D_variable_50um_mesh_5990, K+, 0.1 M KHCO3, V=-1: the %d dry-run steps "
                                       "(Newton rtol=atol=1e-4, omega=1, max 50; linear solve = block cyclic reduction, direct)" % steps,
-                          "n_vertices": nv, "n_dofs": nd, "newton_iterations": its, "windows_seconds": windows},
-               "roofline": {"bound": "hbm", "kernel": "1D direct solve, block cyclic reduction over %d levels: k_tri_extract, k_bcr_forward per level, k_bcr_tail "
-                                                      "(the levels of up to 4 rows, the single row, and back: one wave), k_bcr_backward per level" % (levels - 1),
-                            "algorithmic_bytes_per_solve": alg_bytes, "mean_solve_us": solve_us,
-                            "achieved": alg_bytes / (solve_us * 1e-6) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                            "frac": alg_bytes / (solve_us * 1e-6) / 1e9 / 8000.0, "traffic": None,
-                            "note": "a chain of ~20 dependent launches over 7.7 MB that halves at every level, each a pivoted 7x7 solve by "
-                                    "shuffles inside 8-lane groups: latency and LDS-crossbar bound, not bandwidth bound; timed with one HIP event "
-                                    "pair around 50 back-to-back solves"}}
+                          "n_vertices": nv, "n_dofs": nd, "newton_iterations": its, "windows_seconds": windows}}
+        if full:
+            # direct solve of the block-tridiagonal Jacobian: every matrix block read once, right-hand side in, solution out
+            alg_bytes = (3 * nv - 2) * nf * nf * 8 + 2 * 8 * nd
+            solve_us = dev.time_kernel(18, 50)
+            levels = int(np.ceil(np.log2(nv))) + 1
+            out["roofline"] = {"bound": "hbm", "kernel": "1D direct solve, block cyclic reduction over %d levels: k_tri_extract, k_bcr_forward per level, k_bcr_tail "
+                                                         "(the levels of up to 4 rows, the single row, and back: one wave), k_bcr_backward per level" % (levels - 1),
+                               "algorithmic_bytes_per_solve": alg_bytes, "mean_solve_us": solve_us,
+                               "achieved": alg_bytes / (solve_us * 1e-6) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                               "frac": alg_bytes / (solve_us * 1e-6) / 1e9 / 8000.0, "traffic": None,
+                               "note": "a chain of ~20 dependent launches over 7.7 MB that halves at every level, each a pivoted 7x7 solve by "
+                                       "shuffles inside 8-lane groups: latency and LDS-crossbar bound, not bandwidth bound; timed with one HIP event "
+                                       "pair around 50 back-to-back solves"}
     finally:
         run.sys.close()
-    if cpu:
+    if full and cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import edl1d as OE
         st = OE.Setup()
@@ -381,7 +394,7 @@ def main():
         if dist is not None:
             dist.barrier()
         outputs = {}
-        o = edl50_case(local, steps=a.steps, warmup=a.warmup, cpu=(rank == 0 and not a.no_cpu_baseline), outputs=outputs)
+        o = edl50_case(local, steps=a.steps, warmup=a.warmup, full=a.full, cpu=(rank == 0 and not a.no_cpu_baseline), outputs=outputs)
         if rank == 0 and a.dump_outputs:
             dump_outputs(a.dump_outputs, outputs)
         val, ms = o["value"], o["ms_per_step"]
@@ -462,10 +475,14 @@ def main():
     # --dump-outputs: what the last timed step computed; at N > 1 the partitioned run's replaces it when that run is the headline
     outputs = {"vertex_values": final_replica, "newton_iterations": np.asarray(run.newton_its, dtype=np.float64)}
     part_outputs = {}
-    if rank == 0 and world == 1 and not a.no_edl50 and a.refine == 0:
+    if rank == 0 and world == 1 and not a.no_edl50 and a.refine == 0 and (a.full or a.dump_outputs):
+        # a plain run steps the 1D case only for its --dump-outputs arrays: one window (each window restarts from t = 0, so the
+        # last one ends on the same state) and no rate on the line
         edl_outputs = {}
         try:
-            out["edl50"] = edl50_case(local, cpu=not a.no_cpu_baseline, repeats=3, outputs=edl_outputs)
+            edl = edl50_case(local, full=a.full, cpu=not a.no_cpu_baseline, repeats=3 if a.full else 1, outputs=edl_outputs)
+            if a.full:
+                out["edl50"] = edl
         except Exception as e:  # noqa: BLE001
             out["edl50"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         outputs.update({"edl50_" + k: v for k, v in edl_outputs.items()})
@@ -611,42 +628,6 @@ def main():
 
 def make_output(a, run, dev, prof, nv, world, dt, its, kry):
     """Everything of the JSON line that does not depend on the partitioned phase."""
-    nb, nd = dev.n_blocks, dev.ndof
-    nf = dev.nf
-    alg_bytes = (nf * nf * 8) * nb + 4 * nb + 4 * (nv + 1) + 16 * nd  # SURVEY §8d, one SpMV
-    mean_us = prof["mean_us"] if prof["sampled"] else dev.time_kernel(4, 200)
-    launches = dev.krylov_launches_per_iteration
-    ml_note = None
-    if a.multilevel and a.refine > 0:
-        # the live event brackets span whole half-iterations, i.e. the ~35 small launches of the multilevel term as well; the
-        # roofline line is about the streaming kernel, so it is timed by itself here (back-to-back launches, HIP events)
-        ml_note = "live half-iteration incl. the multilevel launches: %.1f us; the tile kernels alone (k_bicg_a_mat / k_bicg_b_mat, back-to-back): see mean_launch_us" % mean_us
-        mean_us = 0.5 * (dev.time_kernel(14, 50) + dev.time_kernel(15, 50))
-    if launches == 2:
-        kernel_name = ("k_half_a / k_half_b (one launch per BiCGStab half-iteration: the coarse workgroups ride in front of "
-                       "the tile workgroups = SELL node-block SpMV + vector updates, fp64; the launch duration includes "
-                       "the in-launch wait for the coarse result, which the 4-launch form spends in a separate launch)")
-    else:
-        kernel_name = "k_bicg_a / k_bicg_b (fused BiCGStab half-iteration = SELL node-block SpMV + vector updates, fp64)"
-    if a.multilevel and a.refine > 0:
-        kernel_name = "k_bicg_a_mat / k_bicg_b_mat (tile kernels of the materialised vector form: SELL node-block SpMV staging one vector, fp64)"
-    achieved = alg_bytes / (mean_us * 1e-6) / 1e9
-    # what an EMPTY start/stop event pair measures on this stream: each timed burst carries that much ONCE (a burst is 2 x
-    # ~20 launches), reported for information
-    try:
-        ev_overhead = dev.event_overhead(200)
-    except Exception:  # noqa: BLE001
-        ev_overhead = None
-    # memory-side bytes per launch from the committed PMC passes; only valid for the build they were measured on
-    traffic, traffic_note = None, "no PMC file"
-    pmc = os.path.join(ROOT, "profiles", "spmv_pmc.json")
-    if os.path.exists(pmc) and a.mesh == "L_50_R_5" and a.refine == 0:
-        with open(pmc) as fh:
-            pj = json.load(fh)
-        if pj.get("build_id") == dev.build_id and pj.get("launches_per_krylov_iteration") == launches:
-            traffic, traffic_note = pj.get("hbm_bytes_per_launch"), pj.get("source")
-        else:
-            traffic_note = "profiles/spmv_pmc.json was measured on build %s, this library is %s: dropped" % (pj.get("build_id"), dev.build_id)
     out = {
         "metric": "newton_iterations_per_sec", "value": its / dt, "unit": "Newton-iterations/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
@@ -659,25 +640,73 @@ def make_output(a, run, dev, prof, nv, world, dt, its, kry):
                    "workload": "3D MPNP_CO2ER_pore %s, 0.5 M KHCO3, K+, V=-1: time steps 0..%d from t=0 "
                                "(Newton rtol=atol=1e-4, omega=0.9, max 50; linear solve = two-level BiCGStab to "
                                "1e-10 relative residual)" % (a.mesh, a.steps - 1),
-                   "n_dofs": nd, "jacobian_nnz": dev.jacobian_nnz, "newton_iterations": its,
+                   "n_dofs": dev.ndof, "jacobian_nnz": dev.jacobian_nnz, "newton_iterations": its,
                    "krylov_iterations": kry,
                    "parallelism": "1 GPU" if world == 1 else "%d independent replicas, one per GPU (no collective)" % world},
-        "roofline": {"bound": "hbm", "kernel": kernel_name, "achieved": achieved,
-                     "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": traffic_note,
-                     "algorithmic_bytes_per_launch": alg_bytes, "mean_launch_us": mean_us,
-                     "empty_event_pair_us": ev_overhead,   # information only: `achieved` uses the raw event time (conservative)
-                     "timing": "one HIP event pair around the first burst of every Nth solve (back-to-back live half-iterations); mean = elapsed / half-iterations, launch gaps included",
-                     "launches_sampled": prof["sampled"], "launches_total": prof["launched"],
-                     "launches_per_krylov_iteration": launches, "multilevel_note": ml_note},
+        "roofline": spmv_roofline(a, dev, prof, nv),
     }
     if world == 1:
         out["scaling_note"] = "N = 1: one problem on one GPU; the field says weak because the contract has two values (at N > 1: strong = ONE problem partitioned, replicas = weak)"
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(run)
     if world > 1:
         out["replicas"] = {"metric": "newton_iterations_per_sec, %d independent L_50_R_5 problems, one per GPU (BASELINE configs[4] mapping)" % world,
                            "value": its / dt, "ms_per_step": 1e3 * dt / a.steps, "newton_iterations": its, "krylov_iterations": kry, "scaling": "weak"}
     return out
+
+
+def spmv_roofline(a, dev, prof, nv):
+    """The roofline object of the 3D line from the live sample `prof` of the timed steps.  What needs launches of its own (the
+    tile kernels of the multilevel form, a run without a sampled solve, the empty event pair) is measured with --full only."""
+    nb, nd = dev.n_blocks, dev.ndof
+    nf = dev.nf
+    alg_bytes = (nf * nf * 8) * nb + 4 * nb + 4 * (nv + 1) + 16 * nd  # SURVEY §8d, one SpMV
+    launches = dev.krylov_launches_per_iteration
+    multilevel = a.multilevel and a.refine > 0
+    if not a.full and (multilevel or not prof["sampled"]):
+        return {"skipped": "needs kernel launches timed by themselves: --full", "launches_sampled": prof["sampled"],
+                "launches_total": prof["launched"], "launches_per_krylov_iteration": launches}
+    mean_us = prof["mean_us"] if prof["sampled"] else dev.time_kernel(4, 200)
+    ml_note = None
+    if multilevel:
+        # the live event brackets span whole half-iterations, i.e. the ~35 small launches of the multilevel term as well; the
+        # roofline line is about the streaming kernel, so it is timed by itself here (back-to-back launches, HIP events)
+        ml_note = "live half-iteration incl. the multilevel launches: %.1f us; the tile kernels alone (k_bicg_a_mat / k_bicg_b_mat, back-to-back): see mean_launch_us" % mean_us
+        mean_us = 0.5 * (dev.time_kernel(14, 50) + dev.time_kernel(15, 50))
+    if launches == 2:
+        kernel_name = ("k_half_a / k_half_b (one launch per BiCGStab half-iteration: the coarse workgroups ride in front of "
+                       "the tile workgroups = SELL node-block SpMV + vector updates, fp64; the launch duration includes "
+                       "the in-launch wait for the coarse result, which the 4-launch form spends in a separate launch)")
+    else:
+        kernel_name = "k_bicg_a / k_bicg_b (fused BiCGStab half-iteration = SELL node-block SpMV + vector updates, fp64)"
+    if multilevel:
+        kernel_name = "k_bicg_a_mat / k_bicg_b_mat (tile kernels of the materialised vector form: SELL node-block SpMV staging one vector, fp64)"
+    achieved = alg_bytes / (mean_us * 1e-6) / 1e9
+    # what an EMPTY start/stop event pair measures on this stream: each timed burst carries that much ONCE (a burst is 2 x
+    # ~20 launches), reported for information
+    ev_overhead = None
+    if a.full:
+        try:
+            ev_overhead = dev.event_overhead(200)
+        except Exception:  # noqa: BLE001
+            pass
+    # memory-side bytes per launch from the committed PMC passes; only valid for the build they were measured on
+    traffic, traffic_note = None, "no PMC file"
+    pmc = os.path.join(ROOT, "profiles", "spmv_pmc.json")
+    if os.path.exists(pmc) and a.mesh == "L_50_R_5" and a.refine == 0:
+        with open(pmc) as fh:
+            pj = json.load(fh)
+        if pj.get("build_id") == dev.build_id and pj.get("launches_per_krylov_iteration") == launches:
+            traffic, traffic_note = pj.get("hbm_bytes_per_launch"), pj.get("source")
+        else:
+            traffic_note = "profiles/spmv_pmc.json was measured on build %s, this library is %s: dropped" % (pj.get("build_id"), dev.build_id)
+    return {"bound": "hbm", "kernel": kernel_name, "achieved": achieved,
+            "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": traffic_note,
+            "algorithmic_bytes_per_launch": alg_bytes, "mean_launch_us": mean_us,
+            "empty_event_pair_us": ev_overhead,   # information only (--full): `achieved` uses the raw event time (conservative)
+            "timing": "one HIP event pair around the first burst of every Nth solve (back-to-back live half-iterations); mean = elapsed / half-iterations, launch gaps included",
+            "launches_sampled": prof["sampled"], "launches_total": prof["launched"],
+            "launches_per_krylov_iteration": launches, "multilevel_note": ml_note}
 
 
 def attach_partitioned(out, a, world, part):

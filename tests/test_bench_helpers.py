@@ -122,3 +122,44 @@ def test_dump_outputs_writes_float64_within_the_limit(tmp_path):
     assert np.array_equal(rows, np.load(str(tmp_path / "s2" / "vertex_values_rows.npy")))
     assert np.array_equal(np.load(str(tmp_path / "s1" / "newton_iterations.npy")), its.astype(np.float64))
     assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))) <= limit
+
+
+class _Dev:
+    """What make_output reads of a DeviceSolver; a launch of its own is recorded."""
+    n_blocks, ndof, nf, jacobian_nnz, build_id, krylov_launches_per_iteration = 1000, 900, 9, 81000, "none", 2
+
+    def __init__(self):
+        self.launched = []
+
+    def time_kernel(self, kernel, launches=50):
+        self.launched.append(("time_kernel", kernel))
+        return 10.0
+
+    def event_overhead(self, pairs=200):
+        self.launched.append(("event_overhead", pairs))
+        return 5.0
+
+
+def test_plain_line_measures_nothing_after_the_timed_steps(monkeypatch):
+    calls = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda run: calls.append("cpu_baseline") or {"value": 1.0})
+    live = {"sampled": 40, "mean_us": 12.5, "launched": 400}
+    for full in (False, True):
+        for multilevel, prof in ((False, live), (True, live), (False, {"sampled": 0, "mean_us": 0.0, "launched": 400})):
+            a = bench.parse(["--steps", "4", "--refine", "1" if multilevel else "0"] + (["--multilevel"] if multilevel else [])
+                            + (["--full"] if full else []))
+            dev, calls[:] = _Dev(), []
+            out = bench.make_output(a, None, dev, prof, 100, 1, 0.5, 20.0, 300.0)
+            assert out["value"] == 40.0 and out["ms_per_step"] == 125.0 and out["higher_is_better"] and out["dtype"] == "f64"
+            r = out["roofline"]
+            if not full:
+                assert dev.launched == [] and calls == [] and "cpu_baseline" not in out
+                if multilevel or not prof["sampled"]:
+                    assert "--full" in r["skipped"] and "frac" not in r
+                else:      # the live sample of the timed steps alone
+                    assert r["mean_launch_us"] == 12.5 and r["empty_event_pair_us"] is None
+            else:
+                assert calls == ["cpu_baseline"] and ("event_overhead", 200) in dev.launched and r["empty_event_pair_us"] == 5.0
+                assert r["mean_launch_us"] == (12.5 if prof["sampled"] and not multilevel else 10.0)
+                assert bool(r["multilevel_note"]) == multilevel
+    assert bench.parse([]).full is False

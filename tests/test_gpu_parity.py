@@ -1035,6 +1035,28 @@ def test_bench_dumps_what_its_last_timed_step_computed(gpu_lib, tmp_path):
     assert relerr(u.ravel(), g["states"][2]) < 1e-8
 
 
+def test_plain_bench_run_dumps_the_1d_arrays_and_measures_nothing_more(gpu_lib, tmp_path):
+    """A plain `bench.py --steps K --dump-outputs DIR` (no --full) writes what the parent layout has — the 3D arrays and those of
+    the secondary 1D case, whose 100 steps start with the oracle's Newton counts — while its line carries the headline and the
+    live roofline only: no CPU baseline, no 1D rate, no launches timed by themselves."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    d = str(tmp_path / "plain")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", d],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert "cpu_baseline" not in line and "edl50" not in line, sorted(line)
+    assert line["roofline"]["empty_event_pair_us"] is None and line["roofline"]["mean_launch_us"] > 0
+    assert sorted(os.listdir(d)) == ["edl50_newton_iterations.npy", "edl50_vertex_values.npy", "newton_iterations.npy", "vertex_values.npy"]
+    its = np.load(os.path.join(d, "edl50_newton_iterations.npy"))
+    g = np.load(os.path.join(GOLDEN, "edl50_default_steps.npz"))
+    assert len(its) == 100 and list(its[:3]) == list(g["newton_its"])
+    assert np.load(os.path.join(d, "edl50_vertex_values.npy")).shape == (5991, 7)
+
+
 @pytest.mark.parametrize("nparts", [4, 8])
 def test_partitioned_time_loop_survives_krylov_breakdowns(gpu_lib, nparts):
     """Twelve time steps of the bench problem on 4 / 8 partitions (all ranks in one process): 88 linear solves, some of which
@@ -1233,7 +1255,7 @@ def _pore_case(L):
 
 def test_refined_multilevel_run_through_the_driver_and_the_bench(tmp_path, monkeypatch, gpu_lib):
     """`--refine 1 --multilevel` through the 3D driver's CLI (outputs on the refined mesh: 12,109 vertices) and through bench.py
-    (the line names the preconditioner and times the tile kernels by themselves for the roofline object)."""
+    --full (the line names the preconditioner and times the tile kernels by themselves for the roofline object)."""
     import json
     import subprocess
     import sys
@@ -1244,7 +1266,7 @@ def test_refined_multilevel_run_through_the_driver_and_the_bench(tmp_path, monke
     a = np.load(os.path.join(out, "arrays_unscaled.npz"))
     assert a["p"].shape == (2, 12109) and a["field_values"].shape == (3 * 12109,) and np.isfinite(a["cat_grad"]).all()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mesh", "L_10_R_5", "--refine", "1", "--multilevel", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-edl50"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-edl50"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert "multilevel" in line["config"]["preconditioner"] and line["config"]["n_vertices"] == 12109

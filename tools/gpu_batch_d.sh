@@ -10,4 +10,4 @@ for lev in 1 2; do
   grep "k_dist_reduce\|k_minv_apply" gpurun_out/refined_level${lev}_kernel_stats_after.csv | cut -d, -f1-4 | cut -c1-120
 done
 python bench.py --refine 1 --steps 10 --warmup 1 --no-cpu-baseline > gpurun_out/bench_refine1.json 2>/dev/null; python -c "import json; d=json.load(open('gpurun_out/bench_refine1.json')); print('refine1', d['value'], d['roofline']['achieved'], d['roofline']['frac'], d['config']['krylov_iterations'])"
-python bench.py --refine 2 --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/bench_refine2.json 2>/dev/null; python -c "import json; d=json.load(open('gpurun_out/bench_refine2.json')); print('refine2', d['value'], d['roofline']['achieved'], d['roofline']['frac'], d['config']['krylov_iterations'])"
+python bench.py --full --refine 2 --steps 5 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -n 1 | python -c "import json, sys; d=json.loads(sys.stdin.read()); print('refine2', d['value'], d['roofline']['achieved'], d['roofline']['frac'], d['config']['krylov_iterations'])"
