@@ -162,6 +162,8 @@ struct gmpnp_solver {
   int ml_mid_jacobi = 1;   // intermediate levels smooth with node-block Jacobi alone (the slab coarse space stays with the coarsest level)
   DevBuf<int32_t> ml_par, ml_child_ptr, ml_child, ml_copy;
   DevBuf<double> ml_r, ml_w, ml_z;
+  DevBuf<uint8_t> ml_tbc;   // partitioned levels: TRUE Dirichlet flags of the local dofs, ghost rows included (k_pml_flags)
+  DevBuf<double> ml_tbd;    // ... their staging as doubles for the halo exchange
 
   ~gmpnp_solver() {
     for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1621,14 +1623,66 @@ int gmpnp_linear_solve(gmpnp_solver* s, const double* b, double* x, int32_t mode
   return download_vec(s, s->kx.p, x);
 }
 
+}  // extern "C"
+namespace {
+// Partition handles of one rank (gmpnp_group.h, "multilevel term"): parents[2 v + {0, 1}] in the coarse handle's LOCAL file order,
+// -1 where a parent is not local there (ghost rows only).  The tables serve the OWNED rows: the prolongation of an owned fine
+// vertex, the restriction onto an owned coarse vertex (its children: every local fine vertex naming it, ascending internal
+// index — the global slab order restricted, so the sums run in the serial order) and the injection of an owned coarse vertex.
+int attach_partitioned_level(gmpnp_solver* fine, gmpnp_solver* coarse, const int32_t* parents, double theta, int32_t sweeps) {
+  if (fine->part_rank != coarse->part_rank || fine->part_size != coarse->part_size)
+    return fail(GMPNP_ERR_INVALID, "multilevel term: the levels must be partition handles of the same rank of partitions of the same size");
+  const int nvf = fine->t.nv, nvc = coarse->t.nv;
+  const int f0 = fine->t.own_node0, f1 = fine->t.own_node1, c0 = coarse->t.own_node0, c1 = coarse->t.own_node1;
+  std::vector<int32_t> par((size_t)2 * nvf, -1), copy(nvc, -1);
+  std::vector<std::vector<int32_t>> kids(nvc);
+  for (int I = 0; I < nvf; ++I) {
+    const int v = fine->t.perm[I];
+    const int a = parents[2 * v], b = parents[2 * v + 1];
+    const bool owned = I >= f0 && I < f1;
+    if (a < -1 || a >= nvc || b < -1 || b >= nvc) return fail(GMPNP_ERR_INVALID, "parent vertex out of range");
+    if (owned && (a < 0 || b < 0)) return fail(GMPNP_ERR_INVALID, "multilevel term: both parents of an owned fine vertex must be local on the coarse level");
+    const int Ia = a >= 0 ? coarse->t.iperm[a] : -1, Ib = b >= 0 ? coarse->t.iperm[b] : -1;
+    if (owned) { par[2 * I] = Ia; par[2 * I + 1] = (a == b) ? -1 : Ib; }
+    else { par[2 * I] = 0; par[2 * I + 1] = -1; }   // never read (ghost rows are masked); kept in range all the same
+    if (a >= 0 && a == b) {
+      if (copy[Ia] >= 0) return fail(GMPNP_ERR_INVALID, "two fine vertices claim to be the copy of one coarse vertex");
+      copy[Ia] = I; kids[Ia].push_back(I << 1);
+    } else {
+      if (Ia >= 0) kids[Ia].push_back((I << 1) | 1);
+      if (Ib >= 0) kids[Ib].push_back((I << 1) | 1);
+    }
+  }
+  std::vector<int32_t> cptr(nvc + 1, 0), clist;
+  for (int Ic = 0; Ic < nvc; ++Ic) {
+    const bool owned = Ic >= c0 && Ic < c1;
+    if (owned && (copy[Ic] < f0 || copy[Ic] >= f1))
+      return fail(GMPNP_ERR_INVALID, "multilevel term: an owned coarse vertex must have its copy among the owned fine vertices (the meshes are not nested, or the plans do not match)");
+    if (!owned) copy[Ic] = -1;
+    else clist.insert(clist.end(), kids[Ic].begin(), kids[Ic].end());
+    cptr[Ic + 1] = (int32_t)clist.size();
+  }
+  HIP_TRY(hipSetDevice(fine->opts.device_id));
+  HIP_TRY(fine->ml_par.upload(par)); HIP_TRY(fine->ml_child_ptr.upload(cptr)); HIP_TRY(fine->ml_child.upload(clist)); HIP_TRY(fine->ml_copy.upload(copy));
+  HIP_TRY(fine->ml_z.alloc(fine->ndof)); HIP_TRY(fine->ml_tbc.alloc(fine->ndof)); HIP_TRY(fine->ml_tbd.alloc(fine->ndof));
+  HIP_TRY(coarse->ml_r.alloc(coarse->ndof)); HIP_TRY(coarse->ml_w.alloc(coarse->ndof));
+  fine->ml_coarse = coarse; fine->ml_theta = theta; coarse->ml_is_coarse = true; coarse->ml_sweeps = sweeps;
+  fine->matp = true; fine->fused_half = false;
+  fine->precond_valid = false;
+  return GMPNP_OK;
+}
+}  // namespace
+extern "C" {
+
 int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const int32_t* parents, double theta, int32_t sweeps) {
   if (!fine || !coarse || !parents) return fail(GMPNP_ERR_INVALID, "NULL argument");
   if (fine == coarse || coarse->ml_is_coarse) return fail(GMPNP_ERR_INVALID, "a level handle serves one finer level");
   if (fine->dim != 3 || coarse->dim != 3 || fine->nf != 9 || coarse->nf != 9) return fail(GMPNP_ERR_INVALID, "multilevel term: 3D pore problems (9 fields)");
-  if (fine->partitioned || coarse->partitioned) return fail(GMPNP_ERR_INVALID, "multilevel term: unpartitioned handles");
+  if (fine->partitioned != coarse->partitioned) return fail(GMPNP_ERR_INVALID, "multilevel term: both levels partitioned, or neither");
   if (fine->opts.device_id != coarse->opts.device_id) return fail(GMPNP_ERR_INVALID, "the levels live on one device");
   if (!(theta > 0.0)) return fail(GMPNP_ERR_INVALID, "theta must be positive");
   if (sweeps < 1 || sweeps > 16) return fail(GMPNP_ERR_INVALID, "sweeps: 1 ... 16");
+  if (fine->partitioned) return attach_partitioned_level(fine, coarse, parents, theta, sweeps);
   const int nvf = fine->t.nv, nvc = coarse->t.nv;
   if (nvc >= nvf) return fail(GMPNP_ERR_INVALID, "the coarse level has fewer vertices");
   std::vector<int32_t> par((size_t)2 * nvf), copy(nvc, -1);

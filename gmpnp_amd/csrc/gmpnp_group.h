@@ -125,6 +125,9 @@ struct gmpnp_group {
   bool hosted = false; gmpnp_host_transport_t host{};
   double* h_stage = nullptr; size_t h_stage_n = 0;   // pinned: [send | recv] or the all-reduce buffer
   std::vector<int64_t> off_s, cnt_s, off_r, cnt_r;
+  // multilevel term (gmpnp_group_attach_coarse_group): the group of the next-coarser level's handles, and whether this group IS such
+  // a level (driven by the finest group's solve, never by a solve of its own)
+  gmpnp_group* ml_next = nullptr; bool ml_level = false;
 };
 
 namespace {
@@ -325,6 +328,164 @@ int group_setup(gmpnp_group* g, int mode, bool rebuild_coarse = true) {
   return GMPNP_OK;
 }
 
+// ---- multilevel term across the partitions (gmpnp_multilevel.h; serial form: gmpnp_api.hip ml_setup / ml_level_apply) ----------
+// Every level is a group of partition handles of the same ranks (gmpnp_group_attach_coarse_group) over the finest group's
+// transport; each level's collectives run over its own group, its launches in the finest handle's stream.  The transfers act on
+// the OWNED rows (the existing kernels on the owned range): the restriction of an owned coarse vertex reads its children, local on
+// the finer level, after a halo exchange of the finer vector; the prolongation of an owned fine vertex reads both parents, local on
+// the coarser level (transfer ghosts), after a halo exchange of the coarser vector.  Ghost dofs are identity rows of a partition
+// handle, so the finer side of a restriction masks with the TRUE Dirichlet flags (ml_tbc, k_pml_flags).  Every rank runs the same
+// sequence of collectives (the V-cycle has a fixed shape), so the lock-step of the partitioned solve holds.
+struct LevelStreams {   // the coarser levels' launches go to the finest handle's stream for the duration (as ml_setup does)
+  std::vector<std::pair<gmpnp_solver*, hipStream_t>> keep;
+  explicit LevelStreams(gmpnp_group* g) {
+    hipStream_t st = g->dom[0]->stream;
+    for (gmpnp_group* l = g->ml_next; l; l = l->ml_next)
+      for (gmpnp_solver* s : l->dom) { keep.emplace_back(s, s->stream); s->stream = st; }
+  }
+  ~LevelStreams() { for (auto& k : keep) k.first->stream = k.second; }
+};
+
+inline VecListW one_vec(double* p) { VecListW w{}; w.p[0] = p; return w; }
+
+// true Dirichlet flags of a finer level's local dofs (the mask of its restriction), ghost rows from their owners
+template <int NF>
+int pml_masks(gmpnp_group* F) {
+  for (gmpnp_solver* s : F->dom)
+    hipLaunchKernelGGL(k_pml_flags, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, (const uint8_t*)s->c.bcflag, s->t.own_node0 * NF,
+                       s->t.own_node1 * NF, s->ml_tbd.p, (int)s->ndof);
+  HIP_TRY(hipGetLastError());
+  int rc = group_exchange(F, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ml_tbd.p); }); if (rc) return rc;
+  for (gmpnp_solver* s : F->dom)
+    hipLaunchKernelGGL(k_pml_flags_bytes, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, (const double*)s->ml_tbd.p, s->ml_tbc.p, (int)s->ndof);
+  HIP_TRY(hipGetLastError());
+  return GMPNP_OK;
+}
+
+// Once per preconditioner set-up: the state goes down by injection (owned rows, then the ghost rows from their owners), every level
+// assembles its Jacobian and sets up its node-block inverse (ghost blocks from their owners); the coarsest level also its GLOBAL slab
+// operator (one all-reduce), rebuilt with the finest level's cadence (`rebuild`: coarse_age / coarse_slow, identical on all ranks).
+template <int DIM, int NF>
+int group_ml_setup(gmpnp_group* g, bool rebuild) {
+  for (gmpnp_group* F = g; F->ml_next; F = F->ml_next) {
+    gmpnp_group* C = F->ml_next;
+    int rc = pml_masks<NF>(F); if (rc) return rc;
+    for (size_t d = 0; d < F->dom.size(); ++d) {
+      gmpnp_solver* f = F->dom[d]; gmpnp_solver* c = C->dom[d];
+      const int c0 = c->t.own_node0, nown = (c->t.own_node1 - c0) * NF;
+      hipLaunchKernelGGL((k_ml_inject<NF>), dim3(grid_for(nown, 256)), dim3(256), 0, f->stream, (const double*)f->u.p, (const int32_t*)f->ml_copy.p + c0,
+                         c->u.p + (size_t)c0 * NF, nown);
+    }
+    HIP_TRY(hipGetLastError());
+    rc = group_exchange(C, NF, 1, [](gmpnp_solver* s) { return one_vec(s->u.p); }); if (rc) return rc;
+    for (gmpnp_solver* c : C->dom) {
+      rc = launch_element<DIM, NF>(c, true); if (rc) return rc;
+      rc = launch_jac_gather<DIM, NF>(c); if (rc) return rc;
+      c->jacobian_valid = true;
+    }
+    // intermediate levels smooth with node-block Jacobi alone (ml_mid_jacobi): no slab operator there
+    rc = group_setup<NF>(C, C->ml_next ? GMPNP_LINEAR_BICGSTAB_JACOBI : GMPNP_LINEAR_BICGSTAB_TWOLEVEL, rebuild); if (rc) return rc;
+  }
+  return GMPNP_OK;
+}
+
+// ml_r of the next-coarser level's owned rows = mask_c P^T mask_f src (src: ghost rows current)
+template <int NF, class F>
+int pml_restrict(gmpnp_group* Fg, F src_of) {
+  gmpnp_group* C = Fg->ml_next;
+  for (size_t d = 0; d < Fg->dom.size(); ++d) {
+    gmpnp_solver* f = Fg->dom[d]; gmpnp_solver* c = C->dom[d];
+    const int c0 = c->t.own_node0, nown = (c->t.own_node1 - c0) * NF;
+    hipLaunchKernelGGL((k_ml_restrict<NF>), dim3(grid_for(nown, 256)), dim3(256), 0, f->stream, src_of(f), (const uint8_t*)f->ml_tbc.p,
+                       (const int32_t*)f->ml_child_ptr.p + c0, (const int32_t*)f->ml_child.p, (const uint8_t*)c->c.bcflag + (size_t)c0 * NF,
+                       c->ml_r.p + (size_t)c0 * NF, nown);
+  }
+  HIP_TRY(hipGetLastError());
+  return GMPNP_OK;
+}
+
+// L's handles hold the restricted residual in ml_r (owned rows); leaves ml_w = S_L ml_r on the owned rows: the V(1,1) cycle of
+// ml_level_apply.  Collectives per cycle: a halo exchange in front of every SpMV, restriction and prolongation that reads ghost rows;
+// one all-reduce per application of the coarsest level's slab coarse space.
+template <int NF>
+int pml_level_apply(gmpnp_group* L) {
+  const int n = L->dom[0]->ncoarse;
+  auto smooth = [&](bool from_r, double scale_dst) -> int {   // ml_w = scale_dst * ml_w + omega * M_L^-1 src, owned rows
+    if (L->ml_next) {
+      for (gmpnp_solver* s : L->dom) {
+        const size_t o = (size_t)s->t.own_node0 * NF; const int nown = (s->t.own_node1 - s->t.own_node0) * NF;
+        const double* src = from_r ? s->ml_r.p : s->ks.p;
+        hipLaunchKernelGGL((k_ml_jacobi<NF>), dim3(grid_for(nown, 256)), dim3(256), 0, s->stream, (const double*)s->c.Dinv + o * NF, src + o,
+                           s->ml_w.p + o, scale_dst, s->ml_omega, nown);
+      }
+      HIP_TRY(hipGetLastError());
+      return GMPNP_OK;
+    }
+    for (gmpnp_solver* s : L->dom) {
+      const double* src = from_r ? s->ml_r.p : s->ks.p;
+      hipLaunchKernelGGL((k_restrict<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c, src, s->cpart_v0.p);
+      hipLaunchKernelGGL(k_dist_reduce, dim3(n), dim3(256), 0, s->stream, s->c, 3, 0, s->red_i.p);
+    }
+    HIP_TRY(hipGetLastError());
+    int rc = group_allreduce(L, [](gmpnp_solver* s) { return s->red_i.p; }, n); if (rc) return rc;
+    for (gmpnp_solver* s : L->dom)
+      hipLaunchKernelGGL((k_minv_apply<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, from_r ? (const double*)s->ml_r.p : (const double*)s->ks.p,
+                         (const double*)s->cpart_v0.p, s->ml_w.p, scale_dst, s->ml_omega, NewtonUpdate{nullptr, nullptr, 0.0, 0.0, 0.0}, (const double*)s->red_i.p);
+    HIP_TRY(hipGetLastError());
+    return GMPNP_OK;
+  };
+  auto residual = [&]() -> int {   // ks = ml_r - J_L ml_w on the owned rows (ghost columns of ml_w from their owners)
+    int rc = group_exchange(L, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ml_w.p); }); if (rc) return rc;
+    for (gmpnp_solver* s : L->dom)
+      hipLaunchKernelGGL((k_spmv_residual<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->ml_w.p,
+                         (const double*)s->ml_r.p, s->ks.p);
+    HIP_TRY(hipGetLastError());
+    return GMPNP_OK;
+  };
+  int rc = smooth(true, 0.0); if (rc) return rc;
+  if (gmpnp_group* C = L->ml_next) {
+    rc = residual(); if (rc) return rc;
+    rc = group_exchange(L, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ks.p); }); if (rc) return rc;
+    rc = pml_restrict<NF>(L, [](gmpnp_solver* s) { return (const double*)s->ks.p; }); if (rc) return rc;
+    rc = pml_level_apply<NF>(C); if (rc) return rc;
+    rc = group_exchange(C, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ml_w.p); }); if (rc) return rc;
+    for (size_t d = 0; d < L->dom.size(); ++d) {
+      gmpnp_solver* s = L->dom[d]; gmpnp_solver* c = C->dom[d];
+      const int o = s->t.own_node0, nown = (s->t.own_node1 - o) * NF;
+      hipLaunchKernelGGL((k_ml_prolong_add<NF>), dim3(grid_for(nown, 256)), dim3(256), 0, s->stream, (const double*)c->ml_w.p, (const int32_t*)s->ml_par.p + 2 * (size_t)o,
+                         (const uint8_t*)s->c.bcflag + (size_t)o * NF, s->ml_w.p + (size_t)o * NF, nown);
+    }
+    HIP_TRY(hipGetLastError());
+    rc = residual(); if (rc) return rc;
+    rc = smooth(false, 1.0); if (rc) return rc;
+  } else {
+    for (int k = 1; k < L->dom[0]->ml_sweeps; ++k) { rc = residual(); if (rc) return rc; rc = smooth(false, 1.0); if (rc) return rc; }
+  }
+  return GMPNP_OK;
+}
+
+// coarse part of T src on the finest level (src: ghost rows current): leaves S P^T src in the next level's ml_w, ghost rows included
+template <int NF, class F>
+int pml_correction(gmpnp_group* g, F src_of) {
+  int rc = pml_restrict<NF>(g, src_of); if (rc) return rc;
+  rc = pml_level_apply<NF>(g->ml_next); if (rc) return rc;
+  return group_exchange(g->ml_next, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ml_w.p); });
+}
+
+// z = vec + theta D T vec on the owned rows (k_ml_stage masks the ghost rows, whose D is an identity block here), then z's ghost
+// rows from their owners: the operand the materialised tile kernel stages
+template <int NF, class F>
+int pml_stage(gmpnp_group* g, F vec_of) {
+  int rc = pml_correction<NF>(g, vec_of); if (rc) return rc;
+  for (size_t d = 0; d < g->dom.size(); ++d) {
+    gmpnp_solver* s = g->dom[d];
+    hipLaunchKernelGGL((k_ml_stage<NF>), dim3(grid_for(s->ndof, kMlStageNodes * NF)), dim3(kMlStageNodes * NF), 0, s->stream, s->c,
+                       (const double*)g->ml_next->dom[d]->ml_w.p, (const int32_t*)s->ml_par.p, vec_of(s), s->ml_z.p, s->ml_theta);
+  }
+  HIP_TRY(hipGetLastError());
+  return group_exchange(g, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ml_z.p); });
+}
+
 // ---- BiCGStab across the ranks: rhs in kr (owned rows; k_res_gather left it there), ||rhs|| = bnorm (global); leaves y in ky ----
 // random_shadow: the shadow vector of this pass is each handle's krand (filled by the caller) and (rhat, r_0) = shadow_rho0
 template <int NF>
@@ -407,8 +568,55 @@ int group_krylov(gmpnp_group* g, int mode, double bnorm, double rtol, double ato
     HIP_TRY(hipGetLastError());
     return GMPNP_OK;
   };
+  // With a multilevel term: the materialised vector form (launch_half), the staged operand z = vec + theta D T vec of every half-
+  // iteration coming out of the V-cycle across the partitioned levels (pml_stage); the sums, the packing and the collectives behind
+  // the tile kernel are those of the form below.
+  auto iteration_ml = [&]() -> int {
+    const int par = k & 1;
+    for (gmpnp_solver* s : g->dom) {
+      const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back();
+      VecListW ub{}; ub.p[0] = s->ks.p; ub.p[1] = s->kt.p;
+      const int un = k > 0 ? nrn : 0;
+      hipLaunchKernelGGL((k_coarse_a_unpack<NF>), dim3(cg.x + grid_for(un * 2 * NF, kCoarseThreads)), dim3(kCoarseThreads), 0, s->stream, s->c, k, ub, 2,
+                         (const int32_t*)s->recv_nodes.p, un, (const double*)s->recvbuf.p);
+      hipLaunchKernelGGL(k_vec_a, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, k);
+    }
+    HIP_TRY(hipGetLastError());
+    int r = pml_stage<NF>(g, [par](gmpnp_solver* s) { return (const double*)s->c.kp[par]; }); if (r) return r;
+    for (gmpnp_solver* s : g->dom) {
+      const int nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
+      Ctx cc = s->c; cc.stage_a = s->ml_z.p;
+      hipLaunchKernelGGL((k_bicg_a_mat<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
+      VecList pa{}; pa.p[0] = s->kr.p; pa.p[1] = s->c.kv[par]; pa.p[2] = s->c.kp[par];
+      hipLaunchKernelGGL(k_dist_reduce_pack, dim3(2 + 3 * n + grid_for(nsn * 3 * NF, 256)), dim3(256), 0, s->stream, s->c, 1, par, s->red_a.p, 2 + 3 * n, pa, 3,
+                         (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p, NF);
+    }
+    r = group_reduce_transfer(g, [](gmpnp_solver* s) { return s->red_a.p; }, 2 + 3 * n, (size_t)3 * NF); if (r) return r;
+    for (gmpnp_solver* s : g->dom) {
+      const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back();
+      VecListW ua{}; ua.p[0] = s->kr.p; ua.p[1] = s->c.kv[par]; ua.p[2] = s->c.kp[par];
+      hipLaunchKernelGGL((k_coarse_b_unpack<NF>), dim3(cg.x + grid_for(nrn * 3 * NF, kCoarseThreads)), dim3(kCoarseThreads), 0, s->stream, s->c, k, ua, 3,
+                         (const int32_t*)s->recv_nodes.p, nrn, (const double*)s->recvbuf.p);
+      hipLaunchKernelGGL(k_vec_b, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, k);
+    }
+    HIP_TRY(hipGetLastError());
+    r = pml_stage<NF>(g, [](gmpnp_solver* s) { return (const double*)s->ks.p; }); if (r) return r;
+    for (gmpnp_solver* s : g->dom) {
+      const int nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
+      Ctx cc = s->c; cc.stage_b = s->ml_z.p;
+      hipLaunchKernelGGL((k_bicg_b_mat<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
+      VecList pb{}; pb.p[0] = s->ks.p; pb.p[1] = s->kt.p;
+      hipLaunchKernelGGL(k_dist_reduce_pack, dim3(4 + n + grid_for(nsn * 2 * NF, 256)), dim3(256), 0, s->stream, s->c, 2, par, s->red_b.p, 4 + n, pb, 2,
+                         (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p, NF);
+    }
+    r = group_reduce_transfer(g, [](gmpnp_solver* s) { return s->red_b.p; }, 4 + n, (size_t)2 * NF); if (r) return r;
+    ++k;
+    HIP_TRY(hipGetLastError());
+    return GMPNP_OK;
+  };
   auto iteration = [&]() -> int {
     if (g->peer) return iteration_peer();
+    if (g->ml_next) return iteration_ml();
     const int par = k & 1;
     for (gmpnp_solver* s : g->dom) {
       const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back(), nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
@@ -482,6 +690,15 @@ int group_update(gmpnp_group* g, int mode, double omega, bool add_to_start) {
     hipLaunchKernelGGL((k_minv_apply<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->ky.p,
                        (const double*)s->cpart_v0.p, s->kx.p, add_to_start ? 1.0 : 0.0, 1.0, NewtonUpdate{nullptr, nullptr, 0.0, 0.0, 0.0},
                        (const double*)s->red_i.p);
+  if (g->ml_next) {   // x += theta T y on the owned rows (the multilevel term of M^-1 applied to the Krylov solution), as the serial solve does
+    int rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ky.p); }); if (rc) return rc;
+    rc = pml_correction<NF>(g, [](gmpnp_solver* s) { return (const double*)s->ky.p; }); if (rc) return rc;
+    for (size_t d = 0; d < g->dom.size(); ++d) {
+      gmpnp_solver* s = g->dom[d];
+      hipLaunchKernelGGL((k_ml_add_solution<NF>), dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, (const double*)g->ml_next->dom[d]->ml_w.p,
+                         (const int32_t*)s->ml_par.p, s->kx.p, s->ml_theta);
+    }
+  }
   int rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { VecListW w{}; w.p[0] = s->kx.p; return w; }); if (rc) return rc;
   for (gmpnp_solver* s : g->dom)
     hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, (const double*)s->kx.p, -omega, (int)s->ndof);
@@ -510,6 +727,7 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
     // too much, 203 instead of 56 iterations with the first iteration's inverse in the second)
     const bool rebuild = two_level && (st.iterations == 0 || g->coarse_age >= 2 || g->coarse_slow || g->dom[0]->state_jumped);
     rc = group_setup<NF>(g, o.linear_solver, rebuild); if (rc) return rc;
+    if (g->ml_next) { rc = group_ml_setup<DIM, NF>(g, rebuild); if (rc) return rc; }
     gmpnp_linear_stats_t ls{};
     // Warm start, as in the single-GPU Newton (gmpnp_api.hip): with the damped update consecutive corrections satisfy
     // dx_{k+1} = (1 - w) dx_k + O(|dx_k|^2); x0 = (1-w) dx_k [+ (1-w)^2 (dx_k - (1-w) dx_{k-1})] is accepted when it removes at
@@ -841,7 +1059,34 @@ int gmpnp_group_newton_solve(gmpnp_group* g, const gmpnp_newton_options_t* o, gm
   gmpnp_newton_stats_t& st = stats ? *stats : local;
   st = gmpnp_newton_stats_t{};
   HIP_TRY(hipSetDevice(g->dom[0]->opts.device_id));
+  if (g->ml_level) return fail(GMPNP_ERR_INVALID, "this group is a coarse level of a multilevel term: the finest level's group drives it");
+  if (g->dom[0]->ml_coarse && !g->ml_next)
+    return fail(GMPNP_ERR_INVALID, "multilevel term: the coarse level's group is not attached (gmpnp_group_attach_coarse_group)");
+  if (g->ml_next && o->linear_solver != GMPNP_LINEAR_BICGSTAB_TWOLEVEL)
+    return fail(GMPNP_ERR_INVALID, "multilevel term: the partitioned solve runs it with the two-level preconditioner");
+  LevelStreams keep(g);
   return group_newton<3, 9>(g, *o, st);
+}
+
+// Multilevel term of partitioned handles: `coarse` holds the coarse levels (gmpnp_attach_coarse_level) of `fine`'s handles, handle
+// by handle, over the same kind of transport; it carries that level's collectives from now on.
+int gmpnp_group_attach_coarse_group(gmpnp_group* fine, gmpnp_group* coarse) {
+  if (!fine || !coarse || fine == coarse) return fail(GMPNP_ERR_INVALID, "bad arguments");
+  if (fine->peer || coarse->peer)
+    return fail(GMPNP_ERR_INVALID, "multilevel term: not over the peer-mailbox transport (its mailbox and sequence numbers serve one halo plan; "
+                                   "use the in-process, host-staged or RCCL transport)");
+  auto kind = [](const gmpnp_group* g) { return g->hosted ? "host-staged" : (g->comm ? "RCCL" : "in-process"); };
+  if (fine->hosted != coarse->hosted || (fine->comm != nullptr) != (coarse->comm != nullptr))
+    return fail(GMPNP_ERR_INVALID, std::string("multilevel term: the coarse group's transport (") + kind(coarse) + ") differs from the fine group's (" + kind(fine) + ")");
+  if (fine->comm && fine->comm != coarse->comm) return fail(GMPNP_ERR_INVALID, "multilevel term: the coarse group must use the fine group's communicator");
+  if (fine->dom.size() != coarse->dom.size() || fine->dom[0]->part_size != coarse->dom[0]->part_size)
+    return fail(GMPNP_ERR_INVALID, "multilevel term: the coarse group holds another number of ranks than the fine group");
+  for (size_t d = 0; d < fine->dom.size(); ++d)
+    if (fine->dom[d]->ml_coarse != coarse->dom[d])
+      return fail(GMPNP_ERR_INVALID, "multilevel term: a handle of the coarse group is not the level attached to the fine group's handle of its rank (gmpnp_attach_coarse_level)");
+  if (fine->ml_next || coarse->ml_level) return fail(GMPNP_ERR_INVALID, "multilevel term: a group serves one finer level and has one coarser level");
+  fine->ml_next = coarse; coarse->ml_level = true;
+  return GMPNP_OK;
 }
 
 // One pass of each collective of the partitioned solve over the group's OWN transport (peer mailboxes, RCCL, host-staged or the

@@ -103,6 +103,20 @@ __global__ __launch_bounds__(kMlStageNodes* NF) void k_ml_stage(const Ctx c, con
   for (int j = 0; j < NF; ++j) acc += d[(size_t)j * kWave] * tn[j];
   z[i] = vec[i] + theta * acc;
 }
+// Mesh-partitioned levels (gmpnp_group.h, "multilevel term"): a partition handle flags every ghost dof as an identity row, so bcflag
+// cannot mask the transfers at ghost rows.  Their mask is the TRUE Dirichlet set: the owned rows' flags as doubles, completed at the
+// ghost rows by the halo exchange with the owners' flags, then back to bytes (once per preconditioner set-up and level).
+__global__ __launch_bounds__(256) void k_pml_flags(const uint8_t* __restrict__ bcflag, int own0, int own1, double* __restrict__ out, int ndof) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= ndof) return;
+  out[i] = (i >= own0 && i < own1 && bcflag[i]) ? 1.0 : 0.0;
+}
+__global__ __launch_bounds__(256) void k_pml_flags_bytes(const double* __restrict__ in, uint8_t* __restrict__ out, int ndof) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= ndof) return;
+  out[i] = in[i] != 0.0 ? 1 : 0;
+}
+
 // finest level, end of a solve:  x += theta * mask P w_c
 template <int NF>
 __global__ __launch_bounds__(256) void k_ml_add_solution(const Ctx c, const double* __restrict__ wc, const int32_t* __restrict__ par, double* __restrict__ x, double theta) {

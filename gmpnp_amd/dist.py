@@ -11,6 +11,7 @@ are complete without any matrix communication; ghost rows are replaced by identi
 What this module is:
 * ``partition_plan`` / ``build_local_domain`` — the partition, the halo plan and the global coarse slabs handed to
   ``gmpnp_create_partition``;
+* ``partition_hierarchy`` — the same for every level of a nested hierarchy (the multilevel term across the partitions);
 * ``PartitionedSolver`` — the product path: Newton, BiCGStab, ghost exchanges and all-reduces run INSIDE libgmpnp.so
   (``gmpnp_group_newton_solve``; RCCL, in-process, or host-staged transport); Python scatters / gathers states and the
   per-step boundary values;
@@ -168,6 +169,158 @@ def partition_plan(prob: Problem, nparts: int, rank: int, n_global_aggregates: i
     return dom, perm_local, part
 
 
+# ---------------------------------------------------------------------------------------------
+# the nested levels of the multilevel term (gmpnp_attach_coarse_level on partitioned handles)
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class LevelPlan:
+    domain: LocalDomain
+    perm: np.ndarray          # local internal order (perm[internal] = local file index)
+    part: dict                # what gmpnp_create_partition takes
+    parents: np.ndarray       # (n_local, 2) parents of every local vertex in the NEXT-COARSER level's local file order, -1 = not
+                              # local there (ghost rows only; equal entries = a copy); None on the coarsest level
+    owner: np.ndarray         # owner of every GLOBAL vertex of the level (all ranks)
+    pos: np.ndarray           # position of every global vertex in the level's slab order
+    aggregate: np.ndarray     # coarse slab of every global vertex
+
+
+def _level_local_domain(prob: Problem, owner: np.ndarray, rank: int, nparts: int, lcells: np.ndarray, ghost_sets: list) -> LocalDomain:
+    """Local problem of `rank` on the cells `lcells` (global vertex ids); the halo plan comes from every rank's ACTUAL ghost set
+    (`ghost_sets[q]`, ascending), so ghosts that no owned cell touches (the transfer ghosts of a coarse level) are served too."""
+    nf = prob.nf
+    verts = np.unique(lcells)
+    owned = np.nonzero(owner == rank)[0]
+    ghosts = ghost_sets[rank]
+    assert np.array_equal(np.union1d(owned, ghosts), verts), "the local cells must cover the owned and the ghost vertices"
+    lverts = np.concatenate([owned, ghosts])
+    g2l = -np.ones(prob.coords.shape[0], dtype=np.int64)
+    g2l[lverts] = np.arange(len(lverts))
+
+    def facets_local(fv):
+        if len(fv) == 0:
+            return np.zeros((0, 3), dtype=np.int32)
+        keep = (owner[fv] == rank).any(axis=1)
+        return g2l[fv[keep]].astype(np.int32)
+
+    gv = prob.bc_dofs // nf
+    inloc = g2l[gv] >= 0
+    table = dict(zip((g2l[gv[inloc]] * nf + prob.bc_dofs[inloc] % nf).tolist(), prob.bc_vals[inloc].tolist()))
+    for d in range(len(owned) * nf, len(lverts) * nf):
+        table[d] = 0.0  # ghost rows are identity rows
+    bd = np.array(sorted(table), dtype=np.int64)
+    bvl = np.array([table[d] for d in bd])
+    local = Problem(coords=prob.coords[lverts], cells=g2l[lcells].astype(np.int32), model=prob.model, quad=prob.quad,
+                    wall_facets=facets_local(prob.wall_facets), exit_facets=facets_local(prob.exit_facets),
+                    point_vertices=np.zeros(0, dtype=np.int32), bc_dofs=bd, bc_vals=bvl)
+    gowner = owner[ghosts]
+    recv = {int(q): len(owned) + np.nonzero(gowner == q)[0] for q in np.unique(gowner)}
+    send = {}
+    for q in range(nparts):
+        if q != rank:
+            mine = ghost_sets[q][owner[ghost_sets[q]] == rank]   # ascending global id == q's ghost order restricted to my vertices
+            if len(mine):
+                send[q] = g2l[mine]
+    return LocalDomain(rank=rank, nparts=nparts, owned=owned, ghosts=ghosts, ghost_owner=gowner, problem=local,
+                       n_owned=len(owned), send=send, recv=recv)
+
+
+def _part_dict(dom: LocalDomain, rank: int, nparts: int, nag: int, agg_of: np.ndarray) -> dict:
+    lverts = np.concatenate([dom.owned, dom.ghosts])
+    nbrs = sorted(set(dom.send) | set(dom.recv))
+    send_ptr, recv_ptr, send_v, recv_v = [0], [0], [], []
+    for q in nbrs:
+        send_v.extend(np.asarray(dom.send.get(q, []), dtype=np.int64).tolist())
+        recv_v.extend(np.asarray(dom.recv.get(q, []), dtype=np.int64).tolist())
+        send_ptr.append(len(send_v))
+        recv_ptr.append(len(recv_v))
+    owned_flag = np.zeros(len(lverts), dtype=np.uint8)
+    owned_flag[:dom.n_owned] = 1
+    return {"rank": rank, "size": nparts, "n_global_aggregates": nag, "vertex_aggregate": agg_of[lverts].astype(np.int32),
+            "vertex_owned": owned_flag, "neighbour_rank": np.array(nbrs, dtype=np.int32), "send_ptr": np.array(send_ptr, dtype=np.int32),
+            "send_vertices": np.array(send_v, dtype=np.int32), "recv_ptr": np.array(recv_ptr, dtype=np.int32),
+            "recv_vertices": np.array(recv_v, dtype=np.int32)}
+
+
+def partition_hierarchy(levels, nparts: int, rank: int, n_global_aggregates: int = None):
+    """Partition plans of a nested hierarchy (``problem.pore_hierarchy``: [(problem, boundaries, parents)], FINEST first) for rank
+    `rank`: one ``LevelPlan`` per level.
+
+    * The finest level is ``partition_plan`` itself: its partitions, slabs and halo lists are those of the two-level solve.
+    * A coarse vertex is owned where its COPY (the fine vertex at the same place) is owned, lies in its copy's slab, and takes its
+      copy's place in the slab order: the coarse slabs never straddle ranks and no tie along the axis reorders anything.
+    * The coarse local mesh holds the cells that touch an owned vertex (its rows are complete) plus, for every parent of an owned
+      fine vertex that those cells miss, one cell that contains it: both parents of every owned fine vertex are local (transfer
+      ghosts), so the prolongation of the owned rows reads local values only.  Ghost rows are identity rows as on the finest level.
+    * Every child of an owned coarse vertex is local on the finer level (the copy's one-cell ring): the restriction of the owned
+      coarse rows reads local values only.  Asserted here."""
+    fine_prob = levels[0][0]
+    dom, perm, part = partition_plan(fine_prob, nparts, rank, n_global_aggregates)
+    nag = part["n_global_aggregates"]
+    nv = fine_prob.coords.shape[0]
+    from .backend import slab_permutation
+    gperm = slab_permutation(fine_prob.coords, fine_prob.cells, window=0)
+    pos = np.empty(nv, dtype=np.int64)
+    pos[gperm] = np.arange(nv)
+    bounds = (nv * np.arange(nag + 1, dtype=np.int64)) // nag
+    agg = np.searchsorted(bounds[1:], pos, side="right").astype(np.int32)
+    owner = (agg // (nag // nparts)).astype(np.int32)
+    plans = [LevelPlan(domain=dom, perm=perm, part=part, parents=None, owner=owner, pos=pos, aggregate=agg)]
+    for k in range(1, len(levels)):
+        prob_f, par_f = levels[k - 1][0], np.asarray(levels[k - 1][2], dtype=np.int64)
+        prob_c = levels[k][0]
+        fine = plans[-1]
+        nvc = prob_c.coords.shape[0]
+        is_copy = par_f[:, 0] == par_f[:, 1]
+        copy = -np.ones(nvc, dtype=np.int64)
+        copy[par_f[is_copy, 0]] = np.nonzero(is_copy)[0]
+        if (copy < 0).any():
+            raise ValueError("level %d: a coarse vertex has no copy on the finer level (the meshes are not nested)" % k)
+        owner_c = fine.owner[copy]
+        pos_c = fine.pos[copy]
+        agg_c = fine.aggregate[copy]
+        cells = prob_c.cells
+        touch = [(owner_c[cells] == q).any(axis=1) for q in range(nparts)]
+        lcells, ghost_sets = [], []
+        for q in range(nparts):
+            need = np.unique(par_f[fine.owner == q].ravel())
+            lc = cells[touch[q]]
+            have = np.zeros(nvc, dtype=bool)
+            have[lc.ravel()] = True
+            missing = need[~have[need]]
+            if len(missing):
+                # one cell per missing parent: the first (lowest cell id) that contains it
+                first = np.full(nvc, -1, dtype=np.int64)
+                flat = cells.ravel()
+                cid = np.repeat(np.arange(cells.shape[0]), cells.shape[1])
+                order = np.argsort(flat, kind="stable")
+                fv, fc = flat[order], cid[order]
+                starts = np.searchsorted(fv, missing)
+                assert (fv[starts] == missing).all(), "a parent vertex belongs to no cell"
+                first[missing] = fc[starts]
+                lc = np.concatenate([lc, cells[np.unique(first[missing])]])
+            lcells.append(lc)
+            verts = np.unique(lc)
+            ghost_sets.append(verts[owner_c[verts] != q])
+        dom_c = _level_local_domain(prob_c, owner_c, rank, nparts, lcells[rank], ghost_sets)
+        lverts_c = np.concatenate([dom_c.owned, dom_c.ghosts])
+        perm_c = np.argsort(pos_c[lverts_c], kind="stable").astype(np.int32)
+        part_c = _part_dict(dom_c, rank, nparts, nag, agg_c)
+        # parents of the finer level's local vertices in this level's local file order
+        g2l_c = -np.ones(nvc, dtype=np.int64)
+        g2l_c[lverts_c] = np.arange(len(lverts_c))
+        lverts_f = np.concatenate([fine.domain.owned, fine.domain.ghosts])
+        lpar = g2l_c[par_f[lverts_f]].astype(np.int32)
+        assert (lpar[:fine.domain.n_owned] >= 0).all(), "both parents of every owned fine vertex must be local"
+        # children of the owned coarse vertices: every fine vertex naming one as a parent is local on the finer level
+        g2l_f = -np.ones(par_f.shape[0], dtype=np.int64)
+        g2l_f[lverts_f] = np.arange(len(lverts_f))
+        kid_of_owned = (owner_c[par_f] == rank).any(axis=1)
+        assert (g2l_f[np.nonzero(kid_of_owned)[0]] >= 0).all(), "every child of an owned coarse vertex must be local on the finer level"
+        fine.parents = lpar
+        plans.append(LevelPlan(domain=dom_c, perm=perm_c, part=part_c, parents=None, owner=owner_c, pos=pos_c, aggregate=agg_c))
+    return plans
+
+
 class PartitionedSolver:
     """One mesh-partitioned problem solved by libgmpnp.so across `nparts` ranks (SURVEY section 8e / BASELINE configs[3]).
 
@@ -178,13 +331,17 @@ class PartitionedSolver:
     The Krylov and Newton loops run in the library; Python only scatters / gathers states and per-step boundary values."""
 
     def __init__(self, prob: Problem, nparts: int, rank: int = None, device_id: int = 0, n_global_aggregates: int = None,
-                 use_torch_dist: bool = True, transport: str = "rccl", exchange_form: int = 0, **device_kwargs):
+                 use_torch_dist: bool = True, transport: str = "rccl", exchange_form: int = 0, levels=None, ml_theta: float = 2.0,
+                 ml_sweeps: int = 4, **device_kwargs):
         """``transport`` (one rank per process only): "peer" — peer mailboxes: every collective is one kernel launch per rank
         that stores into the other ranks' IPC-mapped mailboxes (xGMI between GPUs; also works for ranks sharing a card);
         "rccl" — collectives inside the library over RCCL; "host" — the library stages every collective through pinned host
         memory and calls back into ``torch.distributed`` (any backend, e.g. gloo).  ``exchange_form`` (peer transport): 0 = the
         exchange of a half-iteration rides inside the next launch where that launch is resident (2 launches per BiCGStab iteration),
-        1 = separate exchange launches (4); every rank must pass the same value (gmpnp_group_set_exchange_form)."""
+        1 = separate exchange launches (4); every rank must pass the same value (gmpnp_group_set_exchange_form).
+        ``levels`` (``problem.pore_hierarchy``, finest first; ``prob`` is its finest problem): the geometric multilevel term of the
+        preconditioner across the partitions (``partition_hierarchy``; gmpnp_attach_coarse_level + gmpnp_group_attach_coarse_group),
+        ``ml_theta`` / ``ml_sweeps`` as on one GPU.  Not over the peer transport (refused by the library)."""
         from ctypes import byref, c_void_p, create_string_buffer
         if rank is not None:
             # one rank per process: torch.distributed carries the set-up (mailbox handles, communicator id, host-staged collectives).
@@ -198,10 +355,26 @@ class PartitionedSolver:
         self.nv_global, self.nf = prob.coords.shape[0], prob.nf
         self.ranks = list(range(nparts)) if rank is None else [rank]
         self.doms, self.devs = [], []
+        self.level_devs, self._level_groups = [], []   # [level k >= 1][local rank]: the coarse levels of the multilevel term
+        plans = []
         for r in self.ranks:
-            dom, perm, part = partition_plan(prob, nparts, r, n_global_aggregates)
+            if levels is not None and len(levels) > 1:
+                plans.append(partition_hierarchy(levels, nparts, r, n_global_aggregates))
+                dom, perm, part = plans[-1][0].domain, plans[-1][0].perm, plans[-1][0].part
+            else:
+                dom, perm, part = partition_plan(prob, nparts, r, n_global_aggregates)
             self.doms.append(dom)
             self.devs.append(backend.DeviceSolver(dom.problem, device_id=device_id, perm=perm, partition=part, **device_kwargs))
+        if plans:
+            # level handles of every local rank, each attached below the next-finer one of its rank (as PoreRun does on one GPU)
+            for k in range(1, len(plans[0])):
+                self.level_devs.append([backend.DeviceSolver(pl[k].domain.problem, device_id=device_id, perm=pl[k].perm, partition=pl[k].part,
+                                                             shared_device=1) for pl in plans])
+            for i, pl in enumerate(plans):
+                finer = self.devs[i]
+                for k in range(1, len(pl)):
+                    finer.attach_coarse_level(self.level_devs[k - 1][i], pl[k - 1].parents, theta=ml_theta, sweeps=ml_sweeps)
+                    finer = self.level_devs[k - 1][i]
         self._comm = c_void_p()
         self._group = c_void_p()
         self.transport = transport if rank is not None else "in-process"
@@ -246,10 +419,12 @@ class PartitionedSolver:
             tdist.all_reduce(form, op=tdist.ReduceOp.MIN)
             if int(form[0]) != 2:
                 self._check(self.lib.gmpnp_group_set_exchange_form(self._group, 1))
+            self._attach_level_groups()
             return
         if rank is not None and transport == "host":
             self._make_host_transport(rank, nparts)
             self._check(self.lib.gmpnp_group_create_hosted(self.devs[0]._h, byref(self._host_transport), byref(self._group)))
+            self._attach_level_groups()
             return
         if rank is not None:
             idbuf = create_string_buffer(backend.COMM_ID_BYTES)
@@ -273,6 +448,25 @@ class PartitionedSolver:
             self._check(self.lib.gmpnp_comm_create(idbuf, rank, nparts, device_id, byref(self._comm)))
         handles = (c_void_p * len(self.devs))(*[d._h for d in self.devs])
         self._check(self.lib.gmpnp_group_create(len(self.devs), handles, self._comm if rank is not None else None, byref(self._group)))
+        self._attach_level_groups()
+
+    def _attach_level_groups(self):
+        """One group per coarse level over this solver's transport (the same communicator / host callbacks), attached below the
+        next-finer level's group: it carries that level's collectives (gmpnp_group_attach_coarse_group)."""
+        from ctypes import byref, c_void_p, create_string_buffer
+        finer = self._group
+        for devs in self.level_devs:
+            g = c_void_p()
+            if self.transport == "peer":
+                self._check(self.lib.gmpnp_group_peer_begin(devs[0]._h, byref(g), create_string_buffer(self.backend.PEER_HANDLE_BYTES)))
+            elif self.transport == "host":
+                self._check(self.lib.gmpnp_group_create_hosted(devs[0]._h, byref(self._host_transport), byref(g)))
+            else:
+                handles = (c_void_p * len(devs))(*[d._h for d in devs])
+                self._check(self.lib.gmpnp_group_create(len(devs), handles, self._comm if self.rank is not None else None, byref(g)))
+            self._level_groups.append(g)
+            self._check(self.lib.gmpnp_group_attach_coarse_group(finer, g))
+            finer = g
 
     def _check(self, code):
         if code != self.backend.OK:
@@ -400,9 +594,16 @@ class PartitionedSolver:
         if getattr(self, "_group", None):
             self.lib.gmpnp_group_destroy(self._group)
             self._group = None
+        for g in getattr(self, "_level_groups", []):
+            self.lib.gmpnp_group_destroy(g)
+        self._level_groups = []
         for d in getattr(self, "devs", []):
             d.close()
         self.devs = []
+        for devs in getattr(self, "level_devs", []):
+            for d in devs:
+                d.close()
+        self.level_devs = []
         if getattr(self, "_comm", None) and self._comm.value:
             self.lib.gmpnp_comm_destroy(self._comm)
             self._comm = None

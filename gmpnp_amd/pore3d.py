@@ -47,12 +47,13 @@ class PoreRun:
         """``partition`` = (nparts, rank): solve this ONE problem across `nparts` mesh partitions (rank None: all of them in
         this process on one GPU; rank r: this process is rank r of a ``torch.distributed`` job, RCCL inside the library).
         ``multilevel`` (with ``refine`` > 0): the preconditioner gets the geometric multilevel term over the nested meshes
-        (gmpnp_attach_coarse_level) — not a reference feature; it changes iteration counts of the linear solves, not results."""
+        (gmpnp_attach_coarse_level; with ``partition`` across the mesh partitions, every level partitioned alike) — not a reference
+        feature; it changes iteration counts of the linear solves, not results."""
         self.kwargs = kwargs
         self.pp = pore_parameters(as_published=as_published, **kwargs)
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), self.pp.mesh_name))
         self._levels = None
-        if multilevel and refine > 0 and not partition:
+        if multilevel and refine > 0:
             from .problem import pore_hierarchy
             self._levels = pore_hierarchy(self.pp, self.mesh, refine)
             self.problem, self.bnd = self._levels[0][0], self._levels[0][1]
@@ -63,7 +64,8 @@ class PoreRun:
             self.mesh = Mesh(dim=3, coords=self.problem.coords, cells=self.problem.cells)
         if partition:
             from .solver import PartitionedSystem
-            self.sys = PartitionedSystem(self.problem, partition[0], rank=partition[1], **(device_kwargs or {}))
+            self.sys = PartitionedSystem(self.problem, partition[0], rank=partition[1], levels=self._levels, ml_theta=ml_theta, ml_sweeps=ml_sweeps,
+                                         **(device_kwargs or {}))
         else:
             self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
             if self._levels:   # coarser levels: ordinary handles of the parent meshes, attached below the finest one

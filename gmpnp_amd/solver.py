@@ -77,10 +77,12 @@ class PartitionedSystem:
     the Newton and BiCGStab loops run inside libgmpnp.so across the ranks (gmpnp_group_newton_solve).  `rank` = None keeps
     every rank in this process (one GPU, rehearsal); `rank` = r is the one-process-per-GPU form over RCCL."""
 
-    def __init__(self, problem: Problem, nparts: int, rank: int = None, **device_kwargs):
+    def __init__(self, problem: Problem, nparts: int, rank: int = None, levels=None, ml_theta: float = 2.0, ml_sweeps: int = 4, **device_kwargs):
+        """``levels`` (``problem.pore_hierarchy``, finest first, ``problem`` its finest): the geometric multilevel term of the
+        preconditioner across the partitions (``ml_theta`` / ``ml_sweeps`` as on one GPU)."""
         from .dist import PartitionedSolver
         self.problem = problem
-        self.ps = PartitionedSolver(problem, nparts, rank=rank, **device_kwargs)
+        self.ps = PartitionedSolver(problem, nparts, rank=rank, levels=levels, ml_theta=ml_theta, ml_sweeps=ml_sweeps, **device_kwargs)
         self.dev = self.ps.devs[0]            # this rank's LOCAL partition handle (local vertex numbering)
         self._device_kwargs = {k: v for k, v in device_kwargs.items() if k in ("device_id",)}
         self._post = None                     # unpartitioned handle on the global mesh, for post-processing only

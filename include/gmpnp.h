@@ -352,8 +352,19 @@ int gmpnp_group_assign_previous(gmpnp_group* g);
  * PRE_c (r - J_c x) from x = 0 with PRE_c = M_c^-1 + [the same term for a level attached below `coarse`] — sweeps = 1 is purely
  * additive, every further sweep costs one SpMV with J_c (1/8 of a fine one) (csrc/gmpnp_multilevel.h).
  * Chains: attach level 2 to level 1, then level 1 to level 0.  `coarse` must outlive `fine` and must not be driven by the caller
- * any more.  BiCGStab then runs in the materialised vector form.  3D, unpartitioned handles on one device. */
+ * any more.  BiCGStab then runs in the materialised vector form.  3D handles on one device.
+ * Partition handles (gmpnp_create_partition): `fine` and `coarse` are handles of the SAME rank of partitions of the same size, the
+ * coarse plan derived from the fine one (gmpnp_amd/dist.py partition_hierarchy: a coarse vertex is owned where its copy is, and both
+ * parents of every owned fine vertex are local); parents are in the two handles' LOCAL file orders, -1 where a parent is not local
+ * (ghost rows only).  The levels of all ranks then form groups of their own, attached with gmpnp_group_attach_coarse_group. */
 int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const int32_t* parents, double theta, int32_t sweeps);
+/* Multilevel term of a mesh-partitioned solve: `coarse` is a group (gmpnp_group_create / _create_hosted, the same communicator for
+ * RCCL) of the coarse-level handles attached to `fine`'s handles, rank by rank, over the same transport kind; it carries that level's
+ * halo exchanges and all-reduces from now on (chains: attach level 2's group to level 1's, level 1's to level 0's).
+ * gmpnp_group_newton_solve of `fine` then runs the V-cycle across the partitioned levels in every BiCGStab half-iteration (two-level
+ * mode only); `coarse` must outlive `fine` and is not driven by itself any more.  Refused (GMPNP_ERR_INVALID): peer-mailbox groups,
+ * groups of another transport kind or rank count, handles that are not the attached levels.  No reference counterpart. */
+int gmpnp_group_attach_coarse_group(gmpnp_group* fine, gmpnp_group* coarse);
 
 /* ---- ensemble of 1D problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py is many separate runs) ------------------------------------------------------------
