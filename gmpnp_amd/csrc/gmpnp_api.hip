@@ -324,13 +324,17 @@ int residual(gmpnp_solver* s, bool want_j, double* norm, int* flags) {
 
 // `refresh` = false keeps the previous Dinv and coarse inverse (any nonsingular block scaling and any coarse operator
 // give a valid right preconditioner) and only re-scales the new matrix: the cheap path of a lagged preconditioner.
+// The coarse chain: the Galerkin product P^T A P (the partitioned set-up all-reduces it before the inverse), then its inverse.
 template <int NF>
-void launch_coarse_chain(gmpnp_solver* s, const Ctx& c, hipStream_t st) {
+void launch_coarse_galerkin(gmpnp_solver* s, const Ctx& c, hipStream_t st) {
   hipLaunchKernelGGL((k_coarse_rows<NF>), dim3(s->t.nslices), dim3(64), 0, st, c);
   hipLaunchKernelGGL((k_coarse_sum<NF>), dim3(s->t.nagg * s->c.coarse_chunks), dim3(kVecBlock), 0, st, c);
-  const int n = s->ncoarse;
-  hipLaunchKernelGGL(k_coarse_reduce, dim3(grid_for(n * n, kVecBlock)), dim3(kVecBlock), 0, st, c);
-  hipLaunchKernelGGL((k_coarse_invert<NF>), dim3(1), dim3(512), coarse_lds_bytes(n, NF), st, c);
+  hipLaunchKernelGGL(k_coarse_reduce, dim3(grid_for(s->ncoarse * s->ncoarse, kVecBlock)), dim3(kVecBlock), 0, st, c);
+}
+template <int NF>
+void launch_coarse_chain(gmpnp_solver* s, const Ctx& c, hipStream_t st) {
+  launch_coarse_galerkin<NF>(s, c, st);
+  hipLaunchKernelGGL((k_coarse_invert<NF>), dim3(1), dim3(512), coarse_lds_bytes(s->ncoarse, NF), st, c);
 }
 
 // `allow_async` (Newton): unless `refresh_coarse` demands an inverse of THIS matrix now, the coarse chain of this matrix
@@ -452,6 +456,19 @@ int ml_setup(gmpnp_solver* s) {
   return GMPNP_OK;
 }
 
+// What half-iteration A (h = 0) or B (h = 1) of an iteration of parity `par` leaves for the next one: its phase, the per-rank
+// sums it all-reduces (into `red`), and the vectors whose ghost rows it sends (the next half unpacks them).
+struct Half {
+  int phase, nout; double* red;
+  int nvec; VecListW vecs;
+};
+inline Half half_of(gmpnp_solver* s, int h, int par) {
+  const int n = s->ncoarse;
+  if (h == 0) return Half{1, 2 + 3 * n, s->red_a.p, 3, VecListW{{s->kr.p, s->c.kv[par], s->c.kp[par], nullptr}}};
+  return Half{2, 4 + n, s->red_b.p, 2, VecListW{{s->ks.p, s->kt.p, nullptr, nullptr}}};
+}
+inline VecList read_only(const VecListW& w) { return VecList{{w.p[0], w.p[1], w.p[2], w.p[3]}}; }
+
 // One half-iteration of the fused BiCGStab: one launch (coarse workgroups inside the tile launch), two, or three.
 template <int NF, int WHICH>
 int launch_half(gmpnp_solver* s, int k) {
@@ -489,9 +506,8 @@ int launch_half(gmpnp_solver* s, int k) {
     hipLaunchKernelGGL((k_bicg_b<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, k);
   }
   if (s->prereduce) {   // the sums the next coarse kernel reads
-    const int n = s->ncoarse;
-    if (WHICH == 0) hipLaunchKernelGGL(k_dist_reduce, dim3(2 + 3 * n), dim3(256), 0, s->stream, s->c, 1, k & 1, s->red_a.p);
-    else hipLaunchKernelGGL(k_dist_reduce, dim3(4 + n), dim3(256), 0, s->stream, s->c, 2, k & 1, s->red_b.p);
+    const Half h = half_of(s, WHICH, k & 1);
+    hipLaunchKernelGGL(k_dist_reduce, dim3(h.nout), dim3(256), 0, s->stream, s->c, h.phase, k & 1, h.red);
   }
   s->spmv_launched++;
   return GMPNP_OK;
@@ -517,6 +533,24 @@ int enqueue_iteration(gmpnp_solver* s, int k) {
   return launch_half<NF, 1>(s, k);
 }
 
+// Start values of a BiCGStab pass; rho0 = (rhat, r_0), ||r_0|| = bnorm
+KrylovScalars krylov_start(double rho0, double bnorm, double rtol, double atol, int maxit) {
+  KrylovScalars init{};
+  init.rho[0] = init.rho[1] = rho0; init.alpha = 1.0;
+  init.tol = std::max(rtol * bnorm, atol); init.rr = init.rr0 = bnorm * bnorm; init.max_iters = maxit;
+  if (!(bnorm > 0.0)) init.done = 1;  // zero right-hand side: dx = 0
+  return init;
+}
+// The stats of a finished pass, and GMPNP_ERR_LINEAR ("<what> stopped without convergence ...") unless it converged
+int krylov_verdict(const KrylovScalars& res, double bnorm, gmpnp_linear_stats_t* st, const char* what) {
+  if (st) { st->iterations = res.iters; st->converged = (res.done == 1); st->residual_norm = std::sqrt(res.rr); st->rhs_norm = bnorm; }
+  if (res.done == 1) return GMPNP_OK;
+  char buf[200];
+  snprintf(buf, sizeof buf, "%s stopped without convergence (code %d) after %d iterations, ||r|| = %.3e, ||b|| = %.3e",
+           what, res.done, res.iters, std::sqrt(res.rr), bnorm);
+  return fail(GMPNP_ERR_LINEAR, buf);
+}
+
 // Solve J dx = rhs (rhs already in c.kr on the device, ||rhs|| = bnorm) with the fused right-preconditioned BiCGStab;
 // leaves y in c.ky; the caller applies M^{-1} (apply_minv).
 template <int NF>
@@ -525,12 +559,7 @@ int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, in
   s->c.use_coarse = use_coarse;
   const int n = s->ndof;
   s->fused_seq = 0;
-  KrylovScalars init{};
-  init.rho[0] = init.rho[1] = s->shadow_src ? s->shadow_rho0 : bnorm * bnorm; init.alpha = 1.0;
-  init.tol = std::max(rtol * bnorm, atol); init.rr = bnorm * bnorm; init.iters = 0; init.it_cur = 0;
-  init.max_iters = maxit; init.done = 0; init.done_next = 0; init.omega = 0.0; init.beta = 0.0;
-  init.rr0 = bnorm * bnorm;
-  if (!(bnorm > 0.0)) init.done = 1;  // zero right-hand side: dx = 0
+  const KrylovScalars init = krylov_start(s->shadow_src ? s->shadow_rho0 : bnorm * bnorm, bnorm, rtol, atol, maxit);
   // one launch: shadow vector (r_0, or a pseudo-random vector after a breakdown), y = 0, P^T r_0 partials
   // where A(0) expects them, hand-over flags cleared, scalars from the kernel argument
   hipLaunchKernelGGL((k_krylov_init<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c, s->shadow_src, init, s->cpart_v1.p);
@@ -617,14 +646,7 @@ int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, in
   if (bracket >= 0 && res.done == 1 && res.iters > first) s->ev_halves[bracket] = 2 * first;   // every launch of the burst did its work
   if (!restart) s->last_krylov_iters[use_coarse] = res.iters;
   s->last_done = res.done;
-  if (st) { st->iterations = res.iters; st->converged = (res.done == 1); st->residual_norm = std::sqrt(res.rr); st->rhs_norm = bnorm; }
-  if (res.done != 1) {
-    char buf[160];
-    snprintf(buf, sizeof buf, "BiCGStab stopped without convergence (code %d) after %d iterations, ||r|| = %.3e, ||b|| = %.3e",
-             res.done, res.iters, std::sqrt(res.rr), bnorm);
-    return fail(GMPNP_ERR_LINEAR, buf);
-  }
-  return GMPNP_OK;
+  return krylov_verdict(res, bnorm, st, "BiCGStab");
 }
 
 // dst = scale_dst*dst + scale_x * M^{-1} src,  M^{-1} = Dinv (I + P Aci P^T)

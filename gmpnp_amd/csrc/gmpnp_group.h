@@ -1,11 +1,13 @@
 // Mesh-partitioned Newton solve inside the library (include/gmpnp.h, "mesh-partitioned solve").
 // Included at the end of gmpnp_api.hip: uses the handle type and the launch helpers defined there.
 //
-// One handle per rank on the rank's local mesh (owned + one ghost layer).  Per BiCGStab half-iteration and rank:
+// One handle per rank on the rank's local mesh (owned + one ghost layer).  Per BiCGStab half-iteration and rank (half_of: which
+// sums it all-reduces, which ghost rows it sends):
 //     coarse kernel (scalars + coarse solve from all-reduced sums)  ->  tile kernel on the owned tiles (SpMV + vector updates)
-//     ->  k_dist_reduce (per-rank sums)  ->  ONE all-reduce  +  ONE grouped send/recv of the ghost rows  ->  k_halo_unpack
-// Nothing of the loop runs on the host except the launches; the host reads the device's verdict once per burst, and every
-// rank launches the same bursts (the burst schedule depends only on all-reduced quantities), so the collectives pair up.
+//     ->  per-rank sums  ->  ONE all-reduce  +  ONE grouped send/recv of the ghost rows  ->  unpacking in the next coarse kernel
+// in one routine per form (group_half; on the peer transport peer_half, or peer_half_x where the exchange rides in front of the
+// next launch).  Every rank launches the same bursts (the burst schedule depends only on all-reduced quantities), so the
+// collectives pair up.
 //
 // Transports: peer mailboxes (one process per rank; every collective is ONE k_peer_exchange launch that stores into the other
 // ranks' IPC-mapped mailboxes — over xGMI between GPUs — and waits on its own flags: gmpnp_dist_kernels.h); RCCL (ncclAllReduce /
@@ -13,6 +15,7 @@
 // a group that holds ALL ranks of the partition in one process, device copies between the handles on one shared stream.
 #pragma once
 #include <dlfcn.h>
+#include <tuple>
 #include <rccl/rccl.h>
 
 namespace {
@@ -132,13 +135,24 @@ struct gmpnp_group {
 
 namespace {
 
+// ghost nodes a handle sends / receives
+inline int n_send(const gmpnp_solver* s) { return s->send_ptr.empty() ? 0 : s->send_ptr.back(); }
+inline int n_recv(const gmpnp_solver* s) { return s->recv_ptr.empty() ? 0 : s->recv_ptr.back(); }
+
+// the peer transport's usability: connected, and no rank's flag late (the device reports that in pinned memory)
+int peer_check(gmpnp_group* g) {
+  if (!g->peer) return GMPNP_OK;
+  if (!g->peer_connected) return fail(GMPNP_ERR_INVALID, "peer transport: gmpnp_group_peer_connect has not been called");
+  if (*g->h_peer_err) return fail(GMPNP_ERR_HIP, "peer transport: a rank's flag did not arrive within 5 s (rank gone, or its process ended with an error)");
+  return GMPNP_OK;
+}
+
 // ---- peer-mailbox transport: one launch = all-reduce of `n_red` doubles (in place) and / or the ghost rows (`per` doubles a node) ----
 int peer_exchange(gmpnp_group* g, double* red, int n_red, size_t per) {
   gmpnp_solver* s = g->dom[0];
-  if (!g->peer_connected) return fail(GMPNP_ERR_INVALID, "peer transport: gmpnp_group_peer_connect has not been called");
+  if (int rc = peer_check(g)) return rc;
   if (n_red > g->pa.red_cap) return fail(GMPNP_ERR_INVALID, "peer transport: all-reduce larger than the mailbox slot");
   if ((int)per > g->pa.wmax) return fail(GMPNP_ERR_INVALID, "peer transport: ghost rows wider than the mailbox unit");
-  if (*g->h_peer_err) return fail(GMPNP_ERR_HIP, "peer transport: a rank's flag did not arrive within 5 s (rank gone, or its process ended with an error)");
   g->pa.seq++;
   hipLaunchKernelGGL(k_peer_exchange, dim3(1), dim3(1024), 0, s->stream, g->pa, (const double*)red, n_red, red,
                      (const double*)s->sendbuf.p, s->recvbuf.p, (int)per);
@@ -146,8 +160,11 @@ int peer_exchange(gmpnp_group* g, double* red, int n_red, size_t per) {
   return GMPNP_OK;
 }
 
-// ---- flagged-word exchange (exchange-prologue launches, gmpnp_dist_kernels.h): arguments of the next one, and what its readers poll ----
-XchArgs make_xch_args(gmpnp_group* g, int phase, int par, int nout, const VecList& v, int nvec) {
+// ---- flagged-word exchange (exchange-prologue launches, gmpnp_dist_kernels.h): whether the peer transport uses it, the arguments of
+// the next one, and what its readers poll ----
+inline bool flagged_words(const gmpnp_group* g) { return g->peer && g->prologue_ok && g->exchange_form != 1 && g->dom[0]->fused_half; }
+// `h`: the half-iteration whose sums and rows it exchanges; `nsn` of its ghost nodes are sent
+XchArgs make_xch_args(gmpnp_group* g, const Half& h, int par, int nsn) {
   gmpnp_solver* s = g->dom[0];
   XchArgs x{};
   const PeerArgs& a = g->pa;
@@ -156,8 +173,8 @@ XchArgs make_xch_args(gmpnp_group* g, int phase, int par, int nout, const VecLis
   x.n_nb = a.n_nb;
   for (int j = 0; j < a.n_nb; ++j) { x.nb_rank[j] = a.nb_rank[j]; x.peer_recv_ptr[j] = a.peer_recv_ptr[j]; }
   for (int j = 0; j <= a.n_nb; ++j) x.send_ptr[j] = a.send_ptr[j];
-  x.phase = phase; x.par = par; x.nout = nout; x.nvec = nvec;
-  x.vecs = v; x.send_nodes = s->send_nodes.p;
+  x.phase = h.phase; x.par = par; x.nout = h.nout; x.nvec = h.nvec; x.nsn = nsn; x.nx = xch_workgroups(h.nout, nsn, h.nvec, s->nf);
+  x.vecs = read_only(h.vecs); x.send_nodes = s->send_nodes.p;
   return x;
 }
 Ctx xch_ctx(gmpnp_group* g, const XchArgs& x) {
@@ -205,7 +222,7 @@ int group_transfer(gmpnp_group* g, size_t per) {
     gmpnp_solver* s = g->dom[0];
     const size_t nb = s->nb_rank.size();
     if (nb) {
-      const size_t ns = (size_t)s->send_ptr.back() * per, nr = (size_t)s->recv_ptr.back() * per;
+      const size_t ns = (size_t)n_send(s) * per, nr = (size_t)n_recv(s) * per;
       if (ns + nr > g->h_stage_n) return fail(GMPNP_ERR_INVALID, "hosted transport: staging buffer too small");
       double* hs = g->h_stage; double* hr = g->h_stage + ns;
       g->off_s.resize(nb); g->cnt_s.resize(nb); g->off_r.resize(nb); g->cnt_r.resize(nb);
@@ -255,26 +272,47 @@ int group_reduce_transfer(gmpnp_group* g, F buf_of, int n, size_t per) {
   return group_transfer(g, per);
 }
 
+inline VecListW one_vec(double* p) { VecListW w{}; w.p[0] = p; return w; }
 template <class F>
 int group_exchange(gmpnp_group* g, int width, int nvec, F vecs_of) {
   for (gmpnp_solver* s : g->dom) {
-    const int nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
+    const int nsn = n_send(s);
     if (nsn == 0) continue;
-    VecListW w = vecs_of(s); VecList src{};
-    for (int v = 0; v < 4; ++v) src.p[v] = w.p[v];
-    hipLaunchKernelGGL(k_halo_pack, dim3(grid_for(nsn * nvec * width, 256)), dim3(256), 0, s->stream, src, nvec, width,
+    hipLaunchKernelGGL(k_halo_pack, dim3(grid_for(nsn * nvec * width, 256)), dim3(256), 0, s->stream, read_only(vecs_of(s)), nvec, width,
                        (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p);
   }
   HIP_TRY(hipGetLastError());
   { int rt = group_transfer(g, (size_t)nvec * width); if (rt) return rt; }
   for (gmpnp_solver* s : g->dom) {
-    const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back();
+    const int nrn = n_recv(s);
     if (nrn == 0) continue;
     hipLaunchKernelGGL(k_halo_unpack, dim3(grid_for(nrn * nvec * width, 256)), dim3(256), 0, s->stream, vecs_of(s), nvec, width,
                        (const int32_t*)s->recv_nodes.p, nrn, (const double*)s->recvbuf.p);
   }
   HIP_TRY(hipGetLastError());
   return GMPNP_OK;
+}
+
+// all-reduces the first n doubles of every handle's red_norm and reads them into dom[0]'s h_red (synchronises the stream)
+int group_sums_to_host(gmpnp_group* g, int n) {
+  int rc = group_allreduce(g, [](gmpnp_solver* s) { return s->red_norm.p; }, n); if (rc) return rc;
+  gmpnp_solver* s0 = g->dom[0];
+  HIP_TRY(hipMemcpyAsync(s0->h_red, s0->red_norm.p, n * sizeof(double), hipMemcpyDeviceToHost, s0->stream));
+  HIP_TRY(hipStreamSynchronize(s0->stream));
+  return peer_check(g);
+}
+
+// (a, b), (a, a), (b, b) over all ranks' owned rows into dom[0]'s h_red; prep(s) launches what comes first on each handle
+template <int NF, class F>
+int group_dots3(gmpnp_group* g, DevBuf<double> gmpnp_solver::*a, DevBuf<double> gmpnp_solver::*b, F prep) {
+  for (gmpnp_solver* s : g->dom) {
+    int rc = prep(s); if (rc) return rc;
+    hipLaunchKernelGGL(k_dots3, dim3(s->n_resblocks), dim3(kVecBlock), 0, s->stream, (const double*)(s->*a).p, (const double*)(s->*b).p, s->c.part_f,
+                       (int)s->ndof, s->n_resblocks, s->t.own_node0 * NF, s->t.own_node1 * NF);
+    hipLaunchKernelGGL(k_dots3_reduce, dim3(1), dim3(256), 0, s->stream, (const double*)s->c.part_f, s->n_resblocks, s->red_norm.p);
+  }
+  HIP_TRY(hipGetLastError());
+  return group_sums_to_host(g, 3);
 }
 
 // ---- residual: ||b||_2 over all ranks' owned rows and the OR of the status bits -----------------------------------------------
@@ -286,11 +324,8 @@ int group_residual(gmpnp_group* g, double* norm, int* flags) {
     hipLaunchKernelGGL(k_norm_reduce, dim3(1), dim3(256), 0, s->stream, (const double*)s->c.part_f, s->n_resblocks,
                        (const int32_t*)s->status.p, s->red_norm.p);
   }
-  int rc = group_allreduce(g, [](gmpnp_solver* s) { return s->red_norm.p; }, 5); if (rc) return rc;
+  int rc = group_sums_to_host(g, 5); if (rc) return rc;
   gmpnp_solver* s0 = g->dom[0];
-  HIP_TRY(hipMemcpyAsync(s0->h_red, s0->red_norm.p, 5 * sizeof(double), hipMemcpyDeviceToHost, s0->stream));
-  HIP_TRY(hipStreamSynchronize(s0->stream));
-  if (g->peer && *g->h_peer_err) return fail(GMPNP_ERR_HIP, "peer transport: a rank's flag did not arrive within 5 s");
   *norm = std::sqrt(s0->h_red[0]);
   int f = 0;
   for (int b = 0; b < 4; ++b) if (s0->h_red[1 + b] > 0.0) f |= 1 << b;
@@ -307,15 +342,13 @@ int group_setup(gmpnp_group* g, int mode, bool rebuild_coarse = true) {
     hipLaunchKernelGGL((k_block_inverse<NF>), dim3(grid_for(s->t.nv, 4)), dim3(64), 0, s->stream, s->c);
   }
   // As = J Dinv needs the owners' inverse blocks at the ghost COLUMNS (the local ghost rows are identity rows)
-  int rc = group_exchange(g, NF * NF, 1, [](gmpnp_solver* s) { VecListW w{}; w.p[0] = s->Dinv.p; return w; }); if (rc) return rc;
+  int rc = group_exchange(g, NF * NF, 1, [](gmpnp_solver* s) { return one_vec(s->Dinv.p); }); if (rc) return rc;
   for (gmpnp_solver* s : g->dom)
     hipLaunchKernelGGL((k_scale_columns<NF>), dim3(grid_for(s->c.n_work * kWave, kVecBlock)), dim3(kVecBlock), 0, s->stream, s->c);
   if (use_coarse && rebuild_coarse) {
     for (gmpnp_solver* s : g->dom) {
       const int n = s->ncoarse;
-      hipLaunchKernelGGL((k_coarse_rows<NF>), dim3(s->t.nslices), dim3(64), 0, s->stream, s->c);
-      hipLaunchKernelGGL((k_coarse_sum<NF>), dim3(s->t.nagg * s->c.coarse_chunks), dim3(kVecBlock), 0, s->stream, s->c);
-      hipLaunchKernelGGL(k_coarse_reduce, dim3(grid_for(n * n, kVecBlock)), dim3(kVecBlock), 0, s->stream, s->c);
+      launch_coarse_galerkin<NF>(s, s->c, s->stream);
       hipLaunchKernelGGL(k_zero_foreign_rows, dim3(grid_for(n * n, 256)), dim3(256), 0, s->stream, s->Ac.p, n, s->t.own_agg0 * NF, s->t.own_agg1 * NF);
     }
     const int n = g->dom[0]->ncoarse;
@@ -346,7 +379,26 @@ struct LevelStreams {   // the coarser levels' launches go to the finest handle'
   ~LevelStreams() { for (auto& k : keep) k.first->stream = k.second; }
 };
 
-inline VecListW one_vec(double* p) { VecListW w{}; w.p[0] = p; return w; }
+// dst = scale_dst * dst + scale_x * M^-1 src on every handle's owned rows, (src, dst, scale_x) = io(s); M^-1 = Dinv (I + P Aci P^T)
+// with the coarse sums all-reduced (`coarse`), Dinv alone otherwise
+template <int NF, class F>
+int group_minv(gmpnp_group* g, bool coarse, double scale_dst, F io) {
+  if (coarse) {
+    for (gmpnp_solver* s : g->dom) {
+      hipLaunchKernelGGL((k_restrict<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c, std::get<0>(io(s)), s->cpart_v0.p);
+      hipLaunchKernelGGL(k_dist_reduce, dim3(s->ncoarse), dim3(256), 0, s->stream, s->c, 3, 0, s->red_i.p);
+    }
+    HIP_TRY(hipGetLastError());
+    int rc = group_allreduce(g, [](gmpnp_solver* s) { return s->red_i.p; }, g->dom[0]->ncoarse); if (rc) return rc;
+  }
+  for (gmpnp_solver* s : g->dom) {
+    const auto [src, dst, scale_x] = io(s);
+    hipLaunchKernelGGL((k_minv_apply<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, src, (const double*)s->cpart_v0.p, dst,
+                       scale_dst, scale_x, NewtonUpdate{nullptr, nullptr, 0.0, 0.0, 0.0}, (const double*)s->red_i.p);
+  }
+  HIP_TRY(hipGetLastError());
+  return GMPNP_OK;
+}
 
 // true Dirichlet flags of a finer level's local dofs (the mask of its restriction), ghost rows from their owners
 template <int NF>
@@ -409,7 +461,6 @@ int pml_restrict(gmpnp_group* Fg, F src_of) {
 // one all-reduce per application of the coarsest level's slab coarse space.
 template <int NF>
 int pml_level_apply(gmpnp_group* L) {
-  const int n = L->dom[0]->ncoarse;
   auto smooth = [&](bool from_r, double scale_dst) -> int {   // ml_w = scale_dst * ml_w + omega * M_L^-1 src, owned rows
     if (L->ml_next) {
       for (gmpnp_solver* s : L->dom) {
@@ -421,18 +472,8 @@ int pml_level_apply(gmpnp_group* L) {
       HIP_TRY(hipGetLastError());
       return GMPNP_OK;
     }
-    for (gmpnp_solver* s : L->dom) {
-      const double* src = from_r ? s->ml_r.p : s->ks.p;
-      hipLaunchKernelGGL((k_restrict<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c, src, s->cpart_v0.p);
-      hipLaunchKernelGGL(k_dist_reduce, dim3(n), dim3(256), 0, s->stream, s->c, 3, 0, s->red_i.p);
-    }
-    HIP_TRY(hipGetLastError());
-    int rc = group_allreduce(L, [](gmpnp_solver* s) { return s->red_i.p; }, n); if (rc) return rc;
-    for (gmpnp_solver* s : L->dom)
-      hipLaunchKernelGGL((k_minv_apply<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, from_r ? (const double*)s->ml_r.p : (const double*)s->ks.p,
-                         (const double*)s->cpart_v0.p, s->ml_w.p, scale_dst, s->ml_omega, NewtonUpdate{nullptr, nullptr, 0.0, 0.0, 0.0}, (const double*)s->red_i.p);
-    HIP_TRY(hipGetLastError());
-    return GMPNP_OK;
+    return group_minv<NF>(L, true, scale_dst, [from_r](gmpnp_solver* s) {
+      return std::make_tuple(from_r ? (const double*)s->ml_r.p : (const double*)s->ks.p, s->ml_w.p, s->ml_omega); });
   };
   auto residual = [&]() -> int {   // ks = ml_r - J_L ml_w on the owned rows (ghost columns of ml_w from their owners)
     int rc = group_exchange(L, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ml_w.p); }); if (rc) return rc;
@@ -486,17 +527,101 @@ int pml_stage(gmpnp_group* g, F vec_of) {
   return group_exchange(g, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ml_z.p); });
 }
 
-// ---- BiCGStab across the ranks: rhs in kr (owned rows; k_res_gather left it there), ||rhs|| = bnorm (global); leaves y in ky ----
+// ---- BiCGStab across the ranks: one half-iteration (H: A = 0, B = 1; half_of says what it all-reduces and sends) per form ----------
+// Over the transport's own collectives, per rank: [coarse kernel + unpacking of the ghost rows the previous half sent], tile kernel,
+// [per-rank sums + packing of the ghost rows to send]; then the all-reduce and the grouped send/recv.  With a multilevel term the
+// tile kernel is the materialised one (launch_half): k_vec_* writes the vector, and the staged operand z = vec + theta D T vec
+// comes out of the V-cycle across the partitioned levels (pml_stage).
+template <int NF, int H>
+int group_half(gmpnp_group* g, int k) {
+  const int par = k & 1;
+  const unsigned cg = std::max(1, g->dom[0]->t.nagg);
+  auto tile_pack = [&](gmpnp_solver* s) {
+    Ctx cc = s->c;
+    if (g->ml_next) {
+      (H == 0 ? cc.stage_a : cc.stage_b) = s->ml_z.p;
+      if (H == 0) hipLaunchKernelGGL((k_bicg_a_mat<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
+      else hipLaunchKernelGGL((k_bicg_b_mat<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
+    } else if (H == 0) hipLaunchKernelGGL((k_bicg_a<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
+    else hipLaunchKernelGGL((k_bicg_b<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
+    const Half out = half_of(s, H, par);
+    const int nsn = n_send(s);
+    hipLaunchKernelGGL(k_dist_reduce_pack, dim3(out.nout + grid_for(nsn * out.nvec * NF, 256)), dim3(256), 0, s->stream, s->c, out.phase, par, out.red,
+                       out.nout, read_only(out.vecs), out.nvec, (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p, NF);
+  };
+  for (gmpnp_solver* s : g->dom) {
+    const Half in = half_of(s, 1 - H, par);
+    const int un = (H == 1 || k > 0) ? n_recv(s) : 0;   // (nothing pending before the first iteration)
+    const dim3 ug(cg + grid_for(un * in.nvec * NF, kCoarseThreads));
+    if (H == 0) hipLaunchKernelGGL((k_coarse_a_unpack<NF>), ug, dim3(kCoarseThreads), 0, s->stream, s->c, k, in.vecs, in.nvec, (const int32_t*)s->recv_nodes.p, un,
+                                   (const double*)s->recvbuf.p);
+    else hipLaunchKernelGGL((k_coarse_b_unpack<NF>), ug, dim3(kCoarseThreads), 0, s->stream, s->c, k, in.vecs, in.nvec, (const int32_t*)s->recv_nodes.p, un,
+                            (const double*)s->recvbuf.p);
+    if (!g->ml_next) tile_pack(s);
+    else if (H == 0) hipLaunchKernelGGL(k_vec_a, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, k);
+    else hipLaunchKernelGGL(k_vec_b, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, k);
+  }
+  if (g->ml_next) {
+    HIP_TRY(hipGetLastError());
+    int rc = pml_stage<NF>(g, [par](gmpnp_solver* s) { return H == 0 ? (const double*)s->c.kp[par] : (const double*)s->ks.p; }); if (rc) return rc;
+    for (gmpnp_solver* s : g->dom) tile_pack(s);
+  }
+  const Half out = half_of(g->dom[0], H, par);
+  return group_reduce_transfer(g, [par](gmpnp_solver* s) { return half_of(s, H, par).red; }, out.nout, (size_t)out.nvec * NF);
+}
+
+// Peer transport, separate launches: coarse kernel and tile kernel (one launch where the coarse workgroups ride in front of the
+// tile workgroups), then ONE k_dist_reduce_exchange: the sums, the ghost rows and their exchange; the received rows are in place and
+// the sums all-reduced when it ends.  No library call.
+template <int NF, int H>
+int peer_half(gmpnp_group* g, int k) {
+  gmpnp_solver* s = g->dom[0];
+  const int par = k & 1, nsn = n_send(s);
+  const dim3 cg(std::max(1, s->t.nagg)), fg(s->t.nagg + s->t.own_ntiles);
+  if (s->fused_half) {
+    if (H == 0) hipLaunchKernelGGL((k_half_a<NF>), fg, dim3(kKrylovThreads), 0, s->stream, s->c, k, (unsigned)(++s->fused_seq));
+    else hipLaunchKernelGGL((k_half_b<NF>), fg, dim3(kKrylovThreads), 0, s->stream, s->c, k, (unsigned)(++s->fused_seq));
+  } else if (H == 0) {
+    hipLaunchKernelGGL((k_coarse_a<NF>), cg, dim3(kCoarseThreads), 0, s->stream, s->c, k);
+    hipLaunchKernelGGL((k_bicg_a<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, k);
+  } else {
+    hipLaunchKernelGGL((k_coarse_b<NF>), cg, dim3(kCoarseThreads), 0, s->stream, s->c, k);
+    hipLaunchKernelGGL((k_bicg_b<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, k);
+  }
+  const Half out = half_of(s, H, par);
+  g->pa.seq++;
+  hipLaunchKernelGGL(k_dist_reduce_exchange, dim3(out.nout + grid_for(nsn * out.nvec * NF, 256)), dim3(256), 0, s->stream, s->c, out.phase, par, out.red,
+                     out.nout, out.vecs, out.nvec, NF, (const int32_t*)s->send_nodes.p, nsn, (const int32_t*)s->recv_nodes.p, g->pa, g->peer_counter);
+  return GMPNP_OK;
+}
+
+// Peer transport, flagged words: ONE launch per half-iteration, the exchange of the previous half's sums and boundary rows riding in
+// front of its coarse workgroups (gmpnp_dist_kernels.h, "exchange as the prologue").  A(0) needs nothing exchanged (the start-up
+// collectives did it).
+template <int NF, int H>
+int peer_half_x(gmpnp_group* g, int k) {
+  gmpnp_solver* s = g->dom[0];
+  const unsigned fg = s->t.nagg + s->t.own_ntiles;
+  if (H == 0 && k == 0) {
+    hipLaunchKernelGGL((k_half_a<NF>), dim3(fg), dim3(kKrylovThreads), 0, s->stream, s->c, k, (unsigned)(++s->fused_seq));
+    return GMPNP_OK;
+  }
+  const XchArgs x = make_xch_args(g, half_of(s, 1 - H, k & 1), k & 1, n_send(s));
+  const Ctx cc = xch_ctx(g, x);
+  if (H == 0) hipLaunchKernelGGL((k_half_a_x<NF>), dim3(x.nx + fg), dim3(kKrylovThreads), 0, s->stream, cc, k, (unsigned)(++s->fused_seq), x);
+  else hipLaunchKernelGGL((k_half_b_x<NF>), dim3(x.nx + fg), dim3(kKrylovThreads), 0, s->stream, cc, k, (unsigned)(++s->fused_seq), x);
+  return GMPNP_OK;
+}
+
+// rhs in kr (owned rows; k_res_gather left it there), ||rhs|| = bnorm (global); leaves y in ky.  Nothing of the loop runs on the host
+// except the launches; the host reads the device's verdict once per burst.
 // random_shadow: the shadow vector of this pass is each handle's krand (filled by the caller) and (rhat, r_0) = shadow_rho0
 template <int NF>
 int group_krylov(gmpnp_group* g, int mode, double bnorm, double rtol, double atol, int maxit, gmpnp_linear_stats_t* st, bool sized_by_previous = true,
                  bool random_shadow = false, double shadow_rho0 = 0.0, int predicted = 0) {
   const int use_coarse = (mode == GMPNP_LINEAR_BICGSTAB_TWOLEVEL) ? 1 : 0;
   const int n = g->dom[0]->ncoarse;
-  KrylovScalars init{};
-  init.rho[0] = init.rho[1] = random_shadow ? shadow_rho0 : bnorm * bnorm; init.alpha = 1.0;
-  init.tol = std::max(rtol * bnorm, atol); init.rr = bnorm * bnorm; init.max_iters = maxit; init.rr0 = bnorm * bnorm;
-  if (!(bnorm > 0.0)) init.done = 1;
+  const KrylovScalars init = krylov_start(random_shadow ? shadow_rho0 : bnorm * bnorm, bnorm, rtol, atol, maxit);
   for (gmpnp_solver* s : g->dom) {
     s->c.use_coarse = use_coarse;
     hipLaunchKernelGGL((k_krylov_init<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c,
@@ -506,141 +631,15 @@ int group_krylov(gmpnp_group* g, int mode, double bnorm, double rtol, double ato
   HIP_TRY(hipGetLastError());
   int rc;
   if (use_coarse) { rc = group_allreduce(g, [](gmpnp_solver* s) { return s->red_i.p; }, n); if (rc) return rc; }
-  rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { VecListW w{}; w.p[0] = s->kr.p; return w; }); if (rc) return rc;   // p_0 = r_0 at the ghost columns
-  const dim3 cg(std::max(1, g->dom[0]->t.nagg));
-  const dim3 cg_peer = cg;
+  rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { return one_vec(s->kr.p); }); if (rc) return rc;   // p_0 = r_0 at the ghost columns
+  const bool flagged = flagged_words(g);
   KrylovScalars res = init;
   int k = 0;
-  // Per half-iteration and rank THREE launches: [coarse kernel + unpacking of the ghost rows received last], tile kernel,
-  // [per-rank sums + packing of the ghost rows to send]; then the all-reduce and the grouped send/recv.
-  // Peer transport: the sums, the ghost rows and their exchange are ONE launch per half-iteration (k_dist_reduce_exchange), the
-  // received rows are in place when it ends: coarse kernel, tile kernel, exchange — 6 launches per iteration (4 where the coarse workgroups ride inside the tile launch), no library call.
-  auto iteration_peer = [&]() -> int {
-    const int par = k & 1;
-    gmpnp_solver* s = g->dom[0];
-    if (!g->peer_connected) return fail(GMPNP_ERR_INVALID, "peer transport: gmpnp_group_peer_connect has not been called");
-    if (*g->h_peer_err) return fail(GMPNP_ERR_HIP, "peer transport: a rank's flag did not arrive within 5 s");
-    const int nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
-    // (the received rows are in place and the sums all-reduced when the previous launch ends, so the coarse workgroups can
-    // ride in front of the tile workgroups as on one GPU wherever the whole launch is resident: 4 launches per iteration)
-    const dim3 fg(s->t.nagg + s->t.own_ntiles);
-    if (s->fused_half && g->prologue_ok && g->exchange_form != 1) {
-      // TWO launches per iteration: the exchange of a launch's sums and boundary rows rides in front of the NEXT launch's coarse
-      // workgroups (gmpnp_dist_kernels.h, "exchange as the prologue").  A(0) needs nothing exchanged (the start-up collectives did it).
-      auto xargs = [&](int phase, int nout, const VecList& v, int nvec) { XchArgs x = make_xch_args(g, phase, par, nout, v, nvec); x.nsn = nsn; x.nx = xch_workgroups(nout, nsn, nvec, NF); return x; };
-      auto xctx = [&](const XchArgs& x) { return xch_ctx(g, x); };
-      if (k == 0) hipLaunchKernelGGL((k_half_a<NF>), fg, dim3(kKrylovThreads), 0, s->stream, s->c, k, (unsigned)(++s->fused_seq));
-      else {   // prologue: what B(k-1) left (sums of phase 2, rows of s and t)
-        VecList vb{}; vb.p[0] = s->ks.p; vb.p[1] = s->kt.p;
-        const XchArgs x = xargs(2, 4 + n, vb, 2);
-        const Ctx cc = xctx(x);
-        hipLaunchKernelGGL((k_half_a_x<NF>), dim3(x.nx + fg.x), dim3(kKrylovThreads), 0, s->stream, cc, k, (unsigned)(++s->fused_seq), x);
-      }
-      {        // prologue: what A(k) left (sums of phase 1, rows of r, v, p)
-        VecList va{}; va.p[0] = s->kr.p; va.p[1] = s->c.kv[par]; va.p[2] = s->c.kp[par];
-        const XchArgs x = xargs(1, 2 + 3 * n, va, 3);
-        const Ctx cc = xctx(x);
-        hipLaunchKernelGGL((k_half_b_x<NF>), dim3(x.nx + fg.x), dim3(kKrylovThreads), 0, s->stream, cc, k, (unsigned)(++s->fused_seq), x);
-      }
-      ++k;
-      HIP_TRY(hipGetLastError());
-      return GMPNP_OK;
-    }
-    if (s->fused_half) hipLaunchKernelGGL((k_half_a<NF>), fg, dim3(kKrylovThreads), 0, s->stream, s->c, k, (unsigned)(++s->fused_seq));
-    else {
-      hipLaunchKernelGGL((k_coarse_a<NF>), cg_peer, dim3(kCoarseThreads), 0, s->stream, s->c, k);
-      hipLaunchKernelGGL((k_bicg_a<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, k);
-    }
-    VecListW va{}; va.p[0] = s->kr.p; va.p[1] = s->c.kv[par]; va.p[2] = s->c.kp[par];
-    g->pa.seq++;
-    hipLaunchKernelGGL(k_dist_reduce_exchange, dim3(2 + 3 * n + grid_for(nsn * 3 * NF, 256)), dim3(256), 0, s->stream, s->c, 1, par, s->red_a.p, 2 + 3 * n,
-                       va, 3, NF, (const int32_t*)s->send_nodes.p, nsn, (const int32_t*)s->recv_nodes.p, g->pa, g->peer_counter);
-    if (s->fused_half) hipLaunchKernelGGL((k_half_b<NF>), fg, dim3(kKrylovThreads), 0, s->stream, s->c, k, (unsigned)(++s->fused_seq));
-    else {
-      hipLaunchKernelGGL((k_coarse_b<NF>), cg_peer, dim3(kCoarseThreads), 0, s->stream, s->c, k);
-      hipLaunchKernelGGL((k_bicg_b<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, k);
-    }
-    VecListW vb{}; vb.p[0] = s->ks.p; vb.p[1] = s->kt.p;
-    g->pa.seq++;
-    hipLaunchKernelGGL(k_dist_reduce_exchange, dim3(4 + n + grid_for(nsn * 2 * NF, 256)), dim3(256), 0, s->stream, s->c, 2, par, s->red_b.p, 4 + n,
-                       vb, 2, NF, (const int32_t*)s->send_nodes.p, nsn, (const int32_t*)s->recv_nodes.p, g->pa, g->peer_counter);
-    ++k;
-    HIP_TRY(hipGetLastError());
-    return GMPNP_OK;
-  };
-  // With a multilevel term: the materialised vector form (launch_half), the staged operand z = vec + theta D T vec of every half-
-  // iteration coming out of the V-cycle across the partitioned levels (pml_stage); the sums, the packing and the collectives behind
-  // the tile kernel are those of the form below.
-  auto iteration_ml = [&]() -> int {
-    const int par = k & 1;
-    for (gmpnp_solver* s : g->dom) {
-      const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back();
-      VecListW ub{}; ub.p[0] = s->ks.p; ub.p[1] = s->kt.p;
-      const int un = k > 0 ? nrn : 0;
-      hipLaunchKernelGGL((k_coarse_a_unpack<NF>), dim3(cg.x + grid_for(un * 2 * NF, kCoarseThreads)), dim3(kCoarseThreads), 0, s->stream, s->c, k, ub, 2,
-                         (const int32_t*)s->recv_nodes.p, un, (const double*)s->recvbuf.p);
-      hipLaunchKernelGGL(k_vec_a, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, k);
-    }
-    HIP_TRY(hipGetLastError());
-    int r = pml_stage<NF>(g, [par](gmpnp_solver* s) { return (const double*)s->c.kp[par]; }); if (r) return r;
-    for (gmpnp_solver* s : g->dom) {
-      const int nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
-      Ctx cc = s->c; cc.stage_a = s->ml_z.p;
-      hipLaunchKernelGGL((k_bicg_a_mat<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
-      VecList pa{}; pa.p[0] = s->kr.p; pa.p[1] = s->c.kv[par]; pa.p[2] = s->c.kp[par];
-      hipLaunchKernelGGL(k_dist_reduce_pack, dim3(2 + 3 * n + grid_for(nsn * 3 * NF, 256)), dim3(256), 0, s->stream, s->c, 1, par, s->red_a.p, 2 + 3 * n, pa, 3,
-                         (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p, NF);
-    }
-    r = group_reduce_transfer(g, [](gmpnp_solver* s) { return s->red_a.p; }, 2 + 3 * n, (size_t)3 * NF); if (r) return r;
-    for (gmpnp_solver* s : g->dom) {
-      const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back();
-      VecListW ua{}; ua.p[0] = s->kr.p; ua.p[1] = s->c.kv[par]; ua.p[2] = s->c.kp[par];
-      hipLaunchKernelGGL((k_coarse_b_unpack<NF>), dim3(cg.x + grid_for(nrn * 3 * NF, kCoarseThreads)), dim3(kCoarseThreads), 0, s->stream, s->c, k, ua, 3,
-                         (const int32_t*)s->recv_nodes.p, nrn, (const double*)s->recvbuf.p);
-      hipLaunchKernelGGL(k_vec_b, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, k);
-    }
-    HIP_TRY(hipGetLastError());
-    r = pml_stage<NF>(g, [](gmpnp_solver* s) { return (const double*)s->ks.p; }); if (r) return r;
-    for (gmpnp_solver* s : g->dom) {
-      const int nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
-      Ctx cc = s->c; cc.stage_b = s->ml_z.p;
-      hipLaunchKernelGGL((k_bicg_b_mat<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, cc, k);
-      VecList pb{}; pb.p[0] = s->ks.p; pb.p[1] = s->kt.p;
-      hipLaunchKernelGGL(k_dist_reduce_pack, dim3(4 + n + grid_for(nsn * 2 * NF, 256)), dim3(256), 0, s->stream, s->c, 2, par, s->red_b.p, 4 + n, pb, 2,
-                         (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p, NF);
-    }
-    r = group_reduce_transfer(g, [](gmpnp_solver* s) { return s->red_b.p; }, 4 + n, (size_t)2 * NF); if (r) return r;
-    ++k;
-    HIP_TRY(hipGetLastError());
-    return GMPNP_OK;
-  };
   auto iteration = [&]() -> int {
-    if (g->peer) return iteration_peer();
-    if (g->ml_next) return iteration_ml();
-    const int par = k & 1;
-    for (gmpnp_solver* s : g->dom) {
-      const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back(), nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
-      VecListW ub{}; ub.p[0] = s->ks.p; ub.p[1] = s->kt.p;    // what B(k-1) sent (nothing pending before the first iteration)
-      const int un = k > 0 ? nrn : 0;
-      hipLaunchKernelGGL((k_coarse_a_unpack<NF>), dim3(cg.x + grid_for(un * 2 * NF, kCoarseThreads)), dim3(kCoarseThreads), 0, s->stream, s->c, k, ub, 2,
-                         (const int32_t*)s->recv_nodes.p, un, (const double*)s->recvbuf.p);
-      hipLaunchKernelGGL((k_bicg_a<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, k);
-      VecList pa{}; pa.p[0] = s->kr.p; pa.p[1] = s->c.kv[par]; pa.p[2] = s->c.kp[par];
-      hipLaunchKernelGGL(k_dist_reduce_pack, dim3(2 + 3 * n + grid_for(nsn * 3 * NF, 256)), dim3(256), 0, s->stream, s->c, 1, par, s->red_a.p, 2 + 3 * n, pa, 3,
-                         (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p, NF);
-    }
-    int r = group_reduce_transfer(g, [](gmpnp_solver* s) { return s->red_a.p; }, 2 + 3 * n, (size_t)3 * NF); if (r) return r;
-    for (gmpnp_solver* s : g->dom) {
-      const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back(), nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
-      VecListW ua{}; ua.p[0] = s->kr.p; ua.p[1] = s->c.kv[par]; ua.p[2] = s->c.kp[par];
-      hipLaunchKernelGGL((k_coarse_b_unpack<NF>), dim3(cg.x + grid_for(nrn * 3 * NF, kCoarseThreads)), dim3(kCoarseThreads), 0, s->stream, s->c, k, ua, 3,
-                         (const int32_t*)s->recv_nodes.p, nrn, (const double*)s->recvbuf.p);
-      hipLaunchKernelGGL((k_bicg_b<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, k);
-      VecList pb{}; pb.p[0] = s->ks.p; pb.p[1] = s->kt.p;
-      hipLaunchKernelGGL(k_dist_reduce_pack, dim3(4 + n + grid_for(nsn * 2 * NF, 256)), dim3(256), 0, s->stream, s->c, 2, par, s->red_b.p, 4 + n, pb, 2,
-                         (const int32_t*)s->send_nodes.p, nsn, s->sendbuf.p, NF);
-    }
-    r = group_reduce_transfer(g, [](gmpnp_solver* s) { return s->red_b.p; }, 4 + n, (size_t)2 * NF); if (r) return r;
+    int r = peer_check(g);
+    if (!r) r = flagged ? peer_half_x<NF, 0>(g, k) : g->peer ? peer_half<NF, 0>(g, k) : group_half<NF, 0>(g, k);
+    if (!r) r = flagged ? peer_half_x<NF, 1>(g, k) : g->peer ? peer_half<NF, 1>(g, k) : group_half<NF, 1>(g, k);
+    if (r) return r;
     ++k;
     HIP_TRY(hipGetLastError());
     return GMPNP_OK;
@@ -655,7 +654,7 @@ int group_krylov(gmpnp_group* g, int mode, double bnorm, double rtol, double ato
       for (int it = 0; it < burst; ++it) { rc = iteration(); if (rc) return rc; }
       HIP_TRY(hipMemcpyAsync(&s0->h_scal[0], s0->scal.p, sizeof(KrylovScalars), hipMemcpyDeviceToHost, s0->stream));
       for (gmpnp_solver* s : g->dom) HIP_TRY(hipStreamSynchronize(s->stream));
-      if (g->peer && *g->h_peer_err) return fail(GMPNP_ERR_HIP, "peer transport: a rank's flag did not arrive within 5 s");
+      rc = peer_check(g); if (rc) return rc;
       res = s0->h_scal[0];
       if (res.done) break;
       if (k > maxit + 8) break;
@@ -664,34 +663,17 @@ int group_krylov(gmpnp_group* g, int mode, double bnorm, double rtol, double ato
   }
   g->last_iters = res.iters;
   for (gmpnp_solver* s : g->dom) s->last_done = res.done;
-  if (st) { st->iterations = res.iters; st->converged = (res.done == 1); st->residual_norm = std::sqrt(res.rr); st->rhs_norm = bnorm; }
-  if (res.done != 1) {
-    char buf[200];
-    snprintf(buf, sizeof buf, "partitioned BiCGStab stopped without convergence (code %d) after %d iterations, ||r|| = %.3e, ||b|| = %.3e",
-             res.done, res.iters, std::sqrt(res.rr), bnorm);
-    return fail(GMPNP_ERR_LINEAR, buf);
-  }
-  return GMPNP_OK;
+  return krylov_verdict(res, bnorm, st, "partitioned BiCGStab");
 }
 
 // x = Dinv (I + P Aci P^T) y on the owned rows, ghost rows from their owners, then u -= omega x on every local row
 template <int NF>
 int group_update(gmpnp_group* g, int mode, double omega, bool add_to_start) {
-  const int use_coarse = (mode == GMPNP_LINEAR_BICGSTAB_TWOLEVEL) ? 1 : 0;
-  const int n = g->dom[0]->ncoarse;
-  if (use_coarse) {
-    for (gmpnp_solver* s : g->dom) {
-      hipLaunchKernelGGL((k_restrict<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c, (const double*)s->ky.p, s->cpart_v0.p);
-      hipLaunchKernelGGL(k_dist_reduce, dim3(n), dim3(256), 0, s->stream, s->c, 3, 0, s->red_i.p);
-    }
-    int rc = group_allreduce(g, [](gmpnp_solver* s) { return s->red_i.p; }, n); if (rc) return rc;
-  }
-  for (gmpnp_solver* s : g->dom)
-    hipLaunchKernelGGL((k_minv_apply<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->ky.p,
-                       (const double*)s->cpart_v0.p, s->kx.p, add_to_start ? 1.0 : 0.0, 1.0, NewtonUpdate{nullptr, nullptr, 0.0, 0.0, 0.0},
-                       (const double*)s->red_i.p);
+  int rc = group_minv<NF>(g, mode == GMPNP_LINEAR_BICGSTAB_TWOLEVEL, add_to_start ? 1.0 : 0.0,
+                          [](gmpnp_solver* s) { return std::make_tuple((const double*)s->ky.p, s->kx.p, 1.0); });
+  if (rc) return rc;
   if (g->ml_next) {   // x += theta T y on the owned rows (the multilevel term of M^-1 applied to the Krylov solution), as the serial solve does
-    int rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ky.p); }); if (rc) return rc;
+    rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { return one_vec(s->ky.p); }); if (rc) return rc;
     rc = pml_correction<NF>(g, [](gmpnp_solver* s) { return (const double*)s->ky.p; }); if (rc) return rc;
     for (size_t d = 0; d < g->dom.size(); ++d) {
       gmpnp_solver* s = g->dom[d];
@@ -699,7 +681,7 @@ int group_update(gmpnp_group* g, int mode, double omega, bool add_to_start) {
                          (const int32_t*)s->ml_par.p, s->kx.p, s->ml_theta);
     }
   }
-  int rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { VecListW w{}; w.p[0] = s->kx.p; return w; }); if (rc) return rc;
+  rc = group_exchange(g, NF, 1, [](gmpnp_solver* s) { return one_vec(s->kx.p); }); if (rc) return rc;
   for (gmpnp_solver* s : g->dom)
     hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, (const double*)s->kx.p, -omega, (int)s->ndof);
   HIP_TRY(hipGetLastError());
@@ -738,19 +720,14 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
     bool warm = false; double rstart = r;
     if (g->dom[0]->warm_start && st.iterations > 0 && q != 0.0 && r > 0.0) {
       const double wa = (g->dom[0]->warm_start > 1 && st.iterations > 1) ? q + q * q : q, wb = (g->dom[0]->warm_start > 1 && st.iterations > 1) ? -q * q * q : 0.0;
-      for (gmpnp_solver* s : g->dom) {
-        const int n = s->ndof;
-        hipLaunchKernelGGL(k_warm_start, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, wa, wb, n);
+      rc = group_dots3<NF>(g, &gmpnp_solver::kt, &gmpnp_solver::kb, [&](gmpnp_solver* s) -> int {
+        hipLaunchKernelGGL(k_warm_start, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, wa, wb, (int)s->ndof);
         hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->kx.p, s->kt.p);
-        hipLaunchKernelGGL(k_dots3, dim3(s->n_resblocks), dim3(kVecBlock), 0, s->stream, (const double*)s->kt.p, (const double*)s->kb.p, s->c.part_f, n,
-                           s->n_resblocks, s->t.own_node0 * NF, s->t.own_node1 * NF);
-        hipLaunchKernelGGL(k_dots3_reduce, dim3(1), dim3(256), 0, s->stream, (const double*)s->c.part_f, s->n_resblocks, s->red_norm.p);
-      }
-      rc = group_allreduce(g, [](gmpnp_solver* s) { return s->red_norm.p; }, 3); if (rc) return rc;
-      gmpnp_solver* s0 = g->dom[0];
-      HIP_TRY(hipMemcpyAsync(s0->h_red, s0->red_norm.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s0->stream));
-      HIP_TRY(hipStreamSynchronize(s0->stream));
-      const double wbd = s0->h_red[0], ww = s0->h_red[1], bb = s0->h_red[2], rn2 = bb - 2.0 * wbd + ww;
+        return GMPNP_OK;
+      });
+      if (rc) return rc;
+      const double* h = g->dom[0]->h_red;
+      const double wbd = h[0], ww = h[1], bb = h[2], rn2 = bb - 2.0 * wbd + ww;
       if (rn2 == rn2 && rn2 >= 0.0 && rn2 < 0.25 * bb) {
         for (gmpnp_solver* s : g->dom)
           hipLaunchKernelGGL(k_start_residual, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p, (const double*)s->kt.p, (int)s->ndof);
@@ -773,7 +750,7 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
         kry_total += ls.iterations;
         if (rc != GMPNP_ERR_LINEAR || attempt >= 4 || g->dom[0]->last_done != 3) break;
         if (warm && attempt >= 1) { warm = false; rstart = r; }
-        for (gmpnp_solver* s : g->dom) {
+        const int r2 = group_dots3<NF>(g, &gmpnp_solver::krand, &gmpnp_solver::kr, [&](gmpnp_solver* s) -> int {
           const int nd = s->ndof;
           HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
           if (warm) {   // kr = b - J x0 again (kt was a work vector of the lost pass)
@@ -781,16 +758,10 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
             hipLaunchKernelGGL(k_start_residual, dim3(grid_for(nd, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p, (const double*)s->kt.p, nd);
           } else HIP_TRY(hipMemcpyAsync(s->kr.p, s->kb.p, nd * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
           hipLaunchKernelGGL(k_fill_hash, dim3(grid_for(nd, 256)), dim3(256), 0, s->stream, s->krand.p, (unsigned)((attempt + 1) * 2654435761u), nd);
-          hipLaunchKernelGGL(k_dots3, dim3(s->n_resblocks), dim3(kVecBlock), 0, s->stream, (const double*)s->krand.p, (const double*)s->kr.p, s->c.part_f, nd,
-                             s->n_resblocks, s->t.own_node0 * NF, s->t.own_node1 * NF);
-          hipLaunchKernelGGL(k_dots3_reduce, dim3(1), dim3(256), 0, s->stream, (const double*)s->c.part_f, s->n_resblocks, s->red_norm.p);
-        }
-        HIP_TRY(hipGetLastError());
-        { int r2 = group_allreduce(g, [](gmpnp_solver* s) { return s->red_norm.p; }, 3); if (r2) return r2; }
-        gmpnp_solver* s0 = g->dom[0];
-        HIP_TRY(hipMemcpyAsync(s0->h_red, s0->red_norm.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s0->stream));
-        HIP_TRY(hipStreamSynchronize(s0->stream));
-        rho0 = s0->h_red[0]; random_shadow = true;   // (rhat, r_0) of the new shadow vector, over all ranks' owned rows
+          return GMPNP_OK;
+        });
+        if (r2) return r2;
+        rho0 = g->dom[0]->h_red[0]; random_shadow = true;   // (rhat, r_0) of the new shadow vector, over all ranks' owned rows
       }
       ls.iterations = kry_total;
     }
@@ -976,7 +947,7 @@ int gmpnp_group_peer_begin(gmpnp_solver* handle, gmpnp_group** out, char ipc_han
   a.n_nb = (int)handle->nb_rank.size();
   for (int j = 0; j < a.n_nb; ++j) a.nb_rank[j] = handle->nb_rank[j];
   for (int j = 0; j <= a.n_nb; ++j) { a.send_ptr[j] = handle->send_ptr[j]; a.recv_ptr[j] = handle->recv_ptr[j]; }
-  g->box_bytes = a.halo_off + (size_t)2 * std::max(1, handle->recv_ptr.back()) * a.wmax * sizeof(double);
+  g->box_bytes = a.halo_off + (size_t)2 * std::max(1, n_recv(handle)) * a.wmax * sizeof(double);
   // uncached: a peer's stores (and this rank's polls of them) must not meet a stale line in this GPU's L2
   HIP_TRY(hipExtMallocWithFlags((void**)&g->box, g->box_bytes, hipDeviceMallocUncached));
   HIP_TRY(hipMemset(g->box, 0, g->box_bytes));
@@ -993,9 +964,10 @@ int gmpnp_group_peer_begin(gmpnp_solver* handle, gmpnp_group** out, char ipc_han
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_a, k_half_a_x<9>, kKrylovThreads, 0));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_b, k_half_b_x<9>, kKrylovThreads, 0));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, handle->opts.device_id));
-    const int nsn = handle->send_ptr.empty() ? 0 : handle->send_ptr.back();
-    const int nx = std::max(xch_workgroups(2 + 3 * (int)n, nsn, 3, 9), xch_workgroups(4 + (int)n, nsn, 2, 9));
-    g->prologue_ok = handle->t.own_ntiles + handle->t.nagg + nx <= std::min(occ_a, occ_b) * cus && handle->recv_ptr.back() <= kLLHaloNodes;
+    const int nsn = n_send(handle);
+    const Half ha = half_of(handle, 0, 0), hb = half_of(handle, 1, 0);
+    const int nx = std::max(xch_workgroups(ha.nout, nsn, ha.nvec, 9), xch_workgroups(hb.nout, nsn, hb.nvec, 9));
+    g->prologue_ok = handle->t.own_ntiles + handle->t.nagg + nx <= std::min(occ_a, occ_b) * cus && n_recv(handle) <= kLLHaloNodes;
   }
   HIP_TRY(hipHostMalloc((void**)&g->h_peer_err, sizeof(int32_t)));
   *g->h_peer_err = 0;
@@ -1101,7 +1073,7 @@ int gmpnp_group_selftest(gmpnp_group* g, double* max_error) {
     double red[5];
     for (int i = 0; i < 5; ++i) red[i] = (double)(s->part_rank + 1) * (i + 1);
     HIP_TRY(hipMemcpyAsync(s->red_norm.p, red, sizeof red, hipMemcpyHostToDevice, s->stream));
-    const int nsn = s->send_ptr.empty() ? 0 : s->send_ptr.back();
+    const int nsn = n_send(s);
     std::vector<double> h((size_t)std::max(nsn, 1));
     for (size_t j = 0; j < s->nb_rank.size(); ++j)
       for (int k = s->send_ptr[j]; k < s->send_ptr[j + 1]; ++k) h[k] = 1e6 * s->part_rank + (k - s->send_ptr[j]);
@@ -1114,7 +1086,7 @@ int gmpnp_group_selftest(gmpnp_group* g, double* max_error) {
     // in-process groups run every handle on dom[0]'s stream
     double red[5];
     HIP_TRY(hipMemcpyAsync(red, s->red_norm.p, sizeof red, hipMemcpyDeviceToHost, g->dom[0]->stream));
-    const int nrn = s->recv_ptr.empty() ? 0 : s->recv_ptr.back();
+    const int nrn = n_recv(s);
     std::vector<double> h((size_t)std::max(nrn, 1), 0.0);
     if (nrn) HIP_TRY(hipMemcpyAsync(h.data(), s->recvbuf.p, (size_t)nrn * sizeof(double), hipMemcpyDeviceToHost, g->dom[0]->stream));
     HIP_TRY(hipStreamSynchronize(g->dom[0]->stream));
@@ -1122,11 +1094,11 @@ int gmpnp_group_selftest(gmpnp_group* g, double* max_error) {
     for (size_t j = 0; j < s->nb_rank.size(); ++j)
       for (int k = s->recv_ptr[j]; k < s->recv_ptr[j + 1]; ++k) err = std::max(err, std::fabs(h[k] - (1e6 * s->nb_rank[j] + (k - s->recv_ptr[j]))));
   }
-  if (g->peer && *g->h_peer_err) return fail(GMPNP_ERR_HIP, "peer transport: a rank's flag did not arrive within 5 s");
-  if (g->peer && g->prologue_ok && g->exchange_form != 1 && g->dom[0]->fused_half) {
+  rc = peer_check(g); if (rc) return rc;
+  if (flagged_words(g)) {
     // ... and the flagged-word areas the exchange-prologue launches of a solve use (k_xch_selftest), over the same mapping
     gmpnp_solver* s = g->dom[0];
-    XchArgs x = make_xch_args(g, 0, 0, 0, VecList{}, 0);
+    XchArgs x = make_xch_args(g, Half{}, 0, 0);
     Ctx cc = xch_ctx(g, x);
     HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
     hipLaunchKernelGGL(k_xch_selftest, dim3(1), dim3(kKrylovThreads), 0, s->stream, cc, x, g->pa, s->red_norm.p);
@@ -1150,7 +1122,7 @@ int gmpnp_group_set_exchange_form(gmpnp_group* g, int32_t form) {
 }
 int32_t gmpnp_group_exchange_form(const gmpnp_group* g) {
   if (!g) return -1;
-  return (g->peer && g->prologue_ok && g->exchange_form != 1 && g->dom[0]->fused_half) ? 2 : (g->peer ? 1 : 0);
+  return flagged_words(g) ? 2 : (g->peer ? 1 : 0);
 }
 
 int gmpnp_group_assign_previous(gmpnp_group* g) {
