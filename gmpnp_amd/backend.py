@@ -32,7 +32,7 @@ EXPORTS = [
     "gmpnp_create_partition", "gmpnp_comm_unique_id", "gmpnp_comm_create", "gmpnp_comm_selftest", "gmpnp_comm_destroy", "gmpnp_group_create", "gmpnp_group_create_hosted",
     "gmpnp_group_peer_begin", "gmpnp_group_peer_connect",
     "gmpnp_group_destroy", "gmpnp_group_newton_solve", "gmpnp_group_assign_previous", "gmpnp_group_selftest", "gmpnp_group_set_exchange_form", "gmpnp_group_exchange_form", "gmpnp_attach_coarse_level", "gmpnp_group_attach_coarse_group",
-    "gmpnp_project_gradient", "gmpnp_project_cellwise",
+    "gmpnp_project_gradient", "gmpnp_project_cellwise", "gmpnp_column_select", "gmpnp_group_column_select",
     "gmpnp_ensemble_create", "gmpnp_ensemble_destroy", "gmpnp_ensemble_size", "gmpnp_ensemble_newton_solve",
     "gmpnp_ensemble_member_error", "gmpnp_ensemble_assign_previous", "gmpnp_ensemble_get_state",
 ]
@@ -169,6 +169,8 @@ def load_library(path: str = None):
     lib.gmpnp_group_attach_coarse_group.argtypes = [c_void_p, c_void_p]
     lib.gmpnp_project_gradient.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(CLinearStats)]
     lib.gmpnp_project_cellwise.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double), POINTER(CLinearStats)]
+    for name in ("gmpnp_column_select", "gmpnp_group_column_select"):
+        getattr(lib, name).argtypes = [c_void_p, c_int32, POINTER(c_int32), POINTER(c_int64), POINTER(c_double), POINTER(c_int32)]
     lib.gmpnp_ensemble_create.argtypes = [c_int32, POINTER(c_void_p), POINTER(c_void_p)]
     lib.gmpnp_ensemble_destroy.argtypes = [c_void_p]
     lib.gmpnp_ensemble_destroy.restype = None
@@ -472,6 +474,12 @@ class DeviceSolver:
         self._check(self.lib.gmpnp_project_cellwise(self._h, ncomp, _dptr(v), _dptr(out), byref(st)))
         return out[:, 0] if v.ndim == 1 else out
 
+    def column_select(self, fields, ranks):
+        """k-th smallest values of vertex columns of u over this handle's owned rows (gmpnp_column_select): ``fields[j]``,
+        ``ranks[j]`` -> (values (n,), nan) with values[j] == np.sort(column fields[j])[ranks[j]] and ``nan`` = some selected column
+        holds a NaN (its value is then undefined)."""
+        return column_select_call(self.lib.gmpnp_column_select, self._h, fields, ranks, self._check)
+
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""
         if rho is None:
@@ -524,6 +532,18 @@ class DeviceSolver:
 
 
 MAX_ENSEMBLE = 64   # gmpnp_ensemble_create refuses more members
+
+
+def column_select_call(fn, handle, fields, ranks, check):
+    """One gmpnp_column_select / gmpnp_group_column_select call: (values, nan flag)."""
+    f = np.ascontiguousarray(fields, dtype=np.int32).ravel()
+    r = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+    if f.shape != r.shape:
+        raise ValueError("fields and ranks differ in length")
+    out = np.empty(f.size)
+    flags = c_int32(0)
+    check(fn(handle, f.size, _iptr(f), r.ctypes.data_as(POINTER(c_int64)), _dptr(out), byref(flags)))
+    return out, bool(flags.value & 1)
 
 
 class DeviceEnsemble:

@@ -68,6 +68,15 @@ struct gmpnp_projector {
   ~gmpnp_projector() { if (h_part) (void)hipHostFree(h_part); }
 };
 
+// device side of gmpnp_column_select / gmpnp_group_column_select (gmpnp_stats.h), allocated on first use
+struct gmpnp_selector {
+  DevBuf<double> cnt;                   // [n][256] bucket counts + [n] NaN counts: what the group all-reduces
+  DevBuf<uint32_t> part, part_nan;      // per-workgroup histogram rows of the local handles (first handle of the call only)
+  DevBuf<uint8_t> io;                   // SelIo: selections, prefixes, results
+  void* h_io = nullptr;                 // pinned SelIo
+  ~gmpnp_selector() { if (h_io) (void)hipHostFree(h_io); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -154,6 +163,7 @@ struct gmpnp_solver {
   DevBuf<double> sendbuf, recvbuf, red_i, red_a, red_b, red_norm;
   double* h_red = nullptr;   // pinned [8]: all-reduced ||b||^2 and status bits
   std::unique_ptr<gmpnp_projector> projector;
+  std::unique_ptr<gmpnp_selector> selector;
   // geometric multilevel term (gmpnp_attach_coarse_level, gmpnp_multilevel.h): the link to the next-coarser level (tables in the
   // internal orders of both handles) and this handle's buffers when it serves as a coarse level itself
   gmpnp_solver* ml_coarse = nullptr; double ml_theta = 1.0; bool ml_is_coarse = false;
@@ -1868,3 +1878,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_group.h"
 #include "gmpnp_project.h"
 #include "gmpnp_ensemble.h"
+#include "gmpnp_stats.h"

@@ -551,6 +551,11 @@ class PartitionedSolver:
                 out = t.cpu().numpy()
         return out.ravel()
 
+    def column_select(self, fields, ranks):
+        """k-th smallest values of vertex columns of u over every rank's OWNED rows (gmpnp_group_column_select: collective over the
+        group's transport, the counts all-reduced inside the library): (values, nan flag), identical on every rank."""
+        return self.backend.column_select_call(self.lib.gmpnp_group_column_select, self._group, fields, ranks, self._check)
+
     def comm_selftest(self, n=4096):
         """Send-to-self + receive + all-reduce through the library's RCCL bindings; returns the largest error."""
         from ctypes import byref, c_double
@@ -613,6 +618,28 @@ class PartitionedSolver:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def init_process_group_from_env(backend="nccl", device=None):
+    """The process group of a process that ``torch.distributed.run`` started: RANK / WORLD_SIZE / LOCAL_RANK from the environment
+    and, with a world size above 1, the default group initialised (``backend`` "nccl": bound to cuda:`device`, LOCAL_RANK by
+    default; any other backend as it is).  Returns (rank, world, local rank, torch.distributed or None)."""
+    import os
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world <= 1:
+        return rank, world, local, None
+    import torch
+    import torch.distributed as tdist
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if backend == "nccl":
+        dev = local if device is None else device
+        torch.cuda.set_device(dev)
+        tdist.init_process_group(backend=backend, device_id=torch.device("cuda", dev))
+    else:
+        tdist.init_process_group(backend=backend)
+    return rank, world, local, tdist
 
 
 def host_transport_callbacks(group=None):

@@ -4,7 +4,8 @@ reference 3D/MPNP_CO2ER_pore.py (``solveEDL`` 3D:96-1085, CLI 3D:1088-1253; SURV
 Differences, all explicit: input/output roots come from ``$GMPNP_UTILITIES`` / ``$GMPNP_OUT`` instead of the
 author's hard-coded macOS paths (SURVEY Q10); ``--num_steps`` (not in the reference) shortens the 1000-step loop;
 ``--as_published`` drops the ds(2)/ds(3) flux terms that the published script never adds to F; ``--refine N`` /
-``--multilevel`` run on the N times uniformly refined mesh (with the multilevel term of the preconditioner)."""
+``--multilevel`` run on the N times uniformly refined mesh (with the multilevel term of the preconditioner); ``--partitions N`` solves
+the one problem on N mesh partitions (in this process on one GPU, or one rank per process under ``torch.distributed.run``)."""
 from __future__ import annotations
 
 import argparse
@@ -17,7 +18,7 @@ import numpy as np
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .problem import pore_dirichlet, pore_problem
-from .solver import GMPNPSystem, column_medians
+from .solver import GMPNPSystem, column_medians, device_medians_and_minima
 from .vtk import write_pvd
 
 SOLVER_PARAMETERS = {  # reference 3D:789-798
@@ -43,12 +44,21 @@ class PoreRun:
     """State of one pore simulation; ``step()`` is one pass of the reference's time loop body (3D:783-858)."""
 
     def __init__(self, num_steps=None, as_published=False, device_kwargs=None, solver_parameters=None, refine=0,
-                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, **kwargs):
+                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", **kwargs):
         """``partition`` = (nparts, rank): solve this ONE problem across `nparts` mesh partitions (rank None: all of them in
         this process on one GPU; rank r: this process is rank r of a ``torch.distributed`` job, RCCL inside the library).
         ``multilevel`` (with ``refine`` > 0): the preconditioner gets the geometric multilevel term over the nested meshes
         (gmpnp_attach_coarse_level; with ``partition`` across the mesh partitions, every level partitioned alike) — not a reference
-        feature; it changes iteration counts of the linear solves, not results."""
+        feature; it changes iteration counts of the linear solves, not results.
+        ``glue`` = "host": every step gathers the whole state to the host (with one rank per process: an all-reduce of it through
+        torch.distributed) for the medians, the CO2 minimum and the history row; "device": the medians and the minimum come from the
+        library's column select (csrc/gmpnp_stats.h: collective inside the library, identical values) and the history keeps this
+        process's OWNED rows only (one device-to-host copy per local partition, no collective); ``write_outputs`` assembles the
+        global history on rank 0, which alone prints and writes."""
+        if glue not in ("host", "device"):
+            raise ValueError("glue must be 'host' or 'device'")
+        self.glue = glue
+        self.rank = partition[1] if partition else None
         self.kwargs = kwargs
         self.pp = pore_parameters(as_published=as_published, **kwargs)
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), self.pp.mesh_name))
@@ -80,8 +90,13 @@ class PoreRun:
         self.tot_num_steps = self.pp.tot_num_steps if num_steps is None else int(num_steps)
         nv = self.mesh.num_vertices
         self.sys.initialise([1.0] * 8 + [0.0])
-        # history rows: initial ones/zeros (3D:771-779), one row appended per step (3D:842-850)
-        self.history = [np.concatenate([np.ones((nv, 8)), np.zeros((nv, 1))], axis=1)]
+        # history rows: initial ones/zeros (3D:771-779), one row appended per step (3D:842-850); "device" glue: the rows this process
+        # owns, one array per local partition (vertex ids in self.owned_ids)
+        if glue == "device":
+            self.owned_ids = [ids for ids, _ in self.sys.owned_vertex_values()]
+            self.history = [[np.concatenate([np.ones((len(ids), 8)), np.zeros((len(ids), 1))], axis=1) for ids in self.owned_ids]]
+        else:
+            self.history = [np.concatenate([np.ones((nv, 8)), np.zeros((nv, 1))], axis=1)]
         self.CO2_min = None
         self.co2_bc = None  # CO2 Dirichlet value in force (None = the equilibrium value of the set-up)
         self.n = 0
@@ -89,6 +104,8 @@ class PoreRun:
         self.newton_its = []
 
     def step(self, verbose=True):
+        if self.glue == "device":
+            return self._step_device(verbose)
         self.t += self.pp.dt
         st = self.sys.solve(self.solver_parameters)
         vals = self.sys.vertex_values()
@@ -107,6 +124,45 @@ class PoreRun:
         self.n += 1
         return st
 
+    def _step_device(self, verbose):
+        """``step`` with the per-step glue on the device: the same values, no gather of the state."""
+        self.t += self.pp.dt
+        st = self.sys.solve(self.solver_parameters)
+        (meds, (co2_min,)) = device_medians_and_minima(self.sys, (1, 2, 3, 7), (4,))
+        co2 = self.pp.sechenov_co2_scaled(*meds)
+        self.co2_bc = co2
+        self.history.append([v for _, v in self.sys.owned_vertex_values()])
+        self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, co2))
+        self.CO2_min = co2_min
+        self.sys.assign_previous()
+        self.newton_its.append(st["iterations"])
+        if verbose and self.rank in (None, 0):
+            print(self.CO2_min)
+            print(datetime.now().strftime("%y-%m-%d-%H-%M-%S"))
+            print(self.n)
+        self.n += 1
+        return st
+
+    def field_history(self, i):
+        """(steps + 1, nv) history of field i in file vertex order.  "device" glue with one rank per process: gathered to rank 0
+        (collective: every rank calls it; None on the other ranks)."""
+        if self.glue == "host":
+            return np.stack([row[:, i] for row in self.history])
+        parts = [(ids, np.stack([row[d][:, i] for row in self.history])) for d, ids in enumerate(self.owned_ids)]
+        if self.rank is not None and self.sys.ps.nparts > 1:
+            import torch.distributed as tdist
+            if not (tdist.is_available() and tdist.is_initialized()):
+                raise RuntimeError("one rank per process: the history is gathered through torch.distributed, which is not initialised")
+            got = [None] * tdist.get_world_size() if self.rank == 0 else None
+            tdist.gather_object(parts, got, dst=0)
+            if self.rank != 0:
+                return None
+            parts = [p for g in got for p in g]
+        out = np.empty((len(self.history), self.mesh.num_vertices))
+        for ids, h in parts:
+            out[:, ids] = h
+        return out
+
     def run(self, verbose=True):
         for _ in range(self.n, self.tot_num_steps):
             self.step(verbose)
@@ -115,6 +171,17 @@ class PoreRun:
     # ---- outputs (3D:860-1085) -------------------------------------------------------------------
     def write_outputs(self, stamp=None):
         pp, mesh, k = self.pp, self.mesh, self.kwargs
+        names = ["H", "OH", "HCO3", "CO32", "CO2", "CO", "H2", "cat", "p"]
+        if self.glue == "device":
+            # the global history, assembled once on rank 0 field by field (one field's rows per gather); other ranks write nothing
+            H = {nme: self.field_history(i) for i, nme in enumerate(names)}
+            if self.rank not in (None, 0):
+                return None
+            last = np.stack([H[nme][-1] for nme in names], axis=1)
+        else:
+            hist = np.stack(self.history)  # (steps+1, nv, 9)
+            H = {nme: hist[:, :, i] for i, nme in enumerate(names)}
+            last = hist[-1]
         stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         end_time = datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         L, R = pp.L, pp.R
@@ -124,10 +191,6 @@ class PoreRun:
                       + "_rough_" + str(k.get("roughness_factor", 150.0)))
         newpath = os.path.join(output_root(), stamp + "_experiment", identifier) + "/"
         os.makedirs(newpath, exist_ok=True)
-        hist = np.stack(self.history)  # (steps+1, nv, 9)
-        names = ["H", "OH", "HCO3", "CO32", "CO2", "CO", "H2", "cat", "p"]
-        H = {nme: hist[:, :, i] for i, nme in enumerate(names)}
-        last = hist[-1]
         for fname, col in (("CO", 5), ("K", 7), ("H2", 6), ("CO2", 4), ("OH", 1), ("H", 0), ("HCO3", 2), ("CO32", 3),
                            ("p", 8)):
             write_pvd(os.path.join(newpath, "solution_" + fname + ".pvd"), mesh.coords, mesh.cells, last[:, col],
@@ -182,11 +245,14 @@ class PoreRun:
 def solveEDL(concentration_elec=1.0, voltage_multiplier=-1.0, H2_FE=0.05, current_rough=3000.0, L=100.0e-9,
              cation="K", R=5.0e-9, press_gas=1.0, pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5,
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
-             roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False):
+             roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
+             device_kwargs=None, glue="host"):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
-    geometric multilevel term of the preconditioner)."""
-    run = PoreRun(num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, concentration_elec=concentration_elec,
+    geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` as ``PoreRun`` takes them (with
+    one rank per process only rank 0 writes and returns the directory; the others return None)."""
+    run = PoreRun(num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
+                  device_kwargs=device_kwargs, glue=glue, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
                   R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier, porosity_eff=porosity_eff,
                   tortuosity_eff=tortuosity_eff, constrictivity_eff=constrictivity_eff, params_file=params_file,
@@ -217,19 +283,50 @@ def build_parser():
     p.add_argument("--as_published", action="store_true", help="drop the ds(2)/ds(3) flux terms (SURVEY Q1)")
     p.add_argument("--refine", required=False, default=0, type=int, help="uniform (red) refinements of the mesh file, markers inherited")
     p.add_argument("--multilevel", action="store_true", help="with --refine > 0: geometric multilevel term of the preconditioner over the nested meshes")
+    p.add_argument("--partitions", required=False, default=None, type=int,
+                   help="solve on N mesh partitions: all in this process on one GPU, or one rank per process under torch.distributed.run "
+                        "(WORLD_SIZE = N; rank 0 prints and writes)")
     return p
+
+
+def partition_setup(nparts):
+    """(partition, device_kwargs, torch.distributed or None) of ``--partitions nparts``.  Without torch.distributed.run: every
+    partition in this process on one GPU.  Under it (WORLD_SIZE == nparts): one rank per process on device LOCAL_RANK, RCCL between
+    the ranks; ranks that share a card (more local ranks than visible devices) run as ``shared_device`` handles over the
+    host-staged transport on gloo (RCCL takes one rank per device)."""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world <= 1:
+        return (nparts, None), {}, None
+    if world != nparts:
+        raise SystemExit("--partitions %d under torch.distributed.run needs WORLD_SIZE == %d (it is %d)" % (nparts, nparts, world))
+    import torch   # before libgmpnp.so (README: two HIP runtimes on one GPU do not mix)
+    from .dist import init_process_group_from_env
+    ndev = max(1, torch.cuda.device_count())
+    shared = int(os.environ.get("LOCAL_WORLD_SIZE", world)) > ndev
+    local = int(os.environ.get("LOCAL_RANK", "0")) % ndev
+    rank, _, _, tdist = init_process_group_from_env("gloo" if shared else "nccl", device=local)
+    return (nparts, rank), {"device_id": local, "shared_device": int(shared), "transport": "host" if shared else "rccl"}, tdist
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    return solveEDL(concentration_elec=a.concentration_elec, voltage_multiplier=a.voltage_multiplier, H2_FE=a.H2_FE,
-                    current_rough=a.current_rough, L=a.L, R=a.R, press_gas=a.press_gas, cation=a.cation,
-                    porosity_eff=a.porosity_eff, tortuosity_eff=a.tortuosity_eff,
-                    constrictivity_eff=a.constrictivity_eff, params_file=a.params_file, y_CO2=a.y_CO2,
-                    pore_geom_multiplier=a.pore_geom_multiplier,
-                    electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
-                    roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                    multilevel=a.multilevel)
+    extra, tdist = {}, None
+    if a.partitions:
+        partition, device_kwargs, tdist = partition_setup(a.partitions)
+        extra = dict(partition=partition, device_kwargs=device_kwargs, glue="device", verbose=partition[1] in (None, 0))
+    try:
+        return solveEDL(concentration_elec=a.concentration_elec, voltage_multiplier=a.voltage_multiplier, H2_FE=a.H2_FE,
+                        current_rough=a.current_rough, L=a.L, R=a.R, press_gas=a.press_gas, cation=a.cation,
+                        porosity_eff=a.porosity_eff, tortuosity_eff=a.tortuosity_eff,
+                        constrictivity_eff=a.constrictivity_eff, params_file=a.params_file, y_CO2=a.y_CO2,
+                        pore_geom_multiplier=a.pore_geom_multiplier,
+                        electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
+                        roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
+                        multilevel=a.multilevel, **extra)
+    finally:
+        if tdist is not None:
+            tdist.barrier()
+            tdist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -57,6 +57,14 @@ class GMPNPSystem:
         """(nv, nf) array = compute_vertex_values() of every sub-function, file vertex order."""
         return self.dev.get_state().reshape(self.nv, self.nf)
 
+    def owned_vertex_values(self):
+        """[(vertex ids, (n, nf) values)] of the rows this process owns: here all of them."""
+        return [(np.arange(self.nv), self.vertex_values())]
+
+    def column_select(self, fields, ranks):
+        """k-th smallest values of vertex columns of u, on the device (gmpnp_column_select): (values, nan flag)."""
+        return self.dev.column_select(fields, ranks)
+
     def assign_previous(self):
         self.dev.assign_previous()
 
@@ -116,6 +124,14 @@ class PartitionedSystem:
     def vertex_values(self):
         return self.ps.get_state().reshape(self.nv, self.nf)
 
+    def owned_vertex_values(self):
+        """[(global vertex ids, (n_owned, nf) values)] of this process's partitions: one device-to-host copy each, no collective."""
+        return self.ps.owned_state()
+
+    def column_select(self, fields, ranks):
+        """k-th smallest values of vertex columns of u over ALL ranks' owned rows (gmpnp_group_column_select; collective)."""
+        return self.ps.column_select(fields, ranks)
+
     def assign_previous(self):
         self.ps.assign_previous()
 
@@ -152,6 +168,38 @@ def column_medians(vals, cols):
         return np.partition(a, h, axis=1)[:, h]
     p = np.partition(a, (h - 1, h), axis=1)
     return np.array([np.mean(p[i, h - 1:h + 1]) for i in range(p.shape[0])])
+
+
+def device_column_medians(sys, cols):
+    """``column_medians(sys.vertex_values(), cols)``, bit for bit, from the library's column select (one call, one host
+    synchronisation; on a partitioned system collective over the ranks, no gather of the state).  A NaN in a selected column falls
+    back to the gathered path, as ``column_medians`` falls back to ``np.median``."""
+    return device_medians_and_minima(sys, cols, ())[0]
+
+
+def device_medians_and_minima(sys, cols, min_cols):
+    """(``column_medians`` of `cols`, ``[np.amin(column) for column in min_cols]``) of the state of `sys` in ONE
+    ``column_select`` call: the middle element, or ``np.mean`` of the two middle ones, as ``column_medians``; the minimum is the
+    smallest element (a zero minimum comes back as +0.0).  NaN in a selected column: the gathered state."""
+    cols, min_cols = list(cols), list(min_cols)
+    n = sys.nv
+    if n == 0:
+        vals = sys.vertex_values()
+        return column_medians(vals, cols), [float(np.amin(vals[:, c])) for c in min_cols]
+    h = n // 2
+    mids = [h] if n % 2 else [h - 1, h]
+    fields = [c for c in cols for _ in mids] + min_cols
+    ranks = mids * len(cols) + [0] * len(min_cols)
+    out, nan = sys.column_select(fields, ranks)
+    if nan:
+        vals = sys.vertex_values()
+        return column_medians(vals, cols), [float(np.amin(vals[:, c])) for c in min_cols]
+    k = len(mids)
+    if k == 1:
+        med = out[:len(cols)].copy()
+    else:
+        med = np.array([np.mean(out[2 * i:2 * i + 2]) for i in range(len(cols))])
+    return med, [float(v) for v in out[k * len(cols):]]
 
 
 def supg_parameters(coords, cells, z, p_prev, project_cellwise, h_vertex=None, fact=1.0, tol=1.0e-14):

@@ -13,7 +13,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
 import time
 
 RADII_NM = (1, 2, 2.5, 4, 5, 7.5, 10)                  # the seven L_50_R_* meshes of the reference's utilities/
@@ -93,20 +92,8 @@ def main(argv=None):
     p.add_argument("--write", action="store_true", help="write the reference's output files of every run under $GMPNP_OUT")
     p.add_argument("--backend", default=None, help="torch.distributed backend for the final gather (default: nccl)")
     a = p.parse_args(argv)
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    dist = None
-    if world > 1:
-        import torch
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        backend = a.backend or "nccl"
-        if backend == "nccl":
-            torch.cuda.set_device(local)
-            dist.init_process_group(backend=backend, device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend=backend)
+    from .dist import init_process_group_from_env
+    rank, world, local, dist = init_process_group_from_env(a.backend or "nccl")
     radii = [int(r) if float(r).is_integer() else r for r in a.radii]
     mine = my_jobs(jobs(radii, a.voltages), rank, world)
     t0 = time.perf_counter()

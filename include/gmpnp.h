@@ -366,6 +366,19 @@ int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const in
  * groups of another transport kind or rank count, handles that are not the attached levels.  No reference counterpart. */
 int gmpnp_group_attach_coarse_group(gmpnp_group* fine, gmpnp_group* coarse);
 
+/* ---- order statistics of the state's vertex columns on the device -----------------------------------------------------------
+ * Replaces the per-step host glue of the reference's time loop, 3D/MPNP_CO2ER_pore.py:817-838: np.median of the H / OH / HCO3 /
+ * cation vertex arrays (the Sechenov update of the CO2 Dirichlet value) and the minimum of the CO2 array.  k-th smallest values of
+ * owned vertex columns of u (global over the group's ranks for the group form).  ncols selections: field[j] in [0, n_fields),
+ * rank[j] in [0, n_global_vertices) (n <= 64).  Returns in out[j] the value NumPy's np.sort(column)[rank[j]] holds (-0.0 counts as
+ * +0.0; subnormals and +-Inf are ordinary values).  *flags bit 0 = a selected column holds a NaN (out[] undefined for it).
+ * Exact radix select on the 64-bit keys of the doubles (csrc/gmpnp_stats.h): eight histogram passes, the integer counts all-reduced
+ * over the group's transport, one host synchronisation per call; the result is the same bit for bit on every transport and rank
+ * count.  The group form is collective (every rank calls it with the same selections); rank[j] not below the global number of
+ * owned rows is GMPNP_ERR_INVALID on every rank. */
+int gmpnp_column_select(gmpnp_solver* s, int32_t n, const int32_t* field, const int64_t* rank, double* out, int32_t* flags);
+int gmpnp_group_column_select(gmpnp_group* g, int32_t n, const int32_t* field, const int64_t* rank, double* out, int32_t* flags);
+
 /* ---- ensemble of 1D problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py is many separate runs) ------------------------------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME 1D mesh (same vertices, cells and vertex order) and device.
