@@ -531,6 +531,13 @@ class DeviceSolver:
         return {"sampled": n.value, "mean_us": mean.value, "launched": launched.value}
 
 
+def attach_level_chain(handles, parents, theta: float = 2.0, sweeps: int = 4):
+    """The multilevel term over `handles` (finest first): handles[k + 1] attached below handles[k] with `parents[k]`, the table of
+    level k's vertices in level k + 1, from the finest level to the coarsest (``DeviceSolver.attach_coarse_level``)."""
+    for finer, coarse, par in zip(handles, handles[1:], parents):
+        finer.attach_coarse_level(coarse, par, theta=theta, sweeps=sweeps)
+
+
 MAX_ENSEMBLE = 64   # gmpnp_ensemble_create refuses more members
 
 

@@ -9,9 +9,9 @@ are GHOSTS (owned by a neighbouring slab).  Cut cells are assembled redundantly 
 are complete without any matrix communication; ghost rows are replaced by identity rows (they are never used).
 
 What this module is:
-* ``partition_plan`` / ``build_local_domain`` — the partition, the halo plan and the global coarse slabs handed to
-  ``gmpnp_create_partition``;
-* ``partition_hierarchy`` — the same for every level of a nested hierarchy (the multilevel term across the partitions);
+* ``slab_cut`` / ``build_local_domain`` / ``partition_hierarchy`` — the partition, the halo plan and the global coarse slabs handed
+  to ``gmpnp_create_partition``, for every level of a nested hierarchy (the multilevel term across the partitions);
+  ``partition_plan`` is the one-level case;
 * ``PartitionedSolver`` — the product path: Newton, BiCGStab, ghost exchanges and all-reduces run INSIDE libgmpnp.so
   (``gmpnp_group_newton_solve``; RCCL, in-process, or host-staged transport); Python scatters / gathers states and the
   per-step boundary values;
@@ -21,7 +21,6 @@ partitioned iteration that drives ``partition_plan`` and these callbacks at worl
 """
 from __future__ import annotations
 
-import copy
 from dataclasses import dataclass
 
 import numpy as np
@@ -32,15 +31,35 @@ from .problem import Problem
 # ---------------------------------------------------------------------------------------------
 # partition
 # ---------------------------------------------------------------------------------------------
-def slab_owner(coords: np.ndarray, cells: np.ndarray, nparts: int) -> np.ndarray:
-    """owner[vertex] for `nparts` equal-count slabs of the slab order (the order the solver uses internally)."""
+def default_global_aggregates(nparts: int) -> int:
+    """Coarse slabs over the whole mesh: 8 (the single-GPU default) when the ranks divide it, else one slab per rank
+    rounded up to a multiple of the rank count; at most 15 (the 9-field coarse operator must fit the LDS-resident inverse)."""
+    if 8 % nparts == 0:
+        return 8
+    n = nparts * max(1, 8 // nparts)
+    if n > 15:
+        raise ValueError("no coarse-slab count <= 15 is a multiple of %d ranks" % nparts)
+    return n
+
+
+def slab_cut(prob: Problem, nparts: int, n_global_aggregates: int = None):
+    """The slab cut of a mesh: (position of every vertex in the slab order, its coarse slab, its owner).
+
+    Global slab order (``backend.slab_permutation``: vertices sorted along the pore axis) is cut into `nparts` contiguous
+    ownership ranges and into `n_global_aggregates` coarse slabs with the SAME integer boundaries, so a slab never
+    straddles two ranks (and the ranges are those of `nparts` equal-count slabs: (nv k m) // (nparts m) == (nv k) // nparts)."""
     from .backend import slab_permutation
-    perm = slab_permutation(coords, cells, window=0)  # pure slab order: sharp partition interfaces
-    owner = np.empty(coords.shape[0], dtype=np.int32)
-    nv = coords.shape[0]
-    for p in range(nparts):
-        owner[perm[(nv * p) // nparts:(nv * (p + 1)) // nparts]] = p
-    return owner
+    nag = n_global_aggregates or default_global_aggregates(nparts)
+    if nag % nparts:
+        raise ValueError("n_global_aggregates must be a multiple of the number of ranks")
+    nv = prob.coords.shape[0]
+    gperm = slab_permutation(prob.coords, prob.cells, window=0)  # pure slab order: sharp partition interfaces
+    pos = np.empty(nv, dtype=np.int64)
+    pos[gperm] = np.arange(nv)
+    bounds = (nv * np.arange(nag + 1, dtype=np.int64)) // nag
+    aggregate = np.searchsorted(bounds[1:], pos, side="right").astype(np.int32)
+    owner = (aggregate // (nag // nparts)).astype(np.int32)
+    return pos, aggregate, owner
 
 
 @dataclass
@@ -49,8 +68,9 @@ class LocalDomain:
     nparts: int
     owned: np.ndarray  # global (file) vertex ids, ascending
     ghosts: np.ndarray  # global vertex ids, ascending
-    ghost_owner: np.ndarray  # rank owning each ghost
-    problem: Problem  # local problem: vertices = [owned..., ghosts...]
+    lverts: np.ndarray  # the local vertices in local order: [owned..., ghosts...]
+    g2l: np.ndarray  # local index of every GLOBAL vertex, -1 = not local
+    problem: Problem  # local problem on `lverts`
     n_owned: int
     send: dict  # neighbour rank -> local indices (into owned) to send, in the receiver's ghost order
     recv: dict  # neighbour rank -> local indices (n_owned + k) that receive
@@ -59,22 +79,28 @@ class LocalDomain:
     def nf(self):
         return self.problem.nf
 
-    def owned_dofs(self):
-        return slice(0, self.n_owned * self.nf)
 
-
-def build_local_domain(prob: Problem, owner: np.ndarray, rank: int, nparts: int) -> LocalDomain:
-    """Local problem of `rank`.  Deterministic and purely local (every rank can build any rank's domain), so the
-    send lists need no negotiation: rank q's ghosts owned by p, in ascending global id, are what p sends to q."""
+def build_local_domain(prob: Problem, owner: np.ndarray, rank: int, nparts: int, lcells: np.ndarray = None,
+                       ghost_sets: list = None) -> LocalDomain:
+    """Local problem of `rank` on the cells `lcells` (global vertex ids).  Deterministic and purely local (every rank can build any
+    rank's domain), so the send lists need no negotiation: rank q's ghosts owned by p, in ascending global id, are what p sends to
+    q.  The halo plan comes from every rank's ACTUAL ghost set (`ghost_sets[q]`, ascending), so ghosts that no owned cell touches
+    (the transfer ghosts of a coarse level) are served too.  By default the local cells are those that touch an owned vertex and
+    the ghosts of a rank are the other vertices of its such cells."""
     nf = prob.nf
-    cells = prob.cells
-    touch = (owner[cells] == rank).any(axis=1)
-    lcells = cells[touch]
-    verts = np.unique(lcells)
-    owned = verts[owner[verts] == rank]
-    ghosts = verts[owner[verts] != rank]
-    all_owned = np.nonzero(owner == rank)[0]
-    assert np.array_equal(owned, all_owned), "every owned vertex must belong to a local cell"
+    owned = np.nonzero(owner == rank)[0]
+    if lcells is None:
+        touched = [prob.cells[(owner[prob.cells] == q).any(axis=1)] for q in range(nparts)]
+        lcells = touched[rank]
+        ghost_sets = []
+        for q in range(nparts):
+            vq = np.unique(touched[q])
+            ghost_sets.append(vq[owner[vq] != q])
+        # these ids have always had the cells' integer type, the ones of explicit cell lists NumPy's index type: the plans are
+        # pinned with their types (tests/golden/partition_plans.json)
+        owned = owned.astype(prob.cells.dtype)
+    ghosts = ghost_sets[rank]
+    assert np.array_equal(np.union1d(owned, ghosts), np.unique(lcells)), "the local cells must cover exactly the owned and the ghost vertices"
     lverts = np.concatenate([owned, ghosts])
     g2l = -np.ones(prob.coords.shape[0], dtype=np.int64)
     g2l[lverts] = np.arange(len(lverts))
@@ -88,11 +114,8 @@ def build_local_domain(prob: Problem, owner: np.ndarray, rank: int, nparts: int)
     # Dirichlet: the global conditions restricted to local vertices + identity rows on every ghost dof
     gv = prob.bc_dofs // nf
     inloc = g2l[gv] >= 0
-    ldofs = g2l[gv[inloc]] * nf + prob.bc_dofs[inloc] % nf
-    lvals = prob.bc_vals[inloc]
-    gh_dofs = (np.arange(len(owned), len(lverts))[:, None] * nf + np.arange(nf)[None, :]).ravel()
-    table = dict(zip(ldofs.tolist(), lvals.tolist()))
-    for d in gh_dofs.tolist():
+    table = dict(zip((g2l[gv[inloc]] * nf + prob.bc_dofs[inloc] % nf).tolist(), prob.bc_vals[inloc].tolist()))
+    for d in range(len(owned) * nf, len(lverts) * nf):
         table[d] = 0.0  # value irrelevant: ghost rows are never used
     bd = np.array(sorted(table), dtype=np.int64)
     bvl = np.array([table[d] for d in bd])
@@ -102,57 +125,23 @@ def build_local_domain(prob: Problem, owner: np.ndarray, rank: int, nparts: int)
                     wall_facets=facets_local(prob.wall_facets), exit_facets=facets_local(prob.exit_facets),
                     point_vertices=pv_local, bc_dofs=bd, bc_vals=bvl)
     # halo plan
-    send, recv = {}, {}
     gowner = owner[ghosts]
-    for q in np.unique(gowner):
-        recv[int(q)] = len(owned) + np.nonzero(gowner == q)[0]
+    recv = {int(q): len(owned) + np.nonzero(gowner == q)[0] for q in np.unique(gowner)}
+    send = {}
     for q in range(nparts):
-        if q == rank:
-            continue
-        tq = (owner[cells] == q).any(axis=1)
-        vq = np.unique(cells[tq])
-        mine = vq[owner[vq] == rank]  # ascending global id == q's ghost order restricted to my vertices
-        if len(mine):
-            send[q] = g2l[mine]
-    return LocalDomain(rank=rank, nparts=nparts, owned=owned, ghosts=ghosts, ghost_owner=gowner, problem=local,
+        if q != rank:
+            mine = ghost_sets[q][owner[ghost_sets[q]] == rank]   # ascending global id == q's ghost order restricted to my vertices
+            if len(mine):
+                send[q] = g2l[mine]
+    return LocalDomain(rank=rank, nparts=nparts, owned=owned, ghosts=ghosts, lverts=lverts, g2l=g2l, problem=local,
                        n_owned=len(owned), send=send, recv=recv)
 
 
 # ---------------------------------------------------------------------------------------------
 # the partitioned solve INSIDE the library (gmpnp_create_partition / gmpnp_group_*): this module only partitions and plans
 # ---------------------------------------------------------------------------------------------
-def default_global_aggregates(nparts: int) -> int:
-    """Coarse slabs over the whole mesh: 8 (the single-GPU default) when the ranks divide it, else one slab per rank
-    rounded up to a multiple of the rank count; at most 15 (the 9-field coarse operator must fit the LDS-resident inverse)."""
-    if 8 % nparts == 0:
-        return 8
-    n = nparts * max(1, 8 // nparts)
-    if n > 15:
-        raise ValueError("no coarse-slab count <= 15 is a multiple of %d ranks" % nparts)
-    return n
-
-
-def partition_plan(prob: Problem, nparts: int, rank: int, n_global_aggregates: int = None):
-    """Everything rank `rank` needs for ``gmpnp_create_partition``: (LocalDomain, local perm, partition dict).
-
-    Global slab order (``backend.slab_permutation``: vertices sorted along the pore axis) is cut into `nparts` contiguous
-    ownership ranges and into `n_global_aggregates` coarse slabs with the SAME integer boundaries, so a slab never
-    straddles two ranks.  The local vertex order handed to the library is the global slab order restricted to the local
-    vertices: ghosts of the lower neighbour, owned vertices, ghosts of the upper neighbour."""
-    from .backend import slab_permutation
-    nag = n_global_aggregates or default_global_aggregates(nparts)
-    if nag % nparts:
-        raise ValueError("n_global_aggregates must be a multiple of the number of ranks")
-    nv = prob.coords.shape[0]
-    gperm = slab_permutation(prob.coords, prob.cells, window=0)
-    pos = np.empty(nv, dtype=np.int64)
-    pos[gperm] = np.arange(nv)
-    bounds = (nv * np.arange(nag + 1, dtype=np.int64)) // nag
-    agg_of = np.searchsorted(bounds[1:], pos, side="right").astype(np.int32)       # slab of every global vertex
-    owner = (agg_of // (nag // nparts)).astype(np.int32)
-    dom = build_local_domain(prob, owner, rank, nparts)
-    lverts = np.concatenate([dom.owned, dom.ghosts])
-    perm_local = np.argsort(pos[lverts], kind="stable").astype(np.int32)
+def _part_dict(dom: LocalDomain, nag: int, aggregate: np.ndarray) -> dict:
+    """What gmpnp_create_partition takes: the halo lists of `dom` neighbour by neighbour and the coarse slab of every local vertex."""
     nbrs = sorted(set(dom.send) | set(dom.recv))
     send_ptr, recv_ptr, send_v, recv_v = [0], [0], [], []
     for q in nbrs:
@@ -160,13 +149,12 @@ def partition_plan(prob: Problem, nparts: int, rank: int, n_global_aggregates: i
         recv_v.extend(np.asarray(dom.recv.get(q, []), dtype=np.int64).tolist())
         send_ptr.append(len(send_v))
         recv_ptr.append(len(recv_v))
-    owned_flag = np.zeros(len(lverts), dtype=np.uint8)
+    owned_flag = np.zeros(len(dom.lverts), dtype=np.uint8)
     owned_flag[:dom.n_owned] = 1
-    part = {"rank": rank, "size": nparts, "n_global_aggregates": nag, "vertex_aggregate": agg_of[lverts], "vertex_owned": owned_flag,
-            "neighbour_rank": np.array(nbrs, dtype=np.int32), "send_ptr": np.array(send_ptr, dtype=np.int32),
+    return {"rank": dom.rank, "size": dom.nparts, "n_global_aggregates": nag, "vertex_aggregate": aggregate[dom.lverts].astype(np.int32),
+            "vertex_owned": owned_flag, "neighbour_rank": np.array(nbrs, dtype=np.int32), "send_ptr": np.array(send_ptr, dtype=np.int32),
             "send_vertices": np.array(send_v, dtype=np.int32), "recv_ptr": np.array(recv_ptr, dtype=np.int32),
             "recv_vertices": np.array(recv_v, dtype=np.int32)}
-    return dom, perm_local, part
 
 
 # ---------------------------------------------------------------------------------------------
@@ -184,68 +172,19 @@ class LevelPlan:
     aggregate: np.ndarray     # coarse slab of every global vertex
 
 
-def _level_local_domain(prob: Problem, owner: np.ndarray, rank: int, nparts: int, lcells: np.ndarray, ghost_sets: list) -> LocalDomain:
-    """Local problem of `rank` on the cells `lcells` (global vertex ids); the halo plan comes from every rank's ACTUAL ghost set
-    (`ghost_sets[q]`, ascending), so ghosts that no owned cell touches (the transfer ghosts of a coarse level) are served too."""
-    nf = prob.nf
-    verts = np.unique(lcells)
-    owned = np.nonzero(owner == rank)[0]
-    ghosts = ghost_sets[rank]
-    assert np.array_equal(np.union1d(owned, ghosts), verts), "the local cells must cover the owned and the ghost vertices"
-    lverts = np.concatenate([owned, ghosts])
-    g2l = -np.ones(prob.coords.shape[0], dtype=np.int64)
-    g2l[lverts] = np.arange(len(lverts))
-
-    def facets_local(fv):
-        if len(fv) == 0:
-            return np.zeros((0, 3), dtype=np.int32)
-        keep = (owner[fv] == rank).any(axis=1)
-        return g2l[fv[keep]].astype(np.int32)
-
-    gv = prob.bc_dofs // nf
-    inloc = g2l[gv] >= 0
-    table = dict(zip((g2l[gv[inloc]] * nf + prob.bc_dofs[inloc] % nf).tolist(), prob.bc_vals[inloc].tolist()))
-    for d in range(len(owned) * nf, len(lverts) * nf):
-        table[d] = 0.0  # ghost rows are identity rows
-    bd = np.array(sorted(table), dtype=np.int64)
-    bvl = np.array([table[d] for d in bd])
-    local = Problem(coords=prob.coords[lverts], cells=g2l[lcells].astype(np.int32), model=prob.model, quad=prob.quad,
-                    wall_facets=facets_local(prob.wall_facets), exit_facets=facets_local(prob.exit_facets),
-                    point_vertices=np.zeros(0, dtype=np.int32), bc_dofs=bd, bc_vals=bvl)
-    gowner = owner[ghosts]
-    recv = {int(q): len(owned) + np.nonzero(gowner == q)[0] for q in np.unique(gowner)}
-    send = {}
-    for q in range(nparts):
-        if q != rank:
-            mine = ghost_sets[q][owner[ghost_sets[q]] == rank]   # ascending global id == q's ghost order restricted to my vertices
-            if len(mine):
-                send[q] = g2l[mine]
-    return LocalDomain(rank=rank, nparts=nparts, owned=owned, ghosts=ghosts, ghost_owner=gowner, problem=local,
-                       n_owned=len(owned), send=send, recv=recv)
-
-
-def _part_dict(dom: LocalDomain, rank: int, nparts: int, nag: int, agg_of: np.ndarray) -> dict:
-    lverts = np.concatenate([dom.owned, dom.ghosts])
-    nbrs = sorted(set(dom.send) | set(dom.recv))
-    send_ptr, recv_ptr, send_v, recv_v = [0], [0], [], []
-    for q in nbrs:
-        send_v.extend(np.asarray(dom.send.get(q, []), dtype=np.int64).tolist())
-        recv_v.extend(np.asarray(dom.recv.get(q, []), dtype=np.int64).tolist())
-        send_ptr.append(len(send_v))
-        recv_ptr.append(len(recv_v))
-    owned_flag = np.zeros(len(lverts), dtype=np.uint8)
-    owned_flag[:dom.n_owned] = 1
-    return {"rank": rank, "size": nparts, "n_global_aggregates": nag, "vertex_aggregate": agg_of[lverts].astype(np.int32),
-            "vertex_owned": owned_flag, "neighbour_rank": np.array(nbrs, dtype=np.int32), "send_ptr": np.array(send_ptr, dtype=np.int32),
-            "send_vertices": np.array(send_v, dtype=np.int32), "recv_ptr": np.array(recv_ptr, dtype=np.int32),
-            "recv_vertices": np.array(recv_v, dtype=np.int32)}
+def _level_plan(prob: Problem, pos, aggregate, owner, rank, nparts, nag, lcells=None, ghost_sets=None) -> LevelPlan:
+    """The plan of one level from its slab cut.  The local vertex order handed to the library is the global slab order restricted to
+    the local vertices: ghosts of the lower neighbour, owned vertices, ghosts of the upper neighbour."""
+    dom = build_local_domain(prob, owner, rank, nparts, lcells, ghost_sets)
+    perm = np.argsort(pos[dom.lverts], kind="stable").astype(np.int32)
+    return LevelPlan(domain=dom, perm=perm, part=_part_dict(dom, nag, aggregate), parents=None, owner=owner, pos=pos, aggregate=aggregate)
 
 
 def partition_hierarchy(levels, nparts: int, rank: int, n_global_aggregates: int = None):
     """Partition plans of a nested hierarchy (``problem.pore_hierarchy``: [(problem, boundaries, parents)], FINEST first) for rank
-    `rank`: one ``LevelPlan`` per level.
+    `rank`: one ``LevelPlan`` per level (a single problem is a hierarchy of one level: ``partition_plan``).
 
-    * The finest level is ``partition_plan`` itself: its partitions, slabs and halo lists are those of the two-level solve.
+    * The finest level is cut by ``slab_cut``; its local mesh is every cell that touches an owned vertex.
     * A coarse vertex is owned where its COPY (the fine vertex at the same place) is owned, lies in its copy's slab, and takes its
       copy's place in the slab order: the coarse slabs never straddle ranks and no tie along the axis reorders anything.
     * The coarse local mesh holds the cells that touch an owned vertex (its rows are complete) plus, for every parent of an owned
@@ -253,21 +192,12 @@ def partition_hierarchy(levels, nparts: int, rank: int, n_global_aggregates: int
       ghosts), so the prolongation of the owned rows reads local values only.  Ghost rows are identity rows as on the finest level.
     * Every child of an owned coarse vertex is local on the finer level (the copy's one-cell ring): the restriction of the owned
       coarse rows reads local values only.  Asserted here."""
-    fine_prob = levels[0][0]
-    dom, perm, part = partition_plan(fine_prob, nparts, rank, n_global_aggregates)
-    nag = part["n_global_aggregates"]
-    nv = fine_prob.coords.shape[0]
-    from .backend import slab_permutation
-    gperm = slab_permutation(fine_prob.coords, fine_prob.cells, window=0)
-    pos = np.empty(nv, dtype=np.int64)
-    pos[gperm] = np.arange(nv)
-    bounds = (nv * np.arange(nag + 1, dtype=np.int64)) // nag
-    agg = np.searchsorted(bounds[1:], pos, side="right").astype(np.int32)
-    owner = (agg // (nag // nparts)).astype(np.int32)
-    plans = [LevelPlan(domain=dom, perm=perm, part=part, parents=None, owner=owner, pos=pos, aggregate=agg)]
+    nag = n_global_aggregates or default_global_aggregates(nparts)
+    plans = [_level_plan(levels[0][0], *slab_cut(levels[0][0], nparts, nag), rank, nparts, nag)]
     for k in range(1, len(levels)):
-        prob_f, par_f = levels[k - 1][0], np.asarray(levels[k - 1][2], dtype=np.int64)
+        par_f = np.asarray(levels[k - 1][2], dtype=np.int64)
         prob_c = levels[k][0]
+        assert len(prob_c.point_vertices) == 0, "point fluxes (1D problems) have no rule on a coarse level"
         fine = plans[-1]
         nvc = prob_c.coords.shape[0]
         is_copy = par_f[:, 0] == par_f[:, 1]
@@ -276,49 +206,40 @@ def partition_hierarchy(levels, nparts: int, rank: int, n_global_aggregates: int
         if (copy < 0).any():
             raise ValueError("level %d: a coarse vertex has no copy on the finer level (the meshes are not nested)" % k)
         owner_c = fine.owner[copy]
-        pos_c = fine.pos[copy]
-        agg_c = fine.aggregate[copy]
         cells = prob_c.cells
-        touch = [(owner_c[cells] == q).any(axis=1) for q in range(nparts)]
+        # the first (lowest cell id) cell that contains each vertex
+        in_cells, at = np.unique(cells.ravel(), return_index=True)
+        first_cell = np.full(nvc, -1, dtype=np.int64)
+        first_cell[in_cells] = at // cells.shape[1]
         lcells, ghost_sets = [], []
         for q in range(nparts):
             need = np.unique(par_f[fine.owner == q].ravel())
-            lc = cells[touch[q]]
+            lc = cells[(owner_c[cells] == q).any(axis=1)]
             have = np.zeros(nvc, dtype=bool)
             have[lc.ravel()] = True
             missing = need[~have[need]]
-            if len(missing):
-                # one cell per missing parent: the first (lowest cell id) that contains it
-                first = np.full(nvc, -1, dtype=np.int64)
-                flat = cells.ravel()
-                cid = np.repeat(np.arange(cells.shape[0]), cells.shape[1])
-                order = np.argsort(flat, kind="stable")
-                fv, fc = flat[order], cid[order]
-                starts = np.searchsorted(fv, missing)
-                assert (fv[starts] == missing).all(), "a parent vertex belongs to no cell"
-                first[missing] = fc[starts]
-                lc = np.concatenate([lc, cells[np.unique(first[missing])]])
+            if len(missing):   # one cell per missing parent
+                assert (first_cell[missing] >= 0).all(), "a parent vertex belongs to no cell"
+                lc = np.concatenate([lc, cells[np.unique(first_cell[missing])]])
             lcells.append(lc)
             verts = np.unique(lc)
             ghost_sets.append(verts[owner_c[verts] != q])
-        dom_c = _level_local_domain(prob_c, owner_c, rank, nparts, lcells[rank], ghost_sets)
-        lverts_c = np.concatenate([dom_c.owned, dom_c.ghosts])
-        perm_c = np.argsort(pos_c[lverts_c], kind="stable").astype(np.int32)
-        part_c = _part_dict(dom_c, rank, nparts, nag, agg_c)
+        coarse = _level_plan(prob_c, fine.pos[copy], fine.aggregate[copy], owner_c, rank, nparts, nag, lcells[rank], ghost_sets)
         # parents of the finer level's local vertices in this level's local file order
-        g2l_c = -np.ones(nvc, dtype=np.int64)
-        g2l_c[lverts_c] = np.arange(len(lverts_c))
-        lverts_f = np.concatenate([fine.domain.owned, fine.domain.ghosts])
-        lpar = g2l_c[par_f[lverts_f]].astype(np.int32)
-        assert (lpar[:fine.domain.n_owned] >= 0).all(), "both parents of every owned fine vertex must be local"
+        fine.parents = coarse.domain.g2l[par_f[fine.domain.lverts]].astype(np.int32)
+        assert (fine.parents[:fine.domain.n_owned] >= 0).all(), "both parents of every owned fine vertex must be local"
         # children of the owned coarse vertices: every fine vertex naming one as a parent is local on the finer level
-        g2l_f = -np.ones(par_f.shape[0], dtype=np.int64)
-        g2l_f[lverts_f] = np.arange(len(lverts_f))
         kid_of_owned = (owner_c[par_f] == rank).any(axis=1)
-        assert (g2l_f[np.nonzero(kid_of_owned)[0]] >= 0).all(), "every child of an owned coarse vertex must be local on the finer level"
-        fine.parents = lpar
-        plans.append(LevelPlan(domain=dom_c, perm=perm_c, part=part_c, parents=None, owner=owner_c, pos=pos_c, aggregate=agg_c))
+        assert (fine.domain.g2l[np.nonzero(kid_of_owned)[0]] >= 0).all(), "every child of an owned coarse vertex must be local on the finer level"
+        plans.append(coarse)
     return plans
+
+
+def partition_plan(prob: Problem, nparts: int, rank: int, n_global_aggregates: int = None):
+    """Everything rank `rank` needs for ``gmpnp_create_partition``: (LocalDomain, local perm, partition dict) of the one-level
+    hierarchy of `prob`."""
+    plan = partition_hierarchy([(prob, None, None)], nparts, rank, n_global_aggregates)[0]
+    return plan.domain, plan.perm, plan.part
 
 
 class PartitionedSolver:
@@ -342,7 +263,7 @@ class PartitionedSolver:
         ``levels`` (``problem.pore_hierarchy``, finest first; ``prob`` is its finest problem): the geometric multilevel term of the
         preconditioner across the partitions (``partition_hierarchy``; gmpnp_attach_coarse_level + gmpnp_group_attach_coarse_group),
         ``ml_theta`` / ``ml_sweeps`` as on one GPU.  Not over the peer transport (refused by the library)."""
-        from ctypes import byref, c_void_p, create_string_buffer
+        from ctypes import c_void_p
         if rank is not None:
             # one rank per process: torch.distributed carries the set-up (mailbox handles, communicator id, host-staged collectives).
             # PyTorch first, THEN libgmpnp.so: the library then binds to the HIP runtime PyTorch ships instead of bringing the
@@ -354,119 +275,120 @@ class PartitionedSolver:
         self.nparts, self.rank = nparts, rank
         self.nv_global, self.nf = prob.coords.shape[0], prob.nf
         self.ranks = list(range(nparts)) if rank is None else [rank]
-        self.doms, self.devs = [], []
-        self.level_devs, self._level_groups = [], []   # [level k >= 1][local rank]: the coarse levels of the multilevel term
-        plans = []
-        for r in self.ranks:
-            if levels is not None and len(levels) > 1:
-                plans.append(partition_hierarchy(levels, nparts, r, n_global_aggregates))
-                dom, perm, part = plans[-1][0].domain, plans[-1][0].perm, plans[-1][0].part
-            else:
-                dom, perm, part = partition_plan(prob, nparts, r, n_global_aggregates)
-            self.doms.append(dom)
-            self.devs.append(backend.DeviceSolver(dom.problem, device_id=device_id, perm=perm, partition=part, **device_kwargs))
-        if plans:
-            # level handles of every local rank, each attached below the next-finer one of its rank (as PoreRun does on one GPU)
-            for k in range(1, len(plans[0])):
-                self.level_devs.append([backend.DeviceSolver(pl[k].domain.problem, device_id=device_id, perm=pl[k].perm, partition=pl[k].part,
-                                                             shared_device=1) for pl in plans])
-            for i, pl in enumerate(plans):
-                finer = self.devs[i]
-                for k in range(1, len(pl)):
-                    finer.attach_coarse_level(self.level_devs[k - 1][i], pl[k - 1].parents, theta=ml_theta, sweeps=ml_sweeps)
-                    finer = self.level_devs[k - 1][i]
-        self._comm = c_void_p()
-        self._group = c_void_p()
+        self._comm, self._group, self._level_groups = c_void_p(), c_void_p(), []
         self.transport = transport if rank is not None else "in-process"
-        if rank is not None and transport == "peer":
-            import torch
-            import torch.distributed as tdist
-            if not (tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() == nparts):
-                raise RuntimeError("the peer transport needs an initialised torch.distributed group of %d ranks (to gather the mailbox handles)" % nparts)
-            # Every step is agreed on by ALL ranks before anyone goes on: a rank that cannot allocate or map a mailbox (no peer
-            # access to a GPU, IPC refused) must not leave the others waiting in a collective it never joins.
-            mine = create_string_buffer(backend.PEER_HANDLE_BYTES)
-            err = None
-            try:
-                self._check(self.lib.gmpnp_group_peer_begin(self.devs[0]._h, byref(self._group), mine))
-            except backend.GmpnpError as e:
-                err = e
-            dev = "cuda" if tdist.get_backend() == "nccl" else "cpu"
-            t = torch.tensor(list(mine.raw) + [0 if err is None else 1], dtype=torch.uint8, device=dev)
-            parts = [torch.empty_like(t) for _ in range(nparts)]
-            tdist.all_gather(parts, t)      # also the point after which every rank's mailbox exists
-            rows = [x.cpu().tolist() for x in parts]
-            if err is None and not any(r[-1] for r in rows):
-                allh = create_string_buffer(backend.PEER_HANDLE_BYTES * nparts)
-                allh.raw = b"".join(bytes(r[:-1]) for r in rows)
-                try:
-                    self._check(self.lib.gmpnp_group_peer_connect(self._group, allh))
-                except backend.GmpnpError as e:
-                    err = e
-            elif err is None:
-                err = RuntimeError("rank(s) %s could not set up a mailbox" % [q for q, r in enumerate(rows) if r[-1]])
-            flag = torch.tensor([0 if err is None else 1], dtype=torch.int32, device=dev)
-            tdist.all_reduce(flag, op=tdist.ReduceOp.MAX)   # (also: every mailbox is mapped everywhere from here on)
-            if int(flag[0]):
-                self.transport = "peer (failed)"
-                self.close()
-                raise RuntimeError("peer-mailbox transport not available: %s" % (err if err is not None else "another rank could not map a mailbox"))
-            # All ranks must run the SAME form (form 2 leaves the exchange behind the last launch of a solve out, so the sequence
-            # numbers of the two forms drift apart): a rank whose launch would not be resident with the exchange workgroups in
-            # front takes everybody back to separate launches.
-            self._check(self.lib.gmpnp_group_set_exchange_form(self._group, int(exchange_form)))
-            form = torch.tensor([int(self.lib.gmpnp_group_exchange_form(self._group))], dtype=torch.int32, device=dev)
-            tdist.all_reduce(form, op=tdist.ReduceOp.MIN)
-            if int(form[0]) != 2:
-                self._check(self.lib.gmpnp_group_set_exchange_form(self._group, 1))
-            self._attach_level_groups()
-            return
-        if rank is not None and transport == "host":
-            self._make_host_transport(rank, nparts)
-            self._check(self.lib.gmpnp_group_create_hosted(self.devs[0]._h, byref(self._host_transport), byref(self._group)))
-            self._attach_level_groups()
-            return
-        if rank is not None:
-            idbuf = create_string_buffer(backend.COMM_ID_BYTES)
-            if nparts > 1 or use_torch_dist:
-                import torch
-                import torch.distributed as tdist
-                if tdist.is_available() and tdist.is_initialized():
-                    if rank == 0:
-                        self._check(self.lib.gmpnp_comm_unique_id(idbuf))
-                    dev = "cuda" if tdist.get_backend() == "nccl" else "cpu"
-                    t = torch.tensor(list(idbuf.raw), dtype=torch.uint8, device=dev)
-                    tdist.broadcast(t, src=0)
-                    idbuf = create_string_buffer(backend.COMM_ID_BYTES)
-                    idbuf.raw = bytes(t.cpu().tolist())
-                elif nparts == 1:
-                    self._check(self.lib.gmpnp_comm_unique_id(idbuf))
-                else:
-                    raise RuntimeError("torch.distributed is not initialised: the communicator id cannot reach the other ranks")
-            else:
-                self._check(self.lib.gmpnp_comm_unique_id(idbuf))
-            self._check(self.lib.gmpnp_comm_create(idbuf, rank, nparts, device_id, byref(self._comm)))
-        handles = (c_void_p * len(self.devs))(*[d._h for d in self.devs])
-        self._check(self.lib.gmpnp_group_create(len(self.devs), handles, self._comm if rank is not None else None, byref(self._group)))
-        self._attach_level_groups()
-
-    def _attach_level_groups(self):
-        """One group per coarse level over this solver's transport (the same communicator / host callbacks), attached below the
-        next-finer level's group: it carries that level's collectives (gmpnp_group_attach_coarse_group)."""
-        from ctypes import byref, c_void_p, create_string_buffer
+        # handles: [local rank] of the finest level, [level k >= 1][local rank] of the coarse levels of the multilevel term
+        plans = [partition_hierarchy(levels or [(prob, None, None)], nparts, r, n_global_aggregates) for r in self.ranks]
+        self.doms = [pl[0].domain for pl in plans]
+        self.devs = [backend.DeviceSolver(pl[0].domain.problem, device_id=device_id, perm=pl[0].perm, partition=pl[0].part, **device_kwargs)
+                     for pl in plans]
+        self.level_devs = [[backend.DeviceSolver(pl[k].domain.problem, device_id=device_id, perm=pl[k].perm, partition=pl[k].part, shared_device=1)
+                            for pl in plans] for k in range(1, len(plans[0]))]
+        for i, pl in enumerate(plans):   # every level attached below the next-finer one of its rank
+            backend.attach_level_chain([self.devs[i]] + [devs[i] for devs in self.level_devs], [p.parents for p in pl], ml_theta, ml_sweeps)
+        if self.transport == "peer":
+            self._connect_peer(exchange_form)
+        elif self.transport == "host":
+            self._connect_host()
+        elif rank is None:
+            self._group = self._new_group(self.devs)   # in-process: the exchanges are device copies between the handles
+        else:
+            self._connect_rccl(device_id, use_torch_dist)
+        # one group per coarse level over the same transport, attached below the next-finer level's group: it carries that level's
+        # collectives (gmpnp_group_attach_coarse_group)
         finer = self._group
         for devs in self.level_devs:
-            g = c_void_p()
-            if self.transport == "peer":
-                self._check(self.lib.gmpnp_group_peer_begin(devs[0]._h, byref(g), create_string_buffer(self.backend.PEER_HANDLE_BYTES)))
-            elif self.transport == "host":
-                self._check(self.lib.gmpnp_group_create_hosted(devs[0]._h, byref(self._host_transport), byref(g)))
+            self._level_groups.append(self._new_group(devs))
+            self._check(self.lib.gmpnp_group_attach_coarse_group(finer, self._level_groups[-1]))
+            finer = self._level_groups[-1]
+
+    def _new_group(self, devs, mailbox=None):
+        """A group of the handles `devs` (one level of the local ranks) over this solver's transport: the peer form hands this
+        rank's mailbox handle back in `mailbox`, the host form takes the callbacks, the others the communicator (none in-process)."""
+        from ctypes import byref, c_void_p, create_string_buffer
+        g = c_void_p()
+        if self.transport == "peer":
+            self._check(self.lib.gmpnp_group_peer_begin(devs[0]._h, byref(g), mailbox if mailbox is not None else create_string_buffer(self.backend.PEER_HANDLE_BYTES)))
+        elif self.transport == "host":
+            self._check(self.lib.gmpnp_group_create_hosted(devs[0]._h, byref(self._host_transport), byref(g)))
+        else:
+            handles = (c_void_p * len(devs))(*[d._h for d in devs])
+            self._check(self.lib.gmpnp_group_create(len(devs), handles, self._comm if self.rank is not None else None, byref(g)))
+        return g
+
+    def _connect_peer(self, exchange_form):
+        """Peer mailboxes: gather every rank's mailbox handle, map them, agree on the exchange form."""
+        from ctypes import create_string_buffer
+        import torch
+        import torch.distributed as tdist
+        backend, nparts = self.backend, self.nparts
+        if not (tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() == nparts):
+            raise RuntimeError("the peer transport needs an initialised torch.distributed group of %d ranks (to gather the mailbox handles)" % nparts)
+        # Every step is agreed on by ALL ranks before anyone goes on: a rank that cannot allocate or map a mailbox (no peer
+        # access to a GPU, IPC refused) must not leave the others waiting in a collective it never joins.
+        mine = create_string_buffer(backend.PEER_HANDLE_BYTES)
+        err = None
+        try:
+            self._group = self._new_group(self.devs, mine)
+        except backend.GmpnpError as e:
+            err = e
+        dev = _default_group_device(tdist)
+        t = torch.tensor(list(mine.raw) + [0 if err is None else 1], dtype=torch.uint8, device=dev)
+        parts = [torch.empty_like(t) for _ in range(nparts)]
+        tdist.all_gather(parts, t)      # also the point after which every rank's mailbox exists
+        rows = [x.cpu().tolist() for x in parts]
+        if err is None and not any(r[-1] for r in rows):
+            allh = create_string_buffer(backend.PEER_HANDLE_BYTES * nparts)
+            allh.raw = b"".join(bytes(r[:-1]) for r in rows)
+            try:
+                self._check(self.lib.gmpnp_group_peer_connect(self._group, allh))
+            except backend.GmpnpError as e:
+                err = e
+        elif err is None:
+            err = RuntimeError("rank(s) %s could not set up a mailbox" % [q for q, r in enumerate(rows) if r[-1]])
+        flag = torch.tensor([0 if err is None else 1], dtype=torch.int32, device=dev)
+        tdist.all_reduce(flag, op=tdist.ReduceOp.MAX)   # (also: every mailbox is mapped everywhere from here on)
+        if int(flag[0]):
+            self.transport = "peer (failed)"
+            self.close()
+            raise RuntimeError("peer-mailbox transport not available: %s" % (err if err is not None else "another rank could not map a mailbox"))
+        # All ranks must run the SAME form (form 2 leaves the exchange behind the last launch of a solve out, so the sequence
+        # numbers of the two forms drift apart): a rank whose launch would not be resident with the exchange workgroups in
+        # front takes everybody back to separate launches.
+        self._check(self.lib.gmpnp_group_set_exchange_form(self._group, int(exchange_form)))
+        form = torch.tensor([int(self.lib.gmpnp_group_exchange_form(self._group))], dtype=torch.int32, device=dev)
+        tdist.all_reduce(form, op=tdist.ReduceOp.MIN)
+        if int(form[0]) != 2:
+            self._check(self.lib.gmpnp_group_set_exchange_form(self._group, 1))
+
+    def _connect_host(self):
+        """Host-staged collectives: the library calls back into torch.distributed."""
+        self._make_host_transport(self.rank, self.nparts)
+        self._group = self._new_group(self.devs)
+
+    def _connect_rccl(self, device_id, use_torch_dist):
+        """The RCCL communicator inside the library, from an id that rank 0 makes and torch.distributed broadcasts."""
+        from ctypes import byref, create_string_buffer
+        backend, rank, nparts = self.backend, self.rank, self.nparts
+        idbuf = create_string_buffer(backend.COMM_ID_BYTES)
+        if nparts > 1 or use_torch_dist:
+            import torch
+            import torch.distributed as tdist
+            if tdist.is_available() and tdist.is_initialized():
+                if rank == 0:
+                    self._check(self.lib.gmpnp_comm_unique_id(idbuf))
+                t = torch.tensor(list(idbuf.raw), dtype=torch.uint8, device=_default_group_device(tdist))
+                tdist.broadcast(t, src=0)
+                idbuf = create_string_buffer(backend.COMM_ID_BYTES)
+                idbuf.raw = bytes(t.cpu().tolist())
+            elif nparts == 1:
+                self._check(self.lib.gmpnp_comm_unique_id(idbuf))
             else:
-                handles = (c_void_p * len(devs))(*[d._h for d in devs])
-                self._check(self.lib.gmpnp_group_create(len(devs), handles, self._comm if self.rank is not None else None, byref(g)))
-            self._level_groups.append(g)
-            self._check(self.lib.gmpnp_group_attach_coarse_group(finer, g))
-            finer = g
+                raise RuntimeError("torch.distributed is not initialised: the communicator id cannot reach the other ranks")
+        else:
+            self._check(self.lib.gmpnp_comm_unique_id(idbuf))
+        self._check(self.lib.gmpnp_comm_create(idbuf, rank, nparts, device_id, byref(self._comm)))
+        self._group = self._new_group(self.devs)
 
     def _check(self, code):
         if code != self.backend.OK:
@@ -515,17 +437,10 @@ class PartitionedSolver:
         (their values never enter anything: ghost rows are masked out of the residual)."""
         nf = self.nf
         dofs, vals = np.asarray(dofs, dtype=np.int64), np.asarray(vals, dtype=np.float64)
-        if not hasattr(self, "_g2l"):
-            self._g2l, self._ghost_dofs = [], []
-            for dom in self.doms:
-                lverts = np.concatenate([dom.owned, dom.ghosts])
-                g2l = -np.ones(self.nv_global, dtype=np.int64)
-                g2l[lverts] = np.arange(len(lverts))
-                self._g2l.append(g2l)
-                self._ghost_dofs.append(np.arange(dom.n_owned * nf, len(lverts) * nf, dtype=np.int64))
-        for g2l, gh, dom, dev in zip(self._g2l, self._ghost_dofs, self.doms, self.devs):
-            lv = g2l[dofs // nf]
+        for dom, dev in zip(self.doms, self.devs):
+            lv = dom.g2l[dofs // nf]
             keep = (lv >= 0) & (lv < dom.n_owned)
+            gh = np.arange(dom.n_owned * nf, len(dom.lverts) * nf, dtype=np.int64)
             dev.set_dirichlet(np.concatenate([lv[keep] * nf + dofs[keep] % nf, gh]), np.concatenate([vals[keep], np.zeros(len(gh))]))
 
     def owned_state(self, previous=False):
@@ -545,8 +460,7 @@ class PartitionedSolver:
             import torch
             import torch.distributed as tdist
             if tdist.is_available() and tdist.is_initialized():
-                dev = "cuda" if tdist.get_backend() == "nccl" else "cpu"
-                t = torch.from_numpy(out).to(dev)
+                t = torch.from_numpy(out).to(_default_group_device(tdist))
                 tdist.all_reduce(t)
                 out = t.cpu().numpy()
         return out.ravel()
@@ -620,6 +534,11 @@ class PartitionedSolver:
         self.close()
 
 
+def _default_group_device(tdist):
+    """Where the tensors of a collective on the default group live: the GPU under nccl, else the host."""
+    return "cuda" if tdist.get_backend() == "nccl" else "cpu"
+
+
 def init_process_group_from_env(backend="nccl", device=None):
     """The process group of a process that ``torch.distributed.run`` started: RANK / WORLD_SIZE / LOCAL_RANK from the environment
     and, with a world size above 1, the default group initialised (``backend`` "nccl": bound to cuda:`device`, LOCAL_RANK by
@@ -681,6 +600,4 @@ def host_transport_callbacks(group=None):
 
 
 def scatter_local(dom: LocalDomain, u_global):
-    nf = dom.nf
-    lverts = np.concatenate([dom.owned, dom.ghosts])
-    return u_global.reshape(-1, nf)[lverts].ravel().copy()
+    return u_global.reshape(-1, dom.nf)[dom.lverts].ravel().copy()

@@ -72,20 +72,12 @@ class PoreRun:
         if refine:  # uniformly refined copy of the reference mesh (not a reference feature: roofline studies)
             from .mesh import Mesh
             self.mesh = Mesh(dim=3, coords=self.problem.coords, cells=self.problem.cells)
+        sys_kwargs = dict(levels=self._levels, ml_theta=ml_theta, ml_sweeps=ml_sweeps, **(device_kwargs or {}))
         if partition:
             from .solver import PartitionedSystem
-            self.sys = PartitionedSystem(self.problem, partition[0], rank=partition[1], levels=self._levels, ml_theta=ml_theta, ml_sweeps=ml_sweeps,
-                                         **(device_kwargs or {}))
+            self.sys = PartitionedSystem(self.problem, partition[0], rank=partition[1], **sys_kwargs)
         else:
-            self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
-            if self._levels:   # coarser levels: ordinary handles of the parent meshes, attached below the finest one
-                from . import backend
-                dev_id = (device_kwargs or {}).get("device_id", 0)
-                finer = self.sys.dev
-                for k in range(1, len(self._levels)):
-                    coarse = backend.DeviceSolver(self._levels[k][0], device_id=dev_id, shared_device=1)
-                    finer.attach_coarse_level(coarse, self._levels[k - 1][2], theta=ml_theta, sweeps=ml_sweeps)
-                    finer = coarse
+            self.sys = GMPNPSystem(self.problem, **sys_kwargs)
         self.solver_parameters = solver_parameters or SOLVER_PARAMETERS
         self.tot_num_steps = self.pp.tot_num_steps if num_steps is None else int(num_steps)
         nv = self.mesh.num_vertices
@@ -104,39 +96,26 @@ class PoreRun:
         self.newton_its = []
 
     def step(self, verbose=True):
-        if self.glue == "device":
-            return self._step_device(verbose)
+        """One time step.  The glue decides where the medians and the CO2 minimum come from and what a history row is; the two
+        settings give the same values.  (The row and the minimum are taken in front of ``set_bcs`` under both: the device glue reads
+        them from the device there, the host glue from the array it has gathered already, where the place makes no difference.)"""
+        device = self.glue == "device"
         self.t += self.pp.dt
         st = self.sys.solve(self.solver_parameters)
-        vals = self.sys.vertex_values()
+        if device:   # the library's column select, no gather of the state; the history keeps this process's owned rows
+            meds, (co2_min,) = device_medians_and_minima(self.sys, (1, 2, 3, 7), (4,))
+            row = [v for _, v in self.sys.owned_vertex_values()]
+        else:
+            row = self.sys.vertex_values()
+            meds, co2_min = column_medians(row, (1, 2, 3, 7)), float(np.amin(row[:, 4]))
+        self.history.append(row)
         # medians of the scaled ion concentrations -> Sechenov -> new CO2 Dirichlet value at S1 (3D:817-838)
-        co2 = self.pp.sechenov_co2_scaled(*column_medians(vals, (1, 2, 3, 7)))
-        self.co2_bc = co2
-        self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, co2))
-        self.history.append(vals)
-        self.CO2_min = float(np.amin(vals[:, 4]))
-        self.sys.assign_previous()
-        self.newton_its.append(st["iterations"])
-        if verbose:
-            print(self.CO2_min)
-            print(datetime.now().strftime("%y-%m-%d-%H-%M-%S"))
-            print(self.n)
-        self.n += 1
-        return st
-
-    def _step_device(self, verbose):
-        """``step`` with the per-step glue on the device: the same values, no gather of the state."""
-        self.t += self.pp.dt
-        st = self.sys.solve(self.solver_parameters)
-        (meds, (co2_min,)) = device_medians_and_minima(self.sys, (1, 2, 3, 7), (4,))
-        co2 = self.pp.sechenov_co2_scaled(*meds)
-        self.co2_bc = co2
-        self.history.append([v for _, v in self.sys.owned_vertex_values()])
-        self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, co2))
+        self.co2_bc = self.pp.sechenov_co2_scaled(*meds)
+        self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, self.co2_bc))
         self.CO2_min = co2_min
         self.sys.assign_previous()
         self.newton_its.append(st["iterations"])
-        if verbose and self.rank in (None, 0):
+        if verbose and (not device or self.rank in (None, 0)):
             print(self.CO2_min)
             print(datetime.now().strftime("%y-%m-%d-%H-%M-%S"))
             print(self.n)
@@ -149,7 +128,7 @@ class PoreRun:
         if self.glue == "host":
             return np.stack([row[:, i] for row in self.history])
         parts = [(ids, np.stack([row[d][:, i] for row in self.history])) for d, ids in enumerate(self.owned_ids)]
-        if self.rank is not None and self.sys.ps.nparts > 1:
+        if self.sys.several_processes:
             import torch.distributed as tdist
             if not (tdist.is_available() and tdist.is_initialized()):
                 raise RuntimeError("one rank per process: the history is gathered through torch.distributed, which is not initialised")

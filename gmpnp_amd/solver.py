@@ -9,13 +9,13 @@ from . import backend
 from .problem import Problem
 
 
-class GMPNPSystem:
-    """The objects a reference script holds between ``FunctionSpace`` and the time loop: mesh, forms (model tables),
-    ``u``/``u_n`` (device resident) and the ``bcs`` list."""
+class _System:
+    """What the two operator surfaces share: the problem, the iteration counters and the calls that go to `solver`, the object that
+    holds the state and runs Newton (a ``DeviceSolver``, or a ``PartitionedSolver`` in GLOBAL file vertex order)."""
 
-    def __init__(self, problem: Problem, **device_kwargs):
+    def __init__(self, problem: Problem, solver):
         self.problem = problem
-        self.dev = backend.DeviceSolver(problem, **device_kwargs)
+        self._solver = solver
         self.nv = problem.coords.shape[0]
         self.nf = problem.nf
         self.newton_iterations = 0
@@ -25,21 +25,21 @@ class GMPNPSystem:
     # u = Function(V) is zero-initialised; u_n = interpolate(u_0, V)  (3D:425-432, 1D:320-326)
     def initialise(self, u0_values):
         u_n = np.tile(np.asarray(u0_values, dtype=np.float64), self.nv)
-        self.dev.set_state(np.zeros(self.problem.ndof), u_n)
+        self.set_state(np.zeros(self.problem.ndof), u_n)
+
+    def set_state(self, u=None, un=None):
+        """u and / or u_n from flat arrays in file vertex order (None: left as it is)."""
+        self._solver.set_state(u, un)
 
     def set_bcs(self, dofs, vals):
         self.problem.bc_dofs, self.problem.bc_vals = dofs, vals
-        self.dev.set_dirichlet(dofs, vals)
-
-    def set_model(self, model):
-        self.problem.model = model
-        self.dev.set_model(model)
+        self._solver.set_dirichlet(dofs, vals)
 
     def solve(self, solver_parameters=None):
         """``solve(F == 0, u, bcs, solver_parameters=...)``.  RuntimeError on non-convergence, as DOLFIN."""
         opts = backend.newton_options(solver_parameters, dim=self.problem.coords.shape[1])
         try:
-            st = self.dev.newton_solve(opts)
+            st = self._solver.newton_solve(opts)
         except backend.GmpnpError as e:
             if e.code == backend.ERR_NOT_CONVERGED:
                 raise RuntimeError("Newton solver did not converge because maximum number of iterations reached") from e
@@ -55,18 +55,37 @@ class GMPNPSystem:
 
     def vertex_values(self):
         """(nv, nf) array = compute_vertex_values() of every sub-function, file vertex order."""
-        return self.dev.get_state().reshape(self.nv, self.nf)
+        return self._solver.get_state().reshape(self.nv, self.nf)
+
+    def column_select(self, fields, ranks):
+        """k-th smallest values of vertex columns of u, on the device (gmpnp_column_select / gmpnp_group_column_select: over ALL
+        ranks' owned rows, collective): (values, nan flag)."""
+        return self._solver.column_select(fields, ranks)
+
+    def assign_previous(self):
+        self._solver.assign_previous()
+
+
+class GMPNPSystem(_System):
+    """The objects a reference script holds between ``FunctionSpace`` and the time loop: mesh, forms (model tables),
+    ``u``/``u_n`` (device resident) and the ``bcs`` list."""
+    several_processes = False
+
+    def __init__(self, problem: Problem, levels=None, ml_theta: float = 2.0, ml_sweeps: int = 4, **device_kwargs):
+        """``levels`` (``problem.pore_hierarchy``, finest first, ``problem`` its finest): the geometric multilevel term of the
+        preconditioner; the coarser levels are ordinary handles of the parent meshes on the same device, owned by this system."""
+        self.dev = backend.DeviceSolver(problem, **device_kwargs)
+        super().__init__(problem, self.dev)
+        self._coarse = [backend.DeviceSolver(lv[0], device_id=device_kwargs.get("device_id", 0), shared_device=1) for lv in (levels or [])[1:]]
+        backend.attach_level_chain([self.dev] + self._coarse, [lv[2] for lv in levels or []], ml_theta, ml_sweeps)
+
+    def set_model(self, model):
+        self.problem.model = model
+        self.dev.set_model(model)
 
     def owned_vertex_values(self):
         """[(vertex ids, (n, nf) values)] of the rows this process owns: here all of them."""
         return [(np.arange(self.nv), self.vertex_values())]
-
-    def column_select(self, fields, ranks):
-        """k-th smallest values of vertex columns of u, on the device (gmpnp_column_select): (values, nan flag)."""
-        return self.dev.column_select(fields, ranks)
-
-    def assign_previous(self):
-        self.dev.assign_previous()
 
     # post-processing of the reference's drivers: project(+-grad(u_X), W) (3D:884-909, 1D:802-805) and the cell-wise
     # projections of the SUPG parameters (1D:599,651-653), on the device
@@ -78,9 +97,11 @@ class GMPNPSystem:
 
     def close(self):
         self.dev.close()
+        for d in self._coarse:
+            d.close()
 
 
-class PartitionedSystem:
+class PartitionedSystem(_System):
     """The same operator surface on ONE problem cut into `nparts` mesh partitions (BASELINE configs[3]):
     the Newton and BiCGStab loops run inside libgmpnp.so across the ranks (gmpnp_group_newton_solve).  `rank` = None keeps
     every rank in this process (one GPU, rehearsal); `rank` = r is the one-process-per-GPU form over RCCL."""
@@ -89,51 +110,16 @@ class PartitionedSystem:
         """``levels`` (``problem.pore_hierarchy``, finest first, ``problem`` its finest): the geometric multilevel term of the
         preconditioner across the partitions (``ml_theta`` / ``ml_sweeps`` as on one GPU)."""
         from .dist import PartitionedSolver
-        self.problem = problem
         self.ps = PartitionedSolver(problem, nparts, rank=rank, levels=levels, ml_theta=ml_theta, ml_sweeps=ml_sweeps, **device_kwargs)
+        super().__init__(problem, self.ps)
         self.dev = self.ps.devs[0]            # this rank's LOCAL partition handle (local vertex numbering)
+        self.several_processes = rank is not None and nparts > 1   # reading the whole state is then a collective
         self._device_kwargs = {k: v for k, v in device_kwargs.items() if k in ("device_id",)}
         self._post = None                     # unpartitioned handle on the global mesh, for post-processing only
-        self.nv = problem.coords.shape[0]
-        self.nf = problem.nf
-        self.newton_iterations = 0
-        self.krylov_iterations = 0
-        self.last_stats = None
-
-    def initialise(self, u0_values):
-        u_n = np.tile(np.asarray(u0_values, dtype=np.float64), self.nv)
-        self.ps.set_state(np.zeros(self.problem.ndof), u_n)
-
-    def set_bcs(self, dofs, vals):
-        self.problem.bc_dofs, self.problem.bc_vals = dofs, vals
-        self.ps.set_dirichlet(dofs, vals)
-
-    def solve(self, solver_parameters=None):
-        opts = backend.newton_options(solver_parameters, dim=3)
-        try:
-            st = self.ps.newton_solve(opts)
-        except backend.GmpnpError as e:
-            if e.code == backend.ERR_NOT_CONVERGED:
-                raise RuntimeError("Newton solver did not converge because maximum number of iterations reached") from e
-            raise
-        self.newton_iterations += st["iterations"]
-        self.krylov_iterations += st["krylov_iterations"]
-        self.last_stats = st
-        return st
-
-    def vertex_values(self):
-        return self.ps.get_state().reshape(self.nv, self.nf)
 
     def owned_vertex_values(self):
         """[(global vertex ids, (n_owned, nf) values)] of this process's partitions: one device-to-host copy each, no collective."""
         return self.ps.owned_state()
-
-    def column_select(self, fields, ranks):
-        """k-th smallest values of vertex columns of u over ALL ranks' owned rows (gmpnp_group_column_select; collective)."""
-        return self.ps.column_select(fields, ranks)
-
-    def assign_previous(self):
-        self.ps.assign_previous()
 
     def _post_handle(self):
         """The projections of the drivers' output stage take GLOBAL vertex arrays: they run on an unpartitioned handle of

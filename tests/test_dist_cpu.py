@@ -23,7 +23,7 @@ def test_partition_and_halo_plan():
     prob = _small_problem()
     nv = prob.coords.shape[0]
     for P in (2, 4):
-        owner = dist.slab_owner(prob.coords, prob.cells, P)
+        owner = dist.slab_cut(prob, P)[2]
         counts = np.bincount(owner, minlength=P)
         assert counts.sum() == nv and counts.max() - counts.min() <= 1
         doms = [dist.build_local_domain(prob, owner, r, P) for r in range(P)]
@@ -122,3 +122,22 @@ def test_partition_plan_is_consistent(nparts, pore10):
             theirs = ql[qp["recv_vertices"][qp["recv_ptr"][jj]:qp["recv_ptr"][jj + 1]]]
             assert len(mine) > 0 and np.array_equal(mine, theirs)                   # same global vertices, same order
     assert (seen == 1).all()
+
+
+@pytest.mark.parametrize("nparts", [1, 2, 3, 4, 5, 8])
+def test_slab_cut_owners_are_equal_count_slabs(nparts, pore10):
+    """The ownership ranges that come out of the coarse-slab boundaries (dist.slab_cut: nag = m nparts slabs, m to a rank) are the
+    `nparts` equal-count ranges of the slab order: (nv k m) // (nparts m) == (nv k) // nparts."""
+    from gmpnp_amd import dist
+    from gmpnp_amd.backend import slab_permutation
+    prob = pore10[2]
+    nv = prob.coords.shape[0]
+    perm = slab_permutation(prob.coords, prob.cells, window=0)
+    want = np.empty(nv, dtype=np.int32)
+    for p in range(nparts):
+        want[perm[(nv * p) // nparts:(nv * (p + 1)) // nparts]] = p
+    pos, aggregate, owner = dist.slab_cut(prob, nparts)
+    assert owner.dtype == np.int32 and np.array_equal(owner, want)
+    assert np.array_equal(perm[pos], np.arange(nv))
+    m = dist.default_global_aggregates(nparts) // nparts
+    assert np.array_equal(aggregate // m, owner) and (np.diff(aggregate[perm]) >= 0).all()

@@ -43,11 +43,7 @@ def make_system(problem, nparts):
 
 
 def set_u(sys_, vals):
-    u = np.ascontiguousarray(vals, dtype=np.float64).ravel()
-    if hasattr(sys_, "ps"):
-        sys_.ps.set_state(u, None)
-    else:
-        sys_.dev.set_state(u, None)
+    sys_.set_state(np.ascontiguousarray(vals, dtype=np.float64).ravel(), None)
 
 
 def adversarial(nv, rng):
