@@ -497,12 +497,7 @@ class DeviceSolver:
         non-convergence like [3P] DOLFIN (error_on_nonconvergence=True)."""
         st = CNewtonStats()
         code = self.lib.gmpnp_newton_solve(self._h, byref(options), byref(st))
-        stats = {"iterations": st.iterations, "converged": bool(st.converged),
-                 "krylov_iterations": st.krylov_iterations,
-                 "residuals": [st.residuals[i] for i in range(st.n_residuals)],
-                 "krylov_per_iteration": [st.krylov_per_iteration[i] for i in range(min(st.iterations, MAX_HISTORY))],
-                 "ms_assemble": st.ms_assemble, "ms_setup": st.ms_setup, "ms_krylov": st.ms_krylov,
-                 "ms_total": st.ms_total, "direct_solves": st.direct_solves, "steric_excursion": st.steric_excursion}
+        stats = dict(self.stats_dict(st), ms_assemble=st.ms_assemble, ms_setup=st.ms_setup, ms_krylov=st.ms_krylov)
         if code == ERR_NOT_CONVERGED and not error_on_nonconvergence:
             return stats
         self._check(code)

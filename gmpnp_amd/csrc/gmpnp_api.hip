@@ -15,6 +15,7 @@
 #include "gmpnp_band_lu.h"
 #include "gmpnp_dist_kernels.h"
 #include "gmpnp_multilevel.h"
+#include "gmpnp_host_rules.h"
 
 using namespace gmpnp;
 
@@ -317,6 +318,13 @@ int launch_jac_gather(gmpnp_solver* s) {
 
 int drain_spmv_events(gmpnp_solver* s);
 
+// sum of row `row` (0 .. 2) of the pinned partials the reduction kernels store (k_res_gather, k_true_residual: row 0; k_dots3: three)
+double sum_partials(const gmpnp_solver* s, int row) {
+  double acc = 0.0;
+  for (int i = 0; i < s->n_resblocks; ++i) acc += s->h_part[(size_t)row * s->n_resblocks + i];
+  return acc;
+}
+
 // residual at the current u: returns ||b||_2 and the device status flags
 template <int DIM, int NF>
 int residual(gmpnp_solver* s, bool want_j, double* norm, int* flags) {
@@ -325,9 +333,7 @@ int residual(gmpnp_solver* s, bool want_j, double* norm, int* flags) {
   // the partials and the status word land in pinned host memory by the kernel's own stores: no copy in the stream
   HIP_TRY(hipStreamSynchronize(s->stream));
   rc = drain_spmv_events(s); if (rc) return rc;
-  double acc = 0.0;
-  for (int i = 0; i < s->n_resblocks; ++i) acc += s->h_part[i];
-  *norm = std::sqrt(acc);
+  *norm = std::sqrt(sum_partials(s, 0));
   *flags = *s->h_status;
   return GMPNP_OK;
 }
@@ -376,9 +382,7 @@ int setup_preconditioner(gmpnp_solver* s, int mode, bool refresh = true, bool re
       HIP_TRY(hipEventRecord(s->ev_chain, s->stream2));
       s->chain_in_flight = true;
     } else if (refresh_coarse) {
-      launch_coarse_chain<NF>(s, s->c, s->stream);   // inverse of this matrix, now (a pending side-stream result is dropped)
-      if (async) {   // ... and the double buffer keeps rolling: nothing in flight, the next set-up starts a new chain
-      }
+      launch_coarse_chain<NF>(s, s->c, s->stream);   // inverse of this matrix, now (a pending side-stream result is dropped; the next set-up starts a new chain)
     }
   }
   HIP_TRY(hipGetLastError());
@@ -423,10 +427,8 @@ int ml_level_apply(gmpnp_solver* top, gmpnp_solver* L) {
                        (const int32_t*)L->ml_child.p, C->c.bcflag, C->ml_r.p, (int)C->ndof);
     rc = ml_level_apply<NF>(top, C); if (rc) return rc;
     hipLaunchKernelGGL((k_ml_prolong_add<NF>), vg, dim3(256), 0, st, (const double*)C->ml_w.p, (const int32_t*)L->ml_par.p, L->c.bcflag, L->ml_w.p, n);
-#ifndef GMPNP_ML_NO_POST   // (A/B builds only: V(1,0) on the intermediate levels)
     residual();
     rc = smooth(L->ks.p, 1.0); if (rc) return rc;
-#endif
   } else {
     for (int k = 1; k < L->ml_sweeps; ++k) { residual(); rc = smooth(L->ks.p, 1.0); if (rc) return rc; }
   }
@@ -567,7 +569,6 @@ template <int NF>
 int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, int maxit, gmpnp_linear_stats_t* st, bool restart = false) {
   const int use_coarse = (mode == GMPNP_LINEAR_BICGSTAB_TWOLEVEL) ? 1 : 0;
   s->c.use_coarse = use_coarse;
-  const int n = s->ndof;
   s->fused_seq = 0;
   const KrylovScalars init = krylov_start(s->shadow_src ? s->shadow_rho0 : bnorm * bnorm, bnorm, rtol, atol, maxit);
   // one launch: shadow vector (r_0, or a pseudo-random vector after a breakdown), y = 0, P^T r_0 partials
@@ -579,13 +580,7 @@ int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, in
   hp->done = 0; hp->iters = 0; hp->rr = 0.0;
   std::atomic_thread_fence(std::memory_order_seq_cst);
   const int B = s->burst_iters;
-  // Bursts of B iterations.  The first burst is 3/4 of what the previous solve with this preconditioner
-  // needed; after that the host polls the device flag one burst BEHIND the launches (copy + event, launch the
-  // next burst, then wait for the event), so the read-back latency hides behind queued work.  Kernels of a
-  // converged solve exit at their first instruction.
-  // first burst: 7/8 of the count the same Newton iteration needed one time step ago (solves of one index resemble each
-  // other far more than consecutive solves do: the first of a step is cold, the others are warm-started), else 3/4 of
-  // the previous solve
+  // Bursts of B iterations; kernels of a converged solve exit at their first instruction.
   // With the pinned progress mirror the host keeps up one iteration at a time, so the first burst is insurance against
   // a slow host rather than a way to save polls: half the expected count (measured on the bench, sixteenths of the
   // hint: 0..8 -> 529-533 its/s, 12 -> 525, 14 -> 522, 16 -> 516; more surplus early-exit launches the longer it is).
@@ -675,11 +670,6 @@ int apply_minv(gmpnp_solver* s, int mode, const double* src, double* dst, double
   return GMPNP_OK;
 }
 
-// Krylov solve with the answer checked: BiCGStab stops on its RECURSIVE residual, which can drift away from
-// b - J dx over thousands of iterations (plain Jacobi mode on stiff systems).  After each pass the true residual is
-// formed with the unscaled matrix; if it misses the target grossly (> 1000x), the solve restarts on it (dx accumulates
-// in kx).  stats->residual_norm reports the TRUE residual.
-// rhs in c.kr on entry; dx = kx on return.
 // kr = kb - J kx with the unscaled matrix; returns ||kr|| (synchronises the stream)
 template <int NF>
 int true_residual(gmpnp_solver* s, double* rn) {
@@ -687,38 +677,47 @@ int true_residual(gmpnp_solver* s, double* rn) {
   hipLaunchKernelGGL(k_true_residual, dim3(s->n_resblocks), dim3(kVecBlock), 0, s->stream, (const double*)s->kb.p, (const double*)s->kt.p,
                      s->kr.p, s->c.part_f, (int)s->ndof);
   HIP_TRY(hipStreamSynchronize(s->stream));
-  double acc = 0.0;
-  for (int i = 0; i < s->n_resblocks; ++i) acc += s->h_part[i];
-  *rn = std::sqrt(acc);
+  *rn = std::sqrt(sum_partials(s, 0));
   return GMPNP_OK;
 }
 
-// `warm_scale` != 0: kx holds the previous Newton correction; the solve starts from x0 = warm_scale * kx, i.e. BiCGStab
-// only has to remove b - J x0.  With the reference's damped update (omega = 0.9) consecutive corrections satisfy
-// dx_{k+1} = (1 - omega) dx_k + O(|dx_k|^2), so x0 = (1 - omega) dx_k leaves a second-order small residual and the
-// same absolute target is reached in far fewer iterations.  Falls back to x0 = 0 when x0 does not reduce the residual.
+// Krylov solve with the answer checked: BiCGStab stops on its RECURSIVE residual, which can drift away from
+// b - J dx over thousands of iterations (plain Jacobi mode on stiff systems).  After each pass the true residual is
+// formed with the unscaled matrix; if it misses the target grossly (> 1000x), the solve restarts on it (dx accumulates
+// in kx).  stats->residual_norm reports the TRUE residual.
+// rhs in c.kr on entry; dx = kx on return.
+// A predicted start (gmpnp_host_rules.h) leaves BiCGStab only b - J x0 to remove: the same absolute target is reached in far
+// fewer iterations.  Falls back to x0 = 0 when x0 does not reduce the residual.
+// What the caller asks for; the defaults: a cold solve, checked after every pass.
+struct KrylovRequest {
+  int mode = GMPNP_LINEAR_BICGSTAB_TWOLEVEL, maxit = 1;
+  double bnorm = 0.0, rtol = 0.0, atol = 0.0;   // ||rhs||; targets on ||b - J x||
+  int verify_above = 0;          // a first pass that converged within this many iterations goes unchecked (short solves do not drift)
+  double warm_scale = 0.0, warm_prev = 0.0;   // predicted_start(): x0 = warm_scale * kx + warm_prev * kxp; (0, 0) = cold start
+  bool rhs_ready = false;        // k_res_gather already left b in kr AND kb (Newton)
+  bool x0_ready = false;         // kx already holds x0 (left by the previous Newton update)
+  bool dots_in_flight = false;   // w = J x0 and its dot products were started on the side stream (ev_dots)
+  bool refine = false;           // go on while passes still halve the true residual (gmpnp_linear_solve)
+  const NewtonUpdate* upd = nullptr;   // Newton update + next predicted start, applied by the final M^-1 launch of a normal solve
+  bool upd_done = false;         // out: that launch applied `upd`
+};
+
 template <int NF>
-int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, int maxit, gmpnp_linear_stats_t* st,
-                    int verify_above = 0, double warm_scale = 0.0, double warm_prev = 0.0, const double* rhs_src = nullptr,
-                    bool rhs_ready = false, bool x0_ready = false, const NewtonUpdate* upd = nullptr, bool* upd_done = nullptr,
-                    bool dots_in_flight = false, bool refine = false) {
+int krylov_verified(gmpnp_solver* s, gmpnp_linear_stats_t* st, KrylovRequest& q) {
   const int n = s->ndof;
-  if (!std::isfinite(bnorm)) return fail(GMPNP_ERR_LINEAR, "right-hand side of the linear system is not finite");
-  const double tol = std::max(rtol * bnorm, atol);
-  // kb keeps the right-hand side; `rhs_src` (Newton: F) saves the caller's separate copy into kr
-  // `rhs_ready`: k_res_gather already left b in kr and kb (Newton)
-  if (rhs_ready) {}
-  else if (rhs_src) hipLaunchKernelGGL(k_copy2, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, s->kr.p, s->kb.p, rhs_src, n);
-  else HIP_TRY(hipMemcpyAsync(s->kb.p, s->kr.p, n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-  if (upd_done) *upd_done = false;
-  gmpnp_linear_stats_t total{}; total.rhs_norm = bnorm;
-  double rhs_norm = bnorm;
+  if (!std::isfinite(q.bnorm)) return fail(GMPNP_ERR_LINEAR, "right-hand side of the linear system is not finite");
+  const double tol = std::max(q.rtol * q.bnorm, q.atol);
+  // kb keeps the right-hand side
+  if (!q.rhs_ready) HIP_TRY(hipMemcpyAsync(s->kb.p, s->kr.p, n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+  q.upd_done = false;
+  gmpnp_linear_stats_t total{}; total.rhs_norm = q.bnorm;
+  double rhs_norm = q.bnorm;
   bool warm = false;
-  if (warm_scale != 0.0 && bnorm > 0.0) {
+  if (q.warm_scale != 0.0 && q.bnorm > 0.0) {
     // x0 = warm_scale * kx + warm_prev * kxp (left in kx by the previous Newton update when `x0_ready`); accepted when
     // it removes at least half of the residual: one plain SpMV, three dots, one host round trip
-    if (!x0_ready) hipLaunchKernelGGL(k_warm_start, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, warm_scale, warm_prev, n);
-    if (dots_in_flight) {   // w = J x0 and the dot products were started on the side stream right after the Jacobian gather
+    if (!q.x0_ready) hipLaunchKernelGGL(k_warm_start, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, q.warm_scale, q.warm_prev, n);
+    if (q.dots_in_flight) {   // w = J x0 and the dot products were started on the side stream right after the Jacobian gather
       HIP_TRY(hipEventSynchronize(s->ev_dots));
       HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_dots, 0));   // kt is read by k_start_residual below
     } else {
@@ -727,15 +726,12 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
                          s->c.part_f, n, s->n_resblocks);
       HIP_TRY(hipStreamSynchronize(s->stream));
     }
-    double wb = 0.0, ww = 0.0, bb = 0.0;
-    for (int i = 0; i < s->n_resblocks; ++i) { wb += s->h_part[i]; ww += s->h_part[s->n_resblocks + i]; bb += s->h_part[2 * s->n_resblocks + i]; }
     // The predicted correction is taken as it is.  (Scaling it by the minimal-residual multiple (w,b)/(w,w) makes |r0|
     // smaller every time and BiCGStab slower all the same: 18.8k instead of 17.3k iterations over the bench, round 1.)
-    const double rn2 = bb - 2.0 * wb + ww;  // ||b - w||^2
-    if (rn2 == rn2 && rn2 >= 0.0 && rn2 < 0.25 * bb) {
+    if (accept_predicted_start(sum_partials(s, 0), sum_partials(s, 1), sum_partials(s, 2), &rhs_norm)) {
       hipLaunchKernelGGL(k_start_residual, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p,
                          (const double*)s->kt.p, n);
-      warm = true; rhs_norm = std::sqrt(rn2);
+      warm = true;
     }  // else: kr still holds b, cold start
   }
   // Restarted BiCGStab.  A pass runs at most `restart_every` iterations; then (and after a breakdown) the true residual
@@ -752,7 +748,7 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
   for (int pass = 0;; ++pass) {
     gmpnp_linear_stats_t ls{};
     int rc = GMPNP_OK;
-    const int cap = std::min(restart_every, maxit - total.iterations);
+    const int cap = std::min(restart_every, q.maxit - total.iterations);
     if (rhs_norm <= tol) { ls.converged = 1; ls.residual_norm = rhs_norm; s->last_done = 1; }  // nothing left to do
     else {
       if (random_shadow) {  // (rhat, r0) of the new shadow vector
@@ -760,12 +756,10 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
         hipLaunchKernelGGL(k_dots3, dim3(s->n_resblocks), dim3(kVecBlock), 0, s->stream, (const double*)s->krand.p, (const double*)s->kr.p,
                            s->c.part_f, n, s->n_resblocks);
         HIP_TRY(hipStreamSynchronize(s->stream));
-        double wb = 0.0;
-        for (int i = 0; i < s->n_resblocks; ++i) wb += s->h_part[i];
-        s->shadow_src = s->krand.p; s->shadow_rho0 = wb;
+        s->shadow_src = s->krand.p; s->shadow_rho0 = sum_partials(s, 0);
       }
       const bool first_cold = (pass == 0 && !warm);
-      rc = krylov<NF>(s, mode, rhs_norm, first_cold ? rtol : 0.0, first_cold ? atol : tol, cap, &ls, pass > 0);
+      rc = krylov<NF>(s, q.mode, rhs_norm, first_cold ? q.rtol : 0.0, first_cold ? q.atol : tol, cap, &ls, pass > 0);
       s->shadow_src = nullptr;
     }
     total.iterations += ls.iterations; total.converged = ls.converged; total.residual_norm = ls.residual_norm;
@@ -774,8 +768,8 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
     if (usable && ls.iterations > 0) {
       // the normal end of a solve inside Newton (first pass, converged, short enough to go unchecked): the final
       // M^-1 application also applies the Newton update and leaves the predicted start of the next solve
-      const bool final_now = upd && pass == 0 && s->last_done == 1 && ls.iterations <= verify_above && bnorm > 0.0 && !s->ml_coarse;
-      int rc2 = apply_minv<NF>(s, mode, s->ky.p, s->kx.p, have_x ? 1.0 : 0.0, 1.0, final_now ? upd : nullptr); if (rc2) return rc2;
+      const bool final_now = q.upd && pass == 0 && s->last_done == 1 && ls.iterations <= q.verify_above && q.bnorm > 0.0 && !s->ml_coarse;
+      int rc2 = apply_minv<NF>(s, q.mode, s->ky.p, s->kx.p, have_x ? 1.0 : 0.0, 1.0, final_now ? q.upd : nullptr); if (rc2) return rc2;
       if constexpr (NF == 9) {
         if (s->ml_coarse) {   // x += theta T y (the multilevel term of M^-1 applied to the Krylov solution)
           rc2 = ml_correction<NF>(s, s->ky.p); if (rc2) return rc2;
@@ -783,7 +777,7 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
                              (const int32_t*)s->ml_par.p, s->kx.p, s->ml_theta);
         }
       }
-      if (final_now && upd_done) *upd_done = true;
+      if (final_now) q.upd_done = true;
       have_x = true; random_shadow = false;
     } else if (!usable) {
       random_shadow = true; ++bad_passes;
@@ -793,8 +787,8 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
     if (!have_x && s->last_done == 1) {  // zero right-hand side
       HIP_TRY(hipMemsetAsync(s->kx.p, 0, n * sizeof(double), s->stream)); have_x = true;
     }
-    if (!(bnorm > 0.0)) break;
-    if (pass == 0 && s->last_done == 1 && ls.iterations <= verify_above) break;  // short solves do not drift
+    if (!(q.bnorm > 0.0)) break;
+    if (pass == 0 && s->last_done == 1 && ls.iterations <= q.verify_above) break;  // short solves do not drift
     double rn = rhs_norm;
     if (have_x) { int rc2 = true_residual<NF>(s, &rn); if (rc2) return rc2; }  // kr = b - J x
     total.residual_norm = rn;
@@ -808,12 +802,12 @@ int krylov_verified(gmpnp_solver* s, int mode, double bnorm, double rtol, double
     // attainable accuracy.  (Without it, the generated 14 ... 370-vertex cylinders ended at 1.6e-9 ... 1.7e-8 of a 1e-10
     // target with 1e-13 attainable, and the solve said converged.)  Inside Newton the rule is unchanged.
     if (s->last_done == 1 && finite && rn <= tol) break;
-    if (s->last_done == 1 && finite && rn <= 1e3 * tol && !(refine && rn < 0.5 * pass_start)) break;
-    if (total.iterations >= maxit || bad_passes > 8 || !finite) {
+    if (s->last_done == 1 && finite && rn <= 1e3 * tol && !(q.refine && rn < 0.5 * pass_start)) break;
+    if (total.iterations >= q.maxit || bad_passes > 8 || !finite) {
       if (st) { total.converged = 0; *st = total; }
       char buf[200];
       snprintf(buf, sizeof buf, "BiCGStab stopped without convergence after %d iterations in %d passes (%d breakdowns), ||b - J x|| = %.3e, ||b|| = %.3e",
-               total.iterations, pass + 1, bad_passes, rn, bnorm);
+               total.iterations, pass + 1, bad_passes, rn, q.bnorm);
       return fail(GMPNP_ERR_LINEAR, buf);
     }
     rhs_norm = rn;  // next pass solves J ddx = r (already in kr)
@@ -855,16 +849,22 @@ int build_tridiagonal(gmpnp_solver* s) {
   return GMPNP_OK;
 }
 
+// The top of the cyclic-reduction pyramid (every level whose upper neighbour has at most kBcrTailRows rows) is ONE launch,
+// k_bcr_tail: levels l0 .. nl - 1 (tri[l0 + 1].n <= kBcrTailRows); the levels below l0 are one launch each, down and up.
+int bcr_tail_first_level(const gmpnp_solver* s) {
+  const int nl = (int)s->tri.size();
+  int l0 = nl - 1;
+  while (l0 > 0 && s->tri[l0].n <= kBcrTailRows && nl - l0 < kBcrTailLevels) --l0;
+  return l0;
+}
+
 // Solve J x = rhs (device pointer, internal order) by block cyclic reduction; x stays in tri[0].x (SoA).
 template <int NF>
 int tri_solve(gmpnp_solver* s, const double* rhs) {
   if (!s->tri_ok) return fail(GMPNP_ERR_INVALID, "block-tridiagonal solver needs a 1D mesh in path order");
   hipLaunchKernelGGL((k_tri_extract<NF>), dim3(grid_for(s->t.nv * NF * NF, kVecBlock)), dim3(kVecBlock), 0, s->stream,
                      s->c, s->tri[0], s->tri_kpos.p, rhs);
-  const int nl = (int)s->tri.size();
-  // the top of the pyramid (every level whose upper neighbour has at most kBcrTailRows rows) is ONE launch: k_bcr_tail
-  int l0 = nl - 1;
-  while (l0 > 0 && s->tri[l0].n <= kBcrTailRows && nl - l0 < kBcrTailLevels) --l0;   // tail = levels l0 .. nl-1 (tri[l0+1].n <= kBcrTailRows)
+  const int nl = (int)s->tri.size(), l0 = bcr_tail_first_level(s);
   for (int l = 0; l < l0; ++l)
     hipLaunchKernelGGL((k_bcr_forward<NF>), dim3(grid_for(s->tri[l + 1].n, 4)), dim3(64), 0, s->stream, s->tri[l],
                        s->tri[l + 1], s->status.p);
@@ -979,15 +979,6 @@ int band_solve(gmpnp_solver* s, double bnorm, double rtol, double atol, gmpnp_li
   return GMPNP_OK;
 }
 
-std::string status_message(int flags) {
-  std::string m;
-  if (flags & 1) m += "1 - sum_j a_j u_j <= 0 at a quadrature point; ";
-  if (flags & 2) m += "singular diagonal node block; ";
-  if (flags & 4) m += "singular coarse operator; ";
-  if (flags & 8) m += "in-launch hand-over timed out; ";
-  return m;
-}
-
 template <int DIM, int NF>
 int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st) {
   const double t0 = now_ms();
@@ -999,17 +990,9 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
   // Jacobian, and the separate element pass per iteration (another 43 us) is gone.  Wasted only on the last test of a solve.
   int rc = residual<DIM, NF>(s, true, &r, &flags); if (rc) return rc;
   st.ms_assemble += now_ms() - ta;
-  if (flags & 1) { st.steric_excursion = 1; if (s->strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags)); }
-  const double r0 = r;
-  st.residuals[0] = r; st.n_residuals = 1;
-  auto conv = [&](double res) {
-    if (!(res == res)) return false;
-    const double rel = res / r0;  // 0/0 = NaN compares false, as in DOLFIN
-    return rel < o.relative_tolerance || res < o.absolute_tolerance;
-  };
-  bool done = conv(r);
-  if (!(r == r)) return fail(GMPNP_ERR_NUMERIC, "residual is NaN before the first Newton iteration");
-  while (!done && st.iterations < o.maximum_iterations) {
+  NewtonJudge judge(o, st, s->strict_steric != 0);
+  NewtonJudge::Verdict v = judge.first(r, flags);
+  while (v == NewtonJudge::go_on) {
     if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[0], s->stream));
     rc = launch_jac_gather<DIM, NF>(s); if (rc) return rc;   // element records: left by the last residual evaluation
     s->jacobian_valid = true;
@@ -1039,11 +1022,9 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
       // (first solve of a run: the Jacobian changes a lot between iterations) or the last reuse cost iterations.
       // Asynchronous scheme (default): every iteration starts the coarse chain of its matrix on the side stream and solves
       // with the inverse of the previous one; an inverse of THIS matrix is only built in-stream when it has to be.
-      // x0 = (1-w) dx_k + (1-w)^2 (dx_k - (1-w) dx_{k-1}): first-order prediction plus the second-order term observed
-      // one iteration earlier, scaled by (1-w)^2 as the quadratic form scales (gmpnp_options_t.warm_start = 1: first order only)
+      // x0 = wa dx_k + wb dx_{k-1}, the predicted start of this solve (gmpnp_host_rules.h; gmpnp_options_t.warm_start)
       const double q = 1.0 - o.relaxation_parameter;
-      double wa = 0.0, wb = 0.0;
-      if (s->warm_start && st.iterations > 0 && q != 0.0) { wa = q; if (s->warm_start > 1 && st.iterations > 1) { wa = q + q * q; wb = -q * q * q; } }
+      const auto [wa, wb] = predicted_start(s->warm_start, q, st.iterations);
       // (The previous time step's total update is useless as a start of a step's FIRST solve: optimal multiple ~1e-5,
       // measured in round 1.)
       const bool x0_ready = s->x0_predicted && st.iterations > 0 && wa != 0.0;
@@ -1064,21 +1045,19 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
       const bool async_ok = s->coarse_async != 0 && DIM == 3;
       const bool coarse_fresh = async_ok ? must : (s->coarse_lag <= 1 || (st.iterations % s->coarse_lag) == 0 || must);
       rc = setup_preconditioner<DIM, NF>(s, o.linear_solver, true, coarse_fresh, async_ok); if (rc) return rc;
-      // rhs = b (current residual vector F): copied into kr and kb by krylov_verified
       if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[2], s->stream));
       gmpnp_linear_stats_t ls{};
       // inside Newton only long solves are checked: a short one does not drift, and Newton's own residual test sees
       // whatever is left
       s->krylov_hint = st.iterations < 32 ? s->hint_by_newton_it[st.iterations] : 0;
-      // coefficients of the NEXT iteration's predicted start (same rule as wa, wb above, one iteration on); the
-      // experiments that decide on host-side dot products of their own keep the separate kernels
-      double na = 0.0, nb = 0.0;
-      if (s->warm_start && q != 0.0) { na = q; if (s->warm_start > 1 && st.iterations + 1 > 1) { na = q + q * q; nb = -q * q * q; } }
+      // coefficients of the NEXT iteration's predicted start, which this solve's update leaves in kx
+      const auto [na, nb] = predicted_start(s->warm_start, q, st.iterations + 1);
       const NewtonUpdate upd{s->u.p, s->kxp.p, o.relaxation_parameter, na, nb};
-      bool upd_done = false;
-      rc = krylov_verified<NF>(s, o.linear_solver, r, o.krylov_relative_tolerance, o.krylov_absolute_tolerance,
-                               o.krylov_maximum_iterations, &ls, 500, wa, wb, nullptr, /*rhs_ready=*/true,
-                               x0_ready, na != 0.0 ? &upd : nullptr, &upd_done, dots_in_flight);
+      KrylovRequest req;
+      req.mode = o.linear_solver; req.bnorm = r; req.rtol = o.krylov_relative_tolerance; req.atol = o.krylov_absolute_tolerance;
+      req.maxit = o.krylov_maximum_iterations; req.verify_above = 500; req.warm_scale = wa; req.warm_prev = wb;
+      req.rhs_ready = true; req.x0_ready = x0_ready; req.dots_in_flight = dots_in_flight; req.upd = na != 0.0 ? &upd : nullptr;
+      rc = krylov_verified<NF>(s, &ls, req);
       if (dots_in_flight) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_dots, 0));  // whatever path the solve took: kt and vals are free again
       // feedback: a reused coarse inverse that doubles the iteration count of the last fresh solve is dropped
       if (st.iterations < 32) s->hint_by_newton_it[st.iterations] = ls.iterations;
@@ -1111,7 +1090,7 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
         return rc;
       }
       // x <- x - omega dx (done by the solve's last kernel in the normal case)
-      if (upd_done) s->x0_predicted = true;
+      if (req.upd_done) s->x0_predicted = true;
       else if (na != 0.0) {
         hipLaunchKernelGGL(k_update_predict, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, s->kx.p, s->kxp.p,
                            o.relaxation_parameter, na, nb, (int)s->ndof);
@@ -1138,19 +1117,13 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
       st.ms_setup += ms12;
       st.ms_krylov += ms23;
     }
-    if (flags & 1) { st.steric_excursion = 1; if (s->strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags)); }
-    if (flags & 14) return fail(GMPNP_ERR_LINEAR, status_message(flags));
-    if (st.n_residuals < GMPNP_MAX_NEWTON_HISTORY) st.residuals[st.n_residuals++] = r;
-    // NaN / Inf stay fatal (DOLFIN would iterate to its limit on a NaN residual and raise there)
-    if (!(r == r) || std::isinf(r)) return fail(GMPNP_ERR_NUMERIC, (flags & 1) ? "residual became NaN / Inf after an iterate left the admissible set (1 - sum_j a_j u_j <= 0)" : "residual became NaN");
-    done = conv(r);
+    v = judge.next(r, flags);
   }
+  if (v == NewtonJudge::failed) return fail(judge.code, judge.message);
   s->state_jumped = false;
   if (s->direct_sticky > 0 && o.linear_solver != GMPNP_LINEAR_BAND_LU) s->direct_sticky--;
-  st.converged = done ? 1 : 0;
   st.ms_total = now_ms() - t0;
-  if (!done) return fail(GMPNP_ERR_NOT_CONVERGED, "Newton solver did not converge because maximum number of iterations reached");
-  return GMPNP_OK;
+  return v == NewtonJudge::converged ? GMPNP_OK : fail(judge.code, judge.message);
 }
 
 int upload_vec(gmpnp_solver* s, const double* file_order, double* dev) {
@@ -1644,8 +1617,9 @@ int gmpnp_linear_solve(gmpnp_solver* s, const double* b, double* x, int32_t mode
   GMPNP_DISPATCH(s, rc = (setup_preconditioner<DIM, NF>(s, mode)));
   if (rc) return rc;
   gmpnp_linear_stats_t ls{};
-  GMPNP_DISPATCH(s, rc = (krylov_verified<NF>(s, mode, bn, rtol, atol, maxit, &ls, 0, 0.0, 0.0, nullptr, false, false, nullptr,
-                                               nullptr, false, /*refine=*/true)));
+  KrylovRequest req;
+  req.mode = mode; req.bnorm = bn; req.rtol = rtol; req.atol = atol; req.maxit = maxit; req.refine = true;
+  GMPNP_DISPATCH(s, rc = (krylov_verified<NF>(s, &ls, req)));
   if (stats) *stats = ls;
   HIP_TRY(hipMemcpy(s->h_status, s->status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1655,57 +1629,6 @@ int gmpnp_linear_solve(gmpnp_solver* s, const double* b, double* x, int32_t mode
   return download_vec(s, s->kx.p, x);
 }
 
-}  // extern "C"
-namespace {
-// Partition handles of one rank (gmpnp_group.h, "multilevel term"): parents[2 v + {0, 1}] in the coarse handle's LOCAL file order,
-// -1 where a parent is not local there (ghost rows only).  The tables serve the OWNED rows: the prolongation of an owned fine
-// vertex, the restriction onto an owned coarse vertex (its children: every local fine vertex naming it, ascending internal
-// index — the global slab order restricted, so the sums run in the serial order) and the injection of an owned coarse vertex.
-int attach_partitioned_level(gmpnp_solver* fine, gmpnp_solver* coarse, const int32_t* parents, double theta, int32_t sweeps) {
-  if (fine->part_rank != coarse->part_rank || fine->part_size != coarse->part_size)
-    return fail(GMPNP_ERR_INVALID, "multilevel term: the levels must be partition handles of the same rank of partitions of the same size");
-  const int nvf = fine->t.nv, nvc = coarse->t.nv;
-  const int f0 = fine->t.own_node0, f1 = fine->t.own_node1, c0 = coarse->t.own_node0, c1 = coarse->t.own_node1;
-  std::vector<int32_t> par((size_t)2 * nvf, -1), copy(nvc, -1);
-  std::vector<std::vector<int32_t>> kids(nvc);
-  for (int I = 0; I < nvf; ++I) {
-    const int v = fine->t.perm[I];
-    const int a = parents[2 * v], b = parents[2 * v + 1];
-    const bool owned = I >= f0 && I < f1;
-    if (a < -1 || a >= nvc || b < -1 || b >= nvc) return fail(GMPNP_ERR_INVALID, "parent vertex out of range");
-    if (owned && (a < 0 || b < 0)) return fail(GMPNP_ERR_INVALID, "multilevel term: both parents of an owned fine vertex must be local on the coarse level");
-    const int Ia = a >= 0 ? coarse->t.iperm[a] : -1, Ib = b >= 0 ? coarse->t.iperm[b] : -1;
-    if (owned) { par[2 * I] = Ia; par[2 * I + 1] = (a == b) ? -1 : Ib; }
-    else { par[2 * I] = 0; par[2 * I + 1] = -1; }   // never read (ghost rows are masked); kept in range all the same
-    if (a >= 0 && a == b) {
-      if (copy[Ia] >= 0) return fail(GMPNP_ERR_INVALID, "two fine vertices claim to be the copy of one coarse vertex");
-      copy[Ia] = I; kids[Ia].push_back(I << 1);
-    } else {
-      if (Ia >= 0) kids[Ia].push_back((I << 1) | 1);
-      if (Ib >= 0) kids[Ib].push_back((I << 1) | 1);
-    }
-  }
-  std::vector<int32_t> cptr(nvc + 1, 0), clist;
-  for (int Ic = 0; Ic < nvc; ++Ic) {
-    const bool owned = Ic >= c0 && Ic < c1;
-    if (owned && (copy[Ic] < f0 || copy[Ic] >= f1))
-      return fail(GMPNP_ERR_INVALID, "multilevel term: an owned coarse vertex must have its copy among the owned fine vertices (the meshes are not nested, or the plans do not match)");
-    if (!owned) copy[Ic] = -1;
-    else clist.insert(clist.end(), kids[Ic].begin(), kids[Ic].end());
-    cptr[Ic + 1] = (int32_t)clist.size();
-  }
-  HIP_TRY(hipSetDevice(fine->opts.device_id));
-  HIP_TRY(fine->ml_par.upload(par)); HIP_TRY(fine->ml_child_ptr.upload(cptr)); HIP_TRY(fine->ml_child.upload(clist)); HIP_TRY(fine->ml_copy.upload(copy));
-  HIP_TRY(fine->ml_z.alloc(fine->ndof)); HIP_TRY(fine->ml_tbc.alloc(fine->ndof)); HIP_TRY(fine->ml_tbd.alloc(fine->ndof));
-  HIP_TRY(coarse->ml_r.alloc(coarse->ndof)); HIP_TRY(coarse->ml_w.alloc(coarse->ndof));
-  fine->ml_coarse = coarse; fine->ml_theta = theta; coarse->ml_is_coarse = true; coarse->ml_sweeps = sweeps;
-  fine->matp = true; fine->fused_half = false;
-  fine->precond_valid = false;
-  return GMPNP_OK;
-}
-}  // namespace
-extern "C" {
-
 int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const int32_t* parents, double theta, int32_t sweeps) {
   if (!fine || !coarse || !parents) return fail(GMPNP_ERR_INVALID, "NULL argument");
   if (fine == coarse || coarse->ml_is_coarse) return fail(GMPNP_ERR_INVALID, "a level handle serves one finer level");
@@ -1714,31 +1637,19 @@ int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const in
   if (fine->opts.device_id != coarse->opts.device_id) return fail(GMPNP_ERR_INVALID, "the levels live on one device");
   if (!(theta > 0.0)) return fail(GMPNP_ERR_INVALID, "theta must be positive");
   if (sweeps < 1 || sweeps > 16) return fail(GMPNP_ERR_INVALID, "sweeps: 1 ... 16");
-  if (fine->partitioned) return attach_partitioned_level(fine, coarse, parents, theta, sweeps);
-  const int nvf = fine->t.nv, nvc = coarse->t.nv;
-  if (nvc >= nvf) return fail(GMPNP_ERR_INVALID, "the coarse level has fewer vertices");
-  std::vector<int32_t> par((size_t)2 * nvf), copy(nvc, -1);
-  std::vector<std::vector<int32_t>> kids(nvc);
-  for (int I = 0; I < nvf; ++I) {
-    const int v = fine->t.perm[I];
-    const int a = parents[2 * v], b = parents[2 * v + 1];
-    if (a < 0 || a >= nvc || b < 0 || b >= nvc) return fail(GMPNP_ERR_INVALID, "parent vertex out of range");
-    const int Ia = coarse->t.iperm[a], Ib = coarse->t.iperm[b];
-    par[2 * I] = Ia; par[2 * I + 1] = (a == b) ? -1 : Ib;
-    if (a == b) {
-      if (copy[Ia] >= 0) return fail(GMPNP_ERR_INVALID, "two fine vertices claim to be the copy of one coarse vertex");
-      copy[Ia] = I; kids[Ia].push_back(I << 1);
-    } else { kids[Ia].push_back((I << 1) | 1); kids[Ib].push_back((I << 1) | 1); }   // ascending fine index: fixed summation order
-  }
-  std::vector<int32_t> cptr(nvc + 1, 0), clist;
-  for (int Ic = 0; Ic < nvc; ++Ic) {
-    if (copy[Ic] < 0) return fail(GMPNP_ERR_INVALID, "a coarse vertex has no copy on the fine level (the meshes are not nested)");
-    clist.insert(clist.end(), kids[Ic].begin(), kids[Ic].end());
-    cptr[Ic + 1] = (int32_t)clist.size();
-  }
+  // partition handles of one rank (gmpnp_group.h, "multilevel term"): `parents` in the coarse handle's LOCAL file order
+  const bool part = fine->partitioned;
+  if (part && (fine->part_rank != coarse->part_rank || fine->part_size != coarse->part_size))
+    return fail(GMPNP_ERR_INVALID, "multilevel term: the levels must be partition handles of the same rank of partitions of the same size");
+  if (!part && coarse->t.nv >= fine->t.nv) return fail(GMPNP_ERR_INVALID, "the coarse level has fewer vertices");
+  LevelTables tb;
+  const std::string err = build_level_tables(fine->t.perm, coarse->t.iperm, fine->t.own_node0, fine->t.own_node1, coarse->t.own_node0,
+                                             coarse->t.own_node1, parents, part, &tb);
+  if (!err.empty()) return fail(GMPNP_ERR_INVALID, err);
   HIP_TRY(hipSetDevice(fine->opts.device_id));
-  HIP_TRY(fine->ml_par.upload(par)); HIP_TRY(fine->ml_child_ptr.upload(cptr)); HIP_TRY(fine->ml_child.upload(clist)); HIP_TRY(fine->ml_copy.upload(copy));
+  HIP_TRY(fine->ml_par.upload(tb.par)); HIP_TRY(fine->ml_child_ptr.upload(tb.child_ptr)); HIP_TRY(fine->ml_child.upload(tb.child)); HIP_TRY(fine->ml_copy.upload(tb.copy));
   HIP_TRY(fine->ml_z.alloc(fine->ndof));
+  if (part) { HIP_TRY(fine->ml_tbc.alloc(fine->ndof)); HIP_TRY(fine->ml_tbd.alloc(fine->ndof)); }
   HIP_TRY(coarse->ml_r.alloc(coarse->ndof)); HIP_TRY(coarse->ml_w.alloc(coarse->ndof));
   fine->ml_coarse = coarse; fine->ml_theta = theta; coarse->ml_is_coarse = true; coarse->ml_sweeps = sweeps;
   // the staged operand exists in the materialised vector form only (k_vec_a / k_vec_b write the vector, the tile kernels stage one)
@@ -1777,7 +1688,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 15: GMPNP_DISPATCH(s, hipLaunchKernelGGL((k_bicg_b_mat<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, 1)); break;
       case 16: hipLaunchKernelGGL(k_vec_a, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, 1); break;
       case 17: hipLaunchKernelGGL(k_vec_b, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->c, 1); break;
-      case 18:   // the whole 1D direct solve: extraction + ~13 levels of block cyclic reduction down and up (k_bcr_forward / _top / _backward)
+      case 18:   // the whole 1D direct solve: extraction + ~13 levels of block cyclic reduction down and up (k_bcr_forward / k_bcr_tail / k_bcr_backward)
         if (s->dim != 1 || !s->tri_ok) return fail(GMPNP_ERR_INVALID, "kernel 18 is the 1D block-cyclic-reduction solve");
         r = tri_solve<7>(s, s->F.p); break;
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
@@ -1799,7 +1710,6 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   if (rc) return rc;
   *avg_us = 1000.0 * ms / launches;
-  if (kernel == 1 || kernel == 2) s->jacobian_valid = (kernel == 2) ? s->jacobian_valid : s->jacobian_valid;
   return GMPNP_OK;
 }
 

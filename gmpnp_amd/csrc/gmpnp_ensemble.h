@@ -9,7 +9,7 @@
 // bcr_top_row, bcr_backward_entry, tri_apply_entry), so a member computes exactly what its handle computes alone.  Members are
 // independent: nothing waits inside a launch, the launch boundaries are the only ordering.  One host synchronisation per
 // iteration: the residual partials of every member land in that member's pinned buffer, the host forms the norms and decides
-// per member with the single handle's rule (newton() in gmpnp_api.hip), then uploads the next active list.
+// per member with the one Newton rule (NewtonJudge, gmpnp_host_rules.h), then uploads the next active list.
 #pragma once
 
 namespace gmpnp {
@@ -194,9 +194,7 @@ int ens_update(gmpnp_ensemble* e, int nact, double omega) {
   constexpr int NF = 7;
   hipLaunchKernelGGL((k_jac_gather_ens<1, NF>), dim3(grid_for(s0->c.n_work * kWave, kVecBlock), nact), dim3(kVecBlock), 0, e->stream, tab, act);
   hipLaunchKernelGGL((k_tri_extract_ens<NF>), dim3(grid_for(s0->t.nv * NF * NF, kVecBlock), nact), dim3(kVecBlock), 0, e->stream, tab, act);
-  const int nl = (int)s0->tri.size();
-  int l0 = nl - 1;   // the same split into per-level launches and tail as tri_solve
-  while (l0 > 0 && s0->tri[l0].n <= kBcrTailRows && nl - l0 < kBcrTailLevels) --l0;
+  const int nl = (int)s0->tri.size(), l0 = bcr_tail_first_level(s0);
   for (int l = 0; l < l0; ++l)
     hipLaunchKernelGGL((k_bcr_forward_ens<NF>), dim3(grid_for(s0->tri[l + 1].n, 4), nact), dim3(64), 0, e->stream, tab, act, l);
   hipLaunchKernelGGL((k_bcr_tail_ens<NF>), dim3(nact), dim3(kBcrTailThreads), 0, e->stream, tab, act, l0, nl - l0);
@@ -260,53 +258,30 @@ int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t*
   { int rc = ens_drain_members(e); if (rc) return rc; }
   // the member table is rebuilt for every solve: a gmpnp_set_* call may have re-allocated member storage since the last one
   { int rc = ens_upload_table(e); if (rc) return rc; }
-  std::vector<double> r0(n, 0.0);
   std::vector<char> live(n, 1);
+  std::vector<NewtonJudge> judge; judge.reserve(n);   // one per member: the single handle's rule (gmpnp_host_rules.h)
   for (int k = 0; k < n; ++k) {
     stats[k] = gmpnp_newton_stats_t{}; status[k] = GMPNP_OK; e->err[k].clear();
+    judge.emplace_back(*o, stats[k], e->m[k]->strict_steric != 0);
     HIP_TRY(hipMemsetAsync(e->m[k]->status.p, 0, sizeof(int32_t), e->stream));
   }
-  // member k ends with code rc: its message is kept, the others go on
-  auto end_member = [&](int k, int rc, const std::string& msg) {
-    status[k] = rc; e->err[k] = msg; live[k] = 0;
-  };
-  // the end of newton() for a member whose loop condition no longer holds
-  auto finish = [&](int k, bool done) {
-    gmpnp_solver* s = e->m[k]; gmpnp_newton_stats_t& st = stats[k];
-    s->state_jumped = false;
-    st.converged = done ? 1 : 0;
-    st.ms_total = now_ms() - t0;
-    if (done) { live[k] = 0; return; }
-    end_member(k, GMPNP_ERR_NOT_CONVERGED, "Newton solver did not converge because maximum number of iterations reached");
-  };
-  auto conv = [&](int k, double res) {
-    if (!(res == res)) return false;
-    const double rel = res / r0[k];  // 0/0 = NaN compares false, as in DOLFIN
-    return rel < o->relative_tolerance || res < o->absolute_tolerance;
-  };
-  auto norm_of = [&](int k, int* flags) {
+  // member k's residual is in its pinned buffer: the verdict, mapped to status[k] / err[k] / live[k] (a member that fails keeps
+  // its message and the others go on; a member that ends its solve ends as newton() does)
+  auto settle = [&](int k, bool first) {
     gmpnp_solver* s = e->m[k];
-    double acc = 0.0;
-    for (int i = 0; i < s->n_resblocks; ++i) acc += s->h_part[i];
-    *flags = *s->h_status;
-    return std::sqrt(acc);
+    const double r = std::sqrt(sum_partials(s, 0));
+    const NewtonJudge::Verdict v = first ? judge[k].first(r, *s->h_status) : judge[k].next(r, *s->h_status);
+    if (v == NewtonJudge::go_on) return;
+    live[k] = 0;
+    if (v != NewtonJudge::failed) { s->state_jumped = false; stats[k].ms_total = now_ms() - t0; }
+    if (v != NewtonJudge::converged) { status[k] = judge[k].code; e->err[k] = judge[k].message; }
   };
   std::vector<int32_t> act(n);
   for (int k = 0; k < n; ++k) act[k] = k;
   { int rc = ens_upload_active(e, act); if (rc) return rc; }
   { int rc = ens_residual(e, n); if (rc) return rc; }
   HIP_TRY(hipStreamSynchronize(e->stream));
-  for (int k = 0; k < n; ++k) {
-    gmpnp_newton_stats_t& st = stats[k];
-    int flags = 0;
-    const double r = norm_of(k, &flags);
-    if (flags & 1) { st.steric_excursion = 1; if (e->m[k]->strict_steric) { end_member(k, GMPNP_ERR_NUMERIC, status_message(flags)); continue; } }
-    r0[k] = r;
-    st.residuals[0] = r; st.n_residuals = 1;
-    const bool done = conv(k, r);
-    if (!(r == r)) { end_member(k, GMPNP_ERR_NUMERIC, "residual is NaN before the first Newton iteration"); continue; }
-    if (done || st.iterations >= o->maximum_iterations) finish(k, done);
-  }
+  for (int k = 0; k < n; ++k) settle(k, true);
   for (;;) {
     act.clear();
     for (int k = 0; k < n; ++k) if (live[k]) act.push_back(k);
@@ -317,20 +292,9 @@ int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t*
     rc = ens_residual(e, nact); if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));   // the one host synchronisation of the iteration
     for (int k : act) {
-      gmpnp_newton_stats_t& st = stats[k];
       e->m[k]->jacobian_valid = true;
-      st.iterations++;
-      int flags = 0;
-      const double r = norm_of(k, &flags);
-      if (flags & 1) { st.steric_excursion = 1; if (e->m[k]->strict_steric) { end_member(k, GMPNP_ERR_NUMERIC, status_message(flags)); continue; } }
-      if (flags & 14) { end_member(k, GMPNP_ERR_LINEAR, status_message(flags)); continue; }
-      if (st.n_residuals < GMPNP_MAX_NEWTON_HISTORY) st.residuals[st.n_residuals++] = r;
-      if (!(r == r) || std::isinf(r)) {
-        end_member(k, GMPNP_ERR_NUMERIC, (flags & 1) ? "residual became NaN / Inf after an iterate left the admissible set (1 - sum_j a_j u_j <= 0)" : "residual became NaN");
-        continue;
-      }
-      const bool done = conv(k, r);
-      if (done || st.iterations >= o->maximum_iterations) finish(k, done);
+      stats[k].iterations++;
+      settle(k, false);
     }
   }
   for (int k = 0; k < n; ++k)

@@ -696,13 +696,9 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
   int rc = group_exchange(g, NF, 2, [](gmpnp_solver* s) { VecListW w{}; w.p[0] = s->u.p; w.p[1] = s->un.p; return w; }); if (rc) return rc;
   double r = 0.0; int flags = 0;
   rc = group_residual<DIM, NF>(g, &r, &flags); if (rc) return rc;
-  if (flags & 1) { st.steric_excursion = 1; if (g->dom[0]->strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags)); }
-  if (!(r == r)) return fail(GMPNP_ERR_NUMERIC, "residual is NaN before the first Newton iteration");
-  const double r0 = r;
-  st.residuals[0] = r; st.n_residuals = 1;
-  auto conv = [&](double res) { const double rel = res / r0; return rel < o.relative_tolerance || res < o.absolute_tolerance; };
-  bool done = conv(r);
-  while (!done && st.iterations < o.maximum_iterations) {
+  NewtonJudge judge(o, st, g->dom[0]->strict_steric != 0);   // r and flags are all-reduced: the same verdict on every rank
+  NewtonJudge::Verdict v = judge.first(r, flags);
+  while (v == NewtonJudge::go_on) {
     for (gmpnp_solver* s : g->dom) { rc = launch_jac_gather<DIM, NF>(s); if (rc) return rc; s->jacobian_valid = true; }
     const bool two_level = o.linear_solver == GMPNP_LINEAR_BICGSTAB_TWOLEVEL;
     // (a solve that starts from a state set from outside — the zero state of time step 0 — rebuilds every time: its Jacobians differ
@@ -711,27 +707,24 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
     rc = group_setup<NF>(g, o.linear_solver, rebuild); if (rc) return rc;
     if (g->ml_next) { rc = group_ml_setup<DIM, NF>(g, rebuild); if (rc) return rc; }
     gmpnp_linear_stats_t ls{};
-    // Warm start, as in the single-GPU Newton (gmpnp_api.hip): with the damped update consecutive corrections satisfy
-    // dx_{k+1} = (1 - w) dx_k + O(|dx_k|^2); x0 = (1-w) dx_k [+ (1-w)^2 (dx_k - (1-w) dx_{k-1})] is accepted when it removes at
-    // least half of the residual (one SpMV, three all-reduced dot products, a decision identical on every rank), and
-    // BiCGStab then only has to remove b - J x0, to the SAME absolute target.
+    // Warm start, as in the single-GPU Newton: the predicted start (gmpnp_host_rules.h) is accepted when it removes at least half
+    // of the residual (one SpMV, three all-reduced dot products, a decision identical on every rank), and BiCGStab then only
+    // has to remove b - J x0, to the SAME absolute target.
     const double tol_abs = std::max(o.krylov_relative_tolerance * r, o.krylov_absolute_tolerance);
-    const double q = 1.0 - o.relaxation_parameter;
+    const std::pair<double, double> w = predicted_start(g->dom[0]->warm_start, 1.0 - o.relaxation_parameter, st.iterations);
     bool warm = false; double rstart = r;
-    if (g->dom[0]->warm_start && st.iterations > 0 && q != 0.0 && r > 0.0) {
-      const double wa = (g->dom[0]->warm_start > 1 && st.iterations > 1) ? q + q * q : q, wb = (g->dom[0]->warm_start > 1 && st.iterations > 1) ? -q * q * q : 0.0;
+    if ((w.first != 0.0 || w.second != 0.0) && r > 0.0) {
       rc = group_dots3<NF>(g, &gmpnp_solver::kt, &gmpnp_solver::kb, [&](gmpnp_solver* s) -> int {
-        hipLaunchKernelGGL(k_warm_start, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, wa, wb, (int)s->ndof);
+        hipLaunchKernelGGL(k_warm_start, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, w.first, w.second, (int)s->ndof);
         hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->kx.p, s->kt.p);
         return GMPNP_OK;
       });
       if (rc) return rc;
       const double* h = g->dom[0]->h_red;
-      const double wbd = h[0], ww = h[1], bb = h[2], rn2 = bb - 2.0 * wbd + ww;
-      if (rn2 == rn2 && rn2 >= 0.0 && rn2 < 0.25 * bb) {
+      if (accept_predicted_start(h[0], h[1], h[2], &rstart)) {
         for (gmpnp_solver* s : g->dom)
           hipLaunchKernelGGL(k_start_residual, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p, (const double*)s->kt.p, (int)s->ndof);
-        warm = true; rstart = std::sqrt(rn2);
+        warm = true;
       }
     }
     int kry_total = 0;
@@ -775,17 +768,12 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
     rc = group_update<NF>(g, o.linear_solver, o.relaxation_parameter, warm); if (rc) return rc;
     st.iterations++;
     rc = group_residual<DIM, NF>(g, &r, &flags); if (rc) return rc;
-    if (flags & 1) { st.steric_excursion = 1; if (g->dom[0]->strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags)); }
-    if (flags & 14) return fail(GMPNP_ERR_LINEAR, status_message(flags));
-    if (st.n_residuals < GMPNP_MAX_NEWTON_HISTORY) st.residuals[st.n_residuals++] = r;
-    if (!(r == r) || std::isinf(r)) return fail(GMPNP_ERR_NUMERIC, "residual became NaN / Inf");
-    done = conv(r);
+    v = judge.next(r, flags);
   }
+  if (v == NewtonJudge::failed) return fail(judge.code, judge.message);
   for (gmpnp_solver* s : g->dom) { s->state_jumped = false; s->x0_predicted = false; }
-  st.converged = done ? 1 : 0;
   st.ms_total = now_ms() - t0;
-  if (!done) return fail(GMPNP_ERR_NOT_CONVERGED, "Newton solver did not converge because maximum number of iterations reached");
-  return GMPNP_OK;
+  return v == NewtonJudge::converged ? GMPNP_OK : fail(judge.code, judge.message);
 }
 
 }  // namespace
