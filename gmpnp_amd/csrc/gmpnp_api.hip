@@ -106,28 +106,19 @@ struct gmpnp_solver {
   // pinned read-back areas
   KrylovScalars* h_scal = nullptr; double* h_part = nullptr; int32_t* h_status = nullptr;
   HostPoll* h_poll = nullptr;   // progress mirror the B kernels write (fine-grained pinned memory)
-  int host_poll = 1;            // opts.progress_by_copy: poll with a device-to-host copy + event per burst instead
-  int burst_iters = 1;  // iterations per polling burst (opts.burst_iterations); with copy + event polling: 1 -> 453, 2 -> 463,
-                        // 4 -> 456, 8 -> 436 Newton its/s; with the pinned progress mirror a poll costs nothing on the
-                        // device: 1 -> 496, 2 -> 492
-  int krylov_hint = 0;  // expected iterations of the next solve (the same Newton iteration of the previous time step), 0 = none
-  int hint_by_newton_it[32] = {0};
-  int last_krylov_iters[2] = {0, 0};
+  // gmpnp_host_rules.h: the resolved options and the policies of the linear solves inside Newton (each owns its state)
+  Settings cfg; BurstHint burst; CoarseReuse coarse; DirectFallback direct; PredictedX0 x0;
   bool jacobian_valid = false, precond_valid = false;
   int precond_mode = -1;
   const double* shadow_src = nullptr; double shadow_rho0 = 0.0;  // shadow vector of the next krylov() pass (after a breakdown: krand)
   int last_done = 0;            // exit code of the last device Krylov loop (1 converged, 2 iteration cap, 3 breakdown / divergence)
   DevBuf<double> krand;         // pseudo-random shadow vector for a pass that follows a breakdown
   bool state_jumped = true;     // u was set from outside since the last Newton solve: the Jacobian moves a lot, no coarse reuse
-  bool coarse_refresh_due = false;  // a solve with a reused coarse inverse took clearly longer than the last fresh one
-  int krylov_fresh_iters = 0;   // iterations of the last solve right after a coarse rebuild
   DevBuf<uint32_t> ticket;
   DevBuf<double> supg_rho;  // [nv][ns] internal order
   bool fused_half = false;  // two launches per BiCGStab iteration (coarse workgroups inside the tile launch); opts.launch_form
   int resident_slots = 0;   // workgroups of k_half_a/b the device holds at once (occupancy query at create)
   unsigned fused_seq = 0;   // fused launches so far in the current solve
-  int warm_start = 2;  // start Newton iteration k+1's linear solve from (1 - omega) dx_k (+ second-order term); opts.warm_start
-  int coarse_lag = 3;   // rebuild the coarse inverse alone every coarse_lag-th Newton iteration of a solve (measured best: 1 -> 3 costs 0.7 % more Krylov iterations and saves 155 us per skipped rebuild)
   // SpMV event sampling (eager mode)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool; size_t ev_used = 0;
   std::vector<int> ev_halves;   // half-iterations inside bracket i (0: the bracket is not counted)
@@ -140,18 +131,9 @@ struct gmpnp_solver {
   // asynchronous coarse refresh: the Galerkin product + inverse of THIS iteration's matrix run on a side stream while
   // BiCGStab uses the inverse built from the previous iteration's matrix; adopted at the next set-up (double buffer)
   hipStream_t stream2 = nullptr; hipEvent_t ev_mat = nullptr, ev_chain = nullptr, ev_jac = nullptr, ev_dots = nullptr;
-  int warm_async = 1;         // opts.warm_in_stream: test of the predicted start in the main stream, behind the set-up
   DevBuf<double> Aci2; double* aci_buf[2] = {nullptr, nullptr}; int aci_cur = 0;
   bool chain_in_flight = false;
-  int coarse_async = 1;       // opts.coarse_refresh = N: rebuild in the main stream every Nth iteration (the older scheme)
-  bool x0_predicted = false;  // kx holds the predicted start of the next linear solve (left by the previous Newton update)
-  bool phase_timing = false;  // opts.phase_timing fills ms_assemble / ms_setup / ms_krylov of the Newton statistics
-  int direct_fallback = 1;      // opts.no_direct_fallback: a failed Krylov solve is an error again
-  int strict_steric = 0;        // opts.strict_steric: 1 - S <= 0 at a quadrature point is fatal (the reference has no such test)
-  double lu_max_gb = 48.0;      // opts.band_lu_max_gb: largest band storage the fallback may allocate
   int direct_solves = 0;        // band LU solves since create (factorisations)
-  int direct_sticky = 0;        // Newton solves that still go straight to the band LU after a Krylov failure
-  int direct_backoff = 0;       // length of the last such stretch (doubles with every new failure, resets on a converged Krylov solve)
   hipEvent_t ev_phase[6] = {};
   hipEvent_t ev_poll[2] = {};
   // mesh partition (gmpnp_create_partition): halo plan in INTERNAL node ids, buffers of the fused exchanges
@@ -372,7 +354,7 @@ int setup_preconditioner(gmpnp_solver* s, int mode, bool refresh = true, bool re
   if (had_chain) { HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_chain, 0)); s->chain_in_flight = false; }
   hipLaunchKernelGGL((k_scale_columns<NF>), dim3(grid_for(s->c.n_work * kWave, kVecBlock)), dim3(kVecBlock), 0, s->stream, s->c);
   if (s->c.use_coarse && refresh) {
-    const bool async = allow_async && s->coarse_async && s->stream2 != nullptr;
+    const bool async = allow_async && s->cfg.coarse_async && s->stream2 != nullptr;
     if (async && !refresh_coarse) {
       if (had_chain) { s->aci_cur ^= 1; s->c.Aci = s->aci_buf[s->aci_cur]; }   // adopt what the previous chain left
       HIP_TRY(hipEventRecord(s->ev_mat, s->stream));
@@ -579,15 +561,9 @@ int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, in
   volatile HostPoll* hp = s->h_poll;
   hp->done = 0; hp->iters = 0; hp->rr = 0.0;
   std::atomic_thread_fence(std::memory_order_seq_cst);
-  const int B = s->burst_iters;
+  const int B = s->cfg.burst_iters;
   // Bursts of B iterations; kernels of a converged solve exit at their first instruction.
-  // With the pinned progress mirror the host keeps up one iteration at a time, so the first burst is insurance against
-  // a slow host rather than a way to save polls: half the expected count (measured on the bench, sixteenths of the
-  // hint: 0..8 -> 529-533 its/s, 12 -> 525, 14 -> 522, 16 -> 516; more surplus early-exit launches the longer it is).
-  const int expect = s->krylov_hint > 0 ? s->krylov_hint / 2 : s->last_krylov_iters[use_coarse] / 2;
-  int first = s->opts.krylov_batch > 0 ? s->opts.krylov_batch : std::max(B, expect);
-  if (restart) first = B;  // a restart pass only has to remove the drift
-  first = ((first + B - 1) / B) * B;
+  const int first = s->burst.first(use_coarse, s->opts.krylov_batch, B, restart);
   int next_k = 0;  // iteration index of the next launch (the device stops advancing once `done` is set)
   auto burst = [&](int iters) -> int {
     for (int it = 0; it < iters; ++it) { int rc = enqueue_iteration<NF>(s, next_k++); if (rc) return rc; }
@@ -613,7 +589,7 @@ int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, in
     int rc = burst(first); if (rc) return rc;
     if (bracket >= 0) HIP_TRY(hipEventRecord(s->ev_pool[bracket].second, s->stream));
     launched = first;
-    bool mirror_ok = s->host_poll != 0;
+    bool mirror_ok = s->cfg.host_poll != 0;
     while (mirror_ok) {
       // The B kernels report progress straight into pinned host memory: launch the next burst, then spin until the
       // iterations launched BEFORE it are done (or the solve is).  No copy kernel and no event in the stream.
@@ -649,7 +625,7 @@ int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, in
     // the end of gmpnp_linear_solve, gmpnp_spmv_profile): no wait of its own
   }
   if (bracket >= 0 && res.done == 1 && res.iters > first) s->ev_halves[bracket] = 2 * first;   // every launch of the burst did its work
-  if (!restart) s->last_krylov_iters[use_coarse] = res.iters;
+  s->burst.solve_done(use_coarse, res.iters, restart);
   s->last_done = res.done;
   return krylov_verdict(res, bnorm, st, "BiCGStab");
 }
@@ -897,8 +873,8 @@ int band_prepare(gmpnp_solver* s) {
   const int n = t.nv, b = std::max(t.lu_band, kBandPanel - 1);   // the substitution's panel triangle lies inside the stored band
   const double gb = (double)n * (2.0 * b + 1.0) * NF * NF * sizeof(double) / 1e9;
   char buf[200];
-  if (gb > s->lu_max_gb) {
-    snprintf(buf, sizeof buf, "block-banded LU needs %.1f GB (%d node blocks, band %d), above gmpnp_options_t.band_lu_max_gb = %.1f", gb, n, b, s->lu_max_gb);
+  if (gb > s->cfg.lu_max_gb) {
+    snprintf(buf, sizeof buf, "block-banded LU needs %.1f GB (%d node blocks, band %d), above gmpnp_options_t.band_lu_max_gb = %.1f", gb, n, b, s->cfg.lu_max_gb);
     return fail(GMPNP_ERR_INVALID, buf);
   }
   HIP_TRY(s->lu_band.alloc((size_t)n * (2 * b + 1) * NF * NF, false));
@@ -979,149 +955,157 @@ int band_solve(gmpnp_solver* s, double bnorm, double rtol, double atol, gmpnp_li
   return GMPNP_OK;
 }
 
+// gmpnp_options_t.phase_timing: device time per phase of a Newton iteration (five event records and one more wait per iteration)
+int mark_phase(gmpnp_solver* s, int i) {
+  if (s->cfg.phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[i], s->stream));
+  return GMPNP_OK;
+}
+int collect_phases(gmpnp_solver* s, gmpnp_newton_stats_t& st) {   // after the residual that follows the update (phases 0-3 marked)
+  if (!s->cfg.phase_timing) return GMPNP_OK;
+  float ms01 = 0.f, ms12 = 0.f, ms23 = 0.f, ms3 = 0.f;
+  (void)hipEventElapsedTime(&ms01, s->ev_phase[0], s->ev_phase[1]);
+  (void)hipEventElapsedTime(&ms12, s->ev_phase[1], s->ev_phase[2]);
+  (void)hipEventElapsedTime(&ms23, s->ev_phase[2], s->ev_phase[3]);
+  HIP_TRY(hipEventRecord(s->ev_phase[4], s->stream));
+  HIP_TRY(hipEventSynchronize(s->ev_phase[4]));
+  (void)hipEventElapsedTime(&ms3, s->ev_phase[3], s->ev_phase[4]);
+  st.ms_assemble += ms01 + ms3;   // Jacobian assembly + next residual (device time)
+  st.ms_setup += ms12;
+  st.ms_krylov += ms23;
+  return GMPNP_OK;
+}
+
+// The linear step of one Newton iteration, by solver kind: solves J dx = F (||F|| = r, the Jacobian gathered) and applies
+// u <- u - omega dx.
+template <int DIM, int NF>
+int tridiagonal_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t&, double) {
+  int rc = mark_phase(s, 2); if (rc) return rc;
+  if constexpr (DIM == 1) {
+    rc = tri_solve<NF>(s, s->F.p); if (rc) return rc;
+    return tri_apply<NF>(s, s->u.p, 1.0, -o.relaxation_parameter);
+  } else {
+    return fail(GMPNP_ERR_INVALID, "block-tridiagonal solver needs a 1D mesh");
+  }
+}
+
+template <int DIM, int NF>
+int direct_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st, double r) {
+  if constexpr (DIM == 3) {
+    HIP_TRY(hipMemcpyAsync(s->kb.p, s->F.p, s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    int rc = mark_phase(s, 2); if (rc) return rc;
+    gmpnp_linear_stats_t ls{};
+    rc = band_solve<NF>(s, r, o.krylov_relative_tolerance, o.krylov_absolute_tolerance, &ls, true); if (rc) return rc;
+    st.direct_solves++; s->x0.left(false);
+    hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, (const double*)s->kx.p,
+                       -o.relaxation_parameter, (int)s->ndof);
+    return GMPNP_OK;
+  } else {
+    return fail(GMPNP_ERR_INVALID, "block-banded LU is the 3D direct solver (1D meshes: GMPNP_LINEAR_BLOCK_TRIDIAGONAL)");
+  }
+}
+
+template <int DIM, int NF>
+int krylov_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st, double r) {
+  const int it = st.iterations;
+  // x0 = wa dx_k + wb dx_{k-1}, the predicted start of this solve (gmpnp_host_rules.h; gmpnp_options_t.warm_start)
+  const double q = 1.0 - o.relaxation_parameter;
+  const auto [wa, wb] = predicted_start(s->cfg.warm_start, q, it);
+  const bool x0_ready = s->x0.ready(it, wa);
+  // The test of the predicted start (w = J x0 and three dot products, then a host decision) needs the new Jacobian only: it runs
+  // on the side stream while the main stream builds the preconditioner, and the host waits for ITS event, so neither the two
+  // kernels nor the round trip sit on the critical path.
+  const bool dots_in_flight = x0_ready && s->stream2 && s->cfg.warm_async;
+  if (dots_in_flight) {
+    HIP_TRY(hipEventRecord(s->ev_jac, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->stream2, s->ev_jac, 0));
+    hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream2, s->c, (const double*)s->kx.p, s->kt.p);
+    hipLaunchKernelGGL(k_dots3, dim3(s->n_resblocks), dim3(kVecBlock), 0, s->stream2, (const double*)s->kt.p, (const double*)s->kb.p,
+                       s->c.part_f, (int)s->ndof, s->n_resblocks);
+    HIP_TRY(hipEventRecord(s->ev_dots, s->stream2));
+  }
+  const bool async_ok = s->cfg.coarse_async != 0 && DIM == 3;
+  const bool coarse_fresh = s->coarse.fresh(async_ok, s->cfg.coarse_lag, it, s->state_jumped);
+  int rc = setup_preconditioner<DIM, NF>(s, o.linear_solver, true, coarse_fresh, async_ok); if (rc) return rc;
+  rc = mark_phase(s, 2); if (rc) return rc;
+  gmpnp_linear_stats_t ls{};
+  s->burst.expect(it);
+  // coefficients of the NEXT iteration's predicted start, which this solve's update leaves in kx
+  const auto [na, nb] = predicted_start(s->cfg.warm_start, q, it + 1);
+  const NewtonUpdate upd{s->u.p, s->kxp.p, o.relaxation_parameter, na, nb};
+  KrylovRequest req;
+  req.mode = o.linear_solver; req.bnorm = r; req.rtol = o.krylov_relative_tolerance; req.atol = o.krylov_absolute_tolerance;
+  // inside Newton only long solves are checked: a short one does not drift, and Newton's own residual test sees whatever is left
+  req.maxit = o.krylov_maximum_iterations; req.verify_above = 500; req.warm_scale = wa; req.warm_prev = wb;
+  req.rhs_ready = true; req.x0_ready = x0_ready; req.dots_in_flight = dots_in_flight; req.upd = na != 0.0 ? &upd : nullptr;
+  rc = krylov_verified<NF>(s, &ls, req);
+  if (dots_in_flight) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_dots, 0));  // whatever path the solve took: kt and vals are free again
+  s->burst.record(it, ls.iterations);
+  if (rc == GMPNP_OK) s->direct.krylov_converged(it);
+  s->coarse.solved(coarse_fresh, ls.iterations);
+  if (it < GMPNP_MAX_NEWTON_HISTORY) st.krylov_per_iteration[it] = ls.iterations;
+  st.krylov_iterations += ls.iterations;
+  if constexpr (DIM == 3) {
+    // the band LU takes over for this system (kb still holds b) and, by DirectFallback, for the solves that follow
+    if (rc == GMPNP_ERR_LINEAR && s->cfg.direct_fallback) {
+      const std::string why = g_err;
+      HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
+      gmpnp_linear_stats_t ds{};
+      rc = band_solve<NF>(s, r, o.krylov_relative_tolerance, o.krylov_absolute_tolerance, &ds, true);
+      if (rc) g_err = why + "; direct fallback: " + g_err;
+      else { st.direct_solves++; s->coarse.fell_back(); s->direct.fell_back(); }
+    }
+  }
+  if (rc) {
+    HIP_TRY(hipMemcpy(s->h_status, s->status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*s->h_status) g_err += " [" + status_message(*s->h_status) + "]";
+    return rc;
+  }
+  // x <- x - omega dx (done by the solve's last kernel in the normal case)
+  if (req.upd_done) s->x0.left(true);
+  else if (na != 0.0) {
+    hipLaunchKernelGGL(k_update_predict, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, s->kx.p, s->kxp.p,
+                       o.relaxation_parameter, na, nb, (int)s->ndof);
+    s->x0.left(true);
+  } else {
+    hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, (const double*)s->kx.p,
+                       -o.relaxation_parameter, (int)s->ndof);
+    s->x0.left(false);
+  }
+  return GMPNP_OK;
+}
+
 template <int DIM, int NF>
 int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st) {
   const double t0 = now_ms();
   HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
   double r = 0.0; int flags = 0;
-  double ta = now_ms();
+  const double ta = now_ms();
   // Every residual evaluation also leaves the element Jacobian records (k_element<.., true>, 43 us instead of 27): the
   // state only changes in the update, so the records of the convergence test ARE those of the next iteration's
   // Jacobian, and the separate element pass per iteration (another 43 us) is gone.  Wasted only on the last test of a solve.
   int rc = residual<DIM, NF>(s, true, &r, &flags); if (rc) return rc;
   st.ms_assemble += now_ms() - ta;
-  NewtonJudge judge(o, st, s->strict_steric != 0);
+  NewtonJudge judge(o, st, s->cfg.strict_steric != 0);
   NewtonJudge::Verdict v = judge.first(r, flags);
+  const bool band_lu_asked = o.linear_solver == GMPNP_LINEAR_BAND_LU;
   while (v == NewtonJudge::go_on) {
-    if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[0], s->stream));
+    rc = mark_phase(s, 0); if (rc) return rc;
     rc = launch_jac_gather<DIM, NF>(s); if (rc) return rc;   // element records: left by the last residual evaluation
     s->jacobian_valid = true;
-    if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[1], s->stream));
-    if (o.linear_solver == GMPNP_LINEAR_BLOCK_TRIDIAGONAL) {
-      if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[2], s->stream));
-      if constexpr (DIM == 1) {
-        rc = tri_solve<NF>(s, s->F.p); if (rc) return rc;
-        rc = tri_apply<NF>(s, s->u.p, 1.0, -o.relaxation_parameter); if (rc) return rc;
-      } else {
-        return fail(GMPNP_ERR_INVALID, "block-tridiagonal solver needs a 1D mesh");
-      }
-    } else if (o.linear_solver == GMPNP_LINEAR_BAND_LU || s->direct_sticky > 0) {
-      if constexpr (DIM == 3) {
-        HIP_TRY(hipMemcpyAsync(s->kb.p, s->F.p, s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[2], s->stream));
-        gmpnp_linear_stats_t ls{};
-        rc = band_solve<NF>(s, r, o.krylov_relative_tolerance, o.krylov_absolute_tolerance, &ls, true); if (rc) return rc;
-        st.direct_solves++; s->x0_predicted = false;
-        hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, (const double*)s->kx.p,
-                           -o.relaxation_parameter, (int)s->ndof);
-      } else {
-        return fail(GMPNP_ERR_INVALID, "block-banded LU is the 3D direct solver (1D meshes: GMPNP_LINEAR_BLOCK_TRIDIAGONAL)");
-      }
-    } else {
-      // The coarse inverse is reused for up to coarse_lag Newton iterations, unless the state was just set from outside
-      // (first solve of a run: the Jacobian changes a lot between iterations) or the last reuse cost iterations.
-      // Asynchronous scheme (default): every iteration starts the coarse chain of its matrix on the side stream and solves
-      // with the inverse of the previous one; an inverse of THIS matrix is only built in-stream when it has to be.
-      // x0 = wa dx_k + wb dx_{k-1}, the predicted start of this solve (gmpnp_host_rules.h; gmpnp_options_t.warm_start)
-      const double q = 1.0 - o.relaxation_parameter;
-      const auto [wa, wb] = predicted_start(s->warm_start, q, st.iterations);
-      // (The previous time step's total update is useless as a start of a step's FIRST solve: optimal multiple ~1e-5,
-      // measured in round 1.)
-      const bool x0_ready = s->x0_predicted && st.iterations > 0 && wa != 0.0;
-      // The test of the predicted start (w = J x0 and three dot products, then a host decision) needs the new Jacobian
-      // only: it runs on the side stream while the main stream builds the preconditioner, and the host waits for ITS
-      // event, so neither the two kernels nor the round trip sit on the critical path.
-      bool dots_in_flight = false;
-      if (x0_ready && s->stream2 && s->warm_async) {
-        HIP_TRY(hipEventRecord(s->ev_jac, s->stream));
-        HIP_TRY(hipStreamWaitEvent(s->stream2, s->ev_jac, 0));
-        hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream2, s->c, (const double*)s->kx.p, s->kt.p);
-        hipLaunchKernelGGL(k_dots3, dim3(s->n_resblocks), dim3(kVecBlock), 0, s->stream2, (const double*)s->kt.p, (const double*)s->kb.p,
-                           s->c.part_f, (int)s->ndof, s->n_resblocks);
-        HIP_TRY(hipEventRecord(s->ev_dots, s->stream2));
-        dots_in_flight = true;
-      }
-      const bool must = s->state_jumped || s->coarse_refresh_due;
-      const bool async_ok = s->coarse_async != 0 && DIM == 3;
-      const bool coarse_fresh = async_ok ? must : (s->coarse_lag <= 1 || (st.iterations % s->coarse_lag) == 0 || must);
-      rc = setup_preconditioner<DIM, NF>(s, o.linear_solver, true, coarse_fresh, async_ok); if (rc) return rc;
-      if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[2], s->stream));
-      gmpnp_linear_stats_t ls{};
-      // inside Newton only long solves are checked: a short one does not drift, and Newton's own residual test sees
-      // whatever is left
-      s->krylov_hint = st.iterations < 32 ? s->hint_by_newton_it[st.iterations] : 0;
-      // coefficients of the NEXT iteration's predicted start, which this solve's update leaves in kx
-      const auto [na, nb] = predicted_start(s->warm_start, q, st.iterations + 1);
-      const NewtonUpdate upd{s->u.p, s->kxp.p, o.relaxation_parameter, na, nb};
-      KrylovRequest req;
-      req.mode = o.linear_solver; req.bnorm = r; req.rtol = o.krylov_relative_tolerance; req.atol = o.krylov_absolute_tolerance;
-      req.maxit = o.krylov_maximum_iterations; req.verify_above = 500; req.warm_scale = wa; req.warm_prev = wb;
-      req.rhs_ready = true; req.x0_ready = x0_ready; req.dots_in_flight = dots_in_flight; req.upd = na != 0.0 ? &upd : nullptr;
-      rc = krylov_verified<NF>(s, &ls, req);
-      if (dots_in_flight) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_dots, 0));  // whatever path the solve took: kt and vals are free again
-      // feedback: a reused coarse inverse that doubles the iteration count of the last fresh solve is dropped
-      if (st.iterations < 32) s->hint_by_newton_it[st.iterations] = ls.iterations;
-      s->krylov_hint = 0;
-      if (rc == GMPNP_OK && st.iterations == 0) s->direct_backoff /= 2;  // BiCGStab works again
-      if (coarse_fresh) { s->krylov_fresh_iters = ls.iterations; s->coarse_refresh_due = false; }
-      else if (ls.iterations > 2 * s->krylov_fresh_iters + 10) s->coarse_refresh_due = true;
-      if (st.iterations < GMPNP_MAX_NEWTON_HISTORY) st.krylov_per_iteration[st.iterations] = ls.iterations;
-      st.krylov_iterations += ls.iterations;
-      if constexpr (DIM == 3) {
-        // The reference's linear solver is direct (MUMPS, 3D:792): a Krylov solve that does not converge is not an
-        // error there.  The block-banded LU takes over for this system, the rest of this Newton solve and the
-        // next few solves (kb still holds b).
-        if (rc == GMPNP_ERR_LINEAR && s->direct_fallback) {
-          const std::string why = g_err;
-          HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
-          gmpnp_linear_stats_t ds{};
-          rc = band_solve<NF>(s, r, o.krylov_relative_tolerance, o.krylov_absolute_tolerance, &ds, true);
-          if (rc) g_err = why + "; direct fallback: " + g_err;
-          else {  // back off: 8, 16, ... 256 Newton solves before BiCGStab is tried again (a failed try costs ~0.25 s)
-            st.direct_solves++; s->coarse_refresh_due = true;
-            s->direct_backoff = std::min(256, std::max(8, 2 * s->direct_backoff));
-            s->direct_sticky = s->direct_backoff;
-          }
-        }
-      }
-      if (rc) {
-        HIP_TRY(hipMemcpy(s->h_status, s->status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (*s->h_status) g_err += " [" + status_message(*s->h_status) + "]";
-        return rc;
-      }
-      // x <- x - omega dx (done by the solve's last kernel in the normal case)
-      if (req.upd_done) s->x0_predicted = true;
-      else if (na != 0.0) {
-        hipLaunchKernelGGL(k_update_predict, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, s->kx.p, s->kxp.p,
-                           o.relaxation_parameter, na, nb, (int)s->ndof);
-        s->x0_predicted = true;
-      } else {
-        hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, (const double*)s->kx.p,
-                           -o.relaxation_parameter, (int)s->ndof);
-        s->x0_predicted = false;
-      }
-    }
-    if (s->phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[3], s->stream));
+    rc = mark_phase(s, 1); if (rc) return rc;
+    if (o.linear_solver == GMPNP_LINEAR_BLOCK_TRIDIAGONAL) rc = tridiagonal_step<DIM, NF>(s, o, st, r);
+    else if (band_lu_asked || s->direct.use_direct()) rc = direct_step<DIM, NF>(s, o, st, r);
+    else rc = krylov_step<DIM, NF>(s, o, st, r);
+    if (rc) return rc;
+    rc = mark_phase(s, 3); if (rc) return rc;
     st.iterations++;
-    ta = now_ms();
     rc = residual<DIM, NF>(s, true, &r, &flags); if (rc) return rc;  // synchronises the stream
-    if (s->phase_timing) {  // gmpnp_options_t.phase_timing: device time per phase (five event records and one more wait per iteration)
-      float ms01 = 0.f, ms12 = 0.f, ms23 = 0.f, ms3 = 0.f;
-      (void)hipEventElapsedTime(&ms01, s->ev_phase[0], s->ev_phase[1]);
-      (void)hipEventElapsedTime(&ms12, s->ev_phase[1], s->ev_phase[2]);
-      (void)hipEventElapsedTime(&ms23, s->ev_phase[2], s->ev_phase[3]);
-      HIP_TRY(hipEventRecord(s->ev_phase[4], s->stream));
-      HIP_TRY(hipEventSynchronize(s->ev_phase[4]));
-      (void)hipEventElapsedTime(&ms3, s->ev_phase[3], s->ev_phase[4]);
-      st.ms_assemble += ms01 + ms3;   // Jacobian assembly + next residual (device time)
-      st.ms_setup += ms12;
-      st.ms_krylov += ms23;
-    }
+    rc = collect_phases(s, st); if (rc) return rc;
     v = judge.next(r, flags);
   }
   if (v == NewtonJudge::failed) return fail(judge.code, judge.message);
   s->state_jumped = false;
-  if (s->direct_sticky > 0 && o.linear_solver != GMPNP_LINEAR_BAND_LU) s->direct_sticky--;
+  s->direct.newton_done(band_lu_asked);
   st.ms_total = now_ms() - t0;
   return v == NewtonJudge::converged ? GMPNP_OK : fail(judge.code, judge.message);
 }
@@ -1196,7 +1180,9 @@ static int create_impl(const gmpnp_mesh_t* mesh, const gmpnp_model_t* model, con
     if (mesh->dim != 3) return fail(GMPNP_ERR_INVALID, "mesh partitions exist for 3D meshes");
     s->opts.shared_device = 1; s->opts.launch_form = 4;
   }
-  std::string err = build_topology(*mesh, nf, s->opts.n_aggregates, s->t, part);
+  std::string err = resolve_options(s->opts, mesh->dim, &s->cfg);
+  if (!err.empty()) return fail(GMPNP_ERR_INVALID, err);
+  err = build_topology(*mesh, nf, s->opts.n_aggregates, s->t, part);
   if (!err.empty()) return fail(GMPNP_ERR_INVALID, err);
   Topology& t = s->t;
   s->dim = mesh->dim; s->nf = nf; s->nn = mesh->dim + 1; s->ndof = t.nv * nf; s->nb = (int)t.cols.size();
@@ -1222,7 +1208,6 @@ static int create_impl(const gmpnp_mesh_t* mesh, const gmpnp_model_t* model, con
   }
   HIP_TRY(hipStreamCreate(&s->stream));
   for (auto& e : s->ev_phase) HIP_TRY(hipEventCreate(&e));
-  if (s->opts.krylov_batch < 0 || s->opts.profile_every < 0) return fail(GMPNP_ERR_INVALID, "negative option");
 
   const int nv = t.nv, nc = t.nc, nn = s->nn, ndof = s->ndof;
   const int ej_stride = (mesh->dim == 3) ? Lay<3, 9>::EJ_STRIDE : Lay<1, 7>::EJ_STRIDE;
@@ -1261,21 +1246,7 @@ static int create_impl(const gmpnp_mesh_t* mesh, const gmpnp_model_t* model, con
   HIP_TRY(s->Ac.alloc((size_t)s->ncoarse * s->ncoarse)); HIP_TRY(s->Aci.alloc((size_t)s->ncoarse * s->ncoarse));
   HIP_TRY(s->Aci2.alloc((size_t)s->ncoarse * s->ncoarse));
   const gmpnp_options_t& po = s->opts;
-  if (po.launch_form != 0 && po.launch_form != 2 && po.launch_form != 4) return fail(GMPNP_ERR_INVALID, "launch_form must be 0, 2 or 4");
-  if (po.coarse_refresh < 0 || po.burst_iterations < 0 || po.warm_start < -1 || po.warm_start > 1 || !(po.band_lu_max_gb >= 0.0) ||
-      po.vector_form < 0 || po.vector_form > 2)
-    return fail(GMPNP_ERR_INVALID, "option out of range");
-  s->coarse_async = (po.coarse_refresh == 0 && !po.shared_device) ? 1 : 0;
-  s->coarse_lag = po.coarse_refresh > 0 ? po.coarse_refresh : 3;
-  s->warm_async = (po.warm_in_stream || po.shared_device) ? 0 : 1;
-  s->warm_start = po.warm_start == 0 ? 2 : (po.warm_start == 1 ? 1 : 0);
-  s->host_poll = po.progress_by_copy ? 0 : 1;
-  s->burst_iters = std::max(1, po.burst_iterations);
-  s->phase_timing = po.phase_timing != 0;
-  s->direct_fallback = po.no_direct_fallback ? 0 : 1;
-  s->strict_steric = po.strict_steric ? 1 : 0;
-  if (po.band_lu_max_gb > 0.0) s->lu_max_gb = po.band_lu_max_gb;
-  if (s->coarse_async || s->warm_async) {   // the side stream exists only when something uses it
+  if (s->cfg.coarse_async || s->cfg.warm_async) {   // the side stream exists only when something uses it
     HIP_TRY(hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&s->ev_mat, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->ev_chain, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&s->ev_jac, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->ev_dots, hipEventDisableTiming));
@@ -1362,8 +1333,6 @@ static int create_impl(const gmpnp_mesh_t* mesh, const gmpnp_model_t* model, con
   // use the same buffers for their all-reduced sums.
   HIP_TRY(s->red_i.alloc(s->ncoarse)); HIP_TRY(s->red_a.alloc(2 + 3 * (size_t)s->ncoarse)); HIP_TRY(s->red_b.alloc(4 + (size_t)s->ncoarse));
   c.red_i = s->red_i.p; c.red_a = s->red_a.p; c.red_b = s->red_b.p;
-  if (s->opts.element_stores < 0 || s->opts.element_stores > 2 || (s->opts.element_stores == 2 && mesh->dim != 3))
-    return fail(GMPNP_ERR_INVALID, "element_stores: 0 (automatic), 1 (direct), 2 (staged, 3D meshes)");
   s->staged_element = mesh->dim == 3 && s->opts.element_stores != 1;   // measured faster at every size: 36.6 vs 40.5 us on L_50_R_5, 1.18 vs 2.00 ms at two refinements
   s->prereduce = !part && mesh->dim == 3 && t.tile_slots > 128;
   if (s->prereduce) c.dist = 1;
@@ -1539,7 +1508,7 @@ int gmpnp_assemble(gmpnp_solver* s, int32_t want_jacobian, double* F_out, double
   }
   if (norm_out) *norm_out = r;
   if (F_out) { rc = download_vec(s, s->F.p, F_out); if (rc) return rc; }
-  if ((flags & 1) && s->strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+  if ((flags & 1) && s->cfg.strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
   return GMPNP_OK;
 }
 

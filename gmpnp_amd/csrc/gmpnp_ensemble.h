@@ -262,7 +262,7 @@ int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t*
   std::vector<NewtonJudge> judge; judge.reserve(n);   // one per member: the single handle's rule (gmpnp_host_rules.h)
   for (int k = 0; k < n; ++k) {
     stats[k] = gmpnp_newton_stats_t{}; status[k] = GMPNP_OK; e->err[k].clear();
-    judge.emplace_back(*o, stats[k], e->m[k]->strict_steric != 0);
+    judge.emplace_back(*o, stats[k], e->m[k]->cfg.strict_steric != 0);
     HIP_TRY(hipMemsetAsync(e->m[k]->status.p, 0, sizeof(int32_t), e->stream));
   }
   // member k's residual is in its pinned buffer: the verdict, mapped to status[k] / err[k] / live[k] (a member that fails keeps

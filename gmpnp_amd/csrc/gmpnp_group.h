@@ -99,19 +99,7 @@ struct gmpnp_group {
   gmpnp_comm* comm = nullptr;           // RCCL transport (exactly one local handle) or nullptr (all ranks in this process)
   std::vector<hipStream_t> own_stream;  // in-process mode: the handles' own streams, given back at destroy
   std::vector<std::vector<int>> peer_slot;  // in-process mode: peer_slot[d][j] = index of d in the neighbour list of d's neighbour j
-  int last_iters = 0;                   // BiCGStab iterations of the previous solve (identical on every rank): sizes the first burst
-  // ... and those of the previous Newton solve BY NEWTON ITERATION (the k-th linear solve of a time step takes within an iteration
-  // or two of what the k-th of the step before took — 85 / 65 / 53 / 44 ... — while consecutive solves differ by tens): the first
-  // burst of a solve is sized by it, so that most solves end inside their first burst (a burst boundary is a device-to-host copy
-  // and a stream synchronisation: 30 us of idle GPU; an iteration launched behind the end of a solve costs 14 us)
-  int iters_by_newton[16] = {0};
-  // Coarse operator of the two-level preconditioner: rebuilt (Galerkin product, one all-reduce, 72 x 72 inverse: 180 us in the
-  // stream) for the first Newton iteration of a solve and every third one after it; in between the solves run with the
-  // inverse they have — any coarse operator gives a valid right preconditioner (the single-GPU solver does the same with a
-  // side stream).  A solve that needs 25 % more iterations than the last one with a fresh inverse forces a rebuild
-  // (from the zero state the Jacobian of the second Newton iteration is far from the first one's: 160 instead of 73 iterations).
-  // Every figure here is identical on all ranks, so all ranks decide alike.
-  int coarse_age = 1 << 20, coarse_fresh_iters = 0; bool coarse_slow = false;
+  GroupBurstHint burst; GroupCoarseReuse coarse;   // gmpnp_host_rules.h: first-burst sizing, cadence of the coarse operator (identical on every rank)
   // peer-mailbox transport (gmpnp_group_peer_begin / _connect): one k_peer_exchange launch per collective, no library, no host step
   bool peer = false, peer_connected = false;
   unsigned* peer_counter = nullptr;                        // arrival counter of k_dist_reduce_exchange (device)
@@ -416,7 +404,7 @@ int pml_masks(gmpnp_group* F) {
 
 // Once per preconditioner set-up: the state goes down by injection (owned rows, then the ghost rows from their owners), every level
 // assembles its Jacobian and sets up its node-block inverse (ghost blocks from their owners); the coarsest level also its GLOBAL slab
-// operator (one all-reduce), rebuilt with the finest level's cadence (`rebuild`: coarse_age / coarse_slow, identical on all ranks).
+// operator (one all-reduce), rebuilt with the finest level's cadence (`rebuild`: GroupCoarseReuse, identical on all ranks).
 template <int DIM, int NF>
 int group_ml_setup(gmpnp_group* g, bool rebuild) {
   for (gmpnp_group* F = g; F->ml_next; F = F->ml_next) {
@@ -645,10 +633,10 @@ int group_krylov(gmpnp_group* g, int mode, double bnorm, double rtol, double ato
     return GMPNP_OK;
   };
   if (!res.done) {
-    // Bursts: every rank launches the SAME number of iterations (the schedule depends only on the previous solve's count and
+    // Bursts: every rank launches the SAME number of iterations (the schedule depends only on earlier solves' counts and
     // on `done`, both identical on all ranks), then reads the device's verdict.  Iterations launched behind the end of the
     // solve exit at their first instruction; their collectives still pair up.
-    int burst = predicted > 0 ? predicted + 1 : (sized_by_previous ? std::max(2, (7 * g->last_iters) / 8) : 4);
+    int burst = g->burst.first(predicted, sized_by_previous);
     gmpnp_solver* s0 = g->dom[0];
     while (true) {
       for (int it = 0; it < burst; ++it) { rc = iteration(); if (rc) return rc; }
@@ -661,7 +649,7 @@ int group_krylov(gmpnp_group* g, int mode, double bnorm, double rtol, double ato
       burst = 4;
     }
   }
-  g->last_iters = res.iters;
+  g->burst.solve_done(res.iters);
   for (gmpnp_solver* s : g->dom) s->last_done = res.done;
   return krylov_verdict(res, bnorm, st, "partitioned BiCGStab");
 }
@@ -688,6 +676,71 @@ int group_update(gmpnp_group* g, int mode, double omega, bool add_to_start) {
   return GMPNP_OK;
 }
 
+// The linear solve of one Newton iteration (J dx = F, ||F|| = r, preconditioner set up): dx is left for group_update, `warm` says
+// whether it adds to the predicted start in kx.  Counts the BiCGStab iterations into st and `iters`, also those of a failed solve.
+struct GroupLinearStep { bool warm = false; int iters = 0; };
+
+template <int NF>
+int group_linear_step(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st, double r, GroupLinearStep* out) {
+  int rc = GMPNP_OK;
+  gmpnp_linear_stats_t ls{};
+  // Warm start, as in the single-GPU Newton: the predicted start (gmpnp_host_rules.h) is accepted when it removes at least half
+  // of the residual (one SpMV, three all-reduced dot products, a decision identical on every rank), and BiCGStab then only
+  // has to remove b - J x0, to the SAME absolute target.
+  const double tol_abs = std::max(o.krylov_relative_tolerance * r, o.krylov_absolute_tolerance);
+  const std::pair<double, double> w = predicted_start(g->dom[0]->cfg.warm_start, 1.0 - o.relaxation_parameter, st.iterations);
+  bool warm = false; double rstart = r;
+  if ((w.first != 0.0 || w.second != 0.0) && r > 0.0) {
+    rc = group_dots3<NF>(g, &gmpnp_solver::kt, &gmpnp_solver::kb, [&](gmpnp_solver* s) -> int {
+      hipLaunchKernelGGL(k_warm_start, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, w.first, w.second, (int)s->ndof);
+      hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->kx.p, s->kt.p);
+      return GMPNP_OK;
+    });
+    if (rc) return rc;
+    const double* h = g->dom[0]->h_red;
+    if (accept_predicted_start(h[0], h[1], h[2], &rstart)) {
+      for (gmpnp_solver* s : g->dom)
+        hipLaunchKernelGGL(k_start_residual, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p, (const double*)s->kt.p, (int)s->ndof);
+      warm = true;
+    }
+  }
+  int kry_total = 0;
+  if (warm && rstart <= tol_abs) { ls.converged = 1; ls.residual_norm = rstart; for (gmpnp_solver* s : g->dom) HIP_TRY(hipMemsetAsync(s->ky.p, 0, s->ndof * sizeof(double), s->stream)); }
+  else {
+    // BiCGStab can break down, or spike past 1e5 times its starting residual, on one (right-hand side, shadow vector) pair
+    // and run smoothly on another: such a pass is thrown away and repeated with a pseudo-random shadow vector — the
+    // second time also without the predicted start — as the single-GPU solver does (gmpnp_api.hip, linear_solve).  The
+    // verdict comes from all-reduced sums, so every rank takes the same branch.
+    bool random_shadow = false; double rho0 = 0.0;
+    for (int attempt = 0;; ++attempt) {
+      const int hist = g->burst.predicted(attempt, g->dom[0]->state_jumped, st.iterations);
+      rc = group_krylov<NF>(g, o.linear_solver, rstart, warm ? 0.0 : o.krylov_relative_tolerance, warm ? tol_abs : o.krylov_absolute_tolerance,
+                            o.krylov_maximum_iterations, &ls, st.iterations > 0 && attempt == 0, random_shadow, rho0, hist);
+      g->burst.record(attempt, rc == GMPNP_OK, st.iterations, ls.iterations);
+      kry_total += ls.iterations;
+      if (rc != GMPNP_ERR_LINEAR || attempt >= 4 || g->dom[0]->last_done != 3) break;
+      if (warm && attempt >= 1) { warm = false; rstart = r; }
+      const int r2 = group_dots3<NF>(g, &gmpnp_solver::krand, &gmpnp_solver::kr, [&](gmpnp_solver* s) -> int {
+        const int nd = s->ndof;
+        HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
+        if (warm) {   // kr = b - J x0 again (kt was a work vector of the lost pass)
+          hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->kx.p, s->kt.p);
+          hipLaunchKernelGGL(k_start_residual, dim3(grid_for(nd, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p, (const double*)s->kt.p, nd);
+        } else HIP_TRY(hipMemcpyAsync(s->kr.p, s->kb.p, nd * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        hipLaunchKernelGGL(k_fill_hash, dim3(grid_for(nd, 256)), dim3(256), 0, s->stream, s->krand.p, (unsigned)((attempt + 1) * 2654435761u), nd);
+        return GMPNP_OK;
+      });
+      if (r2) return r2;
+      rho0 = g->dom[0]->h_red[0]; random_shadow = true;   // (rhat, r_0) of the new shadow vector, over all ranks' owned rows
+    }
+    ls.iterations = kry_total;
+  }
+  if (st.iterations < GMPNP_MAX_NEWTON_HISTORY) st.krylov_per_iteration[st.iterations] = ls.iterations;
+  st.krylov_iterations += ls.iterations;
+  out->warm = warm; out->iters = ls.iterations;
+  return rc;
+}
+
 template <int DIM, int NF>
 int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st) {
   const double t0 = now_ms();
@@ -696,82 +749,24 @@ int group_newton(gmpnp_group* g, const gmpnp_newton_options_t& o, gmpnp_newton_s
   int rc = group_exchange(g, NF, 2, [](gmpnp_solver* s) { VecListW w{}; w.p[0] = s->u.p; w.p[1] = s->un.p; return w; }); if (rc) return rc;
   double r = 0.0; int flags = 0;
   rc = group_residual<DIM, NF>(g, &r, &flags); if (rc) return rc;
-  NewtonJudge judge(o, st, g->dom[0]->strict_steric != 0);   // r and flags are all-reduced: the same verdict on every rank
+  NewtonJudge judge(o, st, g->dom[0]->cfg.strict_steric != 0);   // r and flags are all-reduced: the same verdict on every rank
   NewtonJudge::Verdict v = judge.first(r, flags);
+  const bool two_level = o.linear_solver == GMPNP_LINEAR_BICGSTAB_TWOLEVEL;
   while (v == NewtonJudge::go_on) {
     for (gmpnp_solver* s : g->dom) { rc = launch_jac_gather<DIM, NF>(s); if (rc) return rc; s->jacobian_valid = true; }
-    const bool two_level = o.linear_solver == GMPNP_LINEAR_BICGSTAB_TWOLEVEL;
-    // (a solve that starts from a state set from outside — the zero state of time step 0 — rebuilds every time: its Jacobians differ
-    // too much, 203 instead of 56 iterations with the first iteration's inverse in the second)
-    const bool rebuild = two_level && (st.iterations == 0 || g->coarse_age >= 2 || g->coarse_slow || g->dom[0]->state_jumped);
+    const bool rebuild = two_level && g->coarse.rebuild(st.iterations, g->dom[0]->state_jumped);
     rc = group_setup<NF>(g, o.linear_solver, rebuild); if (rc) return rc;
     if (g->ml_next) { rc = group_ml_setup<DIM, NF>(g, rebuild); if (rc) return rc; }
-    gmpnp_linear_stats_t ls{};
-    // Warm start, as in the single-GPU Newton: the predicted start (gmpnp_host_rules.h) is accepted when it removes at least half
-    // of the residual (one SpMV, three all-reduced dot products, a decision identical on every rank), and BiCGStab then only
-    // has to remove b - J x0, to the SAME absolute target.
-    const double tol_abs = std::max(o.krylov_relative_tolerance * r, o.krylov_absolute_tolerance);
-    const std::pair<double, double> w = predicted_start(g->dom[0]->warm_start, 1.0 - o.relaxation_parameter, st.iterations);
-    bool warm = false; double rstart = r;
-    if ((w.first != 0.0 || w.second != 0.0) && r > 0.0) {
-      rc = group_dots3<NF>(g, &gmpnp_solver::kt, &gmpnp_solver::kb, [&](gmpnp_solver* s) -> int {
-        hipLaunchKernelGGL(k_warm_start, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, s->kxp.p, w.first, w.second, (int)s->ndof);
-        hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->kx.p, s->kt.p);
-        return GMPNP_OK;
-      });
-      if (rc) return rc;
-      const double* h = g->dom[0]->h_red;
-      if (accept_predicted_start(h[0], h[1], h[2], &rstart)) {
-        for (gmpnp_solver* s : g->dom)
-          hipLaunchKernelGGL(k_start_residual, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p, (const double*)s->kt.p, (int)s->ndof);
-        warm = true;
-      }
-    }
-    int kry_total = 0;
-    if (warm && rstart <= tol_abs) { ls.converged = 1; ls.residual_norm = rstart; for (gmpnp_solver* s : g->dom) HIP_TRY(hipMemsetAsync(s->ky.p, 0, s->ndof * sizeof(double), s->stream)); }
-    else {
-      // BiCGStab can break down, or spike past 1e5 times its starting residual, on one (right-hand side, shadow vector) pair
-      // and run smoothly on another: such a pass is thrown away and repeated with a pseudo-random shadow vector — the
-      // second time also without the predicted start — as the single-GPU solver does (gmpnp_api.hip, linear_solve).  The
-      // verdict comes from all-reduced sums, so every rank takes the same branch.
-      bool random_shadow = false; double rho0 = 0.0;
-      for (int attempt = 0;; ++attempt) {
-        const int hist = (attempt == 0 && !g->dom[0]->state_jumped && st.iterations < 16) ? g->iters_by_newton[st.iterations] : 0;
-        rc = group_krylov<NF>(g, o.linear_solver, rstart, warm ? 0.0 : o.krylov_relative_tolerance, warm ? tol_abs : o.krylov_absolute_tolerance,
-                              o.krylov_maximum_iterations, &ls, st.iterations > 0 && attempt == 0, random_shadow, rho0, hist);
-        if (attempt == 0 && rc == GMPNP_OK && st.iterations < 16) g->iters_by_newton[st.iterations] = ls.iterations;
-        kry_total += ls.iterations;
-        if (rc != GMPNP_ERR_LINEAR || attempt >= 4 || g->dom[0]->last_done != 3) break;
-        if (warm && attempt >= 1) { warm = false; rstart = r; }
-        const int r2 = group_dots3<NF>(g, &gmpnp_solver::krand, &gmpnp_solver::kr, [&](gmpnp_solver* s) -> int {
-          const int nd = s->ndof;
-          HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
-          if (warm) {   // kr = b - J x0 again (kt was a work vector of the lost pass)
-            hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)s->kx.p, s->kt.p);
-            hipLaunchKernelGGL(k_start_residual, dim3(grid_for(nd, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p, (const double*)s->kt.p, nd);
-          } else HIP_TRY(hipMemcpyAsync(s->kr.p, s->kb.p, nd * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-          hipLaunchKernelGGL(k_fill_hash, dim3(grid_for(nd, 256)), dim3(256), 0, s->stream, s->krand.p, (unsigned)((attempt + 1) * 2654435761u), nd);
-          return GMPNP_OK;
-        });
-        if (r2) return r2;
-        rho0 = g->dom[0]->h_red[0]; random_shadow = true;   // (rhat, r_0) of the new shadow vector, over all ranks' owned rows
-      }
-      ls.iterations = kry_total;
-    }
-    if (st.iterations < GMPNP_MAX_NEWTON_HISTORY) st.krylov_per_iteration[st.iterations] = ls.iterations;
-    st.krylov_iterations += ls.iterations;
-    if (rc) return rc;
-    if (two_level) {
-      if (rebuild) { g->coarse_age = 0; g->coarse_fresh_iters = ls.iterations; g->coarse_slow = false; }
-      else { g->coarse_age++; g->coarse_slow = ls.iterations > g->coarse_fresh_iters + g->coarse_fresh_iters / 4 + 5; }
-    }
-    rc = group_update<NF>(g, o.linear_solver, o.relaxation_parameter, warm); if (rc) return rc;
+    GroupLinearStep lin;
+    rc = group_linear_step<NF>(g, o, st, r, &lin); if (rc) return rc;
+    if (two_level) g->coarse.solved(rebuild, lin.iters);
+    rc = group_update<NF>(g, o.linear_solver, o.relaxation_parameter, lin.warm); if (rc) return rc;
     st.iterations++;
     rc = group_residual<DIM, NF>(g, &r, &flags); if (rc) return rc;
     v = judge.next(r, flags);
   }
   if (v == NewtonJudge::failed) return fail(judge.code, judge.message);
-  for (gmpnp_solver* s : g->dom) { s->state_jumped = false; s->x0_predicted = false; }
+  for (gmpnp_solver* s : g->dom) { s->state_jumped = false; s->x0.left(false); }
   st.ms_total = now_ms() - t0;
   return v == NewtonJudge::converged ? GMPNP_OK : fail(judge.code, judge.message);
 }

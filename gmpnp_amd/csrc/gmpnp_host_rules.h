@@ -1,8 +1,10 @@
 // Host-side decisions that have no device in them: what a Newton residual means (one verdict for newton(), group_newton()
-// and the ensemble driver), the predicted start of a linear solve, and the tables of the geometric multilevel term.
+// and the ensemble driver), the predicted start of a linear solve, the policies of the linear solves inside Newton (coarse reuse,
+// direct fallback, burst sizing), the options' resolution, and the tables of the geometric multilevel term.
 // Includes gmpnp.h and the C++ standard library only, so it compiles (and is tested) with the host compiler alone.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -89,6 +91,143 @@ inline bool accept_predicted_start(double wb, double ww, double bb, double* rnor
   if (!(rn2 == rn2 && rn2 >= 0.0 && rn2 < 0.25 * bb)) return false;
   *rnorm = std::sqrt(rn2);
   return true;
+}
+
+// ---- policies of the linear solves inside Newton: each owns its state; newton() / group_newton() ask and report, nothing else --------
+
+// kx holds the predicted start of the next linear solve (left by the previous Newton update).  (The previous time step's total
+// update is useless as a start of a step's FIRST solve: optimal multiple ~1e-5, measured in round 1.)
+struct PredictedX0 {
+  bool held = false;
+  void left(bool by_update) { held = by_update; }
+  bool ready(int newton_it, double scale) const { return held && newton_it > 0 && scale != 0.0; }
+};
+
+// Coarse inverse of a single handle: reused for up to `lag` Newton iterations, unless the state was just set from outside (first
+// solve of a run: the Jacobian changes a lot between iterations) or the last reuse cost iterations.  Asynchronous scheme (default):
+// every iteration starts the coarse chain of its matrix on the side stream and solves with the inverse of the previous one; an
+// inverse of THIS matrix is only built in-stream when it has to be.
+struct CoarseReuse {
+  bool refresh_due = false;  // a solve with a reused coarse inverse took clearly longer than the last fresh one
+  int fresh_iters = 0;       // iterations of the last solve right after a coarse rebuild
+  bool fresh(bool async, int lag, int newton_it, bool state_jumped) const {
+    const bool must = state_jumped || refresh_due;
+    return async ? must : (lag <= 1 || (newton_it % lag) == 0 || must);
+  }
+  // feedback: a reused coarse inverse that doubles the iteration count of the last fresh solve is dropped
+  void solved(bool was_fresh, int iters) {
+    if (was_fresh) { fresh_iters = iters; refresh_due = false; }
+    else if (iters > 2 * fresh_iters + 10) refresh_due = true;
+  }
+  void fell_back() { refresh_due = true; }
+};
+
+// Coarse operator of the partitioned two-level preconditioner: rebuilt (Galerkin product, one all-reduce, 72 x 72 inverse: 180 us
+// in the stream) for the first Newton iteration of a solve and every third one after it; in between the solves run with the
+// inverse they have — any coarse operator gives a valid right preconditioner (the single-GPU solver does the same with a
+// side stream).  A solve that needs 25 % more iterations than the last one with a fresh inverse forces a rebuild
+// (from the zero state the Jacobian of the second Newton iteration is far from the first one's: 160 instead of 73 iterations).
+// Every figure here is identical on all ranks, so all ranks decide alike.  Schedule and threshold differ from CoarseReuse's on
+// purpose: either one's rule in the other's place changes iteration counts.
+struct GroupCoarseReuse {
+  int age = 1 << 20, fresh_iters = 0; bool slow = false;
+  // (a solve that starts from a state set from outside — the zero state of time step 0 — rebuilds every time: its Jacobians differ
+  // too much, 203 instead of 56 iterations with the first iteration's inverse in the second)
+  bool rebuild(int newton_it, bool state_jumped) const { return newton_it == 0 || age >= 2 || slow || state_jumped; }
+  void solved(bool rebuilt, int iters) {
+    if (rebuilt) { age = 0; fresh_iters = iters; slow = false; }
+    else { age++; slow = iters > fresh_iters + fresh_iters / 4 + 5; }
+  }
+};
+
+// The reference's linear solver is direct (MUMPS, 3D:792): a Krylov solve that does not converge is not an error there.  The
+// block-banded LU takes over for that system, the rest of that Newton solve and the next few solves.
+struct DirectFallback {
+  int sticky = 0;    // Newton solves that still go straight to the band LU after a Krylov failure
+  int backoff = 0;   // length of the last such stretch (doubles with every new failure, resets on a converged Krylov solve)
+  bool use_direct() const { return sticky > 0; }
+  void krylov_converged(int newton_it) { if (newton_it == 0) backoff /= 2; }  // BiCGStab works again
+  // back off: 8, 16, ... 256 Newton solves before BiCGStab is tried again (a failed try costs ~0.25 s)
+  void fell_back() { backoff = std::min(256, std::max(8, 2 * backoff)); sticky = backoff; }
+  void newton_done(bool band_lu_asked) { if (sticky > 0 && !band_lu_asked) sticky--; }
+};
+
+// First launch burst of a single handle's BiCGStab solve.  With the pinned progress mirror the host keeps up one iteration at a
+// time, so the first burst is insurance against a slow host rather than a way to save polls: half the expected count (measured on
+// the bench, sixteenths of the hint: 0..8 -> 529-533 its/s, 12 -> 525, 14 -> 522, 16 -> 516; more surplus early-exit launches the
+// longer it is).
+struct BurstHint {
+  int hint = 0;  // expected iterations of the next solve (the same Newton iteration of the previous time step), 0 = none
+  int by_newton_it[32] = {0};
+  int last[2] = {0, 0};   // iterations of the last first-pass solve, [use_coarse]
+  void expect(int newton_it) { hint = newton_it < 32 ? by_newton_it[newton_it] : 0; }
+  void record(int newton_it, int iters) { if (newton_it < 32) by_newton_it[newton_it] = iters; hint = 0; }
+  // krylov_batch: gmpnp_options_t; B: iterations per polling burst; the result is a multiple of B
+  int first(int use_coarse, int krylov_batch, int B, bool restart) const {
+    const int expect = hint > 0 ? hint / 2 : last[use_coarse] / 2;
+    int n = krylov_batch > 0 ? krylov_batch : std::max(B, expect);
+    if (restart) n = B;  // a restart pass only has to remove the drift
+    return ((n + B - 1) / B) * B;
+  }
+  void solve_done(int use_coarse, int iters, bool restart) { if (!restart) last[use_coarse] = iters; }
+};
+
+// ... and of a partitioned solve: every rank launches the SAME number of iterations (the schedule depends only on earlier
+// solves' counts, identical on all ranks).
+struct GroupBurstHint {
+  int last = 0;   // BiCGStab iterations of the previous solve (identical on every rank)
+  // ... and those of the previous Newton solve BY NEWTON ITERATION (the k-th linear solve of a time step takes within an iteration
+  // or two of what the k-th of the step before took — 85 / 65 / 53 / 44 ... — while consecutive solves differ by tens): the first
+  // burst of a solve is sized by it, so that most solves end inside their first burst (a burst boundary is a device-to-host copy
+  // and a stream synchronisation: 30 us of idle GPU; an iteration launched behind the end of a solve costs 14 us)
+  int by_newton_it[16] = {0};
+  int predicted(int attempt, bool state_jumped, int newton_it) const {
+    return (attempt == 0 && !state_jumped && newton_it < 16) ? by_newton_it[newton_it] : 0;
+  }
+  void record(int attempt, bool solved, int newton_it, int iters) { if (attempt == 0 && solved && newton_it < 16) by_newton_it[newton_it] = iters; }
+  int first(int predicted, bool sized_by_previous) const { return predicted > 0 ? predicted + 1 : (sized_by_previous ? std::max(2, (7 * last) / 8) : 4); }
+  void solve_done(int iters) { last = iters; }
+};
+
+// gmpnp_options_t resolved into what the solver reads (every option's 0 is its default)
+struct Settings {
+  int coarse_async = 1;       // opts.coarse_refresh = N: rebuild in the main stream every Nth iteration (the older scheme)
+  int coarse_lag = 3;   // rebuild the coarse inverse alone every coarse_lag-th Newton iteration of a solve (measured best: 1 -> 3 costs 0.7 % more Krylov iterations and saves 155 us per skipped rebuild)
+  int warm_async = 1;         // opts.warm_in_stream: test of the predicted start in the main stream, behind the set-up
+  int warm_start = 2;  // start Newton iteration k+1's linear solve from (1 - omega) dx_k (+ second-order term); opts.warm_start
+  int host_poll = 1;            // opts.progress_by_copy: poll with a device-to-host copy + event per burst instead
+  int burst_iters = 1;  // iterations per polling burst (opts.burst_iterations); with copy + event polling: 1 -> 453, 2 -> 463,
+                        // 4 -> 456, 8 -> 436 Newton its/s; with the pinned progress mirror a poll costs nothing on the
+                        // device: 1 -> 496, 2 -> 492
+  bool phase_timing = false;  // opts.phase_timing fills ms_assemble / ms_setup / ms_krylov of the Newton statistics
+  int direct_fallback = 1;      // opts.no_direct_fallback: a failed Krylov solve is an error again
+  int strict_steric = 0;        // opts.strict_steric: 1 - S <= 0 at a quadrature point is fatal (the reference has no such test)
+  double lu_max_gb = 48.0;      // opts.band_lu_max_gb: largest band storage the fallback may allocate
+};
+
+// The options' range checks and their mapping; returns the error text, empty when *out is set.  (launch_form 2, vector_form and
+// the residency of a launch need the device and the topology: gmpnp_create decides those.)
+inline std::string resolve_options(const gmpnp_options_t& po, int dim, Settings* out) {
+  if (po.krylov_batch < 0 || po.profile_every < 0) return "negative option";
+  if (po.launch_form != 0 && po.launch_form != 2 && po.launch_form != 4) return "launch_form must be 0, 2 or 4";
+  if (po.coarse_refresh < 0 || po.burst_iterations < 0 || po.warm_start < -1 || po.warm_start > 1 || !(po.band_lu_max_gb >= 0.0) ||
+      po.vector_form < 0 || po.vector_form > 2)
+    return "option out of range";
+  if (po.element_stores < 0 || po.element_stores > 2 || (po.element_stores == 2 && dim != 3))
+    return "element_stores: 0 (automatic), 1 (direct), 2 (staged, 3D meshes)";
+  Settings s;
+  s.coarse_async = (po.coarse_refresh == 0 && !po.shared_device) ? 1 : 0;
+  s.coarse_lag = po.coarse_refresh > 0 ? po.coarse_refresh : 3;
+  s.warm_async = (po.warm_in_stream || po.shared_device) ? 0 : 1;
+  s.warm_start = po.warm_start == 0 ? 2 : (po.warm_start == 1 ? 1 : 0);
+  s.host_poll = po.progress_by_copy ? 0 : 1;
+  s.burst_iters = std::max(1, po.burst_iterations);
+  s.phase_timing = po.phase_timing != 0;
+  s.direct_fallback = po.no_direct_fallback ? 0 : 1;
+  s.strict_steric = po.strict_steric ? 1 : 0;
+  if (po.band_lu_max_gb > 0.0) s.lu_max_gb = po.band_lu_max_gb;
+  *out = s;
+  return std::string();
 }
 
 // Tables of the multilevel term between a fine and a coarse handle, in the INTERNAL orders of both (perm[internal] = file,

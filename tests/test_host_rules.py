@@ -1,8 +1,10 @@
-"""gmpnp_host_rules.h — the Newton verdict, the predicted start and the multilevel level tables — compiled with the host compiler
-alone (that it compiles without HIP is the assertion that the header is device-free) and checked against the oracle's stop rule,
-the recorded reference histories and NumPy restatements written out here."""
+"""gmpnp_host_rules.h — the Newton verdict, the predicted start, the policies of the linear solves inside Newton, the options'
+resolution and the multilevel level tables — compiled with the host compiler alone (that it compiles without HIP is the assertion
+that the header is device-free) and checked against the oracle's stop rule, the recorded reference histories and Python / NumPy
+restatements written out here."""
 import glob
 import os
+import random
 import subprocess
 
 import numpy as np
@@ -25,6 +27,14 @@ BITS = {1: "1 - sum_j a_j u_j <= 0 at a quadrature point; ", 2: "singular diagon
 #   start warm_start omega iteration
 #   accept wb ww bb
 #   tables partitions f0 f1 c0 c1 nvf perm[nvf] nvc iperm[nvc] parents[2 nvf]
+# The policies: a history of n events in one line, the decision and the whole state after every event in the answer (";" between events)
+#   coarse async lag n  (newton_it jumped fell_back iters)*n          fresh(), solved() [, fell_back()]
+#   gcoarse n  (newton_it jumped iters)*n                             rebuild(), solved()
+#   direct n  (event arg)*n                                           0 use_direct()  1 krylov_converged(arg)  2 fell_back()  3 newton_done(arg)
+#   burst krylov_batch B n  (event a b c)*n                           0 expect(a)  1 first(a, .., b)  2 solve_done(a, b, c)  3 record(a, b)
+#   gburst n  (event a b c d)*n                                       0 predicted(a, b, c)  1 first(a, b)  2 record(a, b, c, d)  3 solve_done(a)
+#   x0 n  (event a scale)*n                                           0 ready(a, scale)  1 left(a)
+#   options dim  <the 16 int32 fields of gmpnp_options_t in order>  band_lu_max_gb
 DRIVER = r"""
 #include <cstdio>
 #include <iostream>
@@ -71,6 +81,83 @@ int main() {
       const std::string err = build_level_tables(perm, iperm, f0, f1, c0, c1, parents.data(), part, &t);
       if (!err.empty()) printf("ERR %s\n", err.c_str());
       else { printf("OK"); ints(t.par); ints(t.copy); ints(t.child_ptr); ints(t.child); printf("\n"); }
+    } else if (cmd == "coarse") {
+      const bool async = num() != 0.0; const int lag = (int)num(), n = (int)num();
+      CoarseReuse c;
+      for (int k = 0; k < n; ++k) {
+        const int it = (int)num(); const bool jumped = num() != 0.0, fell = num() != 0.0; const int iters = (int)num();
+        const bool fresh = c.fresh(async, lag, it, jumped);
+        c.solved(fresh, iters);
+        if (fell) c.fell_back();
+        printf("%d %d %d;", fresh ? 1 : 0, c.refresh_due ? 1 : 0, c.fresh_iters);
+      }
+      printf("\n");
+    } else if (cmd == "gcoarse") {
+      const int n = (int)num();
+      GroupCoarseReuse c;
+      for (int k = 0; k < n; ++k) {
+        const int it = (int)num(); const bool jumped = num() != 0.0; const int iters = (int)num();
+        const bool rebuild = c.rebuild(it, jumped);
+        c.solved(rebuild, iters);
+        printf("%d %d %d %d;", rebuild ? 1 : 0, c.age, c.fresh_iters, c.slow ? 1 : 0);
+      }
+      printf("\n");
+    } else if (cmd == "direct") {
+      const int n = (int)num();
+      DirectFallback d;
+      for (int k = 0; k < n; ++k) {
+        const int ev = (int)num(), arg = (int)num();
+        if (ev == 1) d.krylov_converged(arg); else if (ev == 2) d.fell_back(); else if (ev == 3) d.newton_done(arg != 0);
+        printf("%d %d %d;", d.use_direct() ? 1 : 0, d.sticky, d.backoff);
+      }
+      printf("\n");
+    } else if (cmd == "burst") {
+      const int batch = (int)num(), B = (int)num(), n = (int)num();
+      BurstHint h;
+      for (int k = 0; k < n; ++k) {
+        const int ev = (int)num(), a = (int)num(), b = (int)num(), c = (int)num();
+        int val = -1;
+        if (ev == 0) h.expect(a); else if (ev == 1) val = h.first(a, batch, B, b != 0); else if (ev == 2) h.solve_done(a, b, c != 0); else h.record(a, b);
+        printf("%d %d %d %d", val, h.hint, h.last[0], h.last[1]);
+        for (int x : h.by_newton_it) printf(" %d", x);
+        printf(";");
+      }
+      printf("\n");
+    } else if (cmd == "gburst") {
+      const int n = (int)num();
+      GroupBurstHint h;
+      for (int k = 0; k < n; ++k) {
+        const int ev = (int)num(), a = (int)num(), b = (int)num(), c = (int)num(), d = (int)num();
+        int val = -1;
+        if (ev == 0) val = h.predicted(a, b != 0, c); else if (ev == 1) val = h.first(a, b != 0); else if (ev == 2) h.record(a, b != 0, c, d); else h.solve_done(a);
+        printf("%d %d", val, h.last);
+        for (int x : h.by_newton_it) printf(" %d", x);
+        printf(";");
+      }
+      printf("\n");
+    } else if (cmd == "x0") {
+      const int n = (int)num();
+      PredictedX0 x;
+      for (int k = 0; k < n; ++k) {
+        const int ev = (int)num(), a = (int)num(); const double scale = num();
+        bool ready = false;
+        if (ev == 0) ready = x.ready(a, scale); else x.left(a != 0);
+        printf("%d %d;", ready ? 1 : 0, x.held ? 1 : 0);
+      }
+      printf("\n");
+    } else if (cmd == "options") {
+      const int dim = (int)num();
+      gmpnp_options_t o{};
+      int32_t* f[] = {&o.device_id, &o.n_aggregates, &o.shared_device, &o.krylov_batch, &o.profile_every, &o.launch_form, &o.warm_start, &o.coarse_refresh,
+                      &o.progress_by_copy, &o.burst_iterations, &o.phase_timing, &o.no_direct_fallback, &o.warm_in_stream, &o.vector_form, &o.strict_steric,
+                      &o.element_stores};
+      for (int32_t* x : f) *x = (int32_t)num();
+      o.band_lu_max_gb = num();
+      Settings s;
+      const std::string err = resolve_options(o, dim, &s);
+      if (!err.empty()) printf("ERR %s\n", err.c_str());
+      else printf("OK %d %d %d %d %d %d %d %d %d %.17g\n", s.coarse_async, s.coarse_lag, s.warm_async, s.warm_start, s.host_poll, s.burst_iters,
+                  s.phase_timing ? 1 : 0, s.direct_fallback, s.strict_steric, s.lu_max_gb);
     }
   }
   return 0;
@@ -302,3 +389,290 @@ def test_level_tables_refusals(rules):
     ]
     for (_, want), line in zip(asks, rules([a for a, _ in asks])):
         assert line == "ERR " + want, line
+
+
+def test_header_reaches_no_hip_include():
+    """Every file the header pulls in, by the preprocessor's own list: the C / C++ library and gmpnp.h, nothing of HIP or ROCm."""
+    out = subprocess.run(["g++", "-std=c++17", "-M", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "gmpnp_amd", "csrc", "gmpnp_host_rules.h")],
+                         check=True, capture_output=True, text=True).stdout
+    deps = [d for d in out.replace("\\\n", " ").split()[1:]]
+    assert any(d.endswith("gmpnp.h") for d in deps)
+    assert not [d for d in deps if "hip" in d.lower() or "rocm" in d.lower()], deps
+
+
+# ---- the policies of the linear solves inside Newton ------------------------------------------------------------------------
+# Each model below restates the PARENT commit's inline rule (975009e: gmpnp_api.hip / gmpnp_group.h, line numbers of that commit);
+# the structs are driven with the same histories and must show the same decision and the same state after every event.
+def events(line):
+    return [[int(x) for x in ev.split()] for ev in line.split(";") if ev.strip()]
+
+
+def history(cmd, head, evs):
+    return "%s %s %d %s" % (cmd, " ".join(map(str, head)), len(evs), " ".join(" ".join(map(repr, e)) for e in evs))
+
+
+def model_coarse(async_, lag, evs):
+    due, fresh_iters, out = False, 0, []          # api.hip:122-123
+    for it, jumped, fell, iters in evs:
+        must = bool(jumped) or due                                                  # api.hip:1044
+        fresh = must if async_ else (lag <= 1 or it % lag == 0 or must)             # api.hip:1046 (async_ok: 1045)
+        if fresh:                                                                   # api.hip:1066
+            fresh_iters, due = iters, False
+        elif iters > 2 * fresh_iters + 10:                                          # api.hip:1067
+            due = True
+        if fell:                                                                    # api.hip:1081
+            due = True
+        out.append([int(fresh), int(due), fresh_iters])
+    return out
+
+
+def model_gcoarse(evs):
+    age, fresh, slow, out = 1 << 20, 0, False, []   # group.h:114
+    for it, jumped, iters in evs:
+        rebuild = it == 0 or age >= 2 or slow or bool(jumped)                       # group.h:706 (two_level: the caller's)
+        if rebuild:                                                                 # group.h:765
+            age, fresh, slow = 0, iters, False
+        else:                                                                       # group.h:766
+            age, slow = age + 1, iters > fresh + fresh // 4 + 5
+        out.append([int(rebuild), age, fresh, int(slow)])
+    return out
+
+
+def model_direct(evs):
+    sticky, backoff, out = 0, 0, []                 # api.hip:153-154
+    for ev, arg in evs:
+        if ev == 1 and arg == 0:                    # api.hip:1065 (rc == GMPNP_OK: the event itself; arg = st.iterations)
+            backoff //= 2
+        elif ev == 2:                               # api.hip:1082-1083
+            backoff = min(256, max(8, 2 * backoff))
+            sticky = backoff
+        elif ev == 3 and sticky > 0 and not arg:    # api.hip:1124 (arg: o.linear_solver == GMPNP_LINEAR_BAND_LU)
+            sticky -= 1
+        out.append([int(sticky > 0), sticky, backoff])   # api.hip:1008
+    return out
+
+
+def model_burst(batch, B, evs):
+    hint, table, last, out = 0, [0] * 32, [0, 0], []   # api.hip:113-115
+    for ev, a, b, c in evs:
+        val = -1
+        if ev == 0:                                 # api.hip:1052
+            hint = table[a] if a < 32 else 0
+        elif ev == 1:                               # api.hip:587-590
+            expect = hint // 2 if hint > 0 else last[a] // 2
+            val = batch if batch > 0 else max(B, expect)
+            if b:
+                val = B
+            val = ((val + B - 1) // B) * B
+        elif ev == 2:                               # api.hip:652
+            if not c:
+                last[a] = b
+        else:                                       # api.hip:1063-1064
+            if a < 32:
+                table[a] = b
+            hint = 0
+        out.append([val, hint] + last + table)
+    return out
+
+
+def model_gburst(evs):
+    last, table, out = 0, [0] * 16, []              # group.h:102, 107
+    for ev, a, b, c, d in evs:
+        val = -1
+        if ev == 0:                                 # group.h:739
+            val = table[c] if (a == 0 and not b and c < 16) else 0
+        elif ev == 1:                               # group.h:651
+            val = a + 1 if a > 0 else (max(2, (7 * last) // 8) if b else 4)
+        elif ev == 2:                               # group.h:742
+            if a == 0 and b and c < 16:
+                table[c] = d
+        else:                                       # group.h:664
+            last = a
+        out.append([val, last] + table)
+    return out
+
+
+def model_x0(evs):
+    held, out = False, []                           # api.hip:147
+    for ev, a, scale in evs:
+        ready = False
+        if ev == 0:
+            ready = held and a > 0 and scale != 0.0            # api.hip:1030
+        else:                                       # api.hip:1014, 1093, 1097, 1101; group.h:774
+            held = bool(a)
+        out.append([int(ready), int(held)])
+    return out
+
+
+def check(rules, cmd, cases, model):
+    """cases: (head, events); model(*head, events) -> the expected answer of every event."""
+    for (head, evs), line in zip(cases, rules([history(cmd, head, evs) for head, evs in cases])):
+        assert events(line) == model(*head, evs), (cmd, head, evs, line)
+
+
+def test_coarse_reuse_single_handle(rules):
+    f = 7
+    edges = [
+        # reused solves at exactly 2 f + 10 (kept) and 2 f + 11 (refresh due, taken at the next iteration, cleared by it)
+        ((1, 3), [(0, 1, 0, f), (1, 0, 0, 2 * f + 10), (2, 0, 0, 2 * f + 11), (3, 0, 0, 5), (4, 0, 0, 2 * 5 + 10), (5, 0, 0, 2 * 5 + 11), (6, 0, 0, 9)]),
+        ((0, 3), [(0, 0, 0, f), (1, 0, 0, 2 * f + 10), (2, 0, 0, 2 * f + 11), (3, 0, 0, 5), (4, 0, 0, 2 * 5 + 11), (5, 0, 0, 9), (6, 0, 0, 9), (7, 0, 0, 40)]),
+        # lag 0 / 1: fresh every time; lag 2; a jumped state in the asynchronous scheme
+        ((0, 0), [(k, 0, 0, 100 * k) for k in range(4)]), ((0, 1), [(k, 0, 0, 100 * k) for k in range(4)]),
+        ((0, 2), [(k, 0, 0, 10) for k in range(5)]), ((1, 3), [(k, int(k < 3), 0, 10) for k in range(6)]),
+        # a direct fallback asks for a refresh whatever the solve was
+        ((1, 3), [(0, 1, 1, 3), (1, 0, 0, 3), (2, 0, 0, 3)]), ((0, 3), [(0, 0, 1, 3), (1, 0, 0, 3), (2, 0, 1, 300), (3, 0, 0, 3)]),
+    ]
+    rng = random.Random(20260101)
+    hist = [((rng.randint(0, 1), rng.randint(0, 4)), [(it, int(rng.random() < 0.1), int(rng.random() < 0.1), rng.choice([rng.randint(0, 40), rng.randint(0, 600)]))
+                                                      for it in range(rng.randint(1, 30))]) for _ in range(300)]
+    check(rules, "coarse", edges + hist, model_coarse)
+    a = events(rules([history("coarse", *edges[0])])[0])   # and by hand: the edge itself, not only the agreement
+    assert [e[:2] for e in a[:4]] == [[1, 0], [0, 0], [0, 1], [1, 0]]
+
+
+def test_coarse_reuse_group(rules):
+    edges = [
+        # f + f / 4 + 5 with f not divisible by 4 (f = 7: 13 is not slow, 14 is); age 0 -> 1 -> 2 -> rebuild
+        ([], [(0, 0, 7), (1, 0, 13), (2, 0, 13), (3, 0, 7), (4, 0, 14), (5, 0, 9), (6, 0, 9 + 2 + 5), (7, 0, 9 + 2 + 6), (8, 0, 1)]),
+        ([], [(0, 0, 6), (1, 0, 6 + 1 + 5), (2, 0, 6 + 1 + 6), (3, 0, 5)]), ([], [(0, 0, 5), (1, 0, 5 + 1 + 6), (2, 0, 0)]),
+        # the initial age rebuilds whatever the iteration; iteration 0 rebuilds whatever the age; a jumped state rebuilds every time
+        ([], [(3, 0, 10), (4, 0, 10), (5, 0, 10), (6, 0, 10)]), ([], [(0, 0, 10), (0, 0, 10), (1, 0, 10), (0, 0, 10)]), ([], [(k, 1, 10) for k in range(5)]),
+    ]
+    rng = random.Random(20260102)
+    hist = [([], [(rng.randint(0, 3) if rng.random() < 0.3 else it, int(rng.random() < 0.1), rng.choice([rng.randint(0, 30), rng.randint(0, 400)]))
+                  for it in range(rng.randint(1, 30))]) for _ in range(300)]
+    check(rules, "gcoarse", edges + hist, model_gcoarse)
+    a = events(rules([history("gcoarse", *edges[0])])[0])
+    assert [e[0] for e in a[:6]] == [1, 0, 0, 1, 0, 1] and [e[1] for e in a[:3]] == [0, 1, 2] and a[4][3] == 1 and a[1][3] == 0
+
+
+def test_direct_fallback(rules):
+    climb = [(2, 0)] * 8
+    edges = [
+        ([], climb),                                                         # back-off 0 -> 8 -> 16 ... -> 256 and staying there
+        ([], [(2, 0), (2, 0), (1, 1), (1, 5), (1, 0), (1, 0), (1, 0), (1, 0), (1, 0)]),   # halving on Newton iteration 0 only, down to 0
+        ([], [(2, 0), (3, 1), (3, 1), (3, 0), (0, 0)] + [(3, 0)] * 9 + [(0, 0)]),         # no decrement when the caller asked for the band LU
+        ([], [(0, 0), (3, 0), (3, 1), (1, 0)]),                                           # nothing to decrement, nothing to halve
+    ]
+    rng = random.Random(20260103)
+    hist = [([], [(rng.choice([0, 1, 1, 2, 3, 3, 3]), rng.randint(0, 2)) for _ in range(rng.randint(1, 60))]) for _ in range(300)]
+    check(rules, "direct", edges + hist, model_direct)
+    assert [e[2] for e in events(rules([history("direct", [], climb)])[0])] == [8, 16, 32, 64, 128, 256, 256, 256]
+    a = events(rules([history("direct", *edges[2])])[0])
+    assert [e[1] for e in a[:5]] == [8, 8, 8, 7, 7] and a[-1] == [0, 0, 8]
+
+
+def test_burst_hint_single_handle(rules):
+    edges = [
+        # table indices 31 / 32: 31 is kept and read back, 32 is neither
+        ((0, 1), [(3, 31, 77, 0), (3, 32, 99, 0), (0, 31, 0, 0), (1, 1, 0, 0), (0, 32, 0, 0), (1, 1, 0, 0)]),
+        # krylov_batch overrides the hint and the last count; a restart pass takes B all the same
+        ((5, 2), [(3, 0, 80, 0), (0, 0, 0, 0), (1, 1, 0, 0), (1, 1, 1, 0)]), ((0, 2), [(3, 0, 80, 0), (0, 0, 0, 0), (1, 1, 0, 0), (1, 1, 1, 0)]),
+        # no hint: half the last first-pass count of the same mode; a restart pass does not count as the last
+        ((0, 1), [(2, 1, 50, 0), (2, 0, 20, 0), (2, 1, 999, 1), (1, 1, 0, 0), (1, 0, 0, 0), (3, 4, 9, 0), (0, 4, 0, 0), (1, 1, 0, 0), (3, 4, 1, 0), (1, 1, 0, 0)]),
+    ]
+    for B in (1, 2, 3):                              # rounding up to a multiple of B
+        edges.append(((0, B), [(2, 1, n, 0) if k == 0 else (1, 1, 0, 0) for n in range(0, 16) for k in (0, 1)]))
+        edges.append(((7, B), [(1, 0, 0, 0), (1, 0, 1, 0)]))
+    rng = random.Random(20260104)
+
+    def ev():
+        k = rng.randint(0, 3)
+        it, n = rng.choice([rng.randint(0, 40), 31, 32]), rng.choice([rng.randint(0, 30), rng.randint(0, 1500)])
+        return {0: (0, it, 0, 0), 1: (1, rng.randint(0, 1), int(rng.random() < 0.2), 0), 2: (2, rng.randint(0, 1), n, int(rng.random() < 0.2)), 3: (3, it, n, 0)}[k]
+    hist = [((rng.choice([0, 0, 0, rng.randint(1, 40)]), rng.randint(1, 8)), [ev() for _ in range(rng.randint(1, 40))]) for _ in range(300)]
+    check(rules, "burst", edges + hist, model_burst)
+    a = events(rules([history("burst", *edges[0])])[0])
+    assert a[1][4 + 31] == 77 and 99 not in a[1] and a[2][1] == 77 and a[3][0] == 38 and a[4][1] == 0 and a[5][0] == 1
+    assert [e[0] for e in events(rules([history("burst", *edges[1])])[0])[2:]] == [6, 2]
+
+
+def test_burst_hint_group(rules):
+    edges = [
+        # table indices 15 / 16; read only on attempt 0 of a state that has not jumped; written only by attempt 0 of a solve that succeeded
+        ([], [(2, 0, 1, 15, 60), (2, 0, 1, 16, 61), (0, 0, 0, 15, 0), (0, 0, 0, 16, 0), (0, 1, 0, 15, 0), (0, 0, 1, 15, 0), (2, 1, 1, 3, 9), (2, 0, 0, 3, 9), (0, 0, 0, 3, 0)]),
+        # predicted + 1; else 7/8 of the previous solve, at least 2; else 4
+        ([], [(1, 60, 1, 0, 0), (1, 60, 0, 0, 0), (1, 0, 1, 0, 0), (1, 0, 0, 0, 0), (3, 85, 0, 0, 0), (1, 0, 1, 0, 0), (1, 0, 0, 0, 0), (3, 3, 0, 0, 0), (1, 0, 1, 0, 0),
+              (3, 9, 0, 0, 0), (1, 0, 1, 0, 0)]),
+    ]
+    rng = random.Random(20260105)
+
+    def ev():
+        k = rng.randint(0, 3)
+        it, n = rng.choice([rng.randint(0, 20), 15, 16]), rng.choice([rng.randint(0, 30), rng.randint(0, 1500)])
+        return {0: (0, rng.randint(0, 2), int(rng.random() < 0.2), it, 0), 1: (1, rng.choice([0, n]), rng.randint(0, 1), 0, 0),
+                2: (2, rng.randint(0, 2), int(rng.random() < 0.8), it, n), 3: (3, n, 0, 0, 0)}[k]
+    hist = [([], [ev() for _ in range(rng.randint(1, 40))]) for _ in range(300)]
+    check(rules, "gburst", edges + hist, model_gburst)
+    assert [e[0] for e in events(rules([history("gburst", *edges[0])])[0])] == [-1, -1, 60, 0, 0, 0, -1, -1, 0]
+    assert [e[0] for e in events(rules([history("gburst", *edges[1])])[0]) if e[0] >= 0] == [61, 61, 2, 4, 74, 4, 2, 7]
+
+
+def test_predicted_x0(rules):
+    edges = [([], [(0, 1, 0.1), (1, 1, 0.0), (0, 0, 0.1), (0, 1, 0.0), (0, 1, 0.1), (0, 2, -0.001), (1, 0, 0.0), (0, 1, 0.1)])]
+    rng = random.Random(20260106)
+    hist = [([], [(rng.randint(0, 1), rng.randint(0, 2), rng.choice([0.0, 0.1, -0.001])) for _ in range(rng.randint(1, 30))]) for _ in range(200)]
+    check(rules, "x0", edges + hist, model_x0)
+    assert [e[0] for e in events(rules([history("x0", *edges[0])])[0])] == [0, 0, 0, 0, 1, 1, 0, 0]
+
+
+OPTION_FIELDS = ["device_id", "n_aggregates", "shared_device", "krylov_batch", "profile_every", "launch_form", "warm_start", "coarse_refresh", "progress_by_copy",
+                 "burst_iterations", "phase_timing", "no_direct_fallback", "warm_in_stream", "vector_form", "strict_steric", "element_stores"]
+T_NEGATIVE, T_FORM, T_RANGE = "negative option", "launch_form must be 0, 2 or 4", "option out of range"
+T_STORES = "element_stores: 0 (automatic), 1 (direct), 2 (staged, 3D meshes)"
+
+
+def model_options(dim, o):
+    """create_impl of the parent: every refusal it can reach, in its order, or the settings."""
+    gb = o["band_lu_max_gb"]
+    errs = []
+    if o["krylov_batch"] < 0 or o["profile_every"] < 0:                                              # api.hip:1225
+        errs.append(T_NEGATIVE)
+    if o["launch_form"] not in (0, 2, 4):                                                            # api.hip:1264
+        errs.append(T_FORM)
+    if (o["coarse_refresh"] < 0 or o["burst_iterations"] < 0 or o["warm_start"] < -1 or o["warm_start"] > 1 or not (gb >= 0.0)   # api.hip:1265-1267
+            or o["vector_form"] < 0 or o["vector_form"] > 2):
+        errs.append(T_RANGE)
+    if o["element_stores"] < 0 or o["element_stores"] > 2 or (o["element_stores"] == 2 and dim != 3):   # api.hip:1365-1366
+        errs.append(T_STORES)
+    settings = [int(o["coarse_refresh"] == 0 and not o["shared_device"]),                            # api.hip:1268
+                o["coarse_refresh"] if o["coarse_refresh"] > 0 else 3,                               # api.hip:1269
+                0 if (o["warm_in_stream"] or o["shared_device"]) else 1,                             # api.hip:1270
+                {0: 2, 1: 1}.get(o["warm_start"], 0),                                                # api.hip:1271
+                0 if o["progress_by_copy"] else 1, max(1, o["burst_iterations"]), int(o["phase_timing"] != 0),   # api.hip:1272-1274
+                0 if o["no_direct_fallback"] else 1, 1 if o["strict_steric"] else 0,                 # api.hip:1275-1276
+                gb if gb > 0.0 else 48.0]                                                            # api.hip:151, 1277
+    return errs, settings
+
+
+def test_resolve_options(rules):
+    nan = float("nan")
+    cases = [(3, {}), (1, {})]
+    # every option at and just outside its range (one option off its default at a time: the parent's error text exactly)
+    at_edges = {"krylov_batch": (-1, 0, 1), "profile_every": (-1, 0, 1), "launch_form": (-1, 0, 1, 2, 3, 4, 5), "warm_start": (-2, -1, 0, 1, 2),
+                "coarse_refresh": (-1, 0, 1, 2), "burst_iterations": (-1, 0, 1, 2), "vector_form": (-1, 0, 1, 2, 3), "element_stores": (-1, 0, 1, 2, 3),
+                "band_lu_max_gb": (-1e-300, -0.0, 0.0, 1e-300, 31.5, nan, float("inf")),
+                "shared_device": (0, 1, -1), "progress_by_copy": (0, 1, -1), "phase_timing": (0, 1, 2), "no_direct_fallback": (0, 1, -3),
+                "warm_in_stream": (0, 1, 5), "strict_steric": (0, 1, -1), "device_id": (-1, 9), "n_aggregates": (-1, 99)}
+    for dim in (1, 3):
+        cases += [(dim, {name: v}) for name, vals in at_edges.items() for v in vals]
+    cases += [(3, {"coarse_refresh": 2, "shared_device": 1, "warm_in_stream": 1}), (3, {"coarse_refresh": 0, "shared_device": 1})]
+    n_single = len(cases)
+    rng = random.Random(20260107)
+    for _ in range(300):
+        cases.append((rng.choice([1, 3]), {name: rng.choice(vals) for name, vals in at_edges.items() if rng.random() < 0.25}))
+    full = [(dim, {**{name: 0 for name in OPTION_FIELDS}, "band_lu_max_gb": 0.0, **ch}) for dim, ch in cases]
+    lines = ["options %d %s %r" % (dim, " ".join(str(o[name]) for name in OPTION_FIELDS), o["band_lu_max_gb"]) for dim, o in full]
+    seen = set()
+    for k, ((dim, o), line) in enumerate(zip(full, rules(lines))):
+        errs, settings = model_options(dim, o)
+        if not errs:
+            assert line.startswith("OK "), (dim, o, line)
+            got = line.split()[1:]
+            assert [int(x) for x in got[:9]] == settings[:9] and float(got[9]) == settings[9], (dim, o, line)
+        else:   # with several invalid options at once the first one reported may differ from the parent's; the text may not
+            assert line.startswith("ERR ") and line[4:] in errs, (dim, o, line, errs)
+            if k < n_single:
+                assert len(errs) == 1 and line[4:] == errs[0], (dim, o, line)
+            seen.add(line[4:])
+    assert seen == {T_NEGATIVE, T_FORM, T_RANGE, T_STORES}
