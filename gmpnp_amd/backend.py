@@ -549,8 +549,9 @@ def column_select_call(fn, handle, fields, ranks, check):
 
 
 class DeviceEnsemble:
-    """``gmpnp_ensemble``: the Newton solves of several 1D ``DeviceSolver`` handles on ONE mesh in one launch chain per iteration
-    (include/gmpnp.h).  The members stay owned by the caller and keep their own surface (set_model, set_state, get_state,
+    """``gmpnp_ensemble``: the Newton solves of several ``DeviceSolver`` handles on ONE mesh in one launch chain per iteration
+    (include/gmpnp.h): all of them 1D, or all of them 3D handles created with ``shared_device=1`` (solved with the two-level or the
+    node-block Jacobi BiCGStab).  The members stay owned by the caller and keep their own surface (set_model, set_state, get_state,
     project_gradient, ...); every call here is complete when it returns."""
 
     def __init__(self, devices, lib=None):

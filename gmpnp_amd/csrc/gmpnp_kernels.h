@@ -198,12 +198,13 @@ __global__ __launch_bounds__(kVecBlock) void k_jac_gather(const Ctx c) {
 #include "gmpnp_jac_gather_body.inc"   // (textual for the same reason as k_element's)
 }
 
-__global__ void k_robin_add(const Ctx c) {
+__device__ __forceinline__ void robin_add_body(const Ctx& c) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= c.n_robin) return;
   if (c.bcflag[c.rob_row[t]]) return;
   c.vals[c.rob_addr[t]] += c.rob_val[t];
 }
+__global__ void k_robin_add(const Ctx c) { robin_add_body(c); }
 
 // ---------------------------------------------------------------------------------------------
 // Node-block Jacobi: invert the NF x NF diagonal blocks (Gauss-Jordan, partial pivoting, LDS-resident).
@@ -211,7 +212,7 @@ __global__ void k_robin_add(const Ctx c) {
 // Dinv = inverse of the diagonal node blocks.  16 lanes per node: lane r (< NF) holds row r of [A | I] in registers;
 // Gauss-Jordan with partial pivoting, pivot search and row broadcasts by shuffles inside the 16-lane group.
 template <int NF>
-__global__ __launch_bounds__(64) void k_block_inverse(const Ctx c) {
+__device__ __forceinline__ void block_inverse_body(const Ctx& c) {
   const int t = threadIdx.x, r = t & 15, I_raw = blockIdx.x * 4 + (t >> 4);
   const bool on = I_raw < c.nv;
   const int I = on ? I_raw : 0, rc = r < NF ? r : 0;
@@ -249,9 +250,11 @@ __global__ __launch_bounds__(64) void k_block_inverse(const Ctx c) {
     for (int j = 0; j < NF; ++j) o[j] = row[NF + j];
   }
 }
+template <int NF>
+__global__ __launch_bounds__(64) void k_block_inverse(const Ctx c) { block_inverse_body<NF>(c); }
 
 template <int NF>
-__global__ __launch_bounds__(64) void k_coarse_rows(const Ctx c) {
+__device__ __forceinline__ void coarse_rows_body(const Ctx& c) {
   constexpr int S = kWave / NF;
   const int s = blockIdx.x, lane = threadIdx.x;
   const int Iloc = lane / NF, i = lane - Iloc * NF;
@@ -280,9 +283,11 @@ __global__ __launch_bounds__(64) void k_coarse_rows(const Ctx c) {
 #pragma unroll
     for (int j = 0; j < NF; ++j) o[q * NF + j] = acc[q][j];
 }
+template <int NF>
+__global__ __launch_bounds__(64) void k_coarse_rows(const Ctx c) { coarse_rows_body<NF>(c); }
 
 template <int NF>
-__global__ __launch_bounds__(kVecBlock) void k_coarse_sum(const Ctx c) {
+__device__ __forceinline__ void coarse_sum_body(const Ctx& c) {
   // workgroup (g, chunk): partial sums over one chunk of the nodes of aggregate g
   const int nch = c.coarse_chunks, g = blockIdx.x / nch, ch = blockIdx.x - g * nch, n = c.ncoarse;
   const int a0 = c.agg_start[g], len = c.agg_start[g + 1] - a0;
@@ -300,21 +305,24 @@ __global__ __launch_bounds__(kVecBlock) void k_coarse_sum(const Ctx c) {
     out[(size_t)i * n + col] = s;
   }
 }
+template <int NF>
+__global__ __launch_bounds__(kVecBlock) void k_coarse_sum(const Ctx c) { coarse_sum_body<NF>(c); }
 
-__global__ __launch_bounds__(kVecBlock) void k_coarse_reduce(const Ctx c) {
+__device__ __forceinline__ void coarse_reduce_body(const Ctx& c) {
   const int n2 = c.ncoarse * c.ncoarse, q = blockIdx.x * kVecBlock + threadIdx.x;
   if (q >= n2) return;
   double s = 0.0;
   for (int ch = 0; ch < c.coarse_chunks; ++ch) s += c.AcPart[(size_t)ch * n2 + q];
   c.Ac[q] = s;
 }
+__global__ __launch_bounds__(kVecBlock) void k_coarse_reduce(const Ctx c) { coarse_reduce_body(c); }
 
 // In-place BLOCK Gauss-Jordan inverse of the coarse operator (block = one aggregate, NF x NF) by one
 // 512-thread workgroup with the whole matrix resident in LDS.  Pivoting happens inside the diagonal
 // block only (its inverse is formed by NF lanes with partial pivoting); the off-diagonal update is a
 // rank-NF update done in 3x3 register tiles.
 template <int NF>
-__global__ __launch_bounds__(512) void k_coarse_invert(const Ctx c) {
+__device__ __forceinline__ void coarse_invert_body(const Ctx& c) {
   extern __shared__ double sm[];
   const int n = c.ncoarse, nblk = n / NF, t = threadIdx.x, nt = blockDim.x;
   double* A = sm;                 // n*n
@@ -423,6 +431,8 @@ __global__ __launch_bounds__(512) void k_coarse_invert(const Ctx c) {
   if (sing) { if (t == 0) atomicOr(c.status, 4); return; }
   for (int q = t; q < n * n; q += nt) c.Aci[q] = A[q];
 }
+template <int NF>
+__global__ __launch_bounds__(512) void k_coarse_invert(const Ctx c) { coarse_invert_body<NF>(c); }
 
 // =================================================================================================
 // Fused BiCGStab.  System: A Dinv (I + P Aci P^T) y = b, x = Dinv (I + P Aci P^T) y, with
@@ -1451,7 +1461,7 @@ __global__ __launch_bounds__(kKrylovThreads) void k_spmv_residual(const Ctx c, c
 
 // As = A Dinv: one wave per (slice, block position) scales the NF-entry row pieces of its block by Dinv of the column node.
 template <int NF>
-__global__ __launch_bounds__(kVecBlock) void k_scale_columns(const Ctx c) {
+__device__ __forceinline__ void scale_columns_body(const Ctx& c) {
   const int wave = xcd_run_wave(c), lane = threadIdx.x & 63;
   if (wave >= c.n_work) return;
   const int s = c.wl_slice[wave], kpos = c.wl_kpos[wave];
@@ -1474,10 +1484,12 @@ __global__ __launch_bounds__(kVecBlock) void k_scale_columns(const Ctx c) {
 #pragma unroll
   for (int j = 0; j < NF; ++j) c.vals_s[off + (size_t)j * kWave] = o[j];
 }
+template <int NF>
+__global__ __launch_bounds__(kVecBlock) void k_scale_columns(const Ctx c) { scale_columns_body<NF>(c); }
 
 // Partial restriction of a fine vector per tile -> cpart_v (used for P^T b at the start and P^T y at the end).
 template <int NF>
-__global__ __launch_bounds__(kVecBlock) void k_restrict(const Ctx c, const double* __restrict__ x, double* __restrict__ part) {
+__device__ __forceinline__ void restrict_body(const Ctx& c, const double* __restrict__ x, double* __restrict__ part) {
   __shared__ double lv[kSlicesPerTile * 64];
   const int tile = c.tile0 + blockIdx.x, t = threadIdx.x;
   if (t < kSlicesPerTile * 64) {
@@ -1494,15 +1506,19 @@ __global__ __launch_bounds__(kVecBlock) void k_restrict(const Ctx c, const doubl
     part[cpart_index(c, c.tile_slot[tile], c.tile_agg[tile], t, NF)] = sacc;
   }
 }
+template <int NF>
+__global__ __launch_bounds__(kVecBlock) void k_restrict(const Ctx c, const double* __restrict__ x, double* __restrict__ part) {
+  restrict_body<NF>(c, x, part);
+}
 
 // dst = scale_dst*dst + scale_x * Dinv (x + P Aci P^T x), P^T x taken from the partials k_restrict left in `part`.
 // `upd` (Newton, final application of a solve): in the same pass u -= omega dx and the predicted start of the next
 // linear solve, dst <- a dx + b xp, xp <- dx  (see newton(): a = (1-w) + (1-w)^2, b = -(1-w)^3 from the third iteration on)
 struct NewtonUpdate { double* u; double* xp; double omega, a, b; };
 template <int NF>
-__global__ __launch_bounds__(kKrylovThreads) void k_minv_apply(const Ctx c, const double* __restrict__ x, const double* __restrict__ part,
-                                                                double* __restrict__ dst, double scale_dst, double scale_x,
-                                                                const NewtonUpdate upd, const double* __restrict__ reduced) {
+__device__ __forceinline__ void minv_apply_body(const Ctx& c, const double* __restrict__ x, const double* __restrict__ part,
+                                                double* __restrict__ dst, double scale_dst, double scale_x,
+                                                const NewtonUpdate& upd, const double* __restrict__ reduced) {
   __shared__ double pcs[kMaxCoarse];
   __shared__ double ycl[kTileAggs * NF];
   __shared__ double xv[kSlicesPerTile][64];
@@ -1555,6 +1571,12 @@ __global__ __launch_bounds__(kKrylovThreads) void k_minv_apply(const Ctx c, cons
     dst[r] = dx;
   }
 }
+template <int NF>
+__global__ __launch_bounds__(kKrylovThreads) void k_minv_apply(const Ctx c, const double* __restrict__ x, const double* __restrict__ part,
+                                                                double* __restrict__ dst, double scale_dst, double scale_x,
+                                                                const NewtonUpdate upd, const double* __restrict__ reduced) {
+  minv_apply_body<NF>(c, x, part, dst, scale_dst, scale_x, upd, reduced);
+}
 
 // bandwidth probe: stream n doubles (16 B per lane) and keep one checksum per workgroup
 __global__ __launch_bounds__(256) void k_stream_read(const double2* __restrict__ a, size_t n2, double* __restrict__ out) {
@@ -1577,14 +1599,18 @@ __global__ __launch_bounds__(kVecBlock) void k_true_residual(const double* __res
 }
 
 // Test of a warm start: partials of (w,b), (w,w), (b,b) with w = J x0 (from k_spmv_plain), three per workgroup.
-__global__ __launch_bounds__(kVecBlock) void k_dots3(const double* __restrict__ w, const double* __restrict__ b,
-                                                     double* __restrict__ part, int n, int nblocks, int lo = 0, int hi = 0x7fffffff) {
+__device__ __forceinline__ void dots3_body(const double* __restrict__ w, const double* __restrict__ b,
+                                           double* __restrict__ part, int n, int nblocks, int lo, int hi) {
   __shared__ double lds[12];
   const int i = blockIdx.x * kVecBlock + threadIdx.x;
   double v[3] = {0.0, 0.0, 0.0};
   if (i < n && i >= lo && i < hi) { const double wi = w[i], bi = b[i]; v[0] = wi * bi; v[1] = wi * wi; v[2] = bi * bi; }   // [lo, hi): the owned dofs of a partitioned handle
   block_sum<3>(v, lds);
   if (threadIdx.x == 0) { part[blockIdx.x] = v[0]; part[nblocks + blockIdx.x] = v[1]; part[2 * nblocks + blockIdx.x] = v[2]; }
+}
+__global__ __launch_bounds__(kVecBlock) void k_dots3(const double* __restrict__ w, const double* __restrict__ b,
+                                                     double* __restrict__ part, int n, int nblocks, int lo = 0, int hi = 0x7fffffff) {
+  dots3_body(w, b, part, n, nblocks, lo, hi);
 }
 // start of a warm solve: r0 = b - w with w = J x0 (x0 stays in kx)
 __global__ void k_start_residual(double* __restrict__ r, const double* __restrict__ b, const double* __restrict__ w, int n) {
@@ -1623,8 +1649,8 @@ __global__ void k_axpy(double* __restrict__ y, const double* __restrict__ x, dou
 // rhat = shadow vector (r_0 unless given), y = 0, restriction partials of r_0 where A(0) expects them, hand-over flags
 // cleared, scalars set from the kernel argument.  One workgroup per tile, as k_restrict.
 template <int NF>
-__global__ __launch_bounds__(kVecBlock) void k_krylov_init(const Ctx c, const double* __restrict__ shadow, const KrylovScalars init,
-                                                           double* __restrict__ part) {
+__device__ __forceinline__ void krylov_init_body(const Ctx& c, const double* __restrict__ shadow, const KrylovScalars& init,
+                                                 double* __restrict__ part) {
   __shared__ double lv[kSlicesPerTile * 64];
   const int tile = c.tile0 + blockIdx.x, t = threadIdx.x;
   if (t < kSlicesPerTile * 64) {
@@ -1651,6 +1677,11 @@ __global__ __launch_bounds__(kVecBlock) void k_krylov_init(const Ctx c, const do
       for (int il = 0; il < kWave / NF; ++il) sacc += lv[q * 64 + il * NF + t];
     part[cpart_index(c, c.tile_slot[tile], c.tile_agg[tile], t, NF)] = sacc;
   }
+}
+template <int NF>
+__global__ __launch_bounds__(kVecBlock) void k_krylov_init(const Ctx c, const double* __restrict__ shadow, const KrylovScalars init,
+                                                           double* __restrict__ part) {
+  krylov_init_body<NF>(c, shadow, init, part);
 }
 __global__ void k_copy2(double* __restrict__ a, double* __restrict__ b, const double* __restrict__ src, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -108,19 +108,25 @@ class PoreRun:
         else:
             row = self.sys.vertex_values()
             meds, co2_min = column_medians(row, (1, 2, 3, 7)), float(np.amin(row[:, 4]))
+        self.accept_solution(st, row, meds, co2_min, verbose=verbose and (not device or self.rank in (None, 0)))
+        return st
+
+    def accept_solution(self, st, row, meds, co2_min, verbose=False, assign=True):
+        """What follows the Newton solve of a step: history row, Sechenov, new Dirichlet set, ``u_n.assign(u)``, counters.
+        ``assign=False``: the caller assigns (``PoreEnsemble`` does it for all its members with one launch)."""
         self.history.append(row)
         # medians of the scaled ion concentrations -> Sechenov -> new CO2 Dirichlet value at S1 (3D:817-838)
         self.co2_bc = self.pp.sechenov_co2_scaled(*meds)
         self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, self.co2_bc))
         self.CO2_min = co2_min
-        self.sys.assign_previous()
+        if assign:
+            self.sys.assign_previous()
         self.newton_its.append(st["iterations"])
-        if verbose and (not device or self.rank in (None, 0)):
+        if verbose:
             print(self.CO2_min)
             print(datetime.now().strftime("%y-%m-%d-%H-%M-%S"))
             print(self.n)
         self.n += 1
-        return st
 
     def field_history(self, i):
         """(steps + 1, nv) history of field i in file vertex order.  "device" glue with one rank per process: gathered to rank 0

@@ -8,6 +8,7 @@ at the end (one ``all_gather_object``).
 
   python -m gmpnp_amd.sweep --num_steps 20                                   # 1 GPU, all 35 jobs in turn
   python -m torch.distributed.run --nproc-per-node 8 -m gmpnp_amd.sweep      # one rank per GPU (RCCL only for the gather)
+  python -m gmpnp_amd.sweep --ensemble --num_steps 20                        # the voltages of one mesh as one device ensemble
 """
 from __future__ import annotations
 
@@ -36,8 +37,54 @@ def ramp_value(target, n, ramp_steps, start=-1.0):
     return float(start + (target - start) * min(n, ramp_steps) / ramp_steps)
 
 
+def group_by_radius(job_list):
+    """The jobs a rank holds, grouped by mesh: [(radius, [indices into job_list])] in order of first appearance, the jobs of a
+    group in their original order; every job appears in exactly one group."""
+    groups = {}
+    for k, (r, _) in enumerate(job_list):
+        groups.setdefault(r, []).append(k)
+    return list(groups.items())
+
+
+def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=0, write=False, as_published=False, ramp_steps=0,
+              L=50e-9, device_kwargs=None):
+    """The runs of ``run_job`` for every voltage on ONE mesh as one ``PoreEnsemble`` (one launch chain per Newton iteration for all
+    of them); returns their summaries in the order of ``voltages``, with the keys ``run_job`` gives (``seconds``: the group's)."""
+    from .pore_ensemble import PoreEnsemble
+    from .problem import pore_dirichlet
+    t0 = time.perf_counter()
+    outs = [{"R_nm": radius_nm, "voltage_multiplier": v, "steps_requested": num_steps, "ramp_steps": ramp_steps} for v in voltages]
+    members = [dict(concentration_elec=concentration_elec, L=L, R=radius_nm * 1e-9, voltage_multiplier=ramp_value(v, 0, ramp_steps),
+                    as_published=as_published) for v in voltages]
+    with PoreEnsemble(members, num_steps=num_steps, device_kwargs=dict({"device_id": device_id}, **(device_kwargs or {})),
+                      keep_history=write) as ens:
+        for n in range(num_steps):
+            ens.step()
+            for k in ens.live():   # --ramp_steps, per member: the Dirichlet set of the NEXT step
+                run = ens.runs[k]
+                v_next = ramp_value(voltages[k], n + 1, ramp_steps)
+                if v_next != run.pp.voltage_scaled:
+                    run.pp.voltage_scaled = v_next
+                    run.sys.set_bcs(*pore_dirichlet(run.pp, run.bnd, run.co2_bc))
+        paths = ens.write_outputs() if write else None
+        for k, (out, run) in enumerate(zip(outs, ens.runs)):
+            out.update(n_vertices=run.mesh.num_vertices, n_dofs=run.problem.ndof)
+            if ens.errors[k] is None:
+                out.update(wall_potential=float(run.pp.voltage_scaled), status="ok")
+                if write:
+                    out["directory"] = paths[k]
+            else:
+                out.update(status="newton_failed", error=ens.errors[k][:200])
+            out.update(steps_done=run.n, newton_iterations=int(sum(run.newton_its)), krylov_iterations=int(run.sys.krylov_iterations),
+                       CO2_min=None if run.CO2_min is None else float(run.CO2_min))
+    dt = time.perf_counter() - t0
+    for out in outs:
+        out["seconds"] = dt
+    return outs
+
+
 def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, write=False, as_published=False, ramp_steps=0,
-            one_stream=False):
+            one_stream=False, L=50e-9, device_kwargs=None):
     """One pore run of ``num_steps`` time steps; returns a small summary dict (never raises for a diverged Newton).
 
     ``ramp_steps`` > 0 is a continuation the reference does not have: the wall potential Dirichlet value (bc3 of
@@ -50,11 +97,12 @@ def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, 
     out = {"R_nm": radius_nm, "voltage_multiplier": voltage, "steps_requested": num_steps, "ramp_steps": ramp_steps}
     run = None
     try:
-        run = PoreRun(num_steps=num_steps, concentration_elec=concentration_elec, L=50e-9, R=radius_nm * 1e-9,
+        run = PoreRun(num_steps=num_steps, concentration_elec=concentration_elec, L=L, R=radius_nm * 1e-9,
                       voltage_multiplier=ramp_value(voltage, 0, ramp_steps), as_published=as_published,
                       # several runs in flight on one GPU: every handle keeps to ONE stream (coarse rebuild and warm-start test in
                       # the main stream): with side streams K handles are 2K streams on the process's four hardware queues
-                      device_kwargs=dict({"device_id": device_id}, **({"coarse_refresh": 3, "warm_in_stream": 1} if one_stream else {})))
+                      device_kwargs=dict({"device_id": device_id}, **dict({"coarse_refresh": 3, "warm_in_stream": 1} if one_stream else {},
+                                                                          **(device_kwargs or {}))))
         out.update(n_vertices=run.mesh.num_vertices, n_dofs=run.problem.ndof)
         for n in range(num_steps):
             run.step(verbose=False)
@@ -89,6 +137,9 @@ def main(argv=None):
                    help="move the wall potential from -1 to the target over this many time steps (continuation; 0 = the "
                         "reference's behaviour, the target applies from step 0)")
     p.add_argument("--jobs_per_gpu", type=int, default=1, help="independent runs kept in flight on each GPU (separate streams; 3 gives 1.56x the throughput of 1)")
+    p.add_argument("--ensemble", action="store_true",
+                   help="run the jobs of one mesh (its voltages) as one device ensemble: one launch chain per Newton iteration for all "
+                        "of them (gmpnp_amd.pore_ensemble; every handle on one stream, four launches per BiCGStab iteration)")
     p.add_argument("--write", action="store_true", help="write the reference's output files of every run under $GMPNP_OUT")
     p.add_argument("--backend", default=None, help="torch.distributed backend for the final gather (default: nccl)")
     a = p.parse_args(argv)
@@ -101,7 +152,14 @@ def main(argv=None):
         return run_job(job[0], job[1], a.num_steps, a.concentration_elec, device_id=local, write=a.write,
                        as_published=a.as_published, ramp_steps=a.ramp_steps, one_stream=a.jobs_per_gpu > 1)
 
-    if a.jobs_per_gpu > 1:
+    if a.ensemble:
+        res = [None] * len(mine)
+        for radius, idx in group_by_radius(mine):
+            outs = run_group(radius, [mine[k][1] for k in idx], a.num_steps, a.concentration_elec, device_id=local, write=a.write,
+                             as_published=a.as_published, ramp_steps=a.ramp_steps)
+            for k, out in zip(idx, outs):
+                res[k] = out
+    elif a.jobs_per_gpu > 1:
         # A 3.7k-vertex problem is launch-latency bound: independent problems on separate HIP streams
         # overlap on one GPU.  Measured (tools/concurrent_runs_probe.py, profiles/r03/concurrent_runs*.json): 2 / 3 / 4 runs from
         # threads of one process = 1.40 / 1.56 / 1.38 x the throughput of one (3 is the sweet spot: a launch needs 537 of the

@@ -379,21 +379,31 @@ int gmpnp_group_attach_coarse_group(gmpnp_group* fine, gmpnp_group* coarse);
 int gmpnp_column_select(gmpnp_solver* s, int32_t n, const int32_t* field, const int64_t* rank, double* out, int32_t* flags);
 int gmpnp_group_column_select(gmpnp_group* g, int32_t n, const int32_t* field, const int64_t* rank, double* out, int32_t* flags);
 
-/* ---- ensemble of 1D problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
- * concentration sweep of 1D/MPNP_CO2ER_EDL.py is many separate runs) ------------------------------------------------------------
- * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME 1D mesh (same vertices, cells and vertex order) and device.
+/* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
+ * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
+ * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
+ * all of them 1D or all of them 3D.
  * Each member keeps its whole per-handle surface (gmpnp_set_model, gmpnp_set_dirichlet, gmpnp_set_state / gmpnp_get_state,
  * gmpnp_project_gradient / gmpnp_project_cellwise) and its own model tables, Dirichlet values and state; the ensemble only runs
  * the Newton iterations of all members in one launch chain per iteration (one host synchronisation per iteration for the
- * whole ensemble).  Refused (GMPNP_ERR_INVALID): 3D handles (3D ensembles are not supported), partitioned handles, members on
- * other devices or with another topology, SUPG terms set on a member (checked again at every solve), n outside 1 ... 64.
+ * whole ensemble).  Refused (GMPNP_ERR_INVALID, the message names the member and the reason): 1D and 3D handles together,
+ * partitioned handles, members on other devices or with another topology, SUPG terms set on a member, n outside 1 ... 64; every
+ * condition is checked again at every solve.
+ * A 3D member (8 species + potential) is created with gmpnp_options_t.shared_device = 1 (one stream, four launches per BiCGStab
+ * iteration: nothing waits inside a launch) and is refused with a multilevel coarse level attached, in the materialised vector
+ * form (vector_form 1), with progress_by_copy, or on a mesh with more than 128 tile slots per aggregate.  Per Newton iteration
+ * the Jacobian gather, the preconditioner set-up, the test of the predicted start, the first BiCGStab pass, the final M^-1
+ * application with the Newton update and the next residual run as one launch chain for all members; a member whose linear solve
+ * leaves that path (first pass not converged within 500 iterations, breakdown, iteration cap, band LU due) is finished by the
+ * single handle's code for that iteration while the others wait, and joins again at the next residual.
  * The members stay owned by the caller and must outlive the ensemble.  Every ensemble call is complete when it returns: a
  * member call made afterwards on the member's own stream sees the ensemble's results. */
 typedef struct gmpnp_ensemble gmpnp_ensemble;
 int gmpnp_ensemble_create(int32_t n, gmpnp_solver* const* members, gmpnp_ensemble** out);
 void gmpnp_ensemble_destroy(gmpnp_ensemble* e);
 int32_t gmpnp_ensemble_size(const gmpnp_ensemble* e);
-/* solve(F == 0, u, bcs, solver_parameters) on every member at once; opts.linear_solver must be GMPNP_LINEAR_BLOCK_TRIDIAGONAL.
+/* solve(F == 0, u, bcs, solver_parameters) on every member at once; opts.linear_solver must be GMPNP_LINEAR_BLOCK_TRIDIAGONAL for
+ * 1D members and GMPNP_LINEAR_BICGSTAB_TWOLEVEL or GMPNP_LINEAR_BICGSTAB_JACOBI for 3D members (GMPNP_LINEAR_BAND_LU is refused).
  * stats[n] and status[n] (a gmpnp_status per member) are what gmpnp_newton_solve on that handle alone returns, timing fields
  * excepted; a member that has converged or failed gets no further updates while the others go on.  Returns 0 when every member
  * succeeded, else the first non-zero member status (gmpnp_last_error names the member). */
