@@ -35,7 +35,11 @@ EXPORTS = [
     "gmpnp_project_gradient", "gmpnp_project_cellwise", "gmpnp_column_select", "gmpnp_group_column_select",
     "gmpnp_ensemble_create", "gmpnp_ensemble_destroy", "gmpnp_ensemble_size", "gmpnp_ensemble_newton_solve",
     "gmpnp_ensemble_member_error", "gmpnp_ensemble_assign_previous", "gmpnp_ensemble_get_state",
+    "gmpnp_species_budget", "gmpnp_group_species_budget",
 ]
+# columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
+#   storage + reaction + wall + exit + point = dirichlet + closure
+BUDGET_COLUMNS = ("inventory", "storage", "reaction", "wall", "exit", "point", "dirichlet", "closure")
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
 
@@ -181,6 +185,8 @@ def load_library(path: str = None):
     lib.gmpnp_ensemble_member_error.restype = ctypes.c_char_p
     lib.gmpnp_ensemble_assign_previous.argtypes = [c_void_p]
     lib.gmpnp_ensemble_get_state.argtypes = [c_void_p, POINTER(c_double)]
+    for name in ("gmpnp_species_budget", "gmpnp_group_species_budget"):
+        getattr(lib, name).argtypes = [c_void_p, POINTER(c_double)]
     if path is None:
         _lib = lib
     return lib
@@ -480,6 +486,12 @@ class DeviceSolver:
         holds a NaN (its value is then undefined)."""
         return column_select_call(self.lib.gmpnp_column_select, self._h, fields, ranks, self._check)
 
+    def species_budget(self):
+        """(nf, 8) table of this handle's owned rows (gmpnp_species_budget; columns ``BUDGET_COLUMNS``, scaled units of the weak
+        form): per field ``storage + reaction + wall + exit + point = dirichlet + closure``; ``dirichlet`` is the consistent flux
+        the Dirichlet rows supply, ``closure`` the sum of the residual over the free rows.  Leaves the handle's state untouched."""
+        return species_budget_call(self.lib.gmpnp_species_budget, self._h, self.nf, self._check)
+
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""
         if rho is None:
@@ -546,6 +558,13 @@ def column_select_call(fn, handle, fields, ranks, check):
     flags = c_int32(0)
     check(fn(handle, f.size, _iptr(f), r.ctypes.data_as(POINTER(c_int64)), _dptr(out), byref(flags)))
     return out, bool(flags.value & 1)
+
+
+def species_budget_call(fn, handle, nf, check):
+    """One gmpnp_species_budget / gmpnp_group_species_budget call: the (nf, len(BUDGET_COLUMNS)) table."""
+    out = np.empty((nf, len(BUDGET_COLUMNS)))
+    check(fn(handle, _dptr(out)))
+    return out
 
 
 class DeviceEnsemble:

@@ -78,6 +78,17 @@ struct gmpnp_selector {
   ~gmpnp_selector() { if (h_io) (void)hipHostFree(h_io); }
 };
 
+// device side of gmpnp_species_budget / gmpnp_group_species_budget (gmpnp_budget.h), allocated on first use
+struct gmpnp_budgeter {
+  DevBuf<double> EF;                                    // element rows at the current u: the budget's own (the solver's EF stays)
+  DevBuf<double> wall_w, exit_w, exit_val, point_w;     // geometry-only facet tables (internal node order)
+  DevBuf<int32_t> exit_ptr, exit_col, status;           // status: where the budget's element pass reports (not the solver's word)
+  DevBuf<double> part_c, part_r, table;                 // workgroup partials of the cell / row pass; [nf][GMPNP_BUDGET_COLUMNS]: what a group all-reduces
+  int nblk_c = 0, nblk_r = 0;
+  double* h_table = nullptr;                            // pinned read-back
+  ~gmpnp_budgeter() { if (h_table) (void)hipHostFree(h_table); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -147,6 +158,7 @@ struct gmpnp_solver {
   double* h_red = nullptr;   // pinned [8]: all-reduced ||b||^2 and status bits
   std::unique_ptr<gmpnp_projector> projector;
   std::unique_ptr<gmpnp_selector> selector;
+  std::unique_ptr<gmpnp_budgeter> budgeter;
   // geometric multilevel term (gmpnp_attach_coarse_level, gmpnp_multilevel.h): the link to the next-coarser level (tables in the
   // internal orders of both handles) and this handle's buffers when it serves as a coarse level itself
   gmpnp_solver* ml_coarse = nullptr; double ml_theta = 1.0; bool ml_is_coarse = false;
@@ -299,6 +311,7 @@ int launch_jac_gather(gmpnp_solver* s) {
 }
 
 int drain_spmv_events(gmpnp_solver* s);
+int budget_launch_any(gmpnp_solver* s);   // gmpnp_budget.h: the launch chain of one species-budget call
 
 // sum of row `row` (0 .. 2) of the pinned partials the reduction kernels store (k_res_gather, k_true_residual: row 0; k_dots3: three)
 double sum_partials(const gmpnp_solver* s, int row) {
@@ -1660,6 +1673,8 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 18:   // the whole 1D direct solve: extraction + ~13 levels of block cyclic reduction down and up (k_bcr_forward / k_bcr_tail / k_bcr_backward)
         if (s->dim != 1 || !s->tri_ok) return fail(GMPNP_ERR_INVALID, "kernel 18 is the 1D block-cyclic-reduction solve");
         r = tri_solve<7>(s, s->F.p); break;
+      case 19: GMPNP_DISPATCH(s, r = (launch_element<DIM, NF>(s, false))); break;
+      case 20: r = budget_launch_any(s); break;   // element pass without J, cell pass, row pass, final sums
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -1758,3 +1773,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_project.h"
 #include "gmpnp_ensemble.h"
 #include "gmpnp_stats.h"
+#include "gmpnp_budget.h"

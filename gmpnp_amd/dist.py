@@ -470,6 +470,11 @@ class PartitionedSolver:
         group's transport, the counts all-reduced inside the library): (values, nan flag), identical on every rank."""
         return self.backend.column_select_call(self.lib.gmpnp_group_column_select, self._group, fields, ranks, self._check)
 
+    def species_budget(self):
+        """(nf, 8) species-budget table of the WHOLE problem (gmpnp_group_species_budget: every rank's owned-row table summed over
+        the group's transport inside the library, no gather of the state; collective, identical on every rank)."""
+        return self.backend.species_budget_call(self.lib.gmpnp_group_species_budget, self._group, self.nf, self._check)
+
     def comm_selftest(self, n=4096):
         """Send-to-self + receive + all-reduce through the library's RCCL bindings; returns the largest error."""
         from ctypes import byref, c_double

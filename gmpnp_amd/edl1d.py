@@ -41,7 +41,8 @@ def output_root():
 
 
 class EDLRun:
-    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, **kwargs):
+    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, **kwargs):
+        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py)."""
         self.kwargs = kwargs
         self.ep = edl_parameters(**kwargs)
         ep = self.ep
@@ -61,10 +62,16 @@ class EDLRun:
         self.current_H_frac = ep.current_H_frac
         self.n, self.t, self.dt = 0, 0.0, ep.dts[0]
         self.newton_its = []
+        self.budget = None
+        if budget:
+            from .budget import BudgetLog, interval_factors
+            self.budget = BudgetLog(list(ep.species[:5]) + ["cat", "p"], *interval_factors(ep.species, ep.diff_coeff, ep.initial_conc, ep.L_n))
 
     def step(self, verbose=True):
         self.advance_clock(verbose)
         st = self.sys.solve(self.solver_parameters)
+        if self.budget is not None:   # after the Newton solve, before set_model / assign_previous
+            self.budget.take(self.sys)
         self.accept_solution(st, self.sys.vertex_values(), verbose)
         self.sys.assign_previous()
         self.newton_its.append(st["iterations"])
@@ -192,6 +199,8 @@ class EDLRun:
             "pH_overpotential": pH_overpotential, "CO2_overpotential": CO2_overpotential, "end_time": end_time,
             "newton_iterations": int(sum(self.newton_its)), "krylov_iterations": int(self.sys.krylov_iterations),
             "num_steps_run": int(self.n)}
+        if self.budget is not None:
+            metadata_dict.update(self.budget.save(newpath))
         with open(newpath + "/metadata.json", "w") as fh:
             fh.write(json.dumps(metadata_dict, indent=0))
         return newpath
@@ -205,9 +214,9 @@ def run_identifier(ep, kwargs):
 
 def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=-1.0, H2_FE=0.2, mesh_structure="variable",
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
-              dry_run=True, num_steps=None, verbose=True):
+              dry_run=True, num_steps=None, verbose=True, budget=False):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory."""
-    run = EDLRun(num_steps=num_steps, concentration_elec=concentration_elec, model=model,
+    run = EDLRun(num_steps=num_steps, budget=budget, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
                  params_file=params_file, dry_run=dry_run)
@@ -234,6 +243,7 @@ def build_parser():
     p.add_argument("--params_file", required=False, default="parameters", type=str)
     p.add_argument("--dry_run", required=False, default=True, type=bool)
     p.add_argument("--num_steps", required=False, default=None, type=int, help="(addition) run only the first N steps")
+    p.add_argument("--budget", action="store_true", help="(addition) record the species budgets and consistent boundary fluxes of every step (budget.npz)")
     return p
 
 
@@ -242,7 +252,7 @@ def main(argv=None):
     return solve_EDL(concentration_elec=a.concentration_elec, model=a.model, voltage_multiplier=a.voltage_multiplier,
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
-                     dry_run=a.dry_run, num_steps=a.num_steps)
+                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget)
 
 
 if __name__ == "__main__":

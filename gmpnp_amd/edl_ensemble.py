@@ -82,16 +82,17 @@ def error_text(code, message):
 
 class EDLEnsemble:
     """``members``: keyword dicts of ``EDLRun`` (voltage, cation, concentration, H2_FE, current_OHP_ss, H_OHP, model may
-    differ; mesh and schedule may not).  ``keep_history=False`` keeps only the latest state of each member (long runs)."""
+    differ; mesh and schedule may not).  ``keep_history=False`` keeps only the latest state of each member (long runs).
+    ``budget=True``: every live member records its species-budget table after the step's solve, as its serial ``EDLRun`` twin does."""
 
-    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True):
+    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False):
         self.kwargs, self.eps, self.tot_num_steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []
         self._ens, self._ens_members = None, None
         try:
             for kw in self.kwargs:
-                self.runs.append(EDLRun(num_steps=self.tot_num_steps, device_kwargs=device_kwargs, **kw))
+                self.runs.append(EDLRun(num_steps=self.tot_num_steps, device_kwargs=device_kwargs, budget=budget, **kw))
         except BaseException:
             self.close()
             raise
@@ -133,6 +134,8 @@ class EDLEnsemble:
                 self.errors[k], self.status[k], self.failed_step[k] = error_text(codes[i], msgs[i]), codes[i], r.n
                 continue
             r.sys.record(stats[i])
+            if r.budget is not None:   # before set_model / assign_previous, as EDLRun.step
+                r.budget.take(r.sys)
             r.accept_solution(stats[i], U[i].reshape(r.sys.nv, r.sys.nf), verbose=False)
             ok.append((k, stats[i]))
         # u_n.assign(u) of the members whose solve succeeded (a failed one stays as its failed solve left it)

@@ -35,17 +35,18 @@ def build_parser():
     p.add_argument("--staged", action="store_true", help="the reference's two-stage schedule instead of the dry run")
     p.add_argument("--num_steps", default=None, type=int, help="run only the first N steps")
     p.add_argument("--device_id", default=0, type=int)
+    p.add_argument("--budget", action="store_true", help="record the species budgets of every step: budget.npz per member, the CO2 uptake in each row")
     return p
 
 
-def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None):
+def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget=False):
     """Run the members in ensembles of at most backend.MAX_ENSEMBLE; returns (summary rows, path of ensemble_summary.json)."""
     stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
     rows = []
     for c0 in range(0, len(members), backend.MAX_ENSEMBLE):
         chunk = members[c0:c0 + backend.MAX_ENSEMBLE]
         chunk_stamp = stamp if c0 == 0 else "%s_part%d" % (stamp, c0 // backend.MAX_ENSEMBLE)
-        with EDLEnsemble(chunk, num_steps=num_steps, device_kwargs={"device_id": device_id}) as ens:
+        with EDLEnsemble(chunk, num_steps=num_steps, device_kwargs={"device_id": device_id}, budget=budget) as ens:
             ens.run()
             ohp = [None if ens.errors[k] is not None else ens.ohp_summary(k) for k in range(len(ens))]
             paths = ens.write_outputs(chunk_stamp)
@@ -54,6 +55,8 @@ def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None):
                 row = {"parameters": kw, "converged": ens.errors[k] is None, "error": ens.errors[k],
                        "failed_step": ens.failed_step[k], "newton_total": int(sum(r.newton_its)), "steps_run": int(r.n)}
                 row.update(ohp[k] or {"field_OHP": None, "eps_rel_OHP": None, "potential_OHP": None})
+                if r.budget is not None:   # CO2 consumed at the OHP [mol / (m^2 s)], CO2 supplied by the bulk face, largest closure
+                    row.update(r.budget.summary())
                 p = paths[k]
                 if isinstance(p, BaseException):
                     row["output_error"] = "%s: %s" % (type(p).__name__, p)
@@ -78,7 +81,7 @@ def main(argv=None):
     common = dict(model=a.model, mesh_structure=a.mesh_structure, H2_FE=a.H2_FE, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                   H_OHP=a.H_OHP, params_file=a.params_file, dry_run=not a.staged)
     members = sweep_members(a.voltage_multiplier, a.cation, a.concentration_elec, **common)
-    rows, path = run_sweep(members, num_steps=a.num_steps, device_id=a.device_id, log=lambda s: print(s, flush=True))
+    rows, path = run_sweep(members, num_steps=a.num_steps, device_id=a.device_id, log=lambda s: print(s, flush=True), budget=a.budget)
     print(path)
     return path
 

@@ -44,7 +44,7 @@ class PoreRun:
     """State of one pore simulation; ``step()`` is one pass of the reference's time loop body (3D:783-858)."""
 
     def __init__(self, num_steps=None, as_published=False, device_kwargs=None, solver_parameters=None, refine=0,
-                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", **kwargs):
+                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", budget=False, **kwargs):
         """``partition`` = (nparts, rank): solve this ONE problem across `nparts` mesh partitions (rank None: all of them in
         this process on one GPU; rank r: this process is rank r of a ``torch.distributed`` job, RCCL inside the library).
         ``multilevel`` (with ``refine`` > 0): the preconditioner gets the geometric multilevel term over the nested meshes
@@ -54,7 +54,10 @@ class PoreRun:
         torch.distributed) for the medians, the CO2 minimum and the history row; "device": the medians and the minimum come from the
         library's column select (csrc/gmpnp_stats.h: collective inside the library, identical values) and the history keeps this
         process's OWNED rows only (one device-to-host copy per local partition, no collective); ``write_outputs`` assembles the
-        global history on rank 0, which alone prints and writes."""
+        global history on rank 0, which alone prints and writes.
+        ``budget`` = True: every step records the species-budget table of its solution (``species_budget()``: integrated storage,
+        reaction, wall / exit fluxes and the consistent Dirichlet flux per field; on a partitioned run summed over the ranks inside
+        the library, no gather of the state) and ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).  Off: nothing changes."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
         self.glue = glue
@@ -94,6 +97,10 @@ class PoreRun:
         self.n = 0
         self.t = 0.0
         self.newton_its = []
+        self.budget = None
+        if budget:
+            from .budget import BudgetLog, pore_factors
+            self.budget = BudgetLog(list(self.pp.species[:7]) + ["cat", "p"], *pore_factors(self.pp))
 
     def step(self, verbose=True):
         """One time step.  The glue decides where the medians and the CO2 minimum come from and what a history row is; the two
@@ -102,6 +109,8 @@ class PoreRun:
         device = self.glue == "device"
         self.t += self.pp.dt
         st = self.sys.solve(self.solver_parameters)
+        if self.budget is not None:   # after the Newton solve, before set_bcs / assign_previous
+            self.budget.take(self.sys)
         if device:   # the library's column select, no gather of the state; the history keeps this process's owned rows
             meds, (co2_min,) = device_medians_and_minima(self.sys, (1, 2, 3, 7), (4,))
             row = [v for _, v in self.sys.owned_vertex_values()]
@@ -222,6 +231,8 @@ class PoreRun:
             # additions of this backend (new keys only)
             "newton_iterations": int(sum(self.newton_its)), "krylov_iterations": int(self.sys.krylov_iterations),
             "num_steps_run": int(self.n)}
+        if self.budget is not None:
+            metadata_dict.update(self.budget.save(newpath))
         with open(newpath + "metadata.json", "w") as fh:
             fh.write(json.dumps(metadata_dict, indent=0))
         return newpath
@@ -231,13 +242,13 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=-1.0, H2_FE=0.05, curren
              cation="K", R=5.0e-9, press_gas=1.0, pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5,
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
-             device_kwargs=None, glue="host"):
+             device_kwargs=None, glue="host", budget=False):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
-    geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` as ``PoreRun`` takes them (with
+    geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
     one rank per process only rank 0 writes and returns the directory; the others return None)."""
     run = PoreRun(num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
-                  device_kwargs=device_kwargs, glue=glue, concentration_elec=concentration_elec,
+                  device_kwargs=device_kwargs, glue=glue, budget=budget, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
                   R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier, porosity_eff=porosity_eff,
                   tortuosity_eff=tortuosity_eff, constrictivity_eff=constrictivity_eff, params_file=params_file,
@@ -271,6 +282,7 @@ def build_parser():
     p.add_argument("--partitions", required=False, default=None, type=int,
                    help="solve on N mesh partitions: all in this process on one GPU, or one rank per process under torch.distributed.run "
                         "(WORLD_SIZE = N; rank 0 prints and writes)")
+    p.add_argument("--budget", action="store_true", help="record the species budgets and consistent boundary fluxes of every step (budget.npz)")
     return p
 
 
@@ -307,7 +319,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, **extra)
+                        multilevel=a.multilevel, budget=a.budget, **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

@@ -58,9 +58,11 @@ def plan_members(members, num_steps=None):
 
 class PoreEnsemble:
     """``members``: keyword dicts of ``PoreRun`` (concentration, voltage, cation, H2_FE, current_rough, roughness_factor, y_CO2 may
-    differ; mesh, weak form and schedule may not).  ``keep_history=False`` keeps only the latest row of each member (long runs)."""
+    differ; mesh, weak form and schedule may not).  ``keep_history=False`` keeps only the latest row of each member (long runs).
+    ``budget=True``: every live member records its species-budget table after the step's solve (the single-handle call per member:
+    the members are ordinary handles), as its serial ``PoreRun`` twin does."""
 
-    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True):
+    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False):
         self.kwargs, steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []
@@ -68,7 +70,7 @@ class PoreEnsemble:
         dk = dict(device_kwargs or {}, shared_device=1)
         try:
             for kw in self.kwargs:
-                self.runs.append(PoreRun(num_steps=steps, device_kwargs=dk, **kw))
+                self.runs.append(PoreRun(num_steps=steps, device_kwargs=dk, budget=budget, **kw))
         except BaseException:
             self.close()
             raise
@@ -111,6 +113,8 @@ class PoreEnsemble:
                 self.errors[k], self.status[k], self.failed_step[k] = error_text(codes[i], msgs[i]), codes[i], r.n
                 continue
             r.sys.record(stats[i])
+            if r.budget is not None:   # before set_bcs / assign_previous, as PoreRun.step
+                r.budget.take(r.sys)
             row = U[i].reshape(r.sys.nv, r.sys.nf).copy()
             r.accept_solution(stats[i], row, column_medians(row, (1, 2, 3, 7)), float(np.amin(row[:, 4])), assign=False)
             if not self.keep_history:

@@ -132,7 +132,8 @@ def rxn_diff_parameters(concentration_KHCO3=0.1, H2_FE=0.2, L_n=50.0e-6, mesh_st
 class RxnDiffRun:
     """State of one run; ``step()`` is one pass of the reference's time loop body (1D/rxn_diff_planar.py:320-360)."""
 
-    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, **kwargs):
+    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, **kwargs):
+        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py)."""
         self.kwargs = kwargs
         self.rp = rxn_diff_parameters(**kwargs)
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), self.rp.mesh_name))
@@ -147,10 +148,17 @@ class RxnDiffRun:
         self.history = [np.ones((nv, 5))]  # H = np.ones(num_vertices) ..., :308-312
         self.n, self.t = 0, 0.0
         self.newton_its = []
+        self.budget = None
+        if budget:
+            from .budget import BudgetLog, interval_factors
+            rp = self.rp
+            self.budget = BudgetLog(SOLVED + ["cat", "p"], *interval_factors(rp.species, rp.diff_coeff, rp.initial_conc, rp.L_n))
 
     def step(self, verbose=True):
         self.t += self.rp.dt
         st = self.sys.solve(self.solver_parameters)
+        if self.budget is not None:   # after the Newton solve, before assign_previous
+            self.budget.take(self.sys)
         self.history.append(self.sys.vertex_values()[:, :5].copy())
         self.sys.assign_previous()
         self.newton_its.append(st["iterations"])
@@ -193,15 +201,17 @@ class RxnDiffRun:
                 "pH_overpotential": -0.059 * (rp.bulk_pH - pH_OHP) * 1.0e+3,
                 "CO2_overpotential": (0.059 / 2) * math.log10(rp.initial_conc["CO2"] / CO2_surf) * 1.0e+3,
                 "CO2_OHP_frac": CO2_surf / rp.initial_conc["CO2"], "num_steps_run": int(self.n)}
+        if self.budget is not None:
+            meta.update(self.budget.save(newpath))
         with open(os.path.join(newpath, "metadata.json"), "w") as fh:
             fh.write(json.dumps(meta, indent=0))
         return newpath
 
 
 def solve_rxn_diff(concentration_KHCO3=0.1, H2_FE=0.2, L_n=50.0e-6, mesh_structure="variable", current_OHP_ss=10.0,
-                   cation="K", params_file="parameters", num_steps=None, verbose=True):
+                   cation="K", params_file="parameters", num_steps=None, verbose=True, budget=False):
     """Same keyword surface as the reference's ``solve_rxn_diff``; returns the output directory."""
-    run = RxnDiffRun(num_steps=num_steps, concentration_KHCO3=concentration_KHCO3, H2_FE=H2_FE, L_n=L_n,
+    run = RxnDiffRun(num_steps=num_steps, budget=budget, concentration_KHCO3=concentration_KHCO3, H2_FE=H2_FE, L_n=L_n,
                      mesh_structure=mesh_structure, current_OHP_ss=current_OHP_ss, cation=cation, params_file=params_file)
     try:
         run.run(verbose=verbose)
@@ -226,10 +236,11 @@ def build_parser():
                    default="parameters", type=str)
     p.add_argument("--cation", required=False, default="K", type=str, help="str, K/Li/Na/Cs (keyword of solve_rxn_diff)")
     p.add_argument("--num_steps", required=False, default=None, type=int, help="int, time steps to run (default: all 500)")
+    p.add_argument("--budget", action="store_true", help="record the species budgets and consistent boundary fluxes of every step (budget.npz)")
     return p
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     return solve_rxn_diff(concentration_KHCO3=a.concentration_KHCO3, H2_FE=a.H2_FE, L_n=a.L_n, mesh_structure=a.mesh_structure,
-                          current_OHP_ss=a.current_OHP_ss, cation=a.cation, params_file=a.params_file, num_steps=a.num_steps)
+                          current_OHP_ss=a.current_OHP_ss, cation=a.cation, params_file=a.params_file, num_steps=a.num_steps, budget=a.budget)

@@ -53,7 +53,8 @@ def rxn_pore_parameters(**kwargs):
 class RxnPoreRun:
     """State of one run; ``step()`` is one pass of the reference's time loop body (:523-598)."""
 
-    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, **kwargs):
+    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, **kwargs):
+        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py)."""
         self.kwargs = kwargs
         self.pp = rxn_pore_parameters(**kwargs)
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), self.pp.mesh_name))
@@ -68,11 +69,17 @@ class RxnPoreRun:
         self.co2_bc = None
         self.n, self.t = 0, 0.0
         self.newton_its = []
+        self.budget = None
+        if budget:
+            from .budget import BudgetLog, pore_factors
+            self.budget = BudgetLog(SOLVED + ["cat", "p"], *pore_factors(self.pp))
 
     def step(self, verbose=True):
         pp = self.pp
         self.t += pp.dt
         st = self.sys.solve(self.solver_parameters)
+        if self.budget is not None:   # after the Newton solve, before set_bcs / assign_previous
+            self.budget.take(self.sys)
         vals = self.sys.vertex_values()
         b, cat = pp.bulk_conc, pp.cation
         med = dict(zip(SOLVED[:4], (float(m) for m in column_medians(vals, range(4)))))
@@ -135,6 +142,8 @@ class RxnPoreRun:
                 # additions of this backend (new keys only)
                 "newton_iterations": int(sum(self.newton_its)), "krylov_iterations": int(self.sys.krylov_iterations),
                 "num_steps_run": int(self.n)}
+        if self.budget is not None:
+            meta.update(self.budget.save(newpath))
         with open(newpath + "metadata.json", "w") as fh:
             fh.write(json.dumps(meta, indent=0))
         return newpath
@@ -143,9 +152,9 @@ class RxnPoreRun:
 def solveEDL(concentration_elec=1.0, H2_FE=0.05, current_rough=3000.0, L=100.0e-9, cation="K", R=5.0e-9, press_gas=1.0,
              pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5, constrictivity_eff=0.9,
              params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0, roughness_factor=150.0,
-             num_steps=None, verbose=True):
+             num_steps=None, verbose=True, budget=False):
     """Same keyword surface as the reference's ``solveEDL`` (:95-110); returns the output directory."""
-    run = RxnPoreRun(num_steps=num_steps, concentration_elec=concentration_elec, H2_FE=H2_FE, current_rough=current_rough,
+    run = RxnPoreRun(num_steps=num_steps, budget=budget, concentration_elec=concentration_elec, H2_FE=H2_FE, current_rough=current_rough,
                      L=L, cation=cation, R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier,
                      porosity_eff=porosity_eff, tortuosity_eff=tortuosity_eff, constrictivity_eff=constrictivity_eff,
                      params_file=params_file, y_CO2=y_CO2, electrolyte_flow_geom_multiplier=electrolyte_flow_geom_multiplier,
@@ -174,4 +183,4 @@ def main(argv=None):
                     R=a.R, press_gas=a.press_gas, pore_geom_multiplier=a.pore_geom_multiplier, porosity_eff=a.porosity_eff,
                     tortuosity_eff=a.tortuosity_eff, constrictivity_eff=a.constrictivity_eff, params_file=a.params_file,
                     y_CO2=a.y_CO2, electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
-                    roughness_factor=a.roughness_factor, num_steps=a.num_steps)
+                    roughness_factor=a.roughness_factor, num_steps=a.num_steps, budget=a.budget)

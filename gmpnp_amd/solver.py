@@ -62,6 +62,11 @@ class _System:
         ranks' owned rows, collective): (values, nan flag)."""
         return self._solver.column_select(fields, ranks)
 
+    def species_budget(self):
+        """(nf, 8) species budgets and consistent boundary fluxes of the current state, on the device (gmpnp_species_budget /
+        gmpnp_group_species_budget: over ALL ranks' owned rows, collective); columns ``backend.BUDGET_COLUMNS``."""
+        return self._solver.species_budget()
+
     def assign_previous(self):
         self._solver.assign_previous()
 

@@ -47,7 +47,7 @@ def group_by_radius(job_list):
 
 
 def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=0, write=False, as_published=False, ramp_steps=0,
-              L=50e-9, device_kwargs=None):
+              L=50e-9, device_kwargs=None, budget=False):
     """The runs of ``run_job`` for every voltage on ONE mesh as one ``PoreEnsemble`` (one launch chain per Newton iteration for all
     of them); returns their summaries in the order of ``voltages``, with the keys ``run_job`` gives (``seconds``: the group's)."""
     from .pore_ensemble import PoreEnsemble
@@ -57,7 +57,7 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
     members = [dict(concentration_elec=concentration_elec, L=L, R=radius_nm * 1e-9, voltage_multiplier=ramp_value(v, 0, ramp_steps),
                     as_published=as_published) for v in voltages]
     with PoreEnsemble(members, num_steps=num_steps, device_kwargs=dict({"device_id": device_id}, **(device_kwargs or {})),
-                      keep_history=write) as ens:
+                      keep_history=write, budget=budget) as ens:
         for n in range(num_steps):
             ens.step()
             for k in ens.live():   # --ramp_steps, per member: the Dirichlet set of the NEXT step
@@ -77,6 +77,8 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
                 out.update(status="newton_failed", error=ens.errors[k][:200])
             out.update(steps_done=run.n, newton_iterations=int(sum(run.newton_its)), krylov_iterations=int(run.sys.krylov_iterations),
                        CO2_min=None if run.CO2_min is None else float(run.CO2_min))
+            if run.budget is not None:
+                out.update(run.budget.summary())
     dt = time.perf_counter() - t0
     for out in outs:
         out["seconds"] = dt
@@ -84,7 +86,7 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
 
 
 def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, write=False, as_published=False, ramp_steps=0,
-            one_stream=False, L=50e-9, device_kwargs=None):
+            one_stream=False, L=50e-9, device_kwargs=None, budget=False):
     """One pore run of ``num_steps`` time steps; returns a small summary dict (never raises for a diverged Newton).
 
     ``ramp_steps`` > 0 is a continuation the reference does not have: the wall potential Dirichlet value (bc3 of
@@ -98,7 +100,7 @@ def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, 
     run = None
     try:
         run = PoreRun(num_steps=num_steps, concentration_elec=concentration_elec, L=L, R=radius_nm * 1e-9,
-                      voltage_multiplier=ramp_value(voltage, 0, ramp_steps), as_published=as_published,
+                      voltage_multiplier=ramp_value(voltage, 0, ramp_steps), as_published=as_published, budget=budget,
                       # several runs in flight on one GPU: every handle keeps to ONE stream (coarse rebuild and warm-start test in
                       # the main stream): with side streams K handles are 2K streams on the process's four hardware queues
                       device_kwargs=dict({"device_id": device_id}, **dict({"coarse_refresh": 3, "warm_in_stream": 1} if one_stream else {},
@@ -119,6 +121,8 @@ def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, 
     if run is not None:
         out.update(steps_done=run.n, newton_iterations=int(sum(run.newton_its)), krylov_iterations=int(run.sys.krylov_iterations),
                    CO2_min=None if run.CO2_min is None else float(run.CO2_min))
+        if run.budget is not None:   # CO2_wall_uptake [mol / s], CO2_entry_supply, max_abs_closure of the last step run
+            out.update(run.budget.summary())
         run.sys.close()
     out["seconds"] = time.perf_counter() - t0
     return out
@@ -140,6 +144,8 @@ def main(argv=None):
     p.add_argument("--ensemble", action="store_true",
                    help="run the jobs of one mesh (its voltages) as one device ensemble: one launch chain per Newton iteration for all "
                         "of them (gmpnp_amd.pore_ensemble; every handle on one stream, four launches per BiCGStab iteration)")
+    p.add_argument("--budget", action="store_true", help="record the species budgets of every step; each job summary gets the CO2 wall uptake, the "
+                   "CO2 supplied by its Dirichlet face and the largest closure (gmpnp_amd/budget.py); with --write also budget.npz")
     p.add_argument("--write", action="store_true", help="write the reference's output files of every run under $GMPNP_OUT")
     p.add_argument("--backend", default=None, help="torch.distributed backend for the final gather (default: nccl)")
     a = p.parse_args(argv)
@@ -150,13 +156,13 @@ def main(argv=None):
     t0 = time.perf_counter()
     def one(job):
         return run_job(job[0], job[1], a.num_steps, a.concentration_elec, device_id=local, write=a.write,
-                       as_published=a.as_published, ramp_steps=a.ramp_steps, one_stream=a.jobs_per_gpu > 1)
+                       as_published=a.as_published, ramp_steps=a.ramp_steps, one_stream=a.jobs_per_gpu > 1, budget=a.budget)
 
     if a.ensemble:
         res = [None] * len(mine)
         for radius, idx in group_by_radius(mine):
             outs = run_group(radius, [mine[k][1] for k in idx], a.num_steps, a.concentration_elec, device_id=local, write=a.write,
-                             as_published=a.as_published, ramp_steps=a.ramp_steps)
+                             as_published=a.as_published, ramp_steps=a.ramp_steps, budget=a.budget)
             for k, out in zip(idx, outs):
                 res[k] = out
     elif a.jobs_per_gpu > 1:

@@ -379,6 +379,35 @@ int gmpnp_group_attach_coarse_group(gmpnp_group* fine, gmpnp_group* coarse);
 int gmpnp_column_select(gmpnp_solver* s, int32_t n, const int32_t* field, const int64_t* rank, double* out, int32_t* flags);
 int gmpnp_group_column_select(gmpnp_group* g, int32_t n, const int32_t* field, const int64_t* rank, double* out, int32_t* flags);
 
+/* ---- species budgets and consistent boundary fluxes on the device (no reference counterpart: the reference writes fields only) ----
+ * P1 test functions sum to one, so the RAW residual rows of one field (before Dirichlet rows are overwritten) sum to that field's
+ * integrated balance; terms whose test-function factor is a gradient (diffusion, migration, steric, SUPG) drop out of the sum.  Per
+ * field f (species 0 .. n_species-1 in model order, potential last) one row of GMPNP_BUDGET_COLUMNS doubles in the scaled units of the
+ * weak form, evaluated at the current u / u_n / model / Dirichlet set:
+ *   inventory  int u_f dx                                   storage  inv_dt int (u_f - u_f^n) dx   (0 for the potential)
+ *   reaction   int (rc0 + sum rc1 u + sum rc2 u u) dx = int -R_f;  potential row: the space-charge term sum_j qzb_j int u_j dx
+ *   wall       wall_flux_f |S2|        exit  exit_kappa_f int_S3 (u_f - 1) ds        point  point_flux_f x number of point vertices
+ *   dirichlet  sum of the raw residual over the Dirichlet dofs of f: the consistent flux the constraint supplies
+ *   closure    sum of the raw residual over the free dofs of f: bounded by sqrt(n_free) times the Newton residual
+ * with  storage + reaction + wall + exit + point = dirichlet + closure  to rounding for any state (the left side from closed-form
+ * P1 integrals, the right side from the gathered element rows: independent arithmetic).  Fixed-order reductions: two calls on one
+ * state return the same bits.  The call evaluates the element residual itself, into storage of its own: u, u_n, F, the Jacobian,
+ * the preconditioner and every policy state of the handle stay as they were.  Sums run over the handle's OWNED rows; the group form
+ * adds the ranks' tables with the group's all-reduce (collective: every rank calls it; the same table on every rank). */
+#define GMPNP_BUDGET_COLUMNS 8
+typedef enum {
+  GMPNP_BUDGET_INVENTORY = 0,
+  GMPNP_BUDGET_STORAGE = 1,
+  GMPNP_BUDGET_REACTION = 2,
+  GMPNP_BUDGET_WALL = 3,
+  GMPNP_BUDGET_EXIT = 4,
+  GMPNP_BUDGET_POINT = 5,
+  GMPNP_BUDGET_DIRICHLET = 6,
+  GMPNP_BUDGET_CLOSURE = 7
+} gmpnp_budget_column;
+int gmpnp_species_budget(gmpnp_solver* s, double* out /* [n_fields][GMPNP_BUDGET_COLUMNS] */);
+int gmpnp_group_species_budget(gmpnp_group* g, double* out /* [n_fields][GMPNP_BUDGET_COLUMNS] */);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -421,7 +450,8 @@ int gmpnp_ensemble_get_state(gmpnp_ensemble* e, double* u_out);
  * read of the matrix buffer with 2048 / 512 / 8192 workgroups (bandwidth probes), 12/13 = the two-launch form of the
  * half-iterations (coarse workgroups inside the tile launch), 14/15 = the tile kernels of the materialised vector form,
  * 16/17 = its streaming vector updates, 18 = one whole 1D direct solve (block cyclic reduction: extraction, every level down
- * and up; needs an assembled Jacobian). */
+ * and up; needs an assembled Jacobian), 19 = element kernel without J (with 3: one residual evaluation), 20 = the launch chain of one
+ * gmpnp_species_budget call (element kernel without J, cell pass, row pass, final sums). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
