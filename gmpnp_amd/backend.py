@@ -101,9 +101,12 @@ class CHostTransport(ctypes.Structure):
 
 
 class GmpnpError(RuntimeError):
-    def __init__(self, code, message):
+    """``stats``: what the library had filled into the call's statistics when it failed (``linear_solve``), else None."""
+
+    def __init__(self, code, message, stats=None):
         super().__init__("libgmpnp status %d: %s" % (code, message))
         self.code = code
+        self.stats = stats
 
 
 _lib = None
@@ -443,9 +446,11 @@ class DeviceSolver:
         x = np.empty(self.ndof)
         st = CLinearStats()
         code = self.lib.gmpnp_linear_solve(self._h, _dptr(b), _dptr(x), linear_solver, rtol, atol, max_iterations, byref(st))
-        self._check(code)
-        return x, {"iterations": st.iterations, "converged": bool(st.converged), "residual_norm": st.residual_norm,
-                   "rhs_norm": st.rhs_norm}
+        stats = {"iterations": st.iterations, "converged": bool(st.converged), "residual_norm": st.residual_norm,
+                 "rhs_norm": st.rhs_norm}
+        if code != OK:   # a solve that stopped at its iteration limit still reports how far it came
+            raise GmpnpError(code, self.lib.gmpnp_last_error().decode(), stats)
+        return x, stats
 
     def attach_coarse_level(self, coarse: "DeviceSolver", parents, theta: float = 2.0, sweeps: int = 4):
         """Geometric multilevel term (gmpnp_attach_coarse_level): ``coarse`` = handle of the parent mesh, ``parents`` (nv, 2) the

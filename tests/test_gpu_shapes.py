@@ -18,45 +18,13 @@ import scipy.sparse.linalg as spla
 import gmpnp_oracle as O
 import hp_reference as H
 from conftest import GOLDEN, box_pore_problem, random_state
+from precond_reference import assembly_matches as _assembly_matches, relerr
 
 pytestmark = pytest.mark.gpu
 
 MUMPS_09 = {"nonlinear_solver": "newton", "newton_solver": {
     "linear_solver": "mumps", "maximum_iterations": 50, "relative_tolerance": 1e-4, "absolute_tolerance": 1e-4,
     "relaxation_parameter": 0.9}}
-
-
-def relerr(a, b):
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
-
-
-def frob_rel(A, B):
-    D = (A - B).tocsr()
-    return np.sqrt((D.data ** 2).sum()) / np.sqrt((B.data ** 2).sum())
-
-
-def _assembly_matches(dev, prob, u, un):
-    """Assembly, CSR pattern and SpMV against the oracle (1e-12, identical pattern, 1e-13) on a random state of the mesh (on
-    the uniform and the converged states F is a difference of nearly equal terms and 1e-12 of its norm is below their
-    rounding), then the state (u, un) is assembled; returns (oracle F, device J) of that state."""
-    nv = prob.coords.shape[0]
-    ur, unr = random_state(nv, prob.nf - 1, seed=3)
-    dev.set_state(ur, unr)
-    F, _ = dev.assemble(True)
-    A = dev.jacobian_csr()
-    Fo, Ao = O.assemble(prob, ur, unr)
-    assert relerr(F, Fo) < 1e-12
-    assert A.nnz == Ao.nnz and np.array_equal(A.indptr, Ao.indptr) and np.array_equal(A.indices, Ao.indices)
-    assert frob_rel(A, Ao) < 1e-12
-    x = np.random.default_rng(12).standard_normal(prob.ndof)
-    assert relerr(dev.spmv(x), Ao @ x) < 1e-13
-    dev.set_state(u, un)
-    dev.assemble(True)
-    A = dev.jacobian_csr()
-    Fo, Ao = O.assemble(prob, u, un)
-    assert A.nnz == Ao.nnz and np.array_equal(A.indptr, Ao.indptr) and np.array_equal(A.indices, Ao.indices)
-    assert frob_rel(A, Ao) < 1e-12
-    return Fo, A
 
 
 # ---- (a) 1D block cyclic reduction -----------------------------------------------------------------------------------
