@@ -36,6 +36,7 @@ EXPORTS = [
     "gmpnp_ensemble_create", "gmpnp_ensemble_destroy", "gmpnp_ensemble_size", "gmpnp_ensemble_newton_solve",
     "gmpnp_ensemble_member_error", "gmpnp_ensemble_assign_previous", "gmpnp_ensemble_get_state",
     "gmpnp_species_budget", "gmpnp_group_species_budget",
+    "gmpnp_step_limit",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -56,7 +57,8 @@ class CNewtonOptions(ctypes.Structure):
     _fields_ = [("maximum_iterations", c_int32), ("relative_tolerance", c_double),
                 ("absolute_tolerance", c_double), ("relaxation_parameter", c_double),
                 ("linear_solver", c_int32), ("krylov_relative_tolerance", c_double),
-                ("krylov_absolute_tolerance", c_double), ("krylov_maximum_iterations", c_int32)]
+                ("krylov_absolute_tolerance", c_double), ("krylov_maximum_iterations", c_int32),
+                ("step_fraction", c_double)]
 
 
 class CNewtonStats(ctypes.Structure):
@@ -64,7 +66,8 @@ class CNewtonStats(ctypes.Structure):
                 ("n_residuals", c_int32), ("residuals", c_double * MAX_HISTORY),
                 ("krylov_per_iteration", c_int32 * MAX_HISTORY),
                 ("ms_assemble", c_double), ("ms_setup", c_double), ("ms_krylov", c_double), ("ms_total", c_double),
-                ("direct_solves", c_int32), ("steric_excursion", c_int32)]
+                ("direct_solves", c_int32), ("steric_excursion", c_int32),
+                ("limited_steps", c_int32), ("min_step", c_double), ("step_factor", c_double * MAX_HISTORY)]
 
 
 class CLinearStats(ctypes.Structure):
@@ -190,6 +193,7 @@ def load_library(path: str = None):
     lib.gmpnp_ensemble_get_state.argtypes = [c_void_p, POINTER(c_double)]
     for name in ("gmpnp_species_budget", "gmpnp_group_species_budget"):
         getattr(lib, name).argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
     return lib
@@ -243,7 +247,8 @@ def newton_options(solver_parameters: dict = None, dim: int = 3) -> CNewtonOptio
     to the block-banded LU inside the library; ``GMPNP_3D_DIRECT=1`` maps them to that LU from the start, the literal
     reading of 'mumps'); 'band_lu' asks for the LU by name; 'bicgstab' honours ``preconditioner``
     ('jacobi' -> node-block Jacobi; 'default', 'ilu', the AMG names -> two-level, with a warning; 'none' / unknown: refused) and a
-    ``krylov_solver`` sub-dict."""
+    ``krylov_solver`` sub-dict.  ``newton_solver["step_fraction"]`` (an extension key, absent = 0 = off) is the fraction-to-boundary
+    step limiter's tau in (0, 1) (gmpnp_newton_options_t.step_fraction, include/gmpnp.h)."""
     sp = dict(solver_parameters or {})
     if sp.get("nonlinear_solver", "newton") != "newton":
         raise RuntimeError("nonlinear_solver %r is not available" % sp.get("nonlinear_solver"))
@@ -285,7 +290,19 @@ def newton_options(solver_parameters: dict = None, dim: int = 3) -> CNewtonOptio
         raise RuntimeError("linear_solver %r is not available in the MI355X backend" % lin)
     o.krylov_absolute_tolerance = float(ks.get("absolute_tolerance", 0.0))
     o.krylov_maximum_iterations = int(ks.get("maximum_iterations", 10000))
+    o.step_fraction = float(ns.get("step_fraction", 0.0))
+    if o.step_fraction != 0.0 and not 0.0 < o.step_fraction < 1.0:
+        raise ValueError("newton_solver['step_fraction'] must be 0 (off) or lie in (0, 1), not %r" % ns.get("step_fraction"))
     return o
+
+
+def with_step_fraction(solver_parameters: dict, step_fraction: float) -> dict:
+    """`solver_parameters` with ``newton_solver["step_fraction"]`` set (a copy); unchanged when `step_fraction` is 0."""
+    if not step_fraction:
+        return solver_parameters
+    sp = dict(solver_parameters or {})
+    sp["newton_solver"] = dict(sp.get("newton_solver", {}), step_fraction=float(step_fraction))
+    return sp
 
 
 class DeviceSolver:
@@ -525,7 +542,18 @@ class DeviceSolver:
         return {"iterations": st.iterations, "converged": bool(st.converged), "krylov_iterations": st.krylov_iterations,
                 "residuals": [st.residuals[i] for i in range(st.n_residuals)],
                 "krylov_per_iteration": [st.krylov_per_iteration[i] for i in range(min(st.iterations, MAX_HISTORY))],
-                "ms_total": st.ms_total, "direct_solves": st.direct_solves, "steric_excursion": st.steric_excursion}
+                "ms_total": st.ms_total, "direct_solves": st.direct_solves, "steric_excursion": st.steric_excursion,
+                "limited_steps": st.limited_steps, "min_step": st.min_step,
+                "step_factor": [st.step_factor[i] for i in range(min(st.iterations, MAX_HISTORY))]}
+
+    def step_limit(self, dx, tau: float):
+        """The step limiter's rule at the current u for the correction `dx` (file order), evaluated by the Newton loop's kernels
+        (gmpnp_step_limit): (alpha, lambda, limiting vertex in file numbering or -1).  Changes nothing on the handle."""
+        dx = np.ascontiguousarray(dx, dtype=np.float64).ravel()
+        assert dx.size == self.ndof
+        alpha, lam, node = c_double(), c_double(), c_int64()
+        self._check(self.lib.gmpnp_step_limit(self._h, _dptr(dx), float(tau), byref(alpha), byref(lam), byref(node)))
+        return alpha.value, lam.value, int(node.value)
 
     def time_kernel(self, kernel: int, launches: int = 50) -> float:
         us = c_double()

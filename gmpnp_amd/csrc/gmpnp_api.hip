@@ -12,6 +12,7 @@
 #include <hip/hip_ext.h>
 
 #include "gmpnp_kernels.h"
+#include "gmpnp_step_limit.h"
 #include "gmpnp_band_lu.h"
 #include "gmpnp_dist_kernels.h"
 #include "gmpnp_multilevel.h"
@@ -89,6 +90,17 @@ struct gmpnp_budgeter {
   ~gmpnp_budgeter() { if (h_table) (void)hipHostFree(h_table); }
 };
 
+// device side of the step limiter (gmpnp_step_limit.h), allocated by the first limited Newton solve / gmpnp_step_limit call: a
+// handle that never asks for it keeps the buffers and launches it had
+struct gmpnp_step_limiter {
+  DevBuf<double> part, dx;          // workgroup partials; the correction of gmpnp_step_limit / gmpnp_time_kernel(21) (internal order)
+  DevBuf<int32_t> part_node;
+  int nblk = 0;
+  StepReport* h_report = nullptr;   // pinned: what workgroup 0 of the update writes
+  StepReport* d_report = nullptr;   // ... its device address
+  ~gmpnp_step_limiter() { if (h_report) (void)hipHostFree(h_report); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -159,6 +171,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_projector> projector;
   std::unique_ptr<gmpnp_selector> selector;
   std::unique_ptr<gmpnp_budgeter> budgeter;
+  std::unique_ptr<gmpnp_step_limiter> limiter;
   // geometric multilevel term (gmpnp_attach_coarse_level, gmpnp_multilevel.h): the link to the next-coarser level (tables in the
   // internal orders of both handles) and this handle's buffers when it serves as a coarse level itself
   gmpnp_solver* ml_coarse = nullptr; double ml_theta = 1.0; bool ml_is_coarse = false;
@@ -988,13 +1001,44 @@ int collect_phases(gmpnp_solver* s, gmpnp_newton_stats_t& st) {   // after the r
   return GMPNP_OK;
 }
 
+// ---- step limiter (gmpnp_step_limit.h) ------------------------------------------------------------
+int step_prepare(gmpnp_solver* s) {
+  if (s->limiter) return GMPNP_OK;
+  std::unique_ptr<gmpnp_step_limiter> L(new gmpnp_step_limiter);
+  L->nblk = std::max(1, grid_for(s->t.nv, kVecBlock));
+  HIP_TRY(L->part.alloc((size_t)L->nblk)); HIP_TRY(L->part_node.alloc((size_t)L->nblk)); HIP_TRY(L->dx.alloc((size_t)s->ndof));
+  HIP_TRY(hipHostMalloc((void**)&L->h_report, 64, hipHostMallocCoherent | hipHostMallocMapped));
+  std::memset(L->h_report, 0, 64);
+  { void* dp = nullptr; HIP_TRY(hipHostGetDevicePointer(&dp, L->h_report, 0)); L->d_report = (StepReport*)dp; }
+  s->limiter = std::move(L);
+  return GMPNP_OK;
+}
+StepLimitIo step_limit_io(const gmpnp_solver* s, const double* dx) {
+  const gmpnp_step_limiter* L = s->limiter.get();
+  return StepLimitIo{s->u.p, dx, s->d_model.p, L->part.p, L->part_node.p, s->t.nv};
+}
+StepUpdateIo step_update_io(const gmpnp_solver* s, const double* dx, double* xp, double omega, double tau, int32_t* status) {
+  const gmpnp_step_limiter* L = s->limiter.get();
+  return StepUpdateIo{s->u.p, dx, xp, L->part.p, L->part_node.p, L->nblk, s->ndof, omega, tau, L->d_report, status};
+}
+// the two launches of a limited update: u -= omega alpha dx, xp = dx, the report in pinned memory (read behind the next synchronisation)
+template <int NF>
+int step_launch(gmpnp_solver* s, const double* dx, double* xp, double omega, double tau, int32_t* status) {
+  const gmpnp_step_limiter* L = s->limiter.get();
+  hipLaunchKernelGGL((k_step_limit<NF>), dim3(L->nblk), dim3(kVecBlock), 0, s->stream, step_limit_io(s, dx));
+  hipLaunchKernelGGL(k_limited_update, dim3(grid_for(s->ndof, kVecBlock)), dim3(kVecBlock), 0, s->stream, step_update_io(s, dx, xp, omega, tau, status));
+  HIP_TRY(hipGetLastError());
+  return GMPNP_OK;
+}
+
 // The linear step of one Newton iteration, by solver kind: solves J dx = F (||F|| = r, the Jacobian gathered) and applies
-// u <- u - omega dx.
+// u <- u - omega dx.  With the step limiter (o.step_fraction != 0) the step ends with dx in kx and newton() applies the update.
 template <int DIM, int NF>
 int tridiagonal_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t&, double) {
   int rc = mark_phase(s, 2); if (rc) return rc;
   if constexpr (DIM == 1) {
     rc = tri_solve<NF>(s, s->F.p); if (rc) return rc;
+    if (o.step_fraction != 0.0) return tri_apply<NF>(s, s->kx.p, 0.0, 1.0);
     return tri_apply<NF>(s, s->u.p, 1.0, -o.relaxation_parameter);
   } else {
     return fail(GMPNP_ERR_INVALID, "block-tridiagonal solver needs a 1D mesh");
@@ -1009,6 +1053,7 @@ int direct_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_s
     gmpnp_linear_stats_t ls{};
     rc = band_solve<NF>(s, r, o.krylov_relative_tolerance, o.krylov_absolute_tolerance, &ls, true); if (rc) return rc;
     st.direct_solves++; s->x0.left(false);
+    if (o.step_fraction != 0.0) return GMPNP_OK;
     hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, (const double*)s->kx.p,
                        -o.relaxation_parameter, (int)s->ndof);
     return GMPNP_OK;
@@ -1021,8 +1066,11 @@ template <int DIM, int NF>
 int krylov_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st, double r) {
   const int it = st.iterations;
   // x0 = wa dx_k + wb dx_{k-1}, the predicted start of this solve (gmpnp_host_rules.h; gmpnp_options_t.warm_start)
+  // (a limited solve starts every linear solve from zero: the prediction assumes a constant step length)
+  const bool limited = o.step_fraction != 0.0;
+  const int warm_start = limited ? 0 : s->cfg.warm_start;
   const double q = 1.0 - o.relaxation_parameter;
-  const auto [wa, wb] = predicted_start(s->cfg.warm_start, q, it);
+  const auto [wa, wb] = predicted_start(warm_start, q, it);
   const bool x0_ready = s->x0.ready(it, wa);
   // The test of the predicted start (w = J x0 and three dot products, then a host decision) needs the new Jacobian only: it runs
   // on the side stream while the main stream builds the preconditioner, and the host waits for ITS event, so neither the two
@@ -1043,7 +1091,7 @@ int krylov_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_s
   gmpnp_linear_stats_t ls{};
   s->burst.expect(it);
   // coefficients of the NEXT iteration's predicted start, which this solve's update leaves in kx
-  const auto [na, nb] = predicted_start(s->cfg.warm_start, q, it + 1);
+  const auto [na, nb] = predicted_start(warm_start, q, it + 1);
   const NewtonUpdate upd{s->u.p, s->kxp.p, o.relaxation_parameter, na, nb};
   KrylovRequest req;
   req.mode = o.linear_solver; req.bnorm = r; req.rtol = o.krylov_relative_tolerance; req.atol = o.krylov_absolute_tolerance;
@@ -1074,7 +1122,8 @@ int krylov_step(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_s
     return rc;
   }
   // x <- x - omega dx (done by the solve's last kernel in the normal case)
-  if (req.upd_done) s->x0.left(true);
+  if (limited) s->x0.left(false);   // dx stays in kx: newton() applies the limited update
+  else if (req.upd_done) s->x0.left(true);
   else if (na != 0.0) {
     hipLaunchKernelGGL(k_update_predict, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->u.p, s->kx.p, s->kxp.p,
                        o.relaxation_parameter, na, nb, (int)s->ndof);
@@ -1101,6 +1150,8 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
   NewtonJudge judge(o, st, s->cfg.strict_steric != 0);
   NewtonJudge::Verdict v = judge.first(r, flags);
   const bool band_lu_asked = o.linear_solver == GMPNP_LINEAR_BAND_LU;
+  const bool limited = o.step_fraction != 0.0;
+  if (limited) { rc = step_prepare(s); if (rc) return rc; }
   while (v == NewtonJudge::go_on) {
     rc = mark_phase(s, 0); if (rc) return rc;
     rc = launch_jac_gather<DIM, NF>(s); if (rc) return rc;   // element records: left by the last residual evaluation
@@ -1110,9 +1161,11 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
     else if (band_lu_asked || s->direct.use_direct()) rc = direct_step<DIM, NF>(s, o, st, r);
     else rc = krylov_step<DIM, NF>(s, o, st, r);
     if (rc) return rc;
+    if (limited) { rc = step_launch<NF>(s, s->kx.p, s->kxp.p, o.relaxation_parameter, o.step_fraction, s->status.p); if (rc) return rc; }
     rc = mark_phase(s, 3); if (rc) return rc;
     st.iterations++;
     rc = residual<DIM, NF>(s, true, &r, &flags); if (rc) return rc;  // synchronises the stream
+    if (limited) record_step(st, st.iterations - 1, s->limiter->h_report->alpha);   // written by the update, in front of that synchronisation
     rc = collect_phases(s, st); if (rc) return rc;
     v = judge.next(r, flags);
   }
@@ -1490,13 +1543,33 @@ int gmpnp_newton_solve(gmpnp_solver* s, const gmpnp_newton_options_t* o, gmpnp_n
   if (o->linear_solver < 0 || o->linear_solver > GMPNP_LINEAR_BAND_LU) return fail(GMPNP_ERR_INVALID, "unknown linear_solver");
   if (o->linear_solver == GMPNP_LINEAR_BLOCK_TRIDIAGONAL && !s->tri_ok)
     return fail(GMPNP_ERR_INVALID, "block-tridiagonal solver needs a 1D mesh in path order");
+  if (!step_fraction_valid(o->step_fraction)) return fail(GMPNP_ERR_INVALID, "step_fraction must be 0 (off) or lie in (0, 1)");
   gmpnp_newton_stats_t local{};
   gmpnp_newton_stats_t& st = stats ? *stats : local;
-  st = gmpnp_newton_stats_t{};
+  st = fresh_newton_stats();
   HIP_TRY(hipSetDevice(s->opts.device_id));
   int rc;
   GMPNP_DISPATCH(s, rc = (newton<DIM, NF>(s, *o, st)));
   return rc;
+}
+
+int gmpnp_step_limit(gmpnp_solver* s, const double* dx, double tau, double* alpha, double* lambda, int64_t* node) {
+  if (!s || !dx) return fail(GMPNP_ERR_INVALID, "NULL argument");
+  if (!(tau > 0.0 && tau < 1.0)) return fail(GMPNP_ERR_INVALID, "step_fraction must lie in (0, 1)");
+  HIP_TRY(hipSetDevice(s->opts.device_id));
+  int rc = step_prepare(s); if (rc) return rc;
+  gmpnp_step_limiter* L = s->limiter.get();
+  rc = upload_vec(s, dx, L->dx.p); if (rc) return rc;
+  GMPNP_DISPATCH(s, hipLaunchKernelGGL((k_step_limit<NF>), dim3(L->nblk), dim3(kVecBlock), 0, s->stream, step_limit_io(s, L->dx.p)));
+  hipLaunchKernelGGL(k_step_report, dim3(1), dim3(kVecBlock), 0, s->stream, step_update_io(s, L->dx.p, nullptr, 1.0, tau, nullptr));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  const StepReport r = *L->h_report;
+  if (r.bad) return fail(GMPNP_ERR_NUMERIC, status_message(16));
+  if (alpha) *alpha = r.alpha;
+  if (lambda) *lambda = r.lambda;
+  if (node) *node = r.node >= 0 ? (int64_t)s->t.perm[r.node] : -1;
+  return GMPNP_OK;
 }
 
 int32_t gmpnp_n_fields(const gmpnp_solver* s) { return s ? s->nf : 0; }
@@ -1675,6 +1748,8 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
         r = tri_solve<7>(s, s->F.p); break;
       case 19: GMPNP_DISPATCH(s, r = (launch_element<DIM, NF>(s, false))); break;
       case 20: r = budget_launch_any(s); break;   // element pass without J, cell pass, row pass, final sums
+      case 21:   // the step limiter's two launches on a zero correction (alpha = 1, u -= 0: the state stays)
+        GMPNP_DISPATCH(s, r = (step_launch<NF>(s, s->limiter->dx.p, s->limiter->dx.p, 1.0, 0.9, nullptr))); break;
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -1683,6 +1758,10 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if ((kernel >= 4 && kernel <= 7) || (kernel >= 12 && kernel <= 17)) {  // Krylov kernels: a live (not finished) solve state
     KrylovScalars z{}; z.rho[0] = z.rho[1] = 1.0; z.alpha = 1.0; z.omega = 1.0; z.beta = 0.5; z.tol = 0.0; z.max_iters = 1 << 30;
     HIP_TRY(hipMemcpy(s->scal.p, &z, sizeof z, hipMemcpyHostToDevice));
+  }
+  if (kernel == 21) {
+    rc = step_prepare(s); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(s->limiter->dx.p, 0, (size_t)s->ndof * sizeof(double), s->stream));
   }
   rc = one(); if (rc) return rc;  // warm
   HIP_TRY(hipStreamSynchronize(s->stream));

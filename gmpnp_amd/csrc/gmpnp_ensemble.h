@@ -22,6 +22,8 @@ struct EnsMember {
   TriLevel tri[kEnsMaxLevels];
   int32_t* status;
   const int32_t* tri_kpos;
+  // step limiter (gmpnp_step_limit.h; set for the members of a limited solve): the member's kxp, partials and pinned report
+  double* kxp; double* sl_part; int32_t* sl_node; StepReport* sl_report;
 };
 
 template <int DIM, int NF, bool STAGED_ = false>
@@ -88,6 +90,23 @@ __global__ __launch_bounds__(kVecBlock) void k_tri_apply_ens(const EnsMember* __
   const EnsMember& M = tab[act[blockIdx.y]];
   const TriLevel l0 = M.tri[0];
   tri_apply_entry<NF>(l0, M.c.u, 1.0, scale_x, M.c.ndof, blockIdx.x * kVecBlock + threadIdx.x);
+}
+// limited update (gmpnp_newton_options_t.step_fraction): kx <- x, the member's ratio partials, then its own alpha and update
+template <int NF>
+__global__ __launch_bounds__(kVecBlock) void k_tri_dx_ens(const EnsMember* __restrict__ tab, const int32_t* __restrict__ act) {
+  const EnsMember& M = tab[act[blockIdx.y]];
+  const TriLevel l0 = M.tri[0];
+  tri_apply_entry<NF>(l0, M.c.kx, 0.0, 1.0, M.c.ndof, blockIdx.x * kVecBlock + threadIdx.x);
+}
+template <int NF>
+__global__ __launch_bounds__(kVecBlock) void k_step_limit_ens(const EnsMember* __restrict__ tab, const int32_t* __restrict__ act) {
+  const EnsMember& M = tab[act[blockIdx.y]];
+  step_limit_body<NF>(StepLimitIo{M.c.u, M.c.kx, M.c.model, M.sl_part, M.sl_node, M.c.nv});
+}
+__global__ __launch_bounds__(kVecBlock) void k_limited_update_ens(const EnsMember* __restrict__ tab, const int32_t* __restrict__ act, const int nblk,
+                                                                  const double omega, const double tau) {
+  const EnsMember& M = tab[act[blockIdx.y]];
+  step_update_body<true>(StepUpdateIo{M.c.u, M.c.kx, M.kxp, M.sl_part, M.sl_node, nblk, M.c.ndof, omega, tau, M.sl_report, M.status});
 }
 // u_n <- u of member blockIdx.y (all members)
 __global__ __launch_bounds__(256) void k_ens_assign(const EnsMember* __restrict__ tab, const int ndof) {
@@ -269,6 +288,8 @@ int ens_upload_table(gmpnp_ensemble* e) {
     rec.c = s->c;
     for (size_t l = 0; l < s->tri.size(); ++l) rec.tri[l] = s->tri[l];
     rec.status = s->status.p; rec.tri_kpos = s->tri_kpos.p;
+    rec.kxp = s->kxp.p;
+    if (s->limiter) { rec.sl_part = s->limiter->part.p; rec.sl_node = s->limiter->part_node.p; rec.sl_report = s->limiter->d_report; }
     std::memcpy(&e->h_tab[k], &rec, sizeof rec);
   }
   HIP_TRY(hipMemcpyAsync(e->tab.p, e->h_tab, (size_t)n * sizeof(EnsMember), hipMemcpyHostToDevice, e->stream));
@@ -296,8 +317,9 @@ int ens_residual(gmpnp_ensemble* e, int nact) {
   return GMPNP_OK;
 }
 
-// J dx = F by block cyclic reduction and u <- u - omega dx for the active members (gather, tri_solve and tri_apply of newton())
-int ens_update(gmpnp_ensemble* e, int nact, double omega) {
+// J dx = F by block cyclic reduction and u <- u - omega dx for the active members (gather, tri_solve and tri_apply of newton());
+// tau != 0: the limited update of newton(), every member with its own alpha
+int ens_update(gmpnp_ensemble* e, int nact, double omega, double tau) {
   gmpnp_solver* s0 = e->m[0];
   const EnsMember* tab = e->tab.p; const int32_t* act = e->act.p;
   constexpr int NF = 7;
@@ -309,7 +331,13 @@ int ens_update(gmpnp_ensemble* e, int nact, double omega) {
   hipLaunchKernelGGL((k_bcr_tail_ens<NF>), dim3(nact), dim3(kBcrTailThreads), 0, e->stream, tab, act, l0, nl - l0);
   for (int l = l0 - 1; l >= 0; --l)
     hipLaunchKernelGGL((k_bcr_backward_ens<NF>), dim3(grid_for(s0->tri[l].n * NF, kVecBlock), nact), dim3(kVecBlock), 0, e->stream, tab, act, l);
-  hipLaunchKernelGGL((k_tri_apply_ens<NF>), dim3(grid_for(s0->ndof, kVecBlock), nact), dim3(kVecBlock), 0, e->stream, tab, act, -omega);
+  if (tau != 0.0) {
+    const int nblk = s0->limiter->nblk;
+    hipLaunchKernelGGL((k_tri_dx_ens<NF>), dim3(grid_for(s0->ndof, kVecBlock), nact), dim3(kVecBlock), 0, e->stream, tab, act);
+    hipLaunchKernelGGL((k_step_limit_ens<NF>), dim3(nblk, nact), dim3(kVecBlock), 0, e->stream, tab, act);
+    hipLaunchKernelGGL(k_limited_update_ens, dim3(grid_for(s0->ndof, kVecBlock), nact), dim3(kVecBlock), 0, e->stream, tab, act, nblk, omega, tau);
+  } else
+    hipLaunchKernelGGL((k_tri_apply_ens<NF>), dim3(grid_for(s0->ndof, kVecBlock), nact), dim3(kVecBlock), 0, e->stream, tab, act, -omega);
   HIP_TRY(hipGetLastError());
   return GMPNP_OK;
 }
@@ -358,7 +386,7 @@ int ens3_newton(gmpnp_ensemble* e, const gmpnp_newton_options_t& o, gmpnp_newton
   std::vector<double> rn(n, 0.0);   // residual norm of the member's current iterate
   std::vector<NewtonJudge> judge; judge.reserve(n);
   for (int k = 0; k < n; ++k) {
-    stats[k] = gmpnp_newton_stats_t{}; status[k] = GMPNP_OK; e->err[k].clear();
+    stats[k] = fresh_newton_stats(); status[k] = GMPNP_OK; e->err[k].clear();
     judge.emplace_back(o, stats[k], e->m[k]->cfg.strict_steric != 0);
     HIP_TRY(hipMemsetAsync(e->m[k]->status.p, 0, sizeof(int32_t), e->stream));
   }
@@ -647,8 +675,11 @@ const char* gmpnp_ensemble_member_error(const gmpnp_ensemble* e, int32_t k) {
 int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t* o, gmpnp_newton_stats_t* stats, int32_t* status) {
   if (!e || !o || !stats || !status) return fail(GMPNP_ERR_INVALID, "NULL argument");
   if (o->maximum_iterations < 0 || o->krylov_maximum_iterations < 1) return fail(GMPNP_ERR_INVALID, "bad iteration limits");
+  if (!step_fraction_valid(o->step_fraction)) return fail(GMPNP_ERR_INVALID, "step_fraction must be 0 (off) or lie in (0, 1)");
   const bool is3d = e->m[0]->dim == 3;
   if (is3d) {
+    if (o->step_fraction != 0.0)
+      return fail(GMPNP_ERR_INVALID, "step_fraction: the step limiter is not available in 3D ensembles (set it to 0)");
     if (o->linear_solver != GMPNP_LINEAR_BICGSTAB_TWOLEVEL && o->linear_solver != GMPNP_LINEAR_BICGSTAB_JACOBI)
       return fail(GMPNP_ERR_INVALID, "3D ensembles solve with GMPNP_LINEAR_BICGSTAB_TWOLEVEL or GMPNP_LINEAR_BICGSTAB_JACOBI");
   } else if (o->linear_solver != GMPNP_LINEAR_BLOCK_TRIDIAGONAL)
@@ -659,12 +690,14 @@ int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t*
   if (is3d) return ens3_newton<9>(e, *o, stats, status);
   const double t0 = now_ms();
   { int rc = ens_drain_members(e); if (rc) return rc; }
+  const double tau = o->step_fraction;
+  if (tau != 0.0) for (gmpnp_solver* s : e->m) { int rc = step_prepare(s); if (rc) return rc; }   // before the table names the buffers
   // the member table is rebuilt for every solve: a gmpnp_set_* call may have re-allocated member storage since the last one
   { int rc = ens_upload_table(e); if (rc) return rc; }
   std::vector<char> live(n, 1);
   std::vector<NewtonJudge> judge; judge.reserve(n);   // one per member: the single handle's rule (gmpnp_host_rules.h)
   for (int k = 0; k < n; ++k) {
-    stats[k] = gmpnp_newton_stats_t{}; status[k] = GMPNP_OK; e->err[k].clear();
+    stats[k] = fresh_newton_stats(); status[k] = GMPNP_OK; e->err[k].clear();
     judge.emplace_back(*o, stats[k], e->m[k]->cfg.strict_steric != 0);
     HIP_TRY(hipMemsetAsync(e->m[k]->status.p, 0, sizeof(int32_t), e->stream));
   }
@@ -691,11 +724,12 @@ int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t*
     if (act.empty()) break;
     const int nact = (int)act.size();
     int rc = ens_upload_active(e, act); if (rc) return rc;
-    rc = ens_update(e, nact, o->relaxation_parameter); if (rc) return rc;
+    rc = ens_update(e, nact, o->relaxation_parameter, tau); if (rc) return rc;
     rc = ens_residual(e, nact); if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));   // the one host synchronisation of the iteration
     for (int k : act) {
       e->m[k]->jacobian_valid = true;
+      if (tau != 0.0) record_step(stats[k], stats[k].iterations, e->m[k]->limiter->h_report->alpha);
       stats[k].iterations++;
       settle(k, false);
     }

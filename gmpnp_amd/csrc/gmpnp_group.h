@@ -1010,9 +1010,11 @@ int gmpnp_group_newton_solve(gmpnp_group* g, const gmpnp_newton_options_t* o, gm
   if (o->maximum_iterations < 0 || o->krylov_maximum_iterations < 1) return fail(GMPNP_ERR_INVALID, "bad iteration limits");
   if (o->linear_solver != GMPNP_LINEAR_BICGSTAB_TWOLEVEL && o->linear_solver != GMPNP_LINEAR_BICGSTAB_JACOBI)
     return fail(GMPNP_ERR_INVALID, "the partitioned solve uses BiCGStab (two-level or Jacobi)");
+  if (o->step_fraction != 0.0)   // the group transports all-reduce sums, the limiter needs a minimum over the ranks
+    return fail(GMPNP_ERR_INVALID, "step_fraction: the step limiter is not available in the partitioned solve (set it to 0)");
   gmpnp_newton_stats_t local{};
   gmpnp_newton_stats_t& st = stats ? *stats : local;
-  st = gmpnp_newton_stats_t{};
+  st = fresh_newton_stats();
   HIP_TRY(hipSetDevice(g->dom[0]->opts.device_id));
   if (g->ml_level) return fail(GMPNP_ERR_INVALID, "this group is a coarse level of a multilevel term: the finest level's group drives it");
   if (g->dom[0]->ml_coarse && !g->ml_next)

@@ -15,13 +15,15 @@
 
 namespace gmpnp {
 
-// device status word: bit 1 = steric excursion (information, unless strict_steric), bits 2 / 4 / 8 = the linear solve failed
+// device status word: bit 1 = steric excursion (information, unless strict_steric), bits 2 / 4 / 8 = the linear solve failed,
+// bit 16 = the step limiter met a NaN / Inf in the correction (the update was not applied)
 inline std::string status_message(int flags) {
   std::string m;
   if (flags & 1) m += "1 - sum_j a_j u_j <= 0 at a quadrature point; ";
   if (flags & 2) m += "singular diagonal node block; ";
   if (flags & 4) m += "singular coarse operator; ";
   if (flags & 8) m += "in-launch hand-over timed out; ";
+  if (flags & 16) m += "NaN / Inf in the Newton correction (step limiter); ";
   return m;
 }
 
@@ -51,6 +53,7 @@ struct NewtonJudge {
   // residual after an update (st.iterations already counts it)
   Verdict next(double r, int flags) {
     if (steric(flags)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+    if (flags & 16) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
     if (flags & 14) return fail(GMPNP_ERR_LINEAR, status_message(flags));
     if (st.n_residuals < GMPNP_MAX_NEWTON_HISTORY) st.residuals[st.n_residuals++] = r;
     // NaN / Inf stay fatal (DOLFIN would iterate to its limit on a NaN residual and raise there)
@@ -74,6 +77,21 @@ struct NewtonJudge {
     return limit;
   }
 };
+
+// Fraction-to-boundary step limiter (gmpnp_newton_options_t.step_fraction = tau; kernels: gmpnp_step_limit.h).  For the correction
+// dx of J dx = b at the state u, over the vertices I:
+//     S_I = sum_j a_j u_{I,j}    dS_I = sum_j a_j dx_{I,j}    lambda = min_{dS_I < 0, S_I < 1} (1 - S_I) / (-dS_I)   (+inf: none)
+//     alpha = tau lambda if lambda < 1, else 1                 u <- u - omega alpha dx      (omega alpha, not min(omega, tau lambda))
+// The device forms lambda and alpha; the host checks the option and keeps the statistics.  A limited solve starts every linear
+// solve from zero (predicted_start below assumes a constant step length: its callers pass warm_start = 0).
+inline bool step_fraction_valid(double tau) { return tau == 0.0 || (tau > 0.0 && tau < 1.0); }
+inline double step_factor(double lambda, double tau) { return lambda < 1.0 ? tau * lambda : 1.0; }
+// alpha of Newton iteration `it` (0-based) into the statistics (min_step starts at 1.0)
+inline void record_step(gmpnp_newton_stats_t& st, int it, double alpha) {
+  if (it >= 0 && it < GMPNP_MAX_NEWTON_HISTORY) st.step_factor[it] = alpha;
+  if (alpha < 1.0) { st.limited_steps++; st.min_step = std::min(st.min_step, alpha); }
+}
+inline gmpnp_newton_stats_t fresh_newton_stats() { gmpnp_newton_stats_t st{}; st.min_step = 1.0; return st; }
 
 // Predicted start x0 = a dx_k + b dx_{k-1} of the linear solve of Newton iteration `iteration` (0-based), q = 1 - omega: with the
 // damped update consecutive corrections satisfy dx_{k+1} = q dx_k + O(|dx_k|^2), so x0 = q dx_k, plus the second-order term

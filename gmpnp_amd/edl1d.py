@@ -18,6 +18,7 @@ from datetime import datetime
 
 import numpy as np
 
+from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import edl_parameters, utilities_dir
 from .problem import edl_problem
@@ -41,9 +42,12 @@ def output_root():
 
 
 class EDLRun:
-    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, **kwargs):
-        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py)."""
+    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, **kwargs):
+        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
+        ``step_fraction`` = tau in (0, 1): the Newton updates go through the fraction-to-boundary step limiter
+        (``newton_solver["step_fraction"]``, include/gmpnp.h; not a reference feature); 0 = off, the reference's plain Newton."""
         self.kwargs = kwargs
+        self.step_fraction = float(step_fraction)
         self.ep = edl_parameters(**kwargs)
         ep = self.ep
         stab = kwargs.get("stabilization", "N") == "Y"
@@ -54,7 +58,7 @@ class EDLRun:
         self.problem = edl_problem(ep, self.mesh)
         self.model = copy.deepcopy(self.problem.model)
         self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
-        self.solver_parameters = solver_parameters or SOLVER_PARAMETERS
+        self.solver_parameters = backend.with_step_fraction(solver_parameters or SOLVER_PARAMETERS, self.step_fraction)
         self.tot_num_steps = ep.tot_num_steps if num_steps is None else int(num_steps)
         nv = self.mesh.num_vertices
         self.sys.initialise([1.0] * 6 + [0.0])
@@ -199,6 +203,8 @@ class EDLRun:
             "pH_overpotential": pH_overpotential, "CO2_overpotential": CO2_overpotential, "end_time": end_time,
             "newton_iterations": int(sum(self.newton_its)), "krylov_iterations": int(self.sys.krylov_iterations),
             "num_steps_run": int(self.n)}
+        if self.step_fraction:
+            metadata_dict["step_fraction"] = self.step_fraction
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         with open(newpath + "/metadata.json", "w") as fh:
@@ -214,9 +220,9 @@ def run_identifier(ep, kwargs):
 
 def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=-1.0, H2_FE=0.2, mesh_structure="variable",
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
-              dry_run=True, num_steps=None, verbose=True, budget=False):
+              dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory."""
-    run = EDLRun(num_steps=num_steps, budget=budget, concentration_elec=concentration_elec, model=model,
+    run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
                  params_file=params_file, dry_run=dry_run)
@@ -244,6 +250,7 @@ def build_parser():
     p.add_argument("--dry_run", required=False, default=True, type=bool)
     p.add_argument("--num_steps", required=False, default=None, type=int, help="(addition) run only the first N steps")
     p.add_argument("--budget", action="store_true", help="(addition) record the species budgets and consistent boundary fluxes of every step (budget.npz)")
+    p.add_argument("--step_fraction", required=False, default=0.0, type=float, help="(addition) fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off")
     return p
 
 
@@ -252,7 +259,7 @@ def main(argv=None):
     return solve_EDL(concentration_elec=a.concentration_elec, model=a.model, voltage_multiplier=a.voltage_multiplier,
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
-                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget)
+                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction)
 
 
 if __name__ == "__main__":

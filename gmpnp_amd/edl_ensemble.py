@@ -83,16 +83,17 @@ def error_text(code, message):
 class EDLEnsemble:
     """``members``: keyword dicts of ``EDLRun`` (voltage, cation, concentration, H2_FE, current_OHP_ss, H_OHP, model may
     differ; mesh and schedule may not).  ``keep_history=False`` keeps only the latest state of each member (long runs).
-    ``budget=True``: every live member records its species-budget table after the step's solve, as its serial ``EDLRun`` twin does."""
+    ``budget=True``: every live member records its species-budget table after the step's solve, as its serial ``EDLRun`` twin does.
+    ``step_fraction``: tau of the step limiter, for all members (each gets its own step length; 0 = off), as ``EDLRun`` takes it."""
 
-    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False):
+    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False, step_fraction=0.0):
         self.kwargs, self.eps, self.tot_num_steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []
         self._ens, self._ens_members = None, None
         try:
             for kw in self.kwargs:
-                self.runs.append(EDLRun(num_steps=self.tot_num_steps, device_kwargs=device_kwargs, budget=budget, **kw))
+                self.runs.append(EDLRun(num_steps=self.tot_num_steps, device_kwargs=device_kwargs, budget=budget, step_fraction=step_fraction, **kw))
         except BaseException:
             self.close()
             raise

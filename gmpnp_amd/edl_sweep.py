@@ -1,7 +1,7 @@
 """Sweep of the 1D EDL model (voltage x cation x concentration) as device ensembles (gmpnp_amd.edl_ensemble):
 
     python -m gmpnp_amd.edl_sweep --voltage_multiplier -2.5 -5 -7.5 -10 -12.5 --cation K Cs [--concentration_elec 0.1 0.5]
-                                  [--staged] [--num_steps N] [--device_id D]
+                                  [--staged] [--num_steps N] [--device_id D] [--step_fraction TAU]
 
 The Cartesian product (voltage outermost, then cation, then concentration) runs as one ensemble, or as consecutive ensembles
 of at most 64 members.  Every member writes the directory ``EDLRun.write_outputs`` writes (``1D/Stern_CO2ER.py --from_run``
@@ -36,17 +36,18 @@ def build_parser():
     p.add_argument("--num_steps", default=None, type=int, help="run only the first N steps")
     p.add_argument("--device_id", default=0, type=int)
     p.add_argument("--budget", action="store_true", help="record the species budgets of every step: budget.npz per member, the CO2 uptake in each row")
+    p.add_argument("--step_fraction", default=0.0, type=float, help="fraction-to-boundary step limiter of the Newton updates: tau in (0, 1), 0 = off")
     return p
 
 
-def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget=False):
+def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget=False, step_fraction=0.0):
     """Run the members in ensembles of at most backend.MAX_ENSEMBLE; returns (summary rows, path of ensemble_summary.json)."""
     stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
     rows = []
     for c0 in range(0, len(members), backend.MAX_ENSEMBLE):
         chunk = members[c0:c0 + backend.MAX_ENSEMBLE]
         chunk_stamp = stamp if c0 == 0 else "%s_part%d" % (stamp, c0 // backend.MAX_ENSEMBLE)
-        with EDLEnsemble(chunk, num_steps=num_steps, device_kwargs={"device_id": device_id}, budget=budget) as ens:
+        with EDLEnsemble(chunk, num_steps=num_steps, device_kwargs={"device_id": device_id}, budget=budget, step_fraction=step_fraction) as ens:
             ens.run()
             ohp = [None if ens.errors[k] is not None else ens.ohp_summary(k) for k in range(len(ens))]
             paths = ens.write_outputs(chunk_stamp)
@@ -81,7 +82,7 @@ def main(argv=None):
     common = dict(model=a.model, mesh_structure=a.mesh_structure, H2_FE=a.H2_FE, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                   H_OHP=a.H_OHP, params_file=a.params_file, dry_run=not a.staged)
     members = sweep_members(a.voltage_multiplier, a.cation, a.concentration_elec, **common)
-    rows, path = run_sweep(members, num_steps=a.num_steps, device_id=a.device_id, log=lambda s: print(s, flush=True), budget=a.budget)
+    rows, path = run_sweep(members, num_steps=a.num_steps, device_id=a.device_id, log=lambda s: print(s, flush=True), budget=a.budget, step_fraction=a.step_fraction)
     print(path)
     return path
 

@@ -15,6 +15,7 @@ from datetime import datetime
 
 import numpy as np
 
+from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .problem import pore_dirichlet, pore_problem
@@ -44,7 +45,7 @@ class PoreRun:
     """State of one pore simulation; ``step()`` is one pass of the reference's time loop body (3D:783-858)."""
 
     def __init__(self, num_steps=None, as_published=False, device_kwargs=None, solver_parameters=None, refine=0,
-                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", budget=False, **kwargs):
+                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", budget=False, step_fraction=0.0, **kwargs):
         """``partition`` = (nparts, rank): solve this ONE problem across `nparts` mesh partitions (rank None: all of them in
         this process on one GPU; rank r: this process is rank r of a ``torch.distributed`` job, RCCL inside the library).
         ``multilevel`` (with ``refine`` > 0): the preconditioner gets the geometric multilevel term over the nested meshes
@@ -57,9 +58,15 @@ class PoreRun:
         global history on rank 0, which alone prints and writes.
         ``budget`` = True: every step records the species-budget table of its solution (``species_budget()``: integrated storage,
         reaction, wall / exit fluxes and the consistent Dirichlet flux per field; on a partitioned run summed over the ranks inside
-        the library, no gather of the state) and ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).  Off: nothing changes."""
+        the library, no gather of the state) and ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).  Off: nothing changes.
+        ``step_fraction`` = tau in (0, 1): the Newton updates go through the fraction-to-boundary step limiter
+        (``newton_solver["step_fraction"]``, include/gmpnp.h; not a reference feature); 0 = off.  Not with ``partition``: the
+        partitioned solve has no limiter (ValueError, before anything touches the device)."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
+        self.step_fraction = float(step_fraction)
+        if self.step_fraction and partition:
+            raise ValueError("step_fraction: the step limiter is not available in a partitioned solve")
         self.glue = glue
         self.rank = partition[1] if partition else None
         self.kwargs = kwargs
@@ -81,7 +88,7 @@ class PoreRun:
             self.sys = PartitionedSystem(self.problem, partition[0], rank=partition[1], **sys_kwargs)
         else:
             self.sys = GMPNPSystem(self.problem, **sys_kwargs)
-        self.solver_parameters = solver_parameters or SOLVER_PARAMETERS
+        self.solver_parameters = backend.with_step_fraction(solver_parameters or SOLVER_PARAMETERS, self.step_fraction)
         self.tot_num_steps = self.pp.tot_num_steps if num_steps is None else int(num_steps)
         nv = self.mesh.num_vertices
         self.sys.initialise([1.0] * 8 + [0.0])
@@ -231,6 +238,8 @@ class PoreRun:
             # additions of this backend (new keys only)
             "newton_iterations": int(sum(self.newton_its)), "krylov_iterations": int(self.sys.krylov_iterations),
             "num_steps_run": int(self.n)}
+        if self.step_fraction:
+            metadata_dict["step_fraction"] = self.step_fraction
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         with open(newpath + "metadata.json", "w") as fh:
@@ -242,13 +251,13 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=-1.0, H2_FE=0.05, curren
              cation="K", R=5.0e-9, press_gas=1.0, pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5,
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
-             device_kwargs=None, glue="host", budget=False):
+             device_kwargs=None, glue="host", budget=False, step_fraction=0.0):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
     geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
     one rank per process only rank 0 writes and returns the directory; the others return None)."""
     run = PoreRun(num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
-                  device_kwargs=device_kwargs, glue=glue, budget=budget, concentration_elec=concentration_elec,
+                  device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
                   R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier, porosity_eff=porosity_eff,
                   tortuosity_eff=tortuosity_eff, constrictivity_eff=constrictivity_eff, params_file=params_file,
@@ -283,6 +292,8 @@ def build_parser():
                    help="solve on N mesh partitions: all in this process on one GPU, or one rank per process under torch.distributed.run "
                         "(WORLD_SIZE = N; rank 0 prints and writes)")
     p.add_argument("--budget", action="store_true", help="record the species budgets and consistent boundary fluxes of every step (budget.npz)")
+    p.add_argument("--step_fraction", required=False, default=0.0, type=float,
+                   help="fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off (not with --partitions)")
     return p
 
 
@@ -319,7 +330,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

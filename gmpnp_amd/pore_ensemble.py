@@ -62,7 +62,10 @@ class PoreEnsemble:
     ``budget=True``: every live member records its species-budget table after the step's solve (the single-handle call per member:
     the members are ordinary handles), as its serial ``PoreRun`` twin does."""
 
-    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False):
+    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False, step_fraction=0.0):
+        """``step_fraction`` other than 0 is refused (ValueError, before anything touches the device): 3D ensembles have no step limiter."""
+        if step_fraction:
+            raise ValueError("step_fraction: the step limiter is not available in a 3D ensemble")
         self.kwargs, steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []

@@ -23,6 +23,7 @@ from datetime import datetime
 
 import numpy as np
 
+from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .model import Model
 from .params import _load_yaml, _reaction_tables, utilities_dir
@@ -132,16 +133,18 @@ def rxn_diff_parameters(concentration_KHCO3=0.1, H2_FE=0.2, L_n=50.0e-6, mesh_st
 class RxnDiffRun:
     """State of one run; ``step()`` is one pass of the reference's time loop body (1D/rxn_diff_planar.py:320-360)."""
 
-    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, **kwargs):
-        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py)."""
+    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, **kwargs):
+        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
+        ``step_fraction``: tau of the step limiter of the Newton update (``newton_solver["step_fraction"]``), 0 = off."""
         self.kwargs = kwargs
+        self.step_fraction = float(step_fraction)
         self.rp = rxn_diff_parameters(**kwargs)
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), self.rp.mesh_name))
         # Dirichlet: every field at x = 1 (bulk = 1, p = 0), p = 0 at x = 0; point fluxes at the x = 0 vertex (the
         # reference's ``ds`` also covers x = 1, where the Dirichlet rows replace the equations)
         self.problem = edl_problem(self.rp, self.mesh)
         self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
-        self.solver_parameters = solver_parameters or SOLVER_PARAMETERS
+        self.solver_parameters = backend.with_step_fraction(solver_parameters or SOLVER_PARAMETERS, self.step_fraction)
         self.tot_num_steps = self.rp.num_steps if num_steps is None else int(num_steps)
         nv = self.mesh.num_vertices
         self.sys.initialise([1.0] * 6 + [0.0])
@@ -201,6 +204,8 @@ class RxnDiffRun:
                 "pH_overpotential": -0.059 * (rp.bulk_pH - pH_OHP) * 1.0e+3,
                 "CO2_overpotential": (0.059 / 2) * math.log10(rp.initial_conc["CO2"] / CO2_surf) * 1.0e+3,
                 "CO2_OHP_frac": CO2_surf / rp.initial_conc["CO2"], "num_steps_run": int(self.n)}
+        if self.step_fraction:
+            meta["step_fraction"] = self.step_fraction
         if self.budget is not None:
             meta.update(self.budget.save(newpath))
         with open(os.path.join(newpath, "metadata.json"), "w") as fh:
@@ -209,9 +214,9 @@ class RxnDiffRun:
 
 
 def solve_rxn_diff(concentration_KHCO3=0.1, H2_FE=0.2, L_n=50.0e-6, mesh_structure="variable", current_OHP_ss=10.0,
-                   cation="K", params_file="parameters", num_steps=None, verbose=True, budget=False):
+                   cation="K", params_file="parameters", num_steps=None, verbose=True, budget=False, step_fraction=0.0):
     """Same keyword surface as the reference's ``solve_rxn_diff``; returns the output directory."""
-    run = RxnDiffRun(num_steps=num_steps, budget=budget, concentration_KHCO3=concentration_KHCO3, H2_FE=H2_FE, L_n=L_n,
+    run = RxnDiffRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, concentration_KHCO3=concentration_KHCO3, H2_FE=H2_FE, L_n=L_n,
                      mesh_structure=mesh_structure, current_OHP_ss=current_OHP_ss, cation=cation, params_file=params_file)
     try:
         run.run(verbose=verbose)
@@ -237,10 +242,11 @@ def build_parser():
     p.add_argument("--cation", required=False, default="K", type=str, help="str, K/Li/Na/Cs (keyword of solve_rxn_diff)")
     p.add_argument("--num_steps", required=False, default=None, type=int, help="int, time steps to run (default: all 500)")
     p.add_argument("--budget", action="store_true", help="record the species budgets and consistent boundary fluxes of every step (budget.npz)")
+    p.add_argument("--step_fraction", required=False, default=0.0, type=float, help="(addition) fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off")
     return p
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     return solve_rxn_diff(concentration_KHCO3=a.concentration_KHCO3, H2_FE=a.H2_FE, L_n=a.L_n, mesh_structure=a.mesh_structure,
-                          current_OHP_ss=a.current_OHP_ss, cation=a.cation, params_file=a.params_file, num_steps=a.num_steps, budget=a.budget)
+                          current_OHP_ss=a.current_OHP_ss, cation=a.cation, params_file=a.params_file, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction)

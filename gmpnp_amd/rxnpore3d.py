@@ -21,6 +21,7 @@ from datetime import datetime
 
 import numpy as np
 
+from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
@@ -53,14 +54,16 @@ def rxn_pore_parameters(**kwargs):
 class RxnPoreRun:
     """State of one run; ``step()`` is one pass of the reference's time loop body (:523-598)."""
 
-    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, **kwargs):
-        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py)."""
+    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, **kwargs):
+        """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
+        ``step_fraction``: tau of the step limiter of the Newton update (``newton_solver["step_fraction"]``), 0 = off."""
         self.kwargs = kwargs
+        self.step_fraction = float(step_fraction)
         self.pp = rxn_pore_parameters(**kwargs)
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), self.pp.mesh_name))
         self.problem, self.bnd = pore_problem(self.pp, self.mesh)
         self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
-        self.solver_parameters = solver_parameters or SOLVER_PARAMETERS  # :531-538 = the MPNP pore script's dict
+        self.solver_parameters = backend.with_step_fraction(solver_parameters or SOLVER_PARAMETERS, self.step_fraction)  # :531-538 = the MPNP pore script's dict
         self.tot_num_steps = self.pp.tot_num_steps if num_steps is None else int(num_steps)
         nv = self.mesh.num_vertices
         self.sys.initialise([1.0] * 8 + [0.0])
@@ -142,6 +145,8 @@ class RxnPoreRun:
                 # additions of this backend (new keys only)
                 "newton_iterations": int(sum(self.newton_its)), "krylov_iterations": int(self.sys.krylov_iterations),
                 "num_steps_run": int(self.n)}
+        if self.step_fraction:
+            meta["step_fraction"] = self.step_fraction
         if self.budget is not None:
             meta.update(self.budget.save(newpath))
         with open(newpath + "metadata.json", "w") as fh:
@@ -152,9 +157,9 @@ class RxnPoreRun:
 def solveEDL(concentration_elec=1.0, H2_FE=0.05, current_rough=3000.0, L=100.0e-9, cation="K", R=5.0e-9, press_gas=1.0,
              pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5, constrictivity_eff=0.9,
              params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0, roughness_factor=150.0,
-             num_steps=None, verbose=True, budget=False):
+             num_steps=None, verbose=True, budget=False, step_fraction=0.0):
     """Same keyword surface as the reference's ``solveEDL`` (:95-110); returns the output directory."""
-    run = RxnPoreRun(num_steps=num_steps, budget=budget, concentration_elec=concentration_elec, H2_FE=H2_FE, current_rough=current_rough,
+    run = RxnPoreRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, concentration_elec=concentration_elec, H2_FE=H2_FE, current_rough=current_rough,
                      L=L, cation=cation, R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier,
                      porosity_eff=porosity_eff, tortuosity_eff=tortuosity_eff, constrictivity_eff=constrictivity_eff,
                      params_file=params_file, y_CO2=y_CO2, electrolyte_flow_geom_multiplier=electrolyte_flow_geom_multiplier,
@@ -183,4 +188,4 @@ def main(argv=None):
                     R=a.R, press_gas=a.press_gas, pore_geom_multiplier=a.pore_geom_multiplier, porosity_eff=a.porosity_eff,
                     tortuosity_eff=a.tortuosity_eff, constrictivity_eff=a.constrictivity_eff, params_file=a.params_file,
                     y_CO2=a.y_CO2, electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
-                    roughness_factor=a.roughness_factor, num_steps=a.num_steps, budget=a.budget)
+                    roughness_factor=a.roughness_factor, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction)

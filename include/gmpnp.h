@@ -118,7 +118,23 @@ typedef struct {
   double krylov_relative_tolerance; /* on ||b - A x|| / ||b||; 1e-10 ~ "exact-equivalent" */
   double krylov_absolute_tolerance;
   int32_t krylov_maximum_iterations;
+  double step_fraction;         /* tau of the fraction-to-boundary step limiter (below); 0 = off (plain damped Newton, bit for bit),
+                                   else in (0, 1); anything else is GMPNP_ERR_INVALID.  No reference counterpart */
 } gmpnp_newton_options_t;
+
+/* Fraction-to-boundary step limiter (step_fraction = tau != 0; no reference counterpart: DOLFIN's NewtonSolver has none).  The
+ * steric quotient u_i / (1 - S), S = sum_j a_j u_j, needs S < 1; an undamped correction can throw the iterate across S = 1, from
+ * where Newton does not return (1 um mesh, Cs+, voltage_multiplier -10: the first solve diverges; a backtracking line search on
+ * ||b|| stalls instead, because the residual has to rise first).  With dx the solution of J dx = b at the state u:
+ *     S_I = sum_j a_j u_{I,j}     dS_I = sum_j a_j dx_{I,j}         (a = gmpnp_model_t.a, j ascending, plain fp64 sums)
+ *     lambda = min over the VERTICES I with dS_I < 0 and S_I < 1 of (1 - S_I) / (-dS_I)      (+inf if there is none)
+ *     alpha  = tau lambda if lambda < 1, else 1                     u <- u - relaxation_parameter alpha dx
+ * S is P1, so admissible vertices give admissible quadrature points.  All rows take part, Dirichlet rows included; a vertex that
+ * is inadmissible already (S_I >= 1) is skipped (no step length repairs it; steric_excursion reports it); model.steric = 0 (PNP)
+ * evaluates the same rule with the model's a.  A NaN / Inf in dx ends the solve with GMPNP_ERR_NUMERIC and the update is not
+ * applied.  Every linear solve of a limited Newton solve starts from zero: the predicted start of gmpnp_options_t.warm_start assumes
+ * a constant step length.  Served by gmpnp_newton_solve (all linear solvers) and by 1D ensembles (per member: its own alpha,
+ * statistics and failure); 3D ensembles and gmpnp_group_newton_solve refuse a non-zero step_fraction (GMPNP_ERR_INVALID). */
 
 typedef struct {
   int32_t iterations;           /* Newton iterations performed ([3P] "Newton iteration k") */
@@ -133,6 +149,9 @@ typedef struct {
   int32_t steric_excursion;     /* 1 = some residual evaluation of this solve met 1 - sum_j a_j u_j <= 0 at a quadrature point
                                    (an iterate outside the admissible set).  UFL/FFC evaluate the quotient u_i/(1 - S) as it
                                    stands (3D:534-750, 1D:457-593), so by default this is information, not an error */
+  int32_t limited_steps;        /* iterations whose update the step limiter shortened (alpha < 1); 0 with step_fraction = 0 */
+  double min_step;              /* smallest alpha of the solve; 1.0 if never limited */
+  double step_factor[GMPNP_MAX_NEWTON_HISTORY]; /* alpha of every iteration (step_fraction != 0; zeros otherwise) */
 } gmpnp_newton_stats_t;
 
 typedef struct {
@@ -217,6 +236,12 @@ int gmpnp_assign_previous(gmpnp_solver* s);
 int gmpnp_newton_solve(gmpnp_solver* s, const gmpnp_newton_options_t* opts, gmpnp_newton_stats_t* stats);
 
 /* ---- lower-level hooks for parity tests and benchmarks ([3P] assemble / DirichletBC.apply / KSP) ---- */
+/* The step limiter's rule (gmpnp_newton_options_t.step_fraction) evaluated on the device at the handle's current u for a
+ * correction dx given in FILE order (n_dofs), with the kernels the Newton loop runs: *alpha, *lambda (+inf: no limiting vertex)
+ * and *node = the limiting vertex in mesh-FILE numbering (-1 = none; equal ratios: the first in the handle's internal order).
+ * tau in (0, 1).  Changes nothing: u, u_n, the Jacobian and the solver's vectors stay as they were.  A NaN / Inf in dx returns
+ * GMPNP_ERR_NUMERIC.  Outputs may be NULL. */
+int gmpnp_step_limit(gmpnp_solver* s, const double* dx, double tau, double* alpha, double* lambda, int64_t* node);
 int32_t gmpnp_n_fields(const gmpnp_solver* s);
 int64_t gmpnp_n_dofs(const gmpnp_solver* s);
 int64_t gmpnp_n_blocks(const gmpnp_solver* s);   /* node blocks of the BSR Jacobian */
@@ -451,7 +476,8 @@ int gmpnp_ensemble_get_state(gmpnp_ensemble* e, double* u_out);
  * half-iterations (coarse workgroups inside the tile launch), 14/15 = the tile kernels of the materialised vector form,
  * 16/17 = its streaming vector updates, 18 = one whole 1D direct solve (block cyclic reduction: extraction, every level down
  * and up; needs an assembled Jacobian), 19 = element kernel without J (with 3: one residual evaluation), 20 = the launch chain of one
- * gmpnp_species_budget call (element kernel without J, cell pass, row pass, final sums). */
+ * gmpnp_species_budget call (element kernel without J, cell pass, row pass, final sums), 21 = the two launches of the step limiter
+ * (k_step_limit + k_limited_update, on a zero correction: the state stays). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
