@@ -7,6 +7,7 @@ vertex order (dof = vertex * n_fields + field).
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 from ctypes import POINTER, byref, c_double, c_int32, c_int64, c_void_p
 
@@ -37,6 +38,7 @@ EXPORTS = [
     "gmpnp_ensemble_member_error", "gmpnp_ensemble_assign_previous", "gmpnp_ensemble_get_state",
     "gmpnp_species_budget", "gmpnp_group_species_budget",
     "gmpnp_step_limit",
+    "gmpnp_set_time_step", "gmpnp_time_error", "gmpnp_time_accept", "gmpnp_time_reject",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -68,6 +70,17 @@ class CNewtonStats(ctypes.Structure):
                 ("ms_assemble", c_double), ("ms_setup", c_double), ("ms_krylov", c_double), ("ms_total", c_double),
                 ("direct_solves", c_int32), ("steric_excursion", c_int32),
                 ("limited_steps", c_int32), ("min_step", c_double), ("step_factor", c_double * MAX_HISTORY)]
+
+
+class CTimeTol(ctypes.Structure):
+    """gmpnp_time_tol_t: rtol and one atol per field of the step-size controller's weights."""
+    _fields_ = [("rtol", c_double), ("atol", c_double * 9)]
+
+
+class CTimeError(ctypes.Structure):
+    """gmpnp_time_error_t (include/gmpnp.h, adaptive time stepping)."""
+    _fields_ = [("err", c_double), ("err_field", c_double * 9), ("rate", c_double), ("rate_field", c_double * 9),
+                ("worst_dof", c_int64), ("has_history", c_int32), ("nonfinite", c_int32)]
 
 
 class CLinearStats(ctypes.Structure):
@@ -154,6 +167,10 @@ def load_library(path: str = None):
                                        c_int32, POINTER(CLinearStats)]
     lib.gmpnp_set_supg.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
     lib.gmpnp_time_kernel.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_double)]
+    lib.gmpnp_set_time_step.argtypes = [c_void_p, c_double]
+    lib.gmpnp_time_error.argtypes = [c_void_p, c_double, c_double, POINTER(CTimeTol), POINTER(CTimeError)]
+    lib.gmpnp_time_accept.argtypes = [c_void_p]
+    lib.gmpnp_time_reject.argtypes = [c_void_p]
     lib.gmpnp_spmv_profile.argtypes = [c_void_p, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]
     lib.gmpnp_event_overhead.argtypes = [c_void_p, c_int32, POINTER(c_double)]
     lib.gmpnp_create_partition.argtypes = [POINTER(CMesh), POINTER(CModel), POINTER(CQuadrature), POINTER(COptions),
@@ -534,7 +551,8 @@ class DeviceSolver:
         stats = dict(self.stats_dict(st), ms_assemble=st.ms_assemble, ms_setup=st.ms_setup, ms_krylov=st.ms_krylov)
         if code == ERR_NOT_CONVERGED and not error_on_nonconvergence:
             return stats
-        self._check(code)
+        if code != OK:
+            raise GmpnpError(code, self.lib.gmpnp_last_error().decode(), stats=stats)
         return stats
 
     @staticmethod
@@ -554,6 +572,25 @@ class DeviceSolver:
         alpha, lam, node = c_double(), c_double(), c_int64()
         self._check(self.lib.gmpnp_step_limit(self._h, _dptr(dx), float(tau), byref(alpha), byref(lam), byref(node)))
         return alpha.value, lam.value, int(node.value)
+
+    def set_time_step(self, inv_dt: float):
+        """model.inv_dt alone, on this handle and every coarse level attached below it (gmpnp_set_time_step); 0 = steady form."""
+        self._check(self.lib.gmpnp_set_time_step(self._h, float(inv_dt)))
+        self.problem.model = dataclasses.replace(self.problem.model, inv_dt=float(inv_dt))   # what a later set_model re-uploads
+
+    def time_error(self, h: float, h_prev: float, rtol: float, atol):
+        """Backward Euler's local error and the rate of change of the step u_n -> u of length h (gmpnp_time_error; h_prev = the
+        accepted step before it, <= 0: none).  ``atol``: a scalar or one value per field.  A dict with err, err_field, rate,
+        rate_field (arrays of nf), worst_dof (file order, -1: none), has_history and nonfinite."""
+        return time_error_call(self.lib.gmpnp_time_error, self._h, self.nf, self._check, h, h_prev, rtol, atol)
+
+    def time_accept(self):
+        """u_nm1 <- u_n, u_n <- u in one launch (gmpnp_time_accept): what an adaptive run calls instead of ``assign_previous``."""
+        self._check(self.lib.gmpnp_time_accept(self._h))
+
+    def time_reject(self):
+        """u <- u_n (gmpnp_time_reject); the history stays."""
+        self._check(self.lib.gmpnp_time_reject(self._h))
 
     def time_kernel(self, kernel: int, launches: int = 50) -> float:
         us = c_double()
@@ -591,6 +628,19 @@ def column_select_call(fn, handle, fields, ranks, check):
     flags = c_int32(0)
     check(fn(handle, f.size, _iptr(f), r.ctypes.data_as(POINTER(c_int64)), _dptr(out), byref(flags)))
     return out, bool(flags.value & 1)
+
+
+def time_error_call(fn, handle, nf, check, h, h_prev, rtol, atol):
+    """One gmpnp_time_error call: the struct as a dict (per-field arrays cut to nf)."""
+    tol = CTimeTol()
+    tol.rtol = float(rtol)
+    a = np.broadcast_to(np.asarray(atol, dtype=np.float64), (nf,))
+    for f in range(nf):
+        tol.atol[f] = float(a[f])
+    e = CTimeError()
+    check(fn(handle, float(h), float(h_prev), byref(tol), byref(e)))
+    return {"err": e.err, "err_field": np.array(e.err_field[:nf]), "rate": e.rate, "rate_field": np.array(e.rate_field[:nf]),
+            "worst_dof": int(e.worst_dof), "has_history": bool(e.has_history), "nonfinite": bool(e.nonfinite)}
 
 
 def species_budget_call(fn, handle, nf, check):

@@ -101,6 +101,20 @@ struct gmpnp_step_limiter {
   ~gmpnp_step_limiter() { if (h_report) (void)hipHostFree(h_report); }
 };
 
+// device side of the adaptive time stepping (gmpnp_time_step.h), allocated by the first call of its family (gmpnp_time_error /
+// _accept / _reject): a handle that never asks for it keeps the buffers and launches it had
+namespace gmpnp { struct TimeReport; }
+struct gmpnp_time_stepper {
+  DevBuf<double> unm1;                          // the accepted state before u_n (internal order)
+  DevBuf<double> part, part_max;                // workgroup partials of the estimator
+  DevBuf<int32_t> part_dof, part_bad;
+  int nblk = 0;
+  bool has_history = false;                     // u_nm1 holds an accepted state (gmpnp_time_accept since create / set_state / assign_previous)
+  TimeReport* h_report = nullptr;               // pinned: what k_time_reduce writes
+  TimeReport* d_report = nullptr;               // ... its device address
+  ~gmpnp_time_stepper() { if (h_report) (void)hipHostFree(h_report); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -172,6 +186,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_selector> selector;
   std::unique_ptr<gmpnp_budgeter> budgeter;
   std::unique_ptr<gmpnp_step_limiter> limiter;
+  std::unique_ptr<gmpnp_time_stepper> stepper;
   // geometric multilevel term (gmpnp_attach_coarse_level, gmpnp_multilevel.h): the link to the next-coarser level (tables in the
   // internal orders of both handles) and this handle's buffers when it serves as a coarse level itself
   gmpnp_solver* ml_coarse = nullptr; double ml_theta = 1.0; bool ml_is_coarse = false;
@@ -325,6 +340,9 @@ int launch_jac_gather(gmpnp_solver* s) {
 
 int drain_spmv_events(gmpnp_solver* s);
 int budget_launch_any(gmpnp_solver* s);   // gmpnp_budget.h: the launch chain of one species-budget call
+int time_launch_any(gmpnp_solver* s);     // gmpnp_time_step.h: estimator + reduce + shift, between the bracket that keeps u_n and u_nm1
+int time_kernel_begin(gmpnp_solver* s, DevBuf<double>& keep);
+int time_kernel_end(gmpnp_solver* s, DevBuf<double>& keep);
 
 // sum of row `row` (0 .. 2) of the pinned partials the reduction kernels store (k_res_gather, k_true_residual: row 0; k_dots3: three)
 double sum_partials(const gmpnp_solver* s, int row) {
@@ -1518,6 +1536,7 @@ int gmpnp_set_state(gmpnp_solver* s, const double* u, const double* u_n) {
   if (u) { int rc = upload_vec(s, u, s->u.p); if (rc) return rc; s->state_jumped = true; }
   if (u_n) { int rc = upload_vec(s, u_n, s->un.p); if (rc) return rc; }
   s->jacobian_valid = false;
+  if (u_n && s->stepper) s->stepper->has_history = false;   // adaptive time stepping: u_nm1 no longer precedes u_n
   return GMPNP_OK;
 }
 
@@ -1534,6 +1553,7 @@ int gmpnp_assign_previous(gmpnp_solver* s) {
   HIP_TRY(hipSetDevice(s->opts.device_id));
   // stream-ordered: whatever reads u_n next is launched behind this copy, and every read-back synchronises the stream
   HIP_TRY(hipMemcpyAsync(s->un.p, s->u.p, s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+  if (s->stepper) s->stepper->has_history = false;   // adaptive time stepping: u_nm1 was not shifted (gmpnp_time_accept does both)
   return GMPNP_OK;
 }
 
@@ -1750,6 +1770,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 20: r = budget_launch_any(s); break;   // element pass without J, cell pass, row pass, final sums
       case 21:   // the step limiter's two launches on a zero correction (alpha = 1, u -= 0: the state stays)
         GMPNP_DISPATCH(s, r = (step_launch<NF>(s, s->limiter->dx.p, s->limiter->dx.p, 1.0, 0.9, nullptr))); break;
+      case 22: r = time_launch_any(s); break;   // k_time_error + k_time_reduce + k_time_shift
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -1763,13 +1784,23 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
     rc = step_prepare(s); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(s->limiter->dx.p, 0, (size_t)s->ndof * sizeof(double), s->stream));
   }
-  rc = one(); if (rc) return rc;  // warm
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipEventRecord(a, s->stream));
-  for (int i = 0; i < launches && rc == GMPNP_OK; ++i) rc = one();
-  HIP_TRY(hipEventRecord(b, s->stream));
-  HIP_TRY(hipEventSynchronize(b));
-  float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, a, b));
+  DevBuf<double> keep;   // kernel 22 shifts u into u_n: u_n and u_nm1 are put back behind the launches
+  if (kernel == 22) { rc = time_kernel_begin(s, keep); if (rc) return rc; }
+  // kernel 22: whatever happens between the bracket's two halves, u_n and u_nm1 are put back (g_err keeps the first message)
+  auto restore = [&](int code) { if (kernel != 22) return code; const std::string msg = g_err; const int rc2 = time_kernel_end(s, keep);
+                                 if (code) { g_err = msg; return code; } return rc2; };
+  rc = one(); if (rc) return restore(rc);  // warm
+  float ms = 0.f;
+  auto timed = [&]() -> int {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipEventRecord(a, s->stream));
+    for (int i = 0; i < launches && rc == GMPNP_OK; ++i) rc = one();
+    HIP_TRY(hipEventRecord(b, s->stream));
+    HIP_TRY(hipEventSynchronize(b));
+    HIP_TRY(hipEventElapsedTime(&ms, a, b));
+    return rc;
+  };
+  rc = restore(timed());
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   if (rc) return rc;
   *avg_us = 1000.0 * ms / launches;
@@ -1853,3 +1884,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_ensemble.h"
 #include "gmpnp_stats.h"
 #include "gmpnp_budget.h"
+#include "gmpnp_time_step.h"

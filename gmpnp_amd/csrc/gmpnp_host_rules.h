@@ -93,6 +93,64 @@ inline void record_step(gmpnp_newton_stats_t& st, int it, double alpha) {
 }
 inline gmpnp_newton_stats_t fresh_newton_stats() { gmpnp_newton_stats_t st{}; st.min_step = 1.0; return st; }
 
+// ---- adaptive time stepping (include/gmpnp.h "adaptive time stepping"; kernels: gmpnp_time_step.h) ---------------------------------
+// gmpnp_set_time_step's argument: finite and >= 0 (0 = the steady form, no time term)
+inline bool time_step_valid(double inv_dt) { return inv_dt >= 0.0 && !std::isinf(inv_dt); }
+
+// The accept / reject rule of one attempted step h at time t.  The exponent of the step factor is 1/2 because backward Euler's
+// LOCAL error is O(h^2): err(h') = err(h) (h'/h)^2 = 1 at h' = h err^(-1/2), times the safety factor.
+struct TimeStepPolicy {
+  double safety = 0.9, min_factor = 0.2, max_factor = 4.0, fail_factor = 0.25;
+  double h_min = 0.0, h_max = INFINITY, t_end = INFINITY;
+  double steady_tol = 0.0;   // 0 = no steady stop
+  int steady_steps = 2;      // consecutive accepted steps with rate < steady_tol
+};
+struct TimeStepDecision {
+  enum Reason { accepted = 0, error_too_large = 1, newton_failed = 2, nonfinite = 3 };
+  bool accept = false;
+  int reason = accepted;
+  double t_next = 0.0;       // t + h when accepted (t_end exactly when the step landed on it), else t
+  double h_next = 0.0;       // the step to try next
+  bool stop_end = false;     // accepted and t_next == t_end
+  bool stop_steady = false;  // accepted and the steady counter reached steady_steps
+  bool give_up = false;      // h_next < h_min (and not the last step, cut to land on t_end): the run ends
+  int steady_run = 0;        // the counter after this attempt (the caller passes it back in)
+};
+// err / has_history / rate: gmpnp_time_error_t; newton_failed: the solve of the step did not converge or its state is not finite
+// (a NaN err counts as such); steady_run: the counter the previous decision returned (0 at the start).
+inline TimeStepDecision next_time_step(const TimeStepPolicy& p, double t, double h, double err, bool has_history, bool newton_failed,
+                                       double rate, int steady_run) {
+  TimeStepDecision d;
+  const bool nan_err = !(err == err);
+  auto clampd = [](double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); };
+  auto factor = [&](double hi) {   // safety err^(-1/2) clamped; err = 0 gives the upper clamp
+    if (!has_history) return 1.0;
+    return err > 0.0 ? clampd(p.safety / std::sqrt(err), p.min_factor, hi) : hi;
+  };
+  if (newton_failed || nan_err) {
+    d.accept = false; d.reason = newton_failed ? TimeStepDecision::newton_failed : TimeStepDecision::nonfinite;
+    d.t_next = t; d.h_next = p.fail_factor * h; d.steady_run = steady_run;
+  } else if (has_history && err > 1.0) {
+    d.accept = false; d.reason = TimeStepDecision::error_too_large;
+    d.t_next = t; d.h_next = h * factor(1.0); d.steady_run = steady_run;
+  } else {
+    d.accept = true; d.reason = TimeStepDecision::accepted;
+    d.t_next = t + h; d.h_next = h * factor(p.max_factor);
+    d.steady_run = (p.steady_tol > 0.0 && rate < p.steady_tol) ? steady_run + 1 : 0;
+    d.stop_steady = p.steady_tol > 0.0 && d.steady_run >= p.steady_steps;
+  }
+  if (d.h_next > p.h_max) d.h_next = p.h_max;
+  // land on t_end exactly: shorten the step, or stretch it by at most 1 % instead of leaving a sliver behind it
+  bool lands = false;   // the next step is the last one, cut (or stretched) to end on t_end: h_min does not judge it
+  if (std::isfinite(p.t_end)) {
+    const double left = p.t_end - d.t_next;
+    if (d.accept && !(left > 1e-12 * std::fabs(p.t_end))) { d.t_next = p.t_end; d.stop_end = true; }
+    else if (left <= 1.01 * d.h_next) { lands = d.h_next >= p.h_min; d.h_next = left; }
+  }
+  if (!d.stop_end && !d.stop_steady && !lands && d.h_next < p.h_min) d.give_up = true;
+  return d;
+}
+
 // Predicted start x0 = a dx_k + b dx_{k-1} of the linear solve of Newton iteration `iteration` (0-based), q = 1 - omega: with the
 // damped update consecutive corrections satisfy dx_{k+1} = q dx_k + O(|dx_k|^2), so x0 = q dx_k, plus the second-order term
 // observed one iteration earlier, q^2 (dx_k - q dx_{k-1}), from the second iteration on (warm_start 1: first order only).

@@ -6,7 +6,11 @@ non-dry-run mode the form keeps the first time step while ``t`` advances by the 
 ``inv_dt`` is never changed after the first stage; the run then ends with NameError for ``time_step`` as the
 reference does (Q3).  ``--stabilization Y`` (1D:597-722): for MPNP the reference only prints a warning and solves the
 unstabilised form, which is what happens here; for PNP the SUPG terms are added on the device (``gmpnp_set_supg``) with
-the nodal parameters recomputed every step from the previous potential (``solver.supg_parameters``).  Paths: ``$GMPNP_UTILITIES`` / ``$GMPNP_OUT`` (Q10)."""
+the nodal parameters recomputed every step from the previous potential (``solver.supg_parameters``).  Paths: ``$GMPNP_UTILITIES`` / ``$GMPNP_OUT`` (Q10).
+
+``--adaptive_dt`` (not a reference feature): backward Euler with the step chosen by the error controller of gmpnp_amd/timestep.py,
+``inv_dt = 1/(h L_D)``.  The staged schedule and Q2 do not apply in adaptive mode: there is one clock, the controller's, from 0 to
+``--t_end`` (default: the end of the driver's own schedule) or to the steady stop (``--steady_tol``)."""
 from __future__ import annotations
 
 import argparse
@@ -23,6 +27,7 @@ from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import edl_parameters, utilities_dir
 from .problem import edl_problem
 from .solver import GMPNPSystem, supg_parameters
+from .timestep import adaptive_keywords, add_adaptive_arguments
 
 SOLVER_PARAMETERS = {  # reference 1D:357-364
     "nonlinear_solver": "newton",
@@ -42,10 +47,20 @@ def output_root():
 
 
 class EDLRun:
-    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, **kwargs):
+    def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, adaptive_dt=False,
+                 dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0, max_steps=None, **kwargs):
         """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
         ``step_fraction`` = tau in (0, 1): the Newton updates go through the fraction-to-boundary step limiter
-        (``newton_solver["step_fraction"]``, include/gmpnp.h; not a reference feature); 0 = off, the reference's plain Newton."""
+        (``newton_solver["step_fraction"]``, include/gmpnp.h; not a reference feature); 0 = off, the reference's plain Newton.
+        ``adaptive_dt`` = True: the step size is the error controller's (gmpnp_amd/timestep.py; all times in the driver's scaled
+        units): ``dt_rtol`` / ``dt_atol`` its weights, ``dt_init`` the first step (default: the reference step), ``dt_min`` /
+        ``dt_max`` its bounds, ``t_end`` the end time (default: the end of the schedule), ``steady_tol`` > 0 the steady stop,
+        ``max_steps`` the largest number of attempted steps.  A rejected step leaves the clock, the history, the budget log and the
+        SUPG parameters as they were.  Not with ``H_OHP``: its multiplicative flux controller is calibrated per fixed step
+        (ValueError, before anything touches the device).  Off: nothing changes."""
+        self.adaptive = bool(adaptive_dt)
+        if self.adaptive and kwargs.get("H_OHP") is not None:
+            raise ValueError("adaptive_dt: the H_OHP flux controller is calibrated per fixed step")
         self.kwargs = kwargs
         self.step_fraction = float(step_fraction)
         self.ep = edl_parameters(**kwargs)
@@ -70,8 +85,51 @@ class EDLRun:
         if budget:
             from .budget import BudgetLog, interval_factors
             self.budget = BudgetLog(list(ep.species[:5]) + ["cat", "p"], *interval_factors(ep.species, ep.diff_coeff, ep.initial_conc, ep.L_n))
+        self.stepper = None
+        if self.adaptive:
+            from .timestep import DriverStepping
+            L_D = ep.L_D
+            self.stepping = DriverStepping(self.sys, self.solver_parameters, lambda h: 1.0 / (h * L_D), ep.dts[0], ep.stage_T[-1],
+                                           dt_rtol=dt_rtol, dt_atol=dt_atol, dt_init=dt_init, dt_min=dt_min, dt_max=dt_max, t_end=t_end,
+                                           steady_tol=steady_tol, max_steps=max_steps)
+            self.stepper, self.times = self.stepping.stepper, self.stepping.times   # times: the actual times of the history rows
+            self._supg_stale = True    # the SUPG parameters follow u_n: recomputed after an accepted step only
+
+    def adaptive_step(self, verbose=True):
+        """One ATTEMPTED step of the adaptive run (``timestep.AdaptiveStepper.attempt``); the glue of ``step`` runs for an accepted
+        step only, with ``time_accept`` in place of ``assign_previous``.  Returns the attempt's log row."""
+        def before_solve(t, h):
+            self.dt = h
+            if self.warn_stab and verbose:
+                print("Warning:stabilization not implemented for MPNP!")
+            if self.supg and self._supg_stale:
+                self.refresh_supg()
+                self._supg_stale = False
+
+        def before_accept(st):
+            if self.budget is not None:   # while u_n is the previous state and inv_dt the step's
+                self.budget.take(self.sys)
+            self.accept_solution(st, self.sys.vertex_values(), verbose)
+            self.newton_its.append(st["iterations"])
+            self.n += 1
+            self._supg_stale = True
+
+        row = self.stepping.attempt(before_solve, before_accept, verbose)
+        self.t = self.stepper.t
+        return row
+
+    def refresh_supg(self):
+        """rho_i from the previous step's potential (u_n), OH's strong residual with grad(u_H)."""
+        ep = self.ep
+        rho, self.h_vertex = supg_parameters(self.mesh.coords, self.mesh.cells, self.model.z, self.history[-1][:, 6],
+                                             self.sys.project_cellwise, self.h_vertex)
+        w = np.arange(6, dtype=np.int32)
+        w[ep.species.index("OH")] = ep.species.index("H")
+        self.sys.dev.set_supg(rho, w)
 
     def step(self, verbose=True):
+        if self.stepper is not None:
+            return self.adaptive_step(verbose)
         self.advance_clock(verbose)
         st = self.sys.solve(self.solver_parameters)
         if self.budget is not None:   # after the Newton solve, before set_model / assign_previous
@@ -99,12 +157,8 @@ class EDLRun:
         self.t += self.dt
         if self.warn_stab and verbose:
             print("Warning:stabilization not implemented for MPNP!")
-        if self.supg:  # rho_i from the previous step's potential (u_n), OH's strong residual with grad(u_H)
-            rho, self.h_vertex = supg_parameters(self.mesh.coords, self.mesh.cells, self.model.z, self.history[-1][:, 6],
-                                                 self.sys.project_cellwise, self.h_vertex)
-            w = np.arange(6, dtype=np.int32)
-            w[ep.species.index("OH")] = ep.species.index("H")
-            self.sys.dev.set_supg(rho, w)
+        if self.supg:
+            self.refresh_supg()
 
     def accept_solution(self, st, vals, verbose=True):
         """Host glue of a step after its Newton solve: the state joins the history and the H_OHP controller (reference
@@ -135,6 +189,9 @@ class EDLRun:
             self.sys.set_model(self.model)
 
     def run(self, verbose=True):
+        if self.stepper is not None:
+            self.stepping.run(lambda: self.adaptive_step(verbose))
+            return self
         for _ in range(self.n, self.tot_num_steps):
             self.step(verbose)
         return self
@@ -164,7 +221,9 @@ class EDLRun:
         field_values = self.sys.project_gradient(hist[-1][:, 6], sign=-1.0)[:, 0]
         field_values_rescaled = field_values * ep.thermal_voltage / ep.L_n
         field_OHP = field_values_rescaled[0] * 1.0e-9
-        if ep.dry_run:
+        if self.stepper is not None:
+            tau_array = np.array(self.times)   # the actual times of the history rows
+        elif ep.dry_run:
             tau_array = np.linspace(0, ep.stage_T[0], self.tot_num_steps)
         else:
             tau_array = np.concatenate((np.linspace(0, ep.stage_T[0], ep.stage_steps[0]),
@@ -207,6 +266,8 @@ class EDLRun:
             metadata_dict["step_fraction"] = self.step_fraction
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
+        if self.stepper is not None:
+            self.stepping.save(newpath, metadata_dict)
         with open(newpath + "/metadata.json", "w") as fh:
             fh.write(json.dumps(metadata_dict, indent=0))
         return newpath
@@ -220,9 +281,10 @@ def run_identifier(ep, kwargs):
 
 def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=-1.0, H2_FE=0.2, mesh_structure="variable",
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
-              dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0):
-    """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory."""
-    run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, concentration_elec=concentration_elec, model=model,
+              dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, **adaptive):
+    """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
+    adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps)."""
+    run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
                  params_file=params_file, dry_run=dry_run)
@@ -251,6 +313,7 @@ def build_parser():
     p.add_argument("--num_steps", required=False, default=None, type=int, help="(addition) run only the first N steps")
     p.add_argument("--budget", action="store_true", help="(addition) record the species budgets and consistent boundary fluxes of every step (budget.npz)")
     p.add_argument("--step_fraction", required=False, default=0.0, type=float, help="(addition) fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off")
+    add_adaptive_arguments(p)
     return p
 
 
@@ -259,7 +322,7 @@ def main(argv=None):
     return solve_EDL(concentration_elec=a.concentration_elec, model=a.model, voltage_multiplier=a.voltage_multiplier,
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
-                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction)
+                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a))
 
 
 if __name__ == "__main__":

@@ -87,6 +87,8 @@ class EDLEnsemble:
     ``step_fraction``: tau of the step limiter, for all members (each gets its own step length; 0 = off), as ``EDLRun`` takes it."""
 
     def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False, step_fraction=0.0):
+        if any(dict(m).get("adaptive_dt") for m in members):   # before anything touches the device
+            raise ValueError("adaptive_dt: an ensemble marches all its members with one fixed step; adaptive time stepping is a single run's")
         self.kwargs, self.eps, self.tot_num_steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []

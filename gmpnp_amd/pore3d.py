@@ -20,6 +20,7 @@ from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .problem import pore_dirichlet, pore_problem
 from .solver import GMPNPSystem, column_medians, device_medians_and_minima
+from .timestep import DriverStepping, adaptive_keywords, add_adaptive_arguments
 from .vtk import write_pvd
 
 SOLVER_PARAMETERS = {  # reference 3D:789-798
@@ -45,7 +46,9 @@ class PoreRun:
     """State of one pore simulation; ``step()`` is one pass of the reference's time loop body (3D:783-858)."""
 
     def __init__(self, num_steps=None, as_published=False, device_kwargs=None, solver_parameters=None, refine=0,
-                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", budget=False, step_fraction=0.0, **kwargs):
+                 partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", budget=False, step_fraction=0.0,
+                 adaptive_dt=False, dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0,
+                 max_steps=None, **kwargs):
         """``partition`` = (nparts, rank): solve this ONE problem across `nparts` mesh partitions (rank None: all of them in
         this process on one GPU; rank r: this process is rank r of a ``torch.distributed`` job, RCCL inside the library).
         ``multilevel`` (with ``refine`` > 0): the preconditioner gets the geometric multilevel term over the nested meshes
@@ -61,9 +64,18 @@ class PoreRun:
         the library, no gather of the state) and ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).  Off: nothing changes.
         ``step_fraction`` = tau in (0, 1): the Newton updates go through the fraction-to-boundary step limiter
         (``newton_solver["step_fraction"]``, include/gmpnp.h; not a reference feature); 0 = off.  Not with ``partition``: the
-        partitioned solve has no limiter (ValueError, before anything touches the device)."""
+        partitioned solve has no limiter (ValueError, before anything touches the device).
+        ``adaptive_dt`` = True: the step size is the error controller's (gmpnp_amd/timestep.py; not a reference feature), ``inv_dt`` =
+        1/h in the driver's scaled time: ``dt_rtol`` / ``dt_atol`` its weights, ``dt_init`` the first step (default: the reference
+        step), ``dt_min`` / ``dt_max`` its bounds, ``t_end`` the end time (default: the driver's T), ``steady_tol`` > 0 the steady
+        stop, ``max_steps`` the largest number of attempted steps.  A rejected step leaves the clock, the history, the budget log and
+        the CO2 Dirichlet value as they were.  Not with ``partition`` (ValueError, before anything touches the device).  Off: nothing
+        changes."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
+        self.adaptive = bool(adaptive_dt)
+        if self.adaptive and partition:
+            raise ValueError("adaptive_dt: adaptive time stepping is not available in a partitioned solve")
         self.step_fraction = float(step_fraction)
         if self.step_fraction and partition:
             raise ValueError("step_fraction: the step limiter is not available in a partitioned solve")
@@ -108,11 +120,39 @@ class PoreRun:
         if budget:
             from .budget import BudgetLog, pore_factors
             self.budget = BudgetLog(list(self.pp.species[:7]) + ["cat", "p"], *pore_factors(self.pp))
+        self.stepper = None
+        if self.adaptive:
+            self.stepping = DriverStepping(self.sys, self.solver_parameters, lambda h: 1.0 / h, self.pp.dt, self.pp.T, dt_rtol=dt_rtol,
+                                           dt_atol=dt_atol, dt_init=dt_init, dt_min=dt_min, dt_max=dt_max, t_end=t_end, steady_tol=steady_tol,
+                                           max_steps=max_steps)
+            self.stepper, self.times = self.stepping.stepper, self.stepping.times   # times: the actual times of the history rows
+
+    def adaptive_step(self, verbose=True):
+        """One ATTEMPTED step of the adaptive run (``timestep.AdaptiveStepper.attempt``): the glue of ``step`` runs for an accepted
+        step only, with ``time_accept`` in place of ``assign_previous``.  Returns the attempt's log row."""
+        device = self.glue == "device"
+
+        def before_accept(st):
+            if self.budget is not None:   # while u_n is the previous state and inv_dt the step's
+                self.budget.take(self.sys)
+            if device:
+                meds, (co2_min,) = device_medians_and_minima(self.sys, (1, 2, 3, 7), (4,))
+                row = [v for _, v in self.sys.owned_vertex_values()]
+            else:
+                row = self.sys.vertex_values()
+                meds, co2_min = column_medians(row, (1, 2, 3, 7)), float(np.amin(row[:, 4]))
+            self.accept_solution(st, row, meds, co2_min, verbose=verbose, assign=False)
+
+        row = self.stepping.attempt(None, before_accept, verbose)
+        self.t = self.stepper.t
+        return row
 
     def step(self, verbose=True):
         """One time step.  The glue decides where the medians and the CO2 minimum come from and what a history row is; the two
         settings give the same values.  (The row and the minimum are taken in front of ``set_bcs`` under both: the device glue reads
         them from the device there, the host glue from the array it has gathered already, where the place makes no difference.)"""
+        if self.stepper is not None:
+            return self.adaptive_step(verbose)
         device = self.glue == "device"
         self.t += self.pp.dt
         st = self.sys.solve(self.solver_parameters)
@@ -165,6 +205,9 @@ class PoreRun:
         return out
 
     def run(self, verbose=True):
+        if self.stepper is not None:
+            self.stepping.run(lambda: self.adaptive_step(verbose))
+            return self
         for _ in range(self.n, self.tot_num_steps):
             self.step(verbose)
         return self
@@ -201,7 +244,7 @@ class PoreRun:
         for i, nme in enumerate(names[:8]):
             grads[nme] = self.sys.project_gradient(last[:, i]).T.ravel()
         field_values = self.sys.project_gradient(last[:, 8], sign=-1.0).T.ravel()
-        tau_array = np.linspace(0, pp.T, self.tot_num_steps)
+        tau_array = np.linspace(0, pp.T, self.tot_num_steps) if self.stepper is None else np.array(self.times)
         np.savez(newpath + "arrays_unscaled.npz", H=H["H"], OH=H["OH"], HCO3=H["HCO3"], CO32=H["CO32"], CO2=H["CO2"],
                  CO=H["CO"], H2=H["H2"], cat=H["cat"], p=H["p"], coor=mesh.coords, tau=tau_array,
                  field_values=field_values, H_grad=grads["H"], OH_grad=grads["OH"], HCO3_grad=grads["HCO3"],
@@ -242,6 +285,8 @@ class PoreRun:
             metadata_dict["step_fraction"] = self.step_fraction
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
+        if self.stepper is not None:
+            self.stepping.save(newpath, metadata_dict)
         with open(newpath + "metadata.json", "w") as fh:
             fh.write(json.dumps(metadata_dict, indent=0))
         return newpath
@@ -251,13 +296,14 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=-1.0, H2_FE=0.05, curren
              cation="K", R=5.0e-9, press_gas=1.0, pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5,
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
-             device_kwargs=None, glue="host", budget=False, step_fraction=0.0):
+             device_kwargs=None, glue="host", budget=False, step_fraction=0.0, **adaptive):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
     geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
-    one rank per process only rank 0 writes and returns the directory; the others return None)."""
+    one rank per process only rank 0 writes and returns the directory; the others return None); ``adaptive``: the adaptive-stepping
+    keywords of ``PoreRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps)."""
     run = PoreRun(num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
-                  device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, concentration_elec=concentration_elec,
+                  device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
                   R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier, porosity_eff=porosity_eff,
                   tortuosity_eff=tortuosity_eff, constrictivity_eff=constrictivity_eff, params_file=params_file,
@@ -294,6 +340,7 @@ def build_parser():
     p.add_argument("--budget", action="store_true", help="record the species budgets and consistent boundary fluxes of every step (budget.npz)")
     p.add_argument("--step_fraction", required=False, default=0.0, type=float,
                    help="fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off (not with --partitions)")
+    add_adaptive_arguments(p)   # (not with --partitions)
     return p
 
 
@@ -319,6 +366,8 @@ def partition_setup(nparts):
 def main(argv=None):
     a = build_parser().parse_args(argv)
     extra, tdist = {}, None
+    if a.partitions and a.adaptive_dt:
+        raise ValueError("--adaptive_dt: adaptive time stepping is not available with --partitions")
     if a.partitions:
         partition, device_kwargs, tdist = partition_setup(a.partitions)
         extra = dict(partition=partition, device_kwargs=device_kwargs, glue="device", verbose=partition[1] in (None, 0))
@@ -330,7 +379,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

@@ -66,6 +66,8 @@ class PoreEnsemble:
         """``step_fraction`` other than 0 is refused (ValueError, before anything touches the device): 3D ensembles have no step limiter."""
         if step_fraction:
             raise ValueError("step_fraction: the step limiter is not available in a 3D ensemble")
+        if any(dict(m).get("adaptive_dt") for m in members):   # before anything touches the device
+            raise ValueError("adaptive_dt: an ensemble marches all its members with one fixed step; adaptive time stepping is a single run's")
         self.kwargs, steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []

@@ -23,7 +23,7 @@ from datetime import datetime
 
 import numpy as np
 
-from . import backend
+from . import backend, timestep
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .model import Model
 from .params import _load_yaml, _reaction_tables, utilities_dir
@@ -135,7 +135,11 @@ class RxnDiffRun:
 
     def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, **kwargs):
         """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
-        ``step_fraction``: tau of the step limiter of the Newton update (``newton_solver["step_fraction"]``), 0 = off."""
+        ``step_fraction``: tau of the step limiter of the Newton update (``newton_solver["step_fraction"]``), 0 = off.
+        ``adaptive_dt`` = True with ``dt_rtol``, ``dt_atol``, ``dt_init``, ``dt_min``, ``dt_max``, ``t_end``, ``steady_tol``, ``max_steps``
+        (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
+        leaves the clock, the history and the budget log as they were.  Off: nothing changes."""
+        adaptive = timestep.pop_adaptive(kwargs)
         self.kwargs = kwargs
         self.step_fraction = float(step_fraction)
         self.rp = rxn_diff_parameters(**kwargs)
@@ -156,8 +160,28 @@ class RxnDiffRun:
             from .budget import BudgetLog, interval_factors
             rp = self.rp
             self.budget = BudgetLog(SOLVED + ["cat", "p"], *interval_factors(rp.species, rp.diff_coeff, rp.initial_conc, rp.L_n))
+        self.stepper = None
+        if adaptive["adaptive_dt"]:
+            self.stepping = timestep.DriverStepping(self.sys, self.solver_parameters, lambda h: 1.0 / h, self.rp.dt, self.rp.T, **adaptive)
+            self.stepper, self.times = self.stepping.stepper, self.stepping.times   # times: the actual times of the history rows
+
+    def adaptive_step(self, verbose=True):
+        """One ATTEMPTED step of the adaptive run: the glue of ``step`` runs for an accepted step only, with ``time_accept`` in place
+        of ``assign_previous``.  Returns the attempt's log row."""
+        def before_accept(st):
+            if self.budget is not None:   # while u_n is the previous state and inv_dt the step's
+                self.budget.take(self.sys)
+            self.history.append(self.sys.vertex_values()[:, :5].copy())
+            self.newton_its.append(st["iterations"])
+            self.n += 1
+
+        row = self.stepping.attempt(None, before_accept, verbose)
+        self.t = self.stepper.t
+        return row
 
     def step(self, verbose=True):
+        if self.stepper is not None:
+            return self.adaptive_step(verbose)
         self.t += self.rp.dt
         st = self.sys.solve(self.solver_parameters)
         if self.budget is not None:   # after the Newton solve, before assign_previous
@@ -171,6 +195,9 @@ class RxnDiffRun:
         return st
 
     def run(self, verbose=True):
+        if self.stepper is not None:
+            self.stepping.run(lambda: self.adaptive_step(verbose))
+            return self
         for _ in range(self.n, self.tot_num_steps):
             self.step(verbose)
         return self
@@ -185,7 +212,7 @@ class RxnDiffRun:
         os.makedirs(newpath, exist_ok=True)
         hist = np.stack(self.history)
         Hh = {nme: hist[:, :, i] for i, nme in enumerate(SOLVED)}
-        tau_array = np.linspace(0, rp.T, self.tot_num_steps)
+        tau_array = np.linspace(0, rp.T, self.tot_num_steps) if self.stepper is None else np.array(self.times)
         np.savez(os.path.join(newpath, "arrays_unscaled.npz"), coor_array=mesh.coords, tau_array=tau_array, **Hh)
         sc = {nme: scale(species=nme, tau=tau_array, C=Hh[nme], initial_conc=rp.initial_conc, diff_coeff=rp.diff_coeff,
                          L_n=rp.L_n) for nme in SOLVED}
@@ -208,15 +235,18 @@ class RxnDiffRun:
             meta["step_fraction"] = self.step_fraction
         if self.budget is not None:
             meta.update(self.budget.save(newpath))
+        if self.stepper is not None:
+            self.stepping.save(newpath, meta)
         with open(os.path.join(newpath, "metadata.json"), "w") as fh:
             fh.write(json.dumps(meta, indent=0))
         return newpath
 
 
 def solve_rxn_diff(concentration_KHCO3=0.1, H2_FE=0.2, L_n=50.0e-6, mesh_structure="variable", current_OHP_ss=10.0,
-                   cation="K", params_file="parameters", num_steps=None, verbose=True, budget=False, step_fraction=0.0):
-    """Same keyword surface as the reference's ``solve_rxn_diff``; returns the output directory."""
-    run = RxnDiffRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, concentration_KHCO3=concentration_KHCO3, H2_FE=H2_FE, L_n=L_n,
+                   cation="K", params_file="parameters", num_steps=None, verbose=True, budget=False, step_fraction=0.0, **adaptive):
+    """Same keyword surface as the reference's ``solve_rxn_diff``; returns the output directory.  ``adaptive``: the adaptive-stepping
+    keywords of ``RxnDiffRun``."""
+    run = RxnDiffRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, concentration_KHCO3=concentration_KHCO3, H2_FE=H2_FE, L_n=L_n,
                      mesh_structure=mesh_structure, current_OHP_ss=current_OHP_ss, cation=cation, params_file=params_file)
     try:
         run.run(verbose=verbose)
@@ -243,10 +273,12 @@ def build_parser():
     p.add_argument("--num_steps", required=False, default=None, type=int, help="int, time steps to run (default: all 500)")
     p.add_argument("--budget", action="store_true", help="record the species budgets and consistent boundary fluxes of every step (budget.npz)")
     p.add_argument("--step_fraction", required=False, default=0.0, type=float, help="(addition) fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off")
+    timestep.add_adaptive_arguments(p)
     return p
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     return solve_rxn_diff(concentration_KHCO3=a.concentration_KHCO3, H2_FE=a.H2_FE, L_n=a.L_n, mesh_structure=a.mesh_structure,
-                          current_OHP_ss=a.current_OHP_ss, cation=a.cation, params_file=a.params_file, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction)
+                          current_OHP_ss=a.current_OHP_ss, cation=a.cation, params_file=a.params_file, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction,
+                          **timestep.adaptive_keywords(a))

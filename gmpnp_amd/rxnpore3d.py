@@ -21,7 +21,7 @@ from datetime import datetime
 
 import numpy as np
 
-from . import backend
+from . import backend, timestep
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
@@ -56,7 +56,11 @@ class RxnPoreRun:
 
     def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, **kwargs):
         """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
-        ``step_fraction``: tau of the step limiter of the Newton update (``newton_solver["step_fraction"]``), 0 = off."""
+        ``step_fraction``: tau of the step limiter of the Newton update (``newton_solver["step_fraction"]``), 0 = off.
+        ``adaptive_dt`` = True with ``dt_rtol``, ``dt_atol``, ``dt_init``, ``dt_min``, ``dt_max``, ``t_end``, ``steady_tol``, ``max_steps``
+        (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
+        leaves the clock, the history, the budget log and the CO2 Dirichlet value as they were.  Off: nothing changes."""
+        adaptive = timestep.pop_adaptive(kwargs)
         self.kwargs = kwargs
         self.step_fraction = float(step_fraction)
         self.pp = rxn_pore_parameters(**kwargs)
@@ -76,11 +80,30 @@ class RxnPoreRun:
         if budget:
             from .budget import BudgetLog, pore_factors
             self.budget = BudgetLog(SOLVED + ["cat", "p"], *pore_factors(self.pp))
+        self.stepper = None
+        if adaptive["adaptive_dt"]:
+            self.stepping = timestep.DriverStepping(self.sys, self.solver_parameters, lambda h: 1.0 / h, self.pp.dt, self.pp.T, **adaptive)
+            self.stepper, self.times = self.stepping.stepper, self.stepping.times   # times: the actual times of the history rows
+
+    def adaptive_step(self, verbose=True):
+        """One ATTEMPTED step of the adaptive run: the glue of ``step`` runs for an accepted step only, with ``time_accept`` in place
+        of ``assign_previous``.  Returns the attempt's log row."""
+        row = self.stepping.attempt(None, lambda st: self.accept_solution(st, verbose, assign=False), verbose)
+        self.t = self.stepper.t
+        return row
 
     def step(self, verbose=True):
-        pp = self.pp
-        self.t += pp.dt
+        if self.stepper is not None:
+            return self.adaptive_step(verbose)
+        self.t += self.pp.dt
         st = self.sys.solve(self.solver_parameters)
+        self.accept_solution(st, verbose)
+        return st
+
+    def accept_solution(self, st, verbose=True, assign=True):
+        """What follows the Newton solve of a step: budget row, Sechenov, new Dirichlet set, history row, ``u_n.assign(u)``
+        (``assign=False``: the caller shifts the states), counters."""
+        pp = self.pp
         if self.budget is not None:   # after the Newton solve, before set_bcs / assign_previous
             self.budget.take(self.sys)
         vals = self.sys.vertex_values()
@@ -93,16 +116,19 @@ class RxnPoreRun:
         self.sys.set_bcs(*pore_dirichlet(pp, self.bnd, co2))  # bc1 rebuilt (:577-580); the potential pins ride along
         self.history.append(vals[:, :7].copy())
         self.CO2_min = float(np.amin(vals[:, 4]))
-        self.sys.assign_previous()
+        if assign:
+            self.sys.assign_previous()
         self.newton_its.append(st["iterations"])
         if verbose:
             print(self.CO2_min)
             print(datetime.now().strftime("%y-%m-%d-%H-%M-%S"))
             print(self.n)
         self.n += 1
-        return st
 
     def run(self, verbose=True):
+        if self.stepper is not None:
+            self.stepping.run(lambda: self.adaptive_step(verbose))
+            return self
         for _ in range(self.n, self.tot_num_steps):
             self.step(verbose)
         return self
@@ -124,7 +150,7 @@ class RxnPoreRun:
         for fname, col in (("CO", 5), ("H2", 6), ("CO2", 4), ("OH", 1), ("H", 0), ("HCO3", 2), ("CO32", 3)):
             write_pvd(os.path.join(newpath, "solution_" + fname + ".pvd"), mesh.coords, mesh.cells, last[:, col], "f_" + fname)
         grads = {nme: self.sys.project_gradient(last[:, i]).T.ravel() for i, nme in enumerate(SOLVED)}
-        tau_array = np.linspace(0, pp.T, self.tot_num_steps)
+        tau_array = np.linspace(0, pp.T, self.tot_num_steps) if self.stepper is None else np.array(self.times)
         np.savez(newpath + "arrays_unscaled.npz", coor=mesh.coords, tau=tau_array, **H,
                  **{nme + "_grad": grads[nme] for nme in SOLVED})
         sc = {nme: scale_conc_time(species=nme, C=H[nme], grad_c=grads[nme], bulk_conc=pp.bulk_conc, tau=tau_array,
@@ -149,6 +175,8 @@ class RxnPoreRun:
             meta["step_fraction"] = self.step_fraction
         if self.budget is not None:
             meta.update(self.budget.save(newpath))
+        if self.stepper is not None:
+            self.stepping.save(newpath, meta)
         with open(newpath + "metadata.json", "w") as fh:
             fh.write(json.dumps(meta, indent=0))
         return newpath
@@ -157,9 +185,10 @@ class RxnPoreRun:
 def solveEDL(concentration_elec=1.0, H2_FE=0.05, current_rough=3000.0, L=100.0e-9, cation="K", R=5.0e-9, press_gas=1.0,
              pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5, constrictivity_eff=0.9,
              params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0, roughness_factor=150.0,
-             num_steps=None, verbose=True, budget=False, step_fraction=0.0):
-    """Same keyword surface as the reference's ``solveEDL`` (:95-110); returns the output directory."""
-    run = RxnPoreRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, concentration_elec=concentration_elec, H2_FE=H2_FE, current_rough=current_rough,
+             num_steps=None, verbose=True, budget=False, step_fraction=0.0, **adaptive):
+    """Same keyword surface as the reference's ``solveEDL`` (:95-110); returns the output directory.  ``adaptive``: the
+    adaptive-stepping keywords of ``RxnPoreRun``."""
+    run = RxnPoreRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec, H2_FE=H2_FE, current_rough=current_rough,
                      L=L, cation=cation, R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier,
                      porosity_eff=porosity_eff, tortuosity_eff=tortuosity_eff, constrictivity_eff=constrictivity_eff,
                      params_file=params_file, y_CO2=y_CO2, electrolyte_flow_geom_multiplier=electrolyte_flow_geom_multiplier,
@@ -188,4 +217,5 @@ def main(argv=None):
                     R=a.R, press_gas=a.press_gas, pore_geom_multiplier=a.pore_geom_multiplier, porosity_eff=a.porosity_eff,
                     tortuosity_eff=a.tortuosity_eff, constrictivity_eff=a.constrictivity_eff, params_file=a.params_file,
                     y_CO2=a.y_CO2, electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
-                    roughness_factor=a.roughness_factor, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction)
+                    roughness_factor=a.roughness_factor, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction,
+                    **timestep.adaptive_keywords(a))

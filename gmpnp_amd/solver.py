@@ -88,6 +88,19 @@ class GMPNPSystem(_System):
         self.problem.model = model
         self.dev.set_model(model)
 
+    # adaptive time stepping (include/gmpnp.h; the loop body lives in timestep.AdaptiveStepper)
+    def set_time_step(self, inv_dt):
+        self.dev.set_time_step(inv_dt)
+
+    def time_error(self, h, h_prev, rtol, atol):
+        return self.dev.time_error(h, h_prev, rtol, atol)
+
+    def time_accept(self):
+        self.dev.time_accept()
+
+    def time_reject(self):
+        self.dev.time_reject()
+
     def owned_vertex_values(self):
         """[(vertex ids, (n, nf) values)] of the rows this process owns: here all of them."""
         return [(np.arange(self.nv), self.vertex_values())]
@@ -121,6 +134,13 @@ class PartitionedSystem(_System):
         self.several_processes = rank is not None and nparts > 1   # reading the whole state is then a collective
         self._device_kwargs = {k: v for k, v in device_kwargs.items() if k in ("device_id",)}
         self._post = None                     # unpartitioned handle on the global mesh, for post-processing only
+
+    # adaptive time stepping is a single handle's: the groups' transports all-reduce sums, and the estimator's maximum and the
+    # per-member step sizes are not built.  Refused here, before anything touches the device.
+    def _no_adaptive(self, *args, **kwargs):
+        raise ValueError("adaptive time stepping is not available on a partitioned system")
+
+    set_time_step = time_error = time_accept = time_reject = _no_adaptive
 
     def owned_vertex_values(self):
         """[(global vertex ids, (n_owned, nf) values)] of this process's partitions: one device-to-host copy each, no collective."""

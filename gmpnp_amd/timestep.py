@@ -1,0 +1,240 @@
+"""Adaptive time stepping with error control and a steady-state stop (not a reference feature: the reference marches with the
+step of its YAML file).  Backward Euler; the step is chosen from the device's estimate of its local error (include/gmpnp.h,
+gmpnp_time_error; kernels: csrc/gmpnp_time_step.h).  ``next_time_step`` is the Python statement of the rule that
+csrc/gmpnp_host_rules.h states in C++ (``next_time_step`` there; tests/test_time_step_reference.py compiles that one with the host
+compiler and holds both against a NumPy restatement of its own).  ``AdaptiveStepper`` owns the loop body of one attempted step."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import backend
+
+REASONS = ("accepted", "error_too_large", "newton_failed", "nonfinite")
+
+
+@dataclass
+class TimeStepPolicy:
+    safety: float = 0.9
+    min_factor: float = 0.2
+    max_factor: float = 4.0
+    fail_factor: float = 0.25
+    h_min: float = 0.0
+    h_max: float = math.inf
+    t_end: float = math.inf
+    steady_tol: float = 0.0    # 0 = no steady stop
+    steady_steps: int = 2      # consecutive accepted steps with rate < steady_tol
+
+
+@dataclass
+class TimeStepDecision:
+    accept: bool
+    reason: int          # index into REASONS
+    t_next: float        # t + h when accepted (t_end exactly when the step landed on it), else t
+    h_next: float        # the step to try next
+    stop_end: bool
+    stop_steady: bool
+    give_up: bool        # h_next < h_min: the run ends
+    steady_run: int      # the steady counter after this attempt (handed back in at the next one)
+
+
+def next_time_step(p: TimeStepPolicy, t, h, err, has_history, newton_failed, rate, steady_run) -> TimeStepDecision:
+    """The accept / reject rule of one attempted step h at time t.  The exponent of the step factor is 1/2 because backward
+    Euler's LOCAL error is O(h^2): err(h') = err(h) (h'/h)^2 = 1 at h' = h err^(-1/2), times the safety factor."""
+    nan_err = err != err
+
+    def factor(hi):
+        if not has_history:
+            return 1.0
+        if err > 0.0:
+            return min(max(p.safety / math.sqrt(err), p.min_factor), hi)
+        return hi
+
+    stop_steady = False
+    if newton_failed or nan_err:
+        accept, reason, t_next, h_next, run = False, (2 if newton_failed else 3), t, p.fail_factor * h, steady_run
+    elif has_history and err > 1.0:
+        accept, reason, t_next, h_next, run = False, 1, t, h * factor(1.0), steady_run
+    else:
+        accept, reason, t_next, h_next = True, 0, t + h, h * factor(p.max_factor)
+        run = steady_run + 1 if (p.steady_tol > 0.0 and rate < p.steady_tol) else 0
+        stop_steady = p.steady_tol > 0.0 and run >= p.steady_steps
+    if h_next > p.h_max:
+        h_next = p.h_max
+    stop_end = lands = False     # lands: the next step is the last one, cut (or stretched) to end on t_end: h_min does not judge it
+    if math.isfinite(p.t_end):   # land on t_end exactly: shorten the step, or stretch it by at most 1 % instead of leaving a sliver
+        left = p.t_end - t_next
+        if accept and not left > 1e-12 * abs(p.t_end):
+            t_next, stop_end = p.t_end, True
+        elif left <= 1.01 * h_next:
+            lands, h_next = h_next >= p.h_min, left
+    give_up = (not stop_end) and (not stop_steady) and (not lands) and h_next < p.h_min
+    return TimeStepDecision(accept, reason, t_next, h_next, stop_end, stop_steady, give_up, run)
+
+
+class AdaptiveStepper:
+    """The loop body of an adaptive run on a ``GMPNPSystem``: set the step, solve, estimate, decide, accept or reject.
+    ``tol`` = (rtol, atol) with atol a scalar or one value per field; ``inv_dt_of_h(h)`` = the model's inv_dt for a step h in the
+    driver's time units (3D: 1/h, 1D: 1/(h L_D), L_D the scaled Debye length).  ``log`` holds one row per attempt."""
+
+    COLUMNS = ("t", "h", "accepted", "reason", "err", "rate", "newton", "krylov", "worst_dof", "steric_excursion")
+
+    def __init__(self, system, policy: TimeStepPolicy, tol, inv_dt_of_h, h_init, t0=0.0, solver_parameters=None):
+        from .solver import PartitionedSystem
+        if isinstance(system, PartitionedSystem):
+            raise ValueError("adaptive time stepping is not available on a partitioned system")
+        self.sys, self.policy, self.inv_dt_of_h = system, policy, inv_dt_of_h
+        self.rtol, self.atol = float(tol[0]), tol[1]
+        self.solver_parameters = solver_parameters
+        self.t, self.h, self.h_prev = float(t0), float(h_init), 0.0
+        self.steady_run = 0
+        self.stop_reason = None   # "t_end", "steady", "h_min"; the drivers add "max_steps"
+        self.log = []
+        self.last_decision = None
+
+    @property
+    def accepted(self):
+        return sum(1 for r in self.log if r["accepted"])
+
+    @property
+    def rejected(self):
+        return sum(1 for r in self.log if not r["accepted"])
+
+    @property
+    def newton_failures(self):
+        return sum(1 for r in self.log if r["reason"] == 2)
+
+    def attempt(self, before_solve=None, before_accept=None):
+        """One attempted step.  ``before_solve(t, h)``: the driver's glue in front of the Newton solve (its clock is the
+        stepper's); ``before_accept(stats)``: the driver's glue of an accepted step, called while u_n is still the previous state
+        (budgets, history row, new Dirichlet values) — a rejected step calls neither it nor anything else of the driver.
+        Returns the log row."""
+        if self.stop_reason is not None:
+            raise RuntimeError("the adaptive run has ended (%s)" % self.stop_reason)
+        t, h = self.t, self.h
+        self.sys.set_time_step(self.inv_dt_of_h(h))
+        if before_solve is not None:
+            before_solve(t, h)
+        st, failed = None, False
+        try:
+            st = self.sys.solve(self.solver_parameters)
+        except backend.GmpnpError as e:
+            if e.code not in (backend.ERR_NUMERIC, backend.ERR_LINEAR):   # (a linear solve that breaks down on an iterate outside
+                raise                                                     # the admissible set is the same failure, found earlier)
+            st, failed = e.stats, True
+        except RuntimeError as e:   # DOLFIN's "Newton solver did not converge"
+            cause = e.__cause__
+            if not (isinstance(cause, backend.GmpnpError) and cause.code == backend.ERR_NOT_CONVERGED):
+                raise
+            st, failed = cause.stats, True
+        if failed and st is not None:   # solve() accounts converged solves only
+            self.sys.record(st)
+        est = None
+        if not failed:
+            est = self.sys.time_error(h, self.h_prev, self.rtol, self.atol)
+        err = est["err"] if est else 0.0
+        rate = est["rate"] if est else math.inf
+        d = next_time_step(self.policy, t, h, err, bool(est and est["has_history"]), failed, rate, self.steady_run)
+        row = {"t": t, "h": h, "accepted": bool(d.accept), "reason": d.reason, "err": err if est else math.nan,
+               "rate": rate if est else math.nan, "newton": st["iterations"] if st else -1,
+               "krylov": st["krylov_iterations"] if st else -1, "worst_dof": est["worst_dof"] if est else -1,
+               "steric_excursion": st["steric_excursion"] if st else -1}
+        if d.accept:
+            if before_accept is not None:
+                before_accept(st)
+            self.sys.time_accept()
+            self.h_prev = h
+        else:
+            self.sys.time_reject()
+        self.t, self.h, self.steady_run = d.t_next, d.h_next, d.steady_run
+        self.log.append(row)
+        self.last_decision = d
+        if d.stop_end:
+            self.stop_reason = "t_end"
+        elif d.stop_steady:
+            self.stop_reason = "steady"
+        elif d.give_up:
+            self.stop_reason = "h_min"
+        return row
+
+    def log_arrays(self):
+        """The log as arrays by column (what ``timestep_log.npz`` holds)."""
+        out = {}
+        for c in self.COLUMNS:
+            kind = np.float64 if c in ("t", "h", "err", "rate") else (np.bool_ if c == "accepted" else np.int64)
+            out[c] = np.array([r[c] for r in self.log], dtype=kind)
+        return out
+
+    def summary(self):
+        """The keys an adaptive run adds to metadata.json."""
+        return {"adaptive_dt": True, "dt_rtol": self.rtol, "dt_atol": np.asarray(self.atol, dtype=float).tolist(),
+                "steps_accepted": self.accepted, "steps_rejected": self.rejected, "newton_failures": self.newton_failures,
+                "t_reached": self.t, "stop_reason": self.stop_reason}
+
+
+# ---- what the four drivers share ----------------------------------------------------------------------------------------------------
+ADAPTIVE_KEYWORDS = dict(adaptive_dt=False, dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0,
+                         max_steps=None)
+
+
+def pop_adaptive(kwargs):
+    """The adaptive-stepping keywords of a run class taken out of its ``**kwargs`` (defaults: ``ADAPTIVE_KEYWORDS``)."""
+    return {k: kwargs.pop(k, d) for k, d in ADAPTIVE_KEYWORDS.items()}
+
+
+def add_adaptive_arguments(p):
+    """The adaptive-stepping flags every driver shares; times in the driver's scaled units."""
+    p.add_argument("--adaptive_dt", action="store_true", help="(addition) adaptive time stepping with error control: the step size is the controller's")
+    p.add_argument("--dt_rtol", required=False, default=1e-2, type=float, help="(addition) relative weight of the controller's error norm")
+    p.add_argument("--dt_atol", required=False, default=1e-4, type=float, help="(addition) absolute weight of the controller's error norm")
+    p.add_argument("--dt_init", required=False, default=None, type=float, help="(addition) first step (default: the reference step)")
+    p.add_argument("--dt_min", required=False, default=0.0, type=float, help="(addition) a smaller step ends the run")
+    p.add_argument("--dt_max", required=False, default=None, type=float, help="(addition) largest step")
+    p.add_argument("--t_end", required=False, default=None, type=float, help="(addition) end time (default: the driver's own T)")
+    p.add_argument("--steady_tol", required=False, default=0.0, type=float, help="(addition) stop when the rate of change stays below it; 0 = off")
+    p.add_argument("--max_steps", required=False, default=None, type=int, help="(addition) largest number of attempted steps")
+
+
+def adaptive_keywords(a):
+    """The parsed adaptive-stepping flags as the keywords of the run classes."""
+    return {k: getattr(a, k) for k in ADAPTIVE_KEYWORDS}
+
+
+class DriverStepping:
+    """The adaptive mode of a driver's run class: the stepper built from the driver's keywords (``h_ref`` = the reference step,
+    ``T`` = the driver's own end time), the actual times of the history rows, the attempt loop and the outputs."""
+
+    def __init__(self, system, solver_parameters, inv_dt_of_h, h_ref, T, dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None,
+                 t_end=None, steady_tol=0.0, max_steps=None, adaptive_dt=True):
+        policy = TimeStepPolicy(h_min=float(dt_min), h_max=math.inf if dt_max is None else float(dt_max),
+                                t_end=float(T) if t_end is None else float(t_end), steady_tol=float(steady_tol))
+        self.stepper = AdaptiveStepper(system, policy, (dt_rtol, dt_atol), inv_dt_of_h, h_ref if dt_init is None else float(dt_init),
+                                       solver_parameters=solver_parameters)
+        self.max_steps = None if max_steps is None else int(max_steps)
+        self.times = [0.0]
+
+    def attempt(self, before_solve, before_accept, verbose=False):
+        """One attempted step; an accepted one adds its time (t_end exactly when the step landed on it).  Returns the log row."""
+        row = self.stepper.attempt(before_solve, before_accept)
+        if row["accepted"]:
+            self.times.append(self.stepper.t)
+        if verbose:
+            print("t = %.6g  h = %.6g  %s  err = %.3g  newton = %d" % (row["t"], row["h"], "accepted" if row["accepted"] else "rejected",
+                                                                     row["err"], row["newton"]))
+        return row
+
+    def run(self, attempt):
+        """``attempt()`` until the run ends: t_end, the steady stop, h_min, or ``max_steps`` attempted steps."""
+        while self.stepper.stop_reason is None:
+            if self.max_steps is not None and len(self.stepper.log) >= self.max_steps:
+                self.stepper.stop_reason = "max_steps"
+                break
+            attempt()
+
+    def save(self, newpath, meta):
+        """timestep_log.npz beside the arrays and the new metadata.json keys."""
+        import os
+        np.savez(os.path.join(newpath, "timestep_log.npz"), **self.stepper.log_arrays())
+        meta.update(self.stepper.summary(), timestep_log="timestep_log.npz")

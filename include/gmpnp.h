@@ -231,6 +231,45 @@ int gmpnp_get_state(gmpnp_solver* s, double* u_out, double* u_n_out);
 /* u_n.assign(u) (3D:856, 1D:796), on device. */
 int gmpnp_assign_previous(gmpnp_solver* s);
 
+/* ---- adaptive time stepping with error control (no reference counterpart: the reference marches with the step of its YAML file) ----
+ * Backward Euler with a step chosen from an estimate of its local error; the accept / reject rule itself is host code
+ * (csrc/gmpnp_host_rules.h, next_time_step; gmpnp_amd/timestep.py drives it).  The handle keeps a third state vector, u_nm1 = the
+ * accepted state before u_n.  Over the FREE dofs (I, f) — a Dirichlet dof's change between steps is boundary data moving, not
+ * truncation error — with h the step just solved and h_prev the accepted step before it (the units of 1 / inv_dt up to a factor
+ * the caller owns: only h / h_prev and the rate's scale depend on them):
+ *     p = u_n + (h / h_prev)(u_n - u_nm1)        d = (u - p) h / (2h + h_prev)        w = atol_f + rtol max(|u|, |u_n|)
+ *     err_f = sqrt(sum_I (d/w)^2 / n_free_f)     rate_f = sqrt(sum_I ((u - u_n)/h)^2 / n_free_f)
+ * (u - p = 1/2 u'' h (2h + h_prev) + O(h^3), so d is backward Euler's local error 1/2 u'' h^2.)  There is no history when no step
+ * was accepted since create / a gmpnp_set_state that wrote u_n / gmpnp_assign_previous, or when h_prev <= 0: has_history = 0 and the err values are
+ * 0; the rates are computed all the same.  A field without a free dof reports 0.  worst_dof: ties go to the smaller index of the
+ * handle's internal order.  A NaN / Inf in u sets nonfinite and makes the err values NaN; the status stays GMPNP_OK (the caller
+ * decides).  Fixed-order reductions, no atomics: two calls on one state return the same bits.  u_nm1 and the estimator's storage
+ * are allocated by the first call of this family; a handle that never calls it keeps the buffers and launches it had.  Partition
+ * handles (gmpnp_create_partition) are refused by all four calls (GMPNP_ERR_INVALID): groups and ensembles have no adaptive
+ * stepping. */
+typedef struct { double rtol; double atol[GMPNP_MAX_SPECIES + 1]; } gmpnp_time_tol_t;
+typedef struct {
+  double err;                                  /* max_f err_field[f]; 0 when there is no history */
+  double err_field[GMPNP_MAX_SPECIES + 1];
+  double rate;                                 /* max_f rate_field[f] */
+  double rate_field[GMPNP_MAX_SPECIES + 1];
+  int64_t worst_dof;                           /* file order (vertex*n_fields+field) of max |d/w|, -1: none */
+  int32_t has_history, nonfinite;
+} gmpnp_time_error_t;
+/* model.inv_dt alone, on the host and the device, of this handle AND of every coarse level attached below it with
+ * gmpnp_attach_coarse_level (gmpnp_set_model leaves those as they are; the time term is the diagonal of the species blocks, so a
+ * stale coarse level costs Krylov iterations).  Invalidates the Jacobian and the preconditioner.  inv_dt finite and >= 0 (0 = the
+ * steady form); NaN, Inf and negative values are GMPNP_ERR_INVALID.  The boundary tables are NOT rebuilt: checked against
+ * rebuild_boundary (gmpnp_api.hip) — wall_flux, exit_kappa, point_flux and the facet areas are all it reads, and the SUPG
+ * parameters (gmpnp_set_supg) are the caller's. */
+int gmpnp_set_time_step(gmpnp_solver* s, double inv_dt);
+int gmpnp_time_error(gmpnp_solver* s, double h, double h_prev, const gmpnp_time_tol_t* tol, gmpnp_time_error_t* out);
+/* u_nm1 <- u_n, u_n <- u in one launch (stream-ordered like gmpnp_assign_previous, which it replaces in an adaptive run: calling
+ * gmpnp_assign_previous afterwards drops the history, has_history = 0, because u_nm1 was not shifted with it). */
+int gmpnp_time_accept(gmpnp_solver* s);
+/* u <- u_n (device copy); the history stays.  The next Newton solve starts from a state set from outside (no coarse reuse). */
+int gmpnp_time_reject(gmpnp_solver* s);
+
 /* solve(F == 0, u, bcs, solver_parameters) (3D:789-799, 1D:737-742): damped Newton on the device state u.
  * Returns GMPNP_ERR_NOT_CONVERGED where DOLFIN raises RuntimeError; stats are filled either way. */
 int gmpnp_newton_solve(gmpnp_solver* s, const gmpnp_newton_options_t* opts, gmpnp_newton_stats_t* stats);
@@ -477,7 +516,8 @@ int gmpnp_ensemble_get_state(gmpnp_ensemble* e, double* u_out);
  * 16/17 = its streaming vector updates, 18 = one whole 1D direct solve (block cyclic reduction: extraction, every level down
  * and up; needs an assembled Jacobian), 19 = element kernel without J (with 3: one residual evaluation), 20 = the launch chain of one
  * gmpnp_species_budget call (element kernel without J, cell pass, row pass, final sums), 21 = the two launches of the step limiter
- * (k_step_limit + k_limited_update, on a zero correction: the state stays). */
+ * (k_step_limit + k_limited_update, on a zero correction: the state stays), 22 = the three launches of an accepted adaptive time step
+ * (estimator + reduce + shift; u_n and u_nm1 are put back afterwards, the history flag stays). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
