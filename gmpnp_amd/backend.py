@@ -36,6 +36,7 @@ EXPORTS = [
     "gmpnp_project_gradient", "gmpnp_project_cellwise", "gmpnp_column_select", "gmpnp_group_column_select",
     "gmpnp_ensemble_create", "gmpnp_ensemble_destroy", "gmpnp_ensemble_size", "gmpnp_ensemble_newton_solve",
     "gmpnp_ensemble_member_error", "gmpnp_ensemble_assign_previous", "gmpnp_ensemble_get_state",
+    "gmpnp_ensemble_set_time_step", "gmpnp_ensemble_time_error", "gmpnp_ensemble_time_advance",
     "gmpnp_species_budget", "gmpnp_group_species_budget",
     "gmpnp_step_limit",
     "gmpnp_set_time_step", "gmpnp_time_error", "gmpnp_time_accept", "gmpnp_time_reject",
@@ -208,6 +209,10 @@ def load_library(path: str = None):
     lib.gmpnp_ensemble_member_error.restype = ctypes.c_char_p
     lib.gmpnp_ensemble_assign_previous.argtypes = [c_void_p]
     lib.gmpnp_ensemble_get_state.argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_ensemble_set_time_step.argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_ensemble_time_error.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(CTimeTol), POINTER(c_int32),
+                                              POINTER(CTimeError)]
+    lib.gmpnp_ensemble_time_advance.argtypes = [c_void_p, POINTER(c_int32)]
     for name in ("gmpnp_species_budget", "gmpnp_group_species_budget"):
         getattr(lib, name).argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -630,17 +635,25 @@ def column_select_call(fn, handle, fields, ranks, check):
     return out, bool(flags.value & 1)
 
 
-def time_error_call(fn, handle, nf, check, h, h_prev, rtol, atol):
-    """One gmpnp_time_error call: the struct as a dict (per-field arrays cut to nf)."""
-    tol = CTimeTol()
+def _fill_time_tol(tol, nf, rtol, atol):
     tol.rtol = float(rtol)
     a = np.broadcast_to(np.asarray(atol, dtype=np.float64), (nf,))
     for f in range(nf):
         tol.atol[f] = float(a[f])
-    e = CTimeError()
-    check(fn(handle, float(h), float(h_prev), byref(tol), byref(e)))
+
+
+def _time_error_dict(e, nf):
     return {"err": e.err, "err_field": np.array(e.err_field[:nf]), "rate": e.rate, "rate_field": np.array(e.rate_field[:nf]),
             "worst_dof": int(e.worst_dof), "has_history": bool(e.has_history), "nonfinite": bool(e.nonfinite)}
+
+
+def time_error_call(fn, handle, nf, check, h, h_prev, rtol, atol):
+    """One gmpnp_time_error call: the struct as a dict (per-field arrays cut to nf)."""
+    tol = CTimeTol()
+    _fill_time_tol(tol, nf, rtol, atol)
+    e = CTimeError()
+    check(fn(handle, float(h), float(h_prev), byref(tol), byref(e)))
+    return _time_error_dict(e, nf)
 
 
 def species_budget_call(fn, handle, nf, check):
@@ -711,3 +724,35 @@ class DeviceEnsemble:
         out = np.empty((len(self.devices), self.ndof))
         self._check(self.lib.gmpnp_ensemble_get_state(self._h, _dptr(out)))
         return out
+
+    # adaptive time stepping, every member on its own clock (include/gmpnp.h; the round lives in timestep.EnsembleStepper)
+    def set_time_step(self, inv_dts):
+        """model.inv_dt of every member (gmpnp_ensemble_set_time_step): one value per member, one synchronisation for all."""
+        x = np.ascontiguousarray(inv_dts, dtype=np.float64).ravel()
+        if x.size != len(self.devices):
+            raise ValueError("one inv_dt per member: %d values for %d members" % (x.size, len(self.devices)))
+        self._check(self.lib.gmpnp_ensemble_set_time_step(self._h, _dptr(x)))
+
+    def time_error(self, h, h_prev, rtol, atol, mask=None):
+        """``DeviceSolver.time_error`` of every member with mask[k] true (None: all) in one launch chain
+        (gmpnp_ensemble_time_error).  ``h``, ``h_prev``, ``rtol`` and ``atol`` hold one entry per member (``atol[k]`` a scalar or
+        one value per field).  Returns the list of the members' dicts; a masked-out member's is all zero."""
+        n, nf = len(self.devices), self.devices[0].nf
+        hh = np.ascontiguousarray(h, dtype=np.float64).ravel()
+        hp = np.ascontiguousarray(h_prev, dtype=np.float64).ravel()
+        if not (hh.size == hp.size == len(rtol) == len(atol) == n) or (mask is not None and len(mask) != n):
+            raise ValueError("h, h_prev, rtol, atol and mask hold one entry per member (%d)" % n)
+        tol = (CTimeTol * n)()
+        for k in range(n):
+            _fill_time_tol(tol[k], nf, rtol[k], atol[k])
+        m = None if mask is None else np.ascontiguousarray([1 if x else 0 for x in mask], dtype=np.int32)
+        out = (CTimeError * n)()
+        self._check(self.lib.gmpnp_ensemble_time_error(self._h, _dptr(hh), _dptr(hp), tol, None if m is None else _iptr(m), out))
+        return [_time_error_dict(out[k], nf) for k in range(n)]
+
+    def time_advance(self, actions):
+        """Per member 0 = leave alone, 1 = ``time_accept``, 2 = ``time_reject``, in one launch (gmpnp_ensemble_time_advance)."""
+        a = np.ascontiguousarray(actions, dtype=np.int32).ravel()
+        if a.size != len(self.devices):
+            raise ValueError("one action per member: %d values for %d members" % (a.size, len(self.devices)))
+        self._check(self.lib.gmpnp_ensemble_time_advance(self._h, _iptr(a)))

@@ -1885,3 +1885,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_stats.h"
 #include "gmpnp_budget.h"
 #include "gmpnp_time_step.h"
+#include "gmpnp_time_step_ens.h"

@@ -214,7 +214,25 @@ __global__ __launch_bounds__(256) void k_axpy_u_ens(const EnsMember* __restrict_
 
 // the active lists of a 3D solve: one device region each (a queued launch keeps reading its own), pinned staging per parity
 constexpr int kEnsLists = 10;
-enum EnsList { L_ACT = 0, L_BATCH, L_COARSE, L_WARM, L_START, L_KRY, L_END, L_AXPY, L_RES };
+enum EnsList { L_ACT = 0, L_BATCH, L_COARSE, L_WARM, L_START, L_KRY, L_END, L_AXPY, L_RES, L_TIME };
+
+// adaptive time stepping of the members (gmpnp_time_step_ens.h), allocated by the first call of that family: an ensemble that
+// never asks keeps the buffers it had
+namespace gmpnp { struct EnsTimeRec; }
+struct gmpnp_ens_time {
+  gmpnp::EnsTimeRec* d_rec = nullptr;     // [kEnsMaxMembers]: per-member arguments of the listed members' launches
+  gmpnp::EnsTimeRec* h_rec = nullptr;     // pinned [2][kEnsMaxMembers]: their staging, alternating
+  gmpnp::TimeReport* h_report = nullptr;  // pinned [kEnsMaxMembers]: what k_time_reduce_ens writes
+  gmpnp::TimeReport* d_report = nullptr;  // ... its device address
+  gmpnp_model_t* h_model = nullptr;       // pinned [n]: staging of gmpnp_ensemble_set_time_step
+  int slot = 0;
+  ~gmpnp_ens_time() {
+    if (d_rec) (void)hipFree(d_rec);
+    if (h_rec) (void)hipHostFree(h_rec);
+    if (h_report) (void)hipHostFree(h_report);
+    if (h_model) (void)hipHostFree(h_model);
+  }
+};
 
 struct gmpnp_ensemble {
   std::vector<gmpnp_solver*> m;   // owned by the caller
@@ -227,8 +245,10 @@ struct gmpnp_ensemble {
   double* h_u = nullptr;        // pinned [n][ndof]
   int act_slot = 0;
   std::vector<std::string> err;   // last failure of each member ("" = none)
+  std::unique_ptr<gmpnp_ens_time> tstep;
   ~gmpnp_ensemble() {
     if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    tstep.reset();
     if (h_tab) (void)hipHostFree(h_tab);
     if (h_act) (void)hipHostFree(h_act);
     if (h_it3) (void)hipHostFree(h_it3);

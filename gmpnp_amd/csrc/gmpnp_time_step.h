@@ -14,7 +14,7 @@
 //   k_time_reduce  ONE workgroup sums the partial rows in workgroup order (two calls give equal bits), takes the maximum (ties: the
 //                  smaller internal dof) and leaves the report in pinned host memory
 //   k_time_shift   the accept as one pass: reads u and u_n, writes u_n and u_nm1
-// The reject is a device copy.  No atomics on data.  u_nm1, the partials and the report are allocated by the first call of the
+// The reject is a device copy.  No atomics on data.  The batched forms for ensembles: gmpnp_time_step_ens.h.  u_nm1, the partials and the report are allocated by the first call of the
 // family: a handle that never asks keeps the buffers and launches it had.  Included at the end of gmpnp_api.hip.
 #pragma once
 
@@ -54,60 +54,14 @@ __device__ __forceinline__ void wave_max_index(double& v, int& idx) {
 
 template <int NF>
 __global__ __launch_bounds__(kVecBlock) void k_time_error(const TimeErrorIo io) {
-  constexpr int K = kTimeCols * NF;
-  __shared__ double su[kVecBlock * NF], sn[kVecBlock * NF], sm[kVecBlock * NF];
-  __shared__ uint8_t sb[kVecBlock * NF];
-  __shared__ double red[4 * K];
-  __shared__ double wl[kVecBlock / kWave];
-  __shared__ int wd[kVecBlock / kWave];
-  const int t = threadIdx.x, n0 = blockIdx.x * kVecBlock;
-  const int cnt = min(kVecBlock, io.nv - n0) * NF;   // doubles of this workgroup's node blocks (gridDim.x = ceil(nv / 256): cnt > 0)
-  const size_t base = (size_t)n0 * NF;
-  int bad = 0;
-  for (int k = t; k < cnt; k += kVecBlock) {
-    const double x = io.u[base + k];
-    su[k] = x; sn[k] = io.un[base + k]; sm[k] = io.unm1[base + k]; sb[k] = io.bcflag[base + k];
-    bad |= ((__double2hiint(x) & 0x7ff00000) == 0x7ff00000) ? 1 : 0;   // NaN or Inf
-  }
-  const int any_bad = __syncthreads_or(bad);
-  double v[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = 0.0;
-  double worst = -1.0; int dof = -1;
-  if (n0 + t < io.nv) {
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const int k = t * NF + f;
-      if (sb[k]) continue;
-      const double x = su[k], xn = sn[k];
-      const double p = xn + io.ratio * (xn - sm[k]);
-      const double d = (x - p) * io.scale;
-      const double w = io.atol[f] + io.rtol * fmax(fabs(x), fabs(xn));
-      const double q = d / w, r = (x - xn) * io.inv_h;
-      v[f] = q * q; v[NF + f] = r * r; v[2 * NF + f] = 1.0;
-      if (fabs(q) > worst) { worst = fabs(q); dof = (n0 + t) * NF + f; }   // fields ascend: a tie keeps the smaller dof
-    }
-  }
-  block_sum<K>(v, red);
-  wave_max_index(worst, dof);
-  if ((t & (kWave - 1)) == 0) { wl[t >> 6] = worst; wd[t >> 6] = dof; }
-  __syncthreads();
-  if (t == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) io.part[(size_t)k * io.nblk + blockIdx.x] = v[k];
-#pragma unroll
-    for (int w = 1; w < kVecBlock / kWave; ++w)
-      if (wl[w] > worst) { worst = wl[w]; dof = wd[w]; }   // the waves' dofs ascend: a tie keeps the smaller
-    io.part_max[blockIdx.x] = worst;
-    io.part_dof[blockIdx.x] = dof;
-    io.part_bad[blockIdx.x] = any_bad;
-  }
+#include "gmpnp_time_error_body.inc"
 }
 
 // one workgroup; thread c < kTimeCols * NF sums column c over the workgroups in their order, thread 64 takes the maximum
+// (the body is k_time_reduce_ens's too, gmpnp_time_step_ens.h: additions in one order and comparisons only)
 template <int NF>
-__global__ __launch_bounds__(kVecBlock) void k_time_reduce(const double* part, const double* part_max, const int32_t* part_dof,
-                                                           const int32_t* part_bad, int nblk, TimeReport* out) {
+__device__ __forceinline__ void time_reduce_body(const double* part, const double* part_max, const int32_t* part_dof,
+                                                 const int32_t* part_bad, int nblk, TimeReport* out) {
   constexpr int K = kTimeCols * NF;
   const int t = threadIdx.x;
   if (t < K) {
@@ -126,6 +80,11 @@ __global__ __launch_bounds__(kVecBlock) void k_time_reduce(const double* part, c
     }
     out->worst = worst; out->dof = dof; out->bad = bad;
   }
+}
+template <int NF>
+__global__ __launch_bounds__(kVecBlock) void k_time_reduce(const double* part, const double* part_max, const int32_t* part_dof,
+                                                           const int32_t* part_bad, int nblk, TimeReport* out) {
+  time_reduce_body<NF>(part, part_max, part_dof, part_bad, nblk, out);
 }
 
 __global__ __launch_bounds__(kVecBlock) void k_time_shift(const double* u, double* un, double* unm1, int ndof) {
@@ -157,10 +116,9 @@ int time_prepare(gmpnp_solver* s, const char* what) {
   return GMPNP_OK;
 }
 
-// estimator + reduce on the handle's stream; without history u_nm1 is not read as a state (ratio = 0: p = u_n)
-template <int NF>
-int time_error_launch(gmpnp_solver* s, double h, double h_prev, bool history, const gmpnp_time_tol_t& tol) {
-  gmpnp_time_stepper* T = s->stepper.get();
+// the estimator's arguments of one handle; without history u_nm1 is not read as a state (ratio = 0: p = u_n)
+TimeErrorIo time_error_io(const gmpnp_solver* s, double h, double h_prev, bool history, const gmpnp_time_tol_t& tol) {
+  const gmpnp_time_stepper* T = s->stepper.get();
   TimeErrorIo io{};
   io.u = s->u.p; io.un = s->un.p; io.unm1 = history ? T->unm1.p : s->un.p; io.bcflag = s->bcflag.p;
   io.part = T->part.p; io.part_max = T->part_max.p; io.part_dof = T->part_dof.p; io.part_bad = T->part_bad.p;
@@ -169,7 +127,15 @@ int time_error_launch(gmpnp_solver* s, double h, double h_prev, bool history, co
   io.scale = history ? h / (2.0 * h + h_prev) : 0.0;
   io.inv_h = 1.0 / h;
   io.rtol = tol.rtol;
-  for (int f = 0; f < NF; ++f) io.atol[f] = tol.atol[f];
+  for (int f = 0; f < s->nf; ++f) io.atol[f] = tol.atol[f];
+  return io;
+}
+
+// estimator + reduce on the handle's stream
+template <int NF>
+int time_error_launch(gmpnp_solver* s, double h, double h_prev, bool history, const gmpnp_time_tol_t& tol) {
+  gmpnp_time_stepper* T = s->stepper.get();
+  const TimeErrorIo io = time_error_io(s, h, h_prev, history, tol);
   hipLaunchKernelGGL((k_time_error<NF>), dim3(T->nblk), dim3(kVecBlock), 0, s->stream, io);
   hipLaunchKernelGGL((k_time_reduce<NF>), dim3(1), dim3(kVecBlock), 0, s->stream, (const double*)T->part.p, (const double*)T->part_max.p,
                      (const int32_t*)T->part_dof.p, (const int32_t*)T->part_bad.p, T->nblk, T->d_report);
@@ -210,6 +176,37 @@ int time_kernel_end(gmpnp_solver* s, DevBuf<double>& keep) {
   return GMPNP_OK;
 }
 
+// the argument rules of gmpnp_time_error (nullptr = fine, else the message without its prefix)
+const char* time_error_invalid(double h, double h_prev, const gmpnp_time_tol_t& tol, int nf) {
+  if (!(h > 0.0) || std::isinf(h) || h_prev != h_prev || std::isinf(h_prev)) return "h must be positive and finite, h_prev finite";
+  if (!(tol.rtol >= 0.0) || std::isinf(tol.rtol)) return "rtol must be finite and >= 0";
+  for (int f = 0; f < nf; ++f)
+    if (!(tol.atol[f] > 0.0) || std::isinf(tol.atol[f])) return "every field's atol must be positive and finite";
+  return nullptr;
+}
+
+// what the caller gets from the device's report
+gmpnp_time_error_t time_report_result(const gmpnp_solver* s, const TimeReport& r, bool history) {
+  const int nf = s->nf;
+  gmpnp_time_error_t e{};
+  e.has_history = history ? 1 : 0; e.nonfinite = r.bad ? 1 : 0;
+  e.worst_dof = -1;
+  bool nan_err = false, nan_rate = false;
+  for (int f = 0; f < nf; ++f) {
+    const double n = r.n_free[f];
+    e.err_field[f] = (history && n > 0.0) ? std::sqrt(r.sum_err[f] / n) : 0.0;
+    e.rate_field[f] = n > 0.0 ? std::sqrt(r.sum_rate[f] / n) : 0.0;
+    if (r.bad) { e.err_field[f] = NAN; e.rate_field[f] = NAN; }
+    nan_err |= e.err_field[f] != e.err_field[f]; nan_rate |= e.rate_field[f] != e.rate_field[f];
+    if (e.err_field[f] > e.err) e.err = e.err_field[f];
+    if (e.rate_field[f] > e.rate) e.rate = e.rate_field[f];
+  }
+  if (nan_err) e.err = NAN;      // a NaN never wins a comparison
+  if (nan_rate) e.rate = NAN;
+  if (!r.bad && history && r.dof >= 0) e.worst_dof = (int64_t)s->t.perm[r.dof / nf] * nf + r.dof % nf;
+  return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -232,35 +229,16 @@ int gmpnp_set_time_step(gmpnp_solver* s, double inv_dt) {
 
 int gmpnp_time_error(gmpnp_solver* s, double h, double h_prev, const gmpnp_time_tol_t* tol, gmpnp_time_error_t* out) {
   if (!s || !tol || !out) return fail(GMPNP_ERR_INVALID, "gmpnp_time_error: NULL argument");
-  if (!(h > 0.0) || std::isinf(h) || h_prev != h_prev || std::isinf(h_prev)) return fail(GMPNP_ERR_INVALID, "gmpnp_time_error: h must be positive and finite, h_prev finite");
-  if (!(tol->rtol >= 0.0) || std::isinf(tol->rtol)) return fail(GMPNP_ERR_INVALID, "gmpnp_time_error: rtol must be finite and >= 0");
+  if (const char* why = time_error_invalid(h, h_prev, *tol, 0)) return fail(GMPNP_ERR_INVALID, std::string("gmpnp_time_error: ") + why);
   int rc = time_prepare(s, "gmpnp_time_error"); if (rc) return rc;
   const int nf = s->nf;
-  for (int f = 0; f < nf; ++f)
-    if (!(tol->atol[f] > 0.0) || std::isinf(tol->atol[f])) return fail(GMPNP_ERR_INVALID, "gmpnp_time_error: every field's atol must be positive and finite");
+  if (const char* why = time_error_invalid(h, h_prev, *tol, nf)) return fail(GMPNP_ERR_INVALID, std::string("gmpnp_time_error: ") + why);
   gmpnp_time_stepper* T = s->stepper.get();
   const bool history = T->has_history && h_prev > 0.0;
   if (nf == 9) rc = time_error_launch<9>(s, h, h_prev, history, *tol); else rc = time_error_launch<7>(s, h, h_prev, history, *tol);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
-  const TimeReport r = *T->h_report;
-  gmpnp_time_error_t e{};
-  e.has_history = history ? 1 : 0; e.nonfinite = r.bad ? 1 : 0;
-  e.worst_dof = -1;
-  bool nan_err = false, nan_rate = false;
-  for (int f = 0; f < nf; ++f) {
-    const double n = r.n_free[f];
-    e.err_field[f] = (history && n > 0.0) ? std::sqrt(r.sum_err[f] / n) : 0.0;
-    e.rate_field[f] = n > 0.0 ? std::sqrt(r.sum_rate[f] / n) : 0.0;
-    if (r.bad) { e.err_field[f] = NAN; e.rate_field[f] = NAN; }
-    nan_err |= e.err_field[f] != e.err_field[f]; nan_rate |= e.rate_field[f] != e.rate_field[f];
-    if (e.err_field[f] > e.err) e.err = e.err_field[f];
-    if (e.rate_field[f] > e.rate) e.rate = e.rate_field[f];
-  }
-  if (nan_err) e.err = NAN;      // a NaN never wins a comparison
-  if (nan_rate) e.rate = NAN;
-  if (!r.bad && history && r.dof >= 0) e.worst_dof = (int64_t)s->t.perm[r.dof / nf] * nf + r.dof % nf;
-  *out = e;
+  *out = time_report_result(s, *T->h_report, history);
   return GMPNP_OK;
 }
 

@@ -98,25 +98,29 @@ class EDLRun:
     def adaptive_step(self, verbose=True):
         """One ATTEMPTED step of the adaptive run (``timestep.AdaptiveStepper.attempt``); the glue of ``step`` runs for an accepted
         step only, with ``time_accept`` in place of ``assign_previous``.  Returns the attempt's log row."""
-        def before_solve(t, h):
-            self.dt = h
-            if self.warn_stab and verbose:
-                print("Warning:stabilization not implemented for MPNP!")
-            if self.supg and self._supg_stale:
-                self.refresh_supg()
-                self._supg_stale = False
-
-        def before_accept(st):
-            if self.budget is not None:   # while u_n is the previous state and inv_dt the step's
-                self.budget.take(self.sys)
-            self.accept_solution(st, self.sys.vertex_values(), verbose)
-            self.newton_its.append(st["iterations"])
-            self.n += 1
-            self._supg_stale = True
-
-        row = self.stepping.attempt(before_solve, before_accept, verbose)
+        row = self.stepping.attempt(lambda t, h: self.adaptive_before_solve(t, h, verbose),
+                                    lambda st: self.adaptive_before_accept(st, None, verbose), verbose)
         self.t = self.stepper.t
         return row
+
+    def adaptive_before_solve(self, t, h, verbose=True):
+        """Host glue of an attempted step in front of its Newton solve (also what ``EDLEnsemble`` runs per member)."""
+        self.dt = h
+        if self.warn_stab and verbose:
+            print("Warning:stabilization not implemented for MPNP!")
+        if self.supg and self._supg_stale:
+            self.refresh_supg()
+            self._supg_stale = False
+
+    def adaptive_before_accept(self, st, vals=None, verbose=True):
+        """Host glue of an ACCEPTED step, while u_n is the previous state and inv_dt the step's.  ``vals``: the (nv, nf) vertex
+        values of u when the caller holds them already (``EDLEnsemble``: the member's row of one copy for all members)."""
+        if self.budget is not None:
+            self.budget.take(self.sys)
+        self.accept_solution(st, self.sys.vertex_values() if vals is None else vals, verbose)
+        self.newton_its.append(st["iterations"])
+        self.n += 1
+        self._supg_stale = True
 
     def refresh_supg(self):
         """rho_i from the previous step's potential (u_n), OH's strong residual with grad(u_H)."""

@@ -5,7 +5,10 @@ Each member is an ordinary ``EDLRun`` (its own handle, model tables, Dirichlet v
 per step the ensemble applies exactly the host glue of ``EDLRun.step`` to every member (``advance_clock`` before the solve,
 ``accept_solution`` after it, then ``u_n.assign(u)``), reads the state of all members with one copy, and freezes a member
 whose solve fails with the error text the serial driver would raise, while the others carry on.  Outputs are the members'
-own ``EDLRun.write_outputs`` / ``ohp_summary``."""
+own ``EDLRun.write_outputs`` / ``ohp_summary``.
+
+``adaptive_dt=True`` on the ensemble: no lock-step; every member is its serial ADAPTIVE run on its own clock, and a step of the
+ensemble is one round of ``timestep.EnsembleStepper``."""
 from __future__ import annotations
 
 import itertools
@@ -13,6 +16,7 @@ import itertools
 from . import backend
 from .edl1d import EDLRun, run_identifier
 from .params import edl_parameters
+from .timestep import member_adaptive_keywords
 
 # keyword surface of solve_EDL / EDLRun (reference 1D:66-79) and its defaults
 MEMBER_DEFAULTS = {"concentration_elec": 0.1, "model": "MPNP", "voltage_multiplier": -1.0, "H2_FE": 0.2,
@@ -80,22 +84,69 @@ def error_text(code, message):
     return str(backend.GmpnpError(code, message))
 
 
-class EDLEnsemble:
+
+class AdaptiveRounds:
+    """The adaptive mode of ``EDLEnsemble`` / ``PoreEnsemble`` (``timestep.EnsembleStepper`` drives the members' own
+    ``DriverStepping``): every member follows its own clock, a step of the ensemble is one round."""
+
+    def start_adaptive(self, before_solve, before_accept):
+        from .timestep import EnsembleStepper
+
+        def after_attempt(k, row):
+            r = self.runs[k]
+            r.stepping.attempted(row)
+            r.t = r.stepper.t
+            if not self.keep_history:
+                r.history = r.history[-1:]
+
+        def on_error(k, code, message):
+            self.errors[k], self.status[k], self.failed_step[k] = error_text(code, message), code, self.runs[k].n
+
+        self.stepper = EnsembleStepper([r.stepper for r in self.runs], self._ensemble, self.opts,
+                                       max_steps=[r.stepping.max_steps for r in self.runs], before_solve=before_solve,
+                                       before_accept=before_accept, after_attempt=after_attempt, on_error=on_error)
+
+    def adaptive_run(self):
+        while self.stepper.live():
+            self.stepper.round()
+            self.n += 1
+        return self
+
+
+ADAPTIVE_REFUSAL = ("adaptive_dt: a member dict cannot ask for it; adaptive time stepping is requested on the ensemble "
+                    "(adaptive_dt=True and the adaptive-stepping keywords there, a scalar or one value per member)")
+
+
+class EDLEnsemble(AdaptiveRounds):
     """``members``: keyword dicts of ``EDLRun`` (voltage, cation, concentration, H2_FE, current_OHP_ss, H_OHP, model may
     differ; mesh and schedule may not).  ``keep_history=False`` keeps only the latest state of each member (long runs).
     ``budget=True``: every live member records its species-budget table after the step's solve, as its serial ``EDLRun`` twin does.
-    ``step_fraction``: tau of the step limiter, for all members (each gets its own step length; 0 = off), as ``EDLRun`` takes it."""
+    ``step_fraction``: tau of the step limiter, for all members (each gets its own step length; 0 = off), as ``EDLRun`` takes it.
+    ``adaptive_dt=True``: every member is its serial adaptive run (``EDLRun(adaptive_dt=True, ...)``) on its OWN clock, driven in
+    rounds (``timestep.EnsembleStepper``: one ensemble Newton solve, one batched estimate and one batched accept / reject per
+    round); the other adaptive-stepping keywords (``timestep.ADAPTIVE_KEYWORDS``) are scalars or sequences with one value per
+    member.  Members stop at different rounds; ``run`` ends when all have.  Not with ``H_OHP``, as in the serial driver.
+    ``solver_parameters``: the Newton parameters of every member (default: the driver's), as ``EDLRun`` takes them."""
 
-    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False, step_fraction=0.0):
-        if any(dict(m).get("adaptive_dt") for m in members):   # before anything touches the device
-            raise ValueError("adaptive_dt: an ensemble marches all its members with one fixed step; adaptive time stepping is a single run's")
+    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False, step_fraction=0.0, adaptive_dt=False,
+                 solver_parameters=None, **adaptive):
+        members = [dict(m) for m in members]
+        if any(m.get("adaptive_dt") for m in members):   # before anything touches the device
+            raise ValueError(ADAPTIVE_REFUSAL)
+        self.adaptive = bool(adaptive_dt)
+        per_member = member_adaptive_keywords(len(members), adaptive)
+        if self.adaptive and any(m.get("H_OHP") is not None for m in members):
+            raise ValueError("adaptive_dt: the H_OHP flux controller is calibrated per fixed step")
         self.kwargs, self.eps, self.tot_num_steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []
         self._ens, self._ens_members = None, None
+        self.stepper = None
         try:
-            for kw in self.kwargs:
-                self.runs.append(EDLRun(num_steps=self.tot_num_steps, device_kwargs=device_kwargs, budget=budget, step_fraction=step_fraction, **kw))
+            for kw, ad in zip(self.kwargs, per_member):
+                extra = dict(ad, adaptive_dt=True) if self.adaptive else {}
+                self.runs.append(EDLRun(num_steps=self.tot_num_steps, device_kwargs=device_kwargs, budget=budget, step_fraction=step_fraction,
+                                        solver_parameters=solver_parameters, **extra, **kw))
         except BaseException:
             self.close()
             raise
@@ -105,6 +156,10 @@ class EDLEnsemble:
         self.status = [0] * n           # its gmpnp_status
         self.failed_step = [None] * n   # the step it failed at (frozen there)
         self.n = 0
+        if self.adaptive:
+            self.start_adaptive(lambda k, t, h: self.runs[k].adaptive_before_solve(t, h, verbose=False),
+                                lambda k, st, u: self.runs[k].adaptive_before_accept(st, u.reshape(self.runs[k].sys.nv, self.runs[k].sys.nf),
+                                                                                     verbose=False))
 
     def __len__(self):
         return len(self.runs)
@@ -121,6 +176,9 @@ class EDLEnsemble:
         return [k for k in range(len(self.runs)) if self.errors[k] is None]
 
     def step(self):
+        if self.stepper is not None:   # adaptive: one round, every live member attempts one step of its own size
+            self.n += 1
+            return self.stepper.round()
         live = self.live()
         if not live:
             self.n += 1
@@ -153,6 +211,8 @@ class EDLEnsemble:
         self.n += 1
 
     def run(self):
+        if self.stepper is not None:
+            return self.adaptive_run()
         while self.n < self.tot_num_steps:
             self.step()
         return self

@@ -130,22 +130,23 @@ class PoreRun:
     def adaptive_step(self, verbose=True):
         """One ATTEMPTED step of the adaptive run (``timestep.AdaptiveStepper.attempt``): the glue of ``step`` runs for an accepted
         step only, with ``time_accept`` in place of ``assign_previous``.  Returns the attempt's log row."""
-        device = self.glue == "device"
-
-        def before_accept(st):
-            if self.budget is not None:   # while u_n is the previous state and inv_dt the step's
-                self.budget.take(self.sys)
-            if device:
-                meds, (co2_min,) = device_medians_and_minima(self.sys, (1, 2, 3, 7), (4,))
-                row = [v for _, v in self.sys.owned_vertex_values()]
-            else:
-                row = self.sys.vertex_values()
-                meds, co2_min = column_medians(row, (1, 2, 3, 7)), float(np.amin(row[:, 4]))
-            self.accept_solution(st, row, meds, co2_min, verbose=verbose, assign=False)
-
-        row = self.stepping.attempt(None, before_accept, verbose)
+        row = self.stepping.attempt(None, lambda st: self.adaptive_before_accept(st, None, verbose), verbose)
         self.t = self.stepper.t
         return row
+
+    def adaptive_before_accept(self, st, row=None, verbose=True):
+        """Host glue of an ACCEPTED step, while u_n is the previous state and inv_dt the step's.  ``row``: the (nv, nf) vertex
+        values of u when the caller holds them already (``PoreEnsemble``: the member's row of one copy for all members)."""
+        if self.budget is not None:
+            self.budget.take(self.sys)
+        if row is None and self.glue == "device":
+            meds, (co2_min,) = device_medians_and_minima(self.sys, (1, 2, 3, 7), (4,))
+            row = [v for _, v in self.sys.owned_vertex_values()]
+        else:
+            if row is None:
+                row = self.sys.vertex_values()
+            meds, co2_min = column_medians(row, (1, 2, 3, 7)), float(np.amin(row[:, 4]))
+        self.accept_solution(st, row, meds, co2_min, verbose=verbose, assign=False)
 
     def step(self, verbose=True):
         """One time step.  The glue decides where the medians and the CO2 minimum come from and what a history row is; the two

@@ -5,15 +5,19 @@ Each member is an ordinary ``PoreRun`` (its own handle, model tables, Dirichlet 
 ``shared_device=1`` so that its handle keeps to one stream and the four-launch BiCGStab form.  Per step the ensemble applies
 exactly the host glue of ``PoreRun.step`` to every member (medians -> Sechenov -> ``set_bcs``, CO2 minimum, history row), reads
 the state of all members with one copy, assigns ``u_n`` of the members that succeeded with one launch, and freezes a member whose
-solve fails with the error text the serial driver would raise, while the others carry on."""
+solve fails with the error text the serial driver would raise, while the others carry on.
+
+``adaptive_dt=True`` on the ensemble: no lock-step; every member is its serial ADAPTIVE run on its own clock, and a step of the
+ensemble is one round of ``timestep.EnsembleStepper``."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import backend
-from .edl_ensemble import error_text
+from .edl_ensemble import ADAPTIVE_REFUSAL, AdaptiveRounds, error_text
 from .pore3d import SOLVER_PARAMETERS, PoreRun
 from .solver import column_medians
+from .timestep import member_adaptive_keywords
 
 # what may differ between the members of one ensemble (keywords of ``solveEDL``, reference 3D:96-113) and their defaults
 MEMBER_DEFAULTS = {"concentration_elec": 1.0, "voltage_multiplier": -1.0, "cation": "K", "H2_FE": 0.05, "current_rough": 3000.0,
@@ -56,26 +60,34 @@ def plan_members(members, num_steps=None):
     return full, (None if steps is None else int(steps))
 
 
-class PoreEnsemble:
+class PoreEnsemble(AdaptiveRounds):
     """``members``: keyword dicts of ``PoreRun`` (concentration, voltage, cation, H2_FE, current_rough, roughness_factor, y_CO2 may
     differ; mesh, weak form and schedule may not).  ``keep_history=False`` keeps only the latest row of each member (long runs).
     ``budget=True``: every live member records its species-budget table after the step's solve (the single-handle call per member:
-    the members are ordinary handles), as its serial ``PoreRun`` twin does."""
+    the members are ordinary handles), as its serial ``PoreRun`` twin does.
+    ``adaptive_dt=True``: every member is its serial adaptive run (``PoreRun(adaptive_dt=True, ...)``) on its OWN clock, driven in
+    rounds (``timestep.EnsembleStepper``); the other adaptive-stepping keywords are scalars or sequences with one value per member."""
 
-    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False, step_fraction=0.0):
+    def __init__(self, members, num_steps=None, device_kwargs=None, keep_history=True, budget=False, step_fraction=0.0, adaptive_dt=False,
+                 **adaptive):
         """``step_fraction`` other than 0 is refused (ValueError, before anything touches the device): 3D ensembles have no step limiter."""
         if step_fraction:
             raise ValueError("step_fraction: the step limiter is not available in a 3D ensemble")
-        if any(dict(m).get("adaptive_dt") for m in members):   # before anything touches the device
-            raise ValueError("adaptive_dt: an ensemble marches all its members with one fixed step; adaptive time stepping is a single run's")
+        members = [dict(m) for m in members]
+        if any(m.get("adaptive_dt") for m in members):   # before anything touches the device
+            raise ValueError(ADAPTIVE_REFUSAL)
+        self.adaptive = bool(adaptive_dt)
+        per_member = member_adaptive_keywords(len(members), adaptive)
         self.kwargs, steps = plan_members(members, num_steps)
         self.keep_history = keep_history
         self.runs = []
         self._ens, self._ens_members = None, None
+        self.stepper = None
         dk = dict(device_kwargs or {}, shared_device=1)
         try:
-            for kw in self.kwargs:
-                self.runs.append(PoreRun(num_steps=steps, device_kwargs=dk, budget=budget, **kw))
+            for kw, ad in zip(self.kwargs, per_member):
+                extra = dict(ad, adaptive_dt=True) if self.adaptive else {}
+                self.runs.append(PoreRun(num_steps=steps, device_kwargs=dk, budget=budget, **extra, **kw))
         except BaseException:
             self.close()
             raise
@@ -86,6 +98,9 @@ class PoreEnsemble:
         self.status = [0] * n           # its gmpnp_status
         self.failed_step = [None] * n   # the step it failed at (frozen there)
         self.n = 0
+        if self.adaptive:
+            self.start_adaptive(None, lambda k, st, u: self.runs[k].adaptive_before_accept(
+                st, u.reshape(self.runs[k].sys.nv, self.runs[k].sys.nf).copy(), verbose=False))
 
     def __len__(self):
         return len(self.runs)
@@ -102,6 +117,9 @@ class PoreEnsemble:
         return [k for k in range(len(self.runs)) if self.errors[k] is None]
 
     def step(self):
+        if self.stepper is not None:   # adaptive: one round, every live member attempts one step of its own size
+            self.n += 1
+            return self.stepper.round()
         live = self.live()
         if not live:
             self.n += 1
@@ -131,6 +149,8 @@ class PoreEnsemble:
         self.n += 1
 
     def run(self):
+        if self.stepper is not None:
+            return self.adaptive_run()
         while self.n < self.tot_num_steps:
             self.step()
         return self

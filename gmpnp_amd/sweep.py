@@ -9,6 +9,7 @@ at the end (one ``all_gather_object``).
   python -m gmpnp_amd.sweep --num_steps 20                                   # 1 GPU, all 35 jobs in turn
   python -m torch.distributed.run --nproc-per-node 8 -m gmpnp_amd.sweep      # one rank per GPU (RCCL only for the gather)
   python -m gmpnp_amd.sweep --ensemble --num_steps 20                        # the voltages of one mesh as one device ensemble
+  python -m gmpnp_amd.sweep --ensemble --adaptive_dt --steady_tol 1e-5       # ... every member stepping adaptively on its own clock
 """
 from __future__ import annotations
 
@@ -47,9 +48,13 @@ def group_by_radius(job_list):
 
 
 def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=0, write=False, as_published=False, ramp_steps=0,
-              L=50e-9, device_kwargs=None, budget=False):
+              L=50e-9, device_kwargs=None, budget=False, **adaptive):
     """The runs of ``run_job`` for every voltage on ONE mesh as one ``PoreEnsemble`` (one launch chain per Newton iteration for all
-    of them); returns their summaries in the order of ``voltages``, with the keys ``run_job`` gives (``seconds``: the group's)."""
+    of them); returns their summaries in the order of ``voltages``, with the keys ``run_job`` gives (``seconds``: the group's).
+    ``adaptive``: the adaptive-stepping keywords of ``PoreEnsemble``; with ``adaptive_dt`` every member runs until it stops
+    (``num_steps`` is not used) and its summary gets ``stop_reason``, ``steps_accepted`` and ``steps_rejected``."""
+    if adaptive.get("adaptive_dt") and ramp_steps > 0:
+        raise ValueError("--adaptive_dt: the voltage ramp (--ramp_steps) counts fixed steps")
     from .pore_ensemble import PoreEnsemble
     from .problem import pore_dirichlet
     t0 = time.perf_counter()
@@ -57,8 +62,10 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
     members = [dict(concentration_elec=concentration_elec, L=L, R=radius_nm * 1e-9, voltage_multiplier=ramp_value(v, 0, ramp_steps),
                     as_published=as_published) for v in voltages]
     with PoreEnsemble(members, num_steps=num_steps, device_kwargs=dict({"device_id": device_id}, **(device_kwargs or {})),
-                      keep_history=write, budget=budget) as ens:
-        for n in range(num_steps):
+                      keep_history=write, budget=budget, **adaptive) as ens:
+        if ens.stepper is not None:
+            ens.run()
+        for n in range(0 if ens.stepper is not None else num_steps):
             ens.step()
             for k in ens.live():   # --ramp_steps, per member: the Dirichlet set of the NEXT step
                 run = ens.runs[k]
@@ -79,6 +86,8 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
                        CO2_min=None if run.CO2_min is None else float(run.CO2_min))
             if run.budget is not None:
                 out.update(run.budget.summary())
+            if run.stepper is not None:
+                out.update(stop_reason=run.stepper.stop_reason, steps_accepted=run.stepper.accepted, steps_rejected=run.stepper.rejected)
     dt = time.perf_counter() - t0
     for out in outs:
         out["seconds"] = dt
@@ -148,7 +157,13 @@ def main(argv=None):
                    "CO2 supplied by its Dirichlet face and the largest closure (gmpnp_amd/budget.py); with --write also budget.npz")
     p.add_argument("--write", action="store_true", help="write the reference's output files of every run under $GMPNP_OUT")
     p.add_argument("--backend", default=None, help="torch.distributed backend for the final gather (default: nccl)")
+    from .timestep import adaptive_keywords, add_adaptive_arguments
+    add_adaptive_arguments(p)   # (with --ensemble)
     a = p.parse_args(argv)
+    if a.adaptive_dt and not a.ensemble:
+        raise ValueError("--adaptive_dt: the sweep steps adaptively as a device ensemble only (add --ensemble); a single adaptive "
+                         "run is gmpnp_amd.pore3d --adaptive_dt")
+    adaptive = adaptive_keywords(a) if a.adaptive_dt else {}
     from .dist import init_process_group_from_env
     rank, world, local, dist = init_process_group_from_env(a.backend or "nccl")
     radii = [int(r) if float(r).is_integer() else r for r in a.radii]
@@ -162,7 +177,7 @@ def main(argv=None):
         res = [None] * len(mine)
         for radius, idx in group_by_radius(mine):
             outs = run_group(radius, [mine[k][1] for k in idx], a.num_steps, a.concentration_elec, device_id=local, write=a.write,
-                             as_published=a.as_published, ramp_steps=a.ramp_steps, budget=a.budget)
+                             as_published=a.as_published, ramp_steps=a.ramp_steps, budget=a.budget, **adaptive)
             for k, out in zip(idx, outs):
                 res[k] = out
     elif a.jobs_per_gpu > 1:

@@ -2,7 +2,8 @@
 step of its YAML file).  Backward Euler; the step is chosen from the device's estimate of its local error (include/gmpnp.h,
 gmpnp_time_error; kernels: csrc/gmpnp_time_step.h).  ``next_time_step`` is the Python statement of the rule that
 csrc/gmpnp_host_rules.h states in C++ (``next_time_step`` there; tests/test_time_step_reference.py compiles that one with the host
-compiler and holds both against a NumPy restatement of its own).  ``AdaptiveStepper`` owns the loop body of one attempted step."""
+compiler and holds both against a NumPy restatement of its own).  ``AdaptiveStepper`` owns the loop body of one attempted step,
+``EnsembleStepper`` the round of a device ensemble whose members each follow their own clock."""
 from __future__ import annotations
 
 import math
@@ -106,14 +107,44 @@ class AdaptiveStepper:
     def newton_failures(self):
         return sum(1 for r in self.log if r["reason"] == 2)
 
+    def start(self):
+        """(t, h) of the step to attempt next; RuntimeError once the run has ended."""
+        if self.stop_reason is not None:
+            raise RuntimeError("the adaptive run has ended (%s)" % self.stop_reason)
+        return self.t, self.h
+
+    def decide(self, t, h, st, failed, est):
+        """The decision and the log row of the attempt (t, h): ``st`` = the Newton statistics (None: none came back), ``failed`` =
+        Newton gave up (``RETRY_CODES``), ``est`` = the estimator's report of a converged solve, else None."""
+        err = est["err"] if est else 0.0
+        rate = est["rate"] if est else math.inf
+        d = next_time_step(self.policy, t, h, err, bool(est and est["has_history"]), failed, rate, self.steady_run)
+        row = {"t": t, "h": h, "accepted": bool(d.accept), "reason": d.reason, "err": err if est else math.nan,
+               "rate": rate if est else math.nan, "newton": st["iterations"] if st else -1,
+               "krylov": st["krylov_iterations"] if st else -1, "worst_dof": est["worst_dof"] if est else -1,
+               "steric_excursion": st["steric_excursion"] if st else -1}
+        return d, row
+
+    def finish(self, d, row):
+        """The clock, the controller's memory, the log and the stop reason after the attempt's accept / reject went to the device."""
+        if d.accept:
+            self.h_prev = row["h"]
+        self.t, self.h, self.steady_run = d.t_next, d.h_next, d.steady_run
+        self.log.append(row)
+        self.last_decision = d
+        if d.stop_end:
+            self.stop_reason = "t_end"
+        elif d.stop_steady:
+            self.stop_reason = "steady"
+        elif d.give_up:
+            self.stop_reason = "h_min"
+
     def attempt(self, before_solve=None, before_accept=None):
         """One attempted step.  ``before_solve(t, h)``: the driver's glue in front of the Newton solve (its clock is the
         stepper's); ``before_accept(stats)``: the driver's glue of an accepted step, called while u_n is still the previous state
         (budgets, history row, new Dirichlet values) — a rejected step calls neither it nor anything else of the driver.
-        Returns the log row."""
-        if self.stop_reason is not None:
-            raise RuntimeError("the adaptive run has ended (%s)" % self.stop_reason)
-        t, h = self.t, self.h
+        Returns the log row.  (``EnsembleStepper.round`` runs the same phases for many members at once.)"""
+        t, h = self.start()
         self.sys.set_time_step(self.inv_dt_of_h(h))
         if before_solve is not None:
             before_solve(t, h)
@@ -134,29 +165,14 @@ class AdaptiveStepper:
         est = None
         if not failed:
             est = self.sys.time_error(h, self.h_prev, self.rtol, self.atol)
-        err = est["err"] if est else 0.0
-        rate = est["rate"] if est else math.inf
-        d = next_time_step(self.policy, t, h, err, bool(est and est["has_history"]), failed, rate, self.steady_run)
-        row = {"t": t, "h": h, "accepted": bool(d.accept), "reason": d.reason, "err": err if est else math.nan,
-               "rate": rate if est else math.nan, "newton": st["iterations"] if st else -1,
-               "krylov": st["krylov_iterations"] if st else -1, "worst_dof": est["worst_dof"] if est else -1,
-               "steric_excursion": st["steric_excursion"] if st else -1}
+        d, row = self.decide(t, h, st, failed, est)
         if d.accept:
             if before_accept is not None:
                 before_accept(st)
             self.sys.time_accept()
-            self.h_prev = h
         else:
             self.sys.time_reject()
-        self.t, self.h, self.steady_run = d.t_next, d.h_next, d.steady_run
-        self.log.append(row)
-        self.last_decision = d
-        if d.stop_end:
-            self.stop_reason = "t_end"
-        elif d.stop_steady:
-            self.stop_reason = "steady"
-        elif d.give_up:
-            self.stop_reason = "h_min"
+        self.finish(d, row)
         return row
 
     def log_arrays(self):
@@ -174,6 +190,104 @@ class AdaptiveStepper:
                 "t_reached": self.t, "stop_reason": self.stop_reason}
 
 
+# a Newton solve that ends with one of these is a failed ATTEMPT (rejected and tried again with a smaller step), as in ``attempt``
+RETRY_CODES = (backend.ERR_NOT_CONVERGED, backend.ERR_NUMERIC, backend.ERR_LINEAR)
+
+
+class EnsembleStepper:
+    """Adaptive runs of the members of a device ensemble, every member on its own clock.  Holds the members' ``AdaptiveStepper``s
+    and owns one *round*: one attempted step of every member that has not stopped, with ONE ensemble Newton solve, ONE batched
+    estimate and ONE batched accept / reject (``backend.DeviceEnsemble``).  The decision and the log row are the members' own
+    (``AdaptiveStepper.decide`` / ``finish``).
+
+    ``ensemble_of(live)``: the ensemble of the members ``live`` (indices, ascending), rebuilt by the caller when the list changes;
+    ``options``: what its ``newton_solve`` takes; ``max_steps``: None, or per member None or the largest number of attempted steps.
+    Hooks, all optional, ``k`` the member: ``before_solve(k, t, h)`` and ``before_accept(k, stats, u_row)`` as in
+    ``AdaptiveStepper.attempt`` (``u_row`` = the member's row of the round's one ``get_state``), ``after_attempt(k, row)``,
+    ``on_error(k, code, message)`` for a member whose solve ends with another status than ``RETRY_CODES``: it stops
+    (``errors[k]`` keeps the message, ``status[k]`` the code) and its neighbours go on."""
+
+    def __init__(self, steppers, ensemble_of, options, max_steps=None, before_solve=None, before_accept=None, after_attempt=None,
+                 on_error=None):
+        self.steppers = list(steppers)
+        n = len(self.steppers)
+        self.ensemble_of, self.options = ensemble_of, options
+        self.max_steps = [None] * n if max_steps is None else [None if m is None else int(m) for m in max_steps]
+        if len(self.max_steps) != n:
+            raise ValueError("max_steps holds one entry per member")
+        self.before_solve, self.before_accept, self.after_attempt, self.on_error = before_solve, before_accept, after_attempt, on_error
+        self.errors, self.status = [None] * n, [0] * n
+        self.rounds = 0
+
+    def live(self):
+        """The members that go into the next round (``max_steps`` ends a member here, as ``DriverStepping.run`` does)."""
+        out = []
+        for k, s in enumerate(self.steppers):
+            if self.errors[k] is not None or s.stop_reason is not None:
+                continue
+            if self.max_steps[k] is not None and len(s.log) >= self.max_steps[k]:
+                s.stop_reason = "max_steps"
+                continue
+            out.append(k)
+        return out
+
+    def round(self):
+        """One attempted step of every live member.  Returns {member: log row} (a member that ended with an error has none)."""
+        live = self.live()
+        if not live:
+            return {}
+        ens = self.ensemble_of(live)
+        S = [self.steppers[k] for k in live]
+        th = [s.start() for s in S]
+        ens.set_time_step([s.inv_dt_of_h(h) for s, (_, h) in zip(S, th)])
+        if self.before_solve is not None:
+            for k, (t, h) in zip(live, th):
+                self.before_solve(k, t, h)
+        stats, codes, msgs = ens.newton_solve(self.options)
+        failed, fatal = [], []
+        for i, k in enumerate(live):
+            failed.append(codes[i] in RETRY_CODES)
+            fatal.append(codes[i] != backend.OK and not failed[i])
+            if fatal[i]:
+                self.errors[k], self.status[k] = msgs[i] or "status %d" % codes[i], codes[i]
+                if self.on_error is not None:
+                    self.on_error(k, codes[i], msgs[i])
+            else:
+                S[i].sys.record(stats[i])
+        mask = [not (failed[i] or fatal[i]) for i in range(len(live))]
+        ests = [None] * len(live)
+        if any(mask):
+            ests = ens.time_error([h for _, h in th], [s.h_prev for s in S], [s.rtol for s in S], [s.atol for s in S], mask)
+        plan, actions = [None] * len(live), [0] * len(live)
+        for i, s in enumerate(S):
+            if fatal[i]:
+                continue
+            plan[i] = s.decide(th[i][0], th[i][1], stats[i], failed[i], ests[i] if mask[i] else None)
+            actions[i] = 1 if plan[i][0].accept else 2
+        if self.before_accept is not None and 1 in actions:   # while u_n is still the previous state
+            U = ens.get_state()
+            for i, k in enumerate(live):
+                if actions[i] == 1:
+                    self.before_accept(k, stats[i], U[i])
+        ens.time_advance(actions)
+        rows = {}
+        for i, k in enumerate(live):
+            if plan[i] is None:
+                continue
+            S[i].finish(*plan[i])
+            rows[k] = plan[i][1]
+            if self.after_attempt is not None:
+                self.after_attempt(k, rows[k])
+        self.rounds += 1
+        return rows
+
+    def run(self):
+        """Rounds until every member has stopped."""
+        while self.live():
+            self.round()
+        return self
+
+
 # ---- what the four drivers share ----------------------------------------------------------------------------------------------------
 ADAPTIVE_KEYWORDS = dict(adaptive_dt=False, dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0,
                          max_steps=None)
@@ -182,6 +296,24 @@ ADAPTIVE_KEYWORDS = dict(adaptive_dt=False, dt_rtol=1e-2, dt_atol=1e-4, dt_init=
 def pop_adaptive(kwargs):
     """The adaptive-stepping keywords of a run class taken out of its ``**kwargs`` (defaults: ``ADAPTIVE_KEYWORDS``)."""
     return {k: kwargs.pop(k, d) for k, d in ADAPTIVE_KEYWORDS.items()}
+
+
+def member_adaptive_keywords(n, adaptive):
+    """The adaptive-stepping keywords of an ensemble of ``n`` members as one dict per member.  Each value of ``adaptive`` is a
+    scalar (all members) or a sequence with one value per member; a wrong length is a ValueError naming the keyword."""
+    out = [dict() for _ in range(n)]
+    for key, v in adaptive.items():
+        if key not in ADAPTIVE_KEYWORDS:
+            raise TypeError("unknown adaptive-stepping keyword %r" % key)
+        if isinstance(v, (list, tuple, np.ndarray)):
+            if len(v) != n:
+                raise ValueError("%s: %d values for %d ensemble members (a scalar, or one value per member)" % (key, len(v), n))
+            vals = list(v)
+        else:
+            vals = [v] * n
+        for d, x in zip(out, vals):
+            d[key] = x
+    return out
 
 
 def add_adaptive_arguments(p):
@@ -217,7 +349,10 @@ class DriverStepping:
 
     def attempt(self, before_solve, before_accept, verbose=False):
         """One attempted step; an accepted one adds its time (t_end exactly when the step landed on it).  Returns the log row."""
-        row = self.stepper.attempt(before_solve, before_accept)
+        return self.attempted(self.stepper.attempt(before_solve, before_accept), verbose)
+
+    def attempted(self, row, verbose=False):
+        """What follows an attempt whoever ran it (``attempt``, or an ensemble's round): the time of an accepted step."""
         if row["accepted"]:
             self.times.append(self.stepper.t)
         if verbose:

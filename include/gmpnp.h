@@ -245,8 +245,9 @@ int gmpnp_assign_previous(gmpnp_solver* s);
  * handle's internal order.  A NaN / Inf in u sets nonfinite and makes the err values NaN; the status stays GMPNP_OK (the caller
  * decides).  Fixed-order reductions, no atomics: two calls on one state return the same bits.  u_nm1 and the estimator's storage
  * are allocated by the first call of this family; a handle that never calls it keeps the buffers and launches it had.  Partition
- * handles (gmpnp_create_partition) are refused by all four calls (GMPNP_ERR_INVALID): groups and ensembles have no adaptive
- * stepping. */
+ * handles (gmpnp_create_partition) are refused by all four calls (GMPNP_ERR_INVALID): groups have no adaptive stepping.  The
+ * members of an ensemble step adaptively, each on its own clock, through the batched forms of these calls
+ * (gmpnp_ensemble_set_time_step, gmpnp_ensemble_time_error, gmpnp_ensemble_time_advance below). */
 typedef struct { double rtol; double atol[GMPNP_MAX_SPECIES + 1]; } gmpnp_time_tol_t;
 typedef struct {
   double err;                                  /* max_f err_field[f]; 0 when there is no history */
@@ -507,6 +508,26 @@ const char* gmpnp_ensemble_member_error(const gmpnp_ensemble* e, int32_t k);
 int gmpnp_ensemble_assign_previous(gmpnp_ensemble* e);
 /* u of every member, u_out[n][n_dofs] in file order, with one device-to-host copy for the whole ensemble. */
 int gmpnp_ensemble_get_state(gmpnp_ensemble* e, double* u_out);
+/* Adaptive time stepping of the members, every member with its own step size (the batched forms of gmpnp_set_time_step,
+ * gmpnp_time_error, gmpnp_time_accept and gmpnp_time_reject; kernels: csrc/gmpnp_time_step_ens.h).  u_nm1 and the estimator's
+ * storage are the member's own, so the history is shared with the single-handle calls: after an accept here gmpnp_time_error on
+ * the member sees it, and the other way round.  All three check the members' configuration again as gmpnp_ensemble_newton_solve
+ * does, and are complete when they return.
+ * set_time_step: inv_dt[k] becomes member k's model.inv_dt on the host and the device, its Jacobian and preconditioner are
+ * invalidated; one synchronisation for the whole ensemble.  Every value is validated first by gmpnp_set_time_step's rule: a bad one
+ * is GMPNP_ERR_INVALID, the message names the member, and nothing is changed.
+ * time_error: gmpnp_time_error of every listed member (mask[k] != 0; NULL = all) with its own h[k], h_prev[k] and tol[k], in two
+ * launches and one host synchronisation.  The arguments of a listed member are validated as gmpnp_time_error validates them (the
+ * message names the member).  out[k] holds, bit for bit, what gmpnp_time_error on member k alone returns; has_history is the
+ * member's.  The row of a member that is not listed is zeroed and its estimator storage is not written.  A NaN / Inf in one
+ * member's u sets that member's nonfinite and err values and leaves the other rows as they are.
+ * time_advance: action[k] = 0 leaves member k alone, 1 accepts its step (u_nm1 <- u_n, u_n <- u, has_history = 1), 2 rejects it
+ * (u <- u_n; the next Newton solve starts from a state set from outside), in one launch.  Any other value is GMPNP_ERR_INVALID
+ * and nothing is launched. */
+int gmpnp_ensemble_set_time_step(gmpnp_ensemble* e, const double* inv_dt /* [n] */);
+int gmpnp_ensemble_time_error(gmpnp_ensemble* e, const double* h /* [n] */, const double* h_prev /* [n] */, const gmpnp_time_tol_t* tol /* [n] */,
+                              const int32_t* mask /* [n], NULL = all */, gmpnp_time_error_t* out /* [n] */);
+int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]: 0 leave, 1 accept, 2 reject */);
 
 /* Benchmark hooks: time `launches` back-to-back launches of one kernel on the handle's stream with HIP
  * events; kernel: 0 = plain Jacobian SpMV, 1 = element kernel (F+J), 2 = Jacobian gather, 3 = residual gather,
