@@ -40,6 +40,7 @@ EXPORTS = [
     "gmpnp_species_budget", "gmpnp_group_species_budget",
     "gmpnp_step_limit",
     "gmpnp_set_time_step", "gmpnp_time_error", "gmpnp_time_accept", "gmpnp_time_reject",
+    "gmpnp_set_time_order", "gmpnp_time_history_levels", "gmpnp_set_time_step_bdf2", "gmpnp_time_error_bdf2", "gmpnp_get_time_history",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -172,6 +173,11 @@ def load_library(path: str = None):
     lib.gmpnp_time_error.argtypes = [c_void_p, c_double, c_double, POINTER(CTimeTol), POINTER(CTimeError)]
     lib.gmpnp_time_accept.argtypes = [c_void_p]
     lib.gmpnp_time_reject.argtypes = [c_void_p]
+    lib.gmpnp_set_time_order.argtypes = [c_void_p, c_int32]
+    lib.gmpnp_time_history_levels.argtypes = [c_void_p, POINTER(c_int32)]
+    lib.gmpnp_set_time_step_bdf2.argtypes = [c_void_p, c_double, c_double]
+    lib.gmpnp_time_error_bdf2.argtypes = [c_void_p, c_double, c_double, c_double, POINTER(CTimeTol), POINTER(CTimeError)]
+    lib.gmpnp_get_time_history.argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_spmv_profile.argtypes = [c_void_p, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]
     lib.gmpnp_event_overhead.argtypes = [c_void_p, c_int32, POINTER(c_double)]
     lib.gmpnp_create_partition.argtypes = [POINTER(CMesh), POINTER(CModel), POINTER(CQuadrature), POINTER(COptions),
@@ -596,6 +602,37 @@ class DeviceSolver:
     def time_reject(self):
         """u <- u_n (gmpnp_time_reject); the history stays."""
         self._check(self.lib.gmpnp_time_reject(self._h))
+
+    # second order: variable-step BDF2 (include/gmpnp.h "second-order adaptive time stepping")
+    def set_time_order(self, order: int):
+        """1 = backward Euler (the default), 2 = variable-step BDF2 (gmpnp_set_time_order): 2 allocates u_nm2 and u*, and
+        ``time_accept`` shifts three deep from then on."""
+        self._check(self.lib.gmpnp_set_time_order(self._h, int(order)))
+
+    def time_history_levels(self) -> int:
+        """Accepted states behind u_n: 0, 1 (u_nm1) or 2 (u_nm1 and u_nm2) (gmpnp_time_history_levels)."""
+        n = c_int32()
+        self._check(self.lib.gmpnp_time_history_levels(self._h, byref(n)))
+        return int(n.value)
+
+    def set_time_step_bdf2(self, inv_dt: float, ratio: float):
+        """The set-up of a BDF2 step of length h after an accepted step h_prev, ``ratio`` = h / h_prev (gmpnp_set_time_step_bdf2):
+        model.inv_dt = alpha0 * ``inv_dt`` here and on the attached coarse levels, the time term reads u*."""
+        self._check(self.lib.gmpnp_set_time_step_bdf2(self._h, float(inv_dt), float(ratio)))
+        a0 = (1.0 + 2.0 * float(ratio)) / (1.0 + float(ratio))
+        self.problem.model = dataclasses.replace(self.problem.model, inv_dt=a0 * float(inv_dt))
+
+    def time_error_bdf2(self, h: float, h_prev: float, h_prev2: float, rtol: float, atol):
+        """BDF2's local error of the step u_n -> u of length h (gmpnp_time_error_bdf2; h_prev, h_prev2: the two accepted steps
+        before it).  The dict of ``time_error``; fewer than 2 levels: has_history False and err 0."""
+        fn = lambda hd, a, b, tol, e: self.lib.gmpnp_time_error_bdf2(hd, a, b, float(h_prev2), tol, e)
+        return time_error_call(fn, self._h, self.nf, self._check, h, h_prev, rtol, atol)
+
+    def get_time_history(self):
+        """u* of the last ``set_time_step_bdf2``, file order (gmpnp_get_time_history; for tests)."""
+        out = np.empty(self.ndof)
+        self._check(self.lib.gmpnp_get_time_history(self._h, _dptr(out)))
+        return out
 
     def time_kernel(self, kernel: int, launches: int = 50) -> float:
         us = c_double()

@@ -110,6 +110,13 @@ struct gmpnp_time_stepper {
   DevBuf<int32_t> part_dof, part_bad;
   int nblk = 0;
   bool has_history = false;                     // u_nm1 holds an accepted state (gmpnp_time_accept since create / set_state / assign_previous)
+  // second order (gmpnp_time_order.h): the two vectors are allocated by the first call that asks for order 2
+  DevBuf<double> unm2, ustar;                   // the accepted state before u_nm1; u* = a u_n - b u_nm1 of the last BDF2 set-up
+  int order = 1;                                // gmpnp_set_time_order
+  int levels = 0;                               // accepted states behind u_n: 0, 1 (u_nm1) or 2 (u_nm2 too); has_history = levels >= 1
+  bool star_formed = false;                     // u* holds what gmpnp_set_time_step_bdf2 wrote
+  void dropped() { has_history = false; levels = 0; }
+  void accepted() { has_history = true; levels = std::min(levels + 1, order == 2 ? 2 : 1); }
   TimeReport* h_report = nullptr;               // pinned: what k_time_reduce writes
   TimeReport* d_report = nullptr;               // ... its device address
   ~gmpnp_time_stepper() { if (h_report) (void)hipHostFree(h_report); }
@@ -343,6 +350,12 @@ int budget_launch_any(gmpnp_solver* s);   // gmpnp_budget.h: the launch chain of
 int time_launch_any(gmpnp_solver* s);     // gmpnp_time_step.h: estimator + reduce + shift, between the bracket that keeps u_n and u_nm1
 int time_kernel_begin(gmpnp_solver* s, DevBuf<double>& keep);
 int time_kernel_end(gmpnp_solver* s, DevBuf<double>& keep);
+int time_launch_any2(gmpnp_solver* s);    // gmpnp_time_order.h: history + estimator + reduce + three-deep shift, bracket as above with u_nm2
+int time_kernel_begin2(gmpnp_solver* s, DevBuf<double>& keep);
+int time_kernel_end2(gmpnp_solver* s, DevBuf<double>& keep);
+// The residual, Jacobian and budget contexts read their previous state from c.un: u_n, or u* after a BDF2 set-up.  Whatever
+// makes u* stale (a plain gmpnp_set_time_step, a u_n written from outside, order 1) points it back at u_n.
+inline void time_read_un(gmpnp_solver* s) { s->c.un = s->un.p; }
 
 // sum of row `row` (0 .. 2) of the pinned partials the reduction kernels store (k_res_gather, k_true_residual: row 0; k_dots3: three)
 double sum_partials(const gmpnp_solver* s, int row) {
@@ -1536,7 +1549,7 @@ int gmpnp_set_state(gmpnp_solver* s, const double* u, const double* u_n) {
   if (u) { int rc = upload_vec(s, u, s->u.p); if (rc) return rc; s->state_jumped = true; }
   if (u_n) { int rc = upload_vec(s, u_n, s->un.p); if (rc) return rc; }
   s->jacobian_valid = false;
-  if (u_n && s->stepper) s->stepper->has_history = false;   // adaptive time stepping: u_nm1 no longer precedes u_n
+  if (u_n && s->stepper) { s->stepper->dropped(); time_read_un(s); }   // adaptive time stepping: u_nm1 no longer precedes u_n
   return GMPNP_OK;
 }
 
@@ -1553,7 +1566,7 @@ int gmpnp_assign_previous(gmpnp_solver* s) {
   HIP_TRY(hipSetDevice(s->opts.device_id));
   // stream-ordered: whatever reads u_n next is launched behind this copy, and every read-back synchronises the stream
   HIP_TRY(hipMemcpyAsync(s->un.p, s->u.p, s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-  if (s->stepper) s->stepper->has_history = false;   // adaptive time stepping: u_nm1 was not shifted (gmpnp_time_accept does both)
+  if (s->stepper) { s->stepper->dropped(); time_read_un(s); }   // adaptive time stepping: u_nm1 was not shifted (gmpnp_time_accept does both)
   return GMPNP_OK;
 }
 
@@ -1771,6 +1784,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 21:   // the step limiter's two launches on a zero correction (alpha = 1, u -= 0: the state stays)
         GMPNP_DISPATCH(s, r = (step_launch<NF>(s, s->limiter->dx.p, s->limiter->dx.p, 1.0, 0.9, nullptr))); break;
       case 22: r = time_launch_any(s); break;   // k_time_error + k_time_reduce + k_time_shift
+      case 23: r = time_launch_any2(s); break;  // k_time_history + k_time_error2 + k_time_reduce + k_time_shift3
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -1786,8 +1800,10 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   }
   DevBuf<double> keep;   // kernel 22 shifts u into u_n: u_n and u_nm1 are put back behind the launches
   if (kernel == 22) { rc = time_kernel_begin(s, keep); if (rc) return rc; }
+  if (kernel == 23) { rc = time_kernel_begin2(s, keep); if (rc) return rc; }
   // kernel 22: whatever happens between the bracket's two halves, u_n and u_nm1 are put back (g_err keeps the first message)
-  auto restore = [&](int code) { if (kernel != 22) return code; const std::string msg = g_err; const int rc2 = time_kernel_end(s, keep);
+  auto restore = [&](int code) { if (kernel != 22 && kernel != 23) return code; const std::string msg = g_err;
+                                 const int rc2 = kernel == 22 ? time_kernel_end(s, keep) : time_kernel_end2(s, keep);
                                  if (code) { g_err = msg; return code; } return rc2; };
   rc = one(); if (rc) return restore(rc);  // warm
   float ms = 0.f;
@@ -1886,3 +1902,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_budget.h"
 #include "gmpnp_time_step.h"
 #include "gmpnp_time_step_ens.h"
+#include "gmpnp_time_order.h"

@@ -273,6 +273,7 @@ int ens_check_member(const gmpnp_solver* s, const gmpnp_solver* s0, int k) {
   if (!is3d && (s->dim != 1 || s->nf != 7)) return bad("ensembles hold 1D problems (6 species + potential) or 3D problems (8 species + potential)");
   if (s0 && s->dim != s0->dim) return bad("1D and 3D members cannot share an ensemble");
   if (s->partitioned) return bad("partitioned handles cannot join an ensemble");
+  if (s->stepper && s->stepper->order == 2) return bad("the handle steps at order 2 (gmpnp_set_time_order): ensembles have no second-order time stepping");
   if (is3d) {
     if (s->ml_coarse || s->ml_is_coarse) return bad("a multilevel coarse level is attached: not supported in an ensemble");
     if (!s->opts.shared_device) return bad("3D members are created with shared_device = 1 (one stream, four launches per BiCGStab iteration)");
@@ -762,6 +763,8 @@ int gmpnp_ensemble_newton_solve(gmpnp_ensemble* e, const gmpnp_newton_options_t*
 int gmpnp_ensemble_assign_previous(gmpnp_ensemble* e) {
   if (!e) return fail(GMPNP_ERR_INVALID, "NULL handle");
   HIP_TRY(hipSetDevice(e->device));
+  for (const gmpnp_solver* s : e->m)
+    if (s->stepper && s->stepper->order == 2) return fail(GMPNP_ERR_INVALID, "gmpnp_ensemble_assign_previous: a member steps at order 2 (gmpnp_set_time_order): ensembles have no second-order time stepping");
   int rc = ens_drain_members(e); if (rc) return rc;
   // u / u_n of a handle are allocated once at create: the table of the last upload addresses them
   hipLaunchKernelGGL(k_ens_assign, dim3(grid_for(e->ndof, 256), (unsigned)e->m.size()), dim3(256), 0, e->stream, (const EnsMember*)e->tab.p, e->ndof);

@@ -99,6 +99,9 @@ inline bool time_step_valid(double inv_dt) { return inv_dt >= 0.0 && !std::isinf
 
 // The accept / reject rule of one attempted step h at time t.  The exponent of the step factor is 1/2 because backward Euler's
 // LOCAL error is O(h^2): err(h') = err(h) (h'/h)^2 = 1 at h' = h err^(-1/2), times the safety factor.
+// At order 2 (variable-step BDF2, "second order" below) the local error is O(h^3): the factor is safety err^(-1/3), and an accepted
+// step grows by min(max_factor, 2) at most, because variable-step BDF2 is zero-stable only for h / h_prev < 1 + sqrt(2).  Everything
+// else is the same rule; order 1 (the default) performs the operations it always performed.
 struct TimeStepPolicy {
   double safety = 0.9, min_factor = 0.2, max_factor = 4.0, fail_factor = 0.25;
   double h_min = 0.0, h_max = INFINITY, t_end = INFINITY;
@@ -119,14 +122,15 @@ struct TimeStepDecision {
 // err / has_history / rate: gmpnp_time_error_t; newton_failed: the solve of the step did not converge or its state is not finite
 // (a NaN err counts as such); steady_run: the counter the previous decision returned (0 at the start).
 inline TimeStepDecision next_time_step(const TimeStepPolicy& p, double t, double h, double err, bool has_history, bool newton_failed,
-                                       double rate, int steady_run) {
+                                       double rate, int steady_run, int order = 1) {
   TimeStepDecision d;
   const bool nan_err = !(err == err);
   auto clampd = [](double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); };
-  auto factor = [&](double hi) {   // safety err^(-1/2) clamped; err = 0 gives the upper clamp
+  auto factor = [&](double hi) {   // safety err^(-1/2) (order 2: err^(-1/3)) clamped; err = 0 gives the upper clamp
     if (!has_history) return 1.0;
-    return err > 0.0 ? clampd(p.safety / std::sqrt(err), p.min_factor, hi) : hi;
+    return err > 0.0 ? clampd(p.safety / (order == 2 ? std::cbrt(err) : std::sqrt(err)), p.min_factor, hi) : hi;
   };
+  const double grow = order == 2 ? std::min(p.max_factor, 2.0) : p.max_factor;
   if (newton_failed || nan_err) {
     d.accept = false; d.reason = newton_failed ? TimeStepDecision::newton_failed : TimeStepDecision::nonfinite;
     d.t_next = t; d.h_next = p.fail_factor * h; d.steady_run = steady_run;
@@ -135,7 +139,7 @@ inline TimeStepDecision next_time_step(const TimeStepPolicy& p, double t, double
     d.t_next = t; d.h_next = h * factor(1.0); d.steady_run = steady_run;
   } else {
     d.accept = true; d.reason = TimeStepDecision::accepted;
-    d.t_next = t + h; d.h_next = h * factor(p.max_factor);
+    d.t_next = t + h; d.h_next = h * factor(grow);
     d.steady_run = (p.steady_tol > 0.0 && rate < p.steady_tol) ? steady_run + 1 : 0;
     d.stop_steady = p.steady_tol > 0.0 && d.steady_run >= p.steady_steps;
   }
@@ -149,6 +153,33 @@ inline TimeStepDecision next_time_step(const TimeStepPolicy& p, double t, double
   }
   if (!d.stop_end && !d.stop_steady && !lands && d.h_next < p.h_min) d.give_up = true;
   return d;
+}
+
+// ---- second order: variable-step BDF2 (include/gmpnp.h "second-order adaptive time stepping"; kernels: gmpnp_time_order.h) ----------
+// With omega = h / h_prev the time term of a BDF2 step is (alpha0 / h) M (u - u*): the element pass reads it as inv_dt M (u - un) with
+// inv_dt = alpha0 inv_dt_of_h(h) and un = u* = a u_n - b u_nm1.
+inline bool time_ratio_valid(double omega) { return omega > 0.0 && !std::isinf(omega); }
+inline double bdf2_alpha0(double omega) { return (1.0 + 2.0 * omega) / (1.0 + omega); }
+inline std::pair<double, double> bdf2_history_weights(double omega) {   // (a, b)
+  const double q = 1.0 + 2.0 * omega;
+  return {(1.0 + omega) * (1.0 + omega) / q, omega * omega / q};
+}
+// The estimator's predictor p = wn u_n + wm1 u_nm1 + wm2 u_nm2: the quadratic through (t - h1 - h2, u_nm2), (t - h1, u_nm1), (t, u_n)
+// at t + h (Lagrange weights; h1 = the accepted step before h, h2 = the one before that).
+struct TimePredictor { double wn, wm1, wm2; };
+inline TimePredictor bdf2_predictor_weights(double h, double h1, double h2) {
+  TimePredictor w;
+  w.wn = (h + h1 + h2) * (h + h1) / ((h1 + h2) * h1);
+  w.wm1 = -((h + h1 + h2) * h) / (h1 * h2);
+  w.wm2 = (h + h1) * h / (h2 * (h1 + h2));
+  return w;
+}
+// d = (u - p) kappa is BDF2's local error: u_exact - p = u'''/6 h (h + h1)(h + h1 + h2), the step's own error is
+// u'''/6 h^2 (h + h1)(1 + omega)/(1 + 2 omega) with the same sign, so with c = h / alpha0 the share of the second in the sum u - p
+// is kappa = c / (h + h1 + h2 + c).
+inline double bdf2_error_share(double h, double h1, double h2) {
+  const double c = h / bdf2_alpha0(h / h1);
+  return c / (h + h1 + h2 + c);
 }
 
 // Predicted start x0 = a dx_k + b dx_{k-1} of the linear solve of Newton iteration `iteration` (0-based), q = 1 - omega: with the

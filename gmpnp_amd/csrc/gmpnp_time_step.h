@@ -16,6 +16,8 @@
 //   k_time_shift   the accept as one pass: reads u and u_n, writes u_n and u_nm1
 // The reject is a device copy.  No atomics on data.  The batched forms for ensembles: gmpnp_time_step_ens.h.  u_nm1, the partials and the report are allocated by the first call of the
 // family: a handle that never asks keeps the buffers and launches it had.  Included at the end of gmpnp_api.hip.
+// Second order (variable-step BDF2: its set-up, its estimator and the three-deep shift gmpnp_time_accept launches on an order-2
+// handle): gmpnp_time_order.h, included behind this file.
 #pragma once
 
 namespace gmpnp {
@@ -143,6 +145,8 @@ int time_error_launch(gmpnp_solver* s, double h, double h_prev, bool history, co
   return GMPNP_OK;
 }
 
+int time_shift3_launch(gmpnp_solver* s);   // gmpnp_time_order.h
+
 int time_shift_launch(gmpnp_solver* s) {
   hipLaunchKernelGGL(k_time_shift, dim3(grid_for(s->ndof, kVecBlock)), dim3(kVecBlock), 0, s->stream, (const double*)s->u.p, s->un.p,
                      s->stepper->unm1.p, s->ndof);
@@ -173,6 +177,20 @@ int time_kernel_end(gmpnp_solver* s, DevBuf<double>& keep) {
   HIP_TRY(hipMemcpyAsync(s->un.p, keep.p, (size_t)s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   HIP_TRY(hipMemcpyAsync(s->stepper->unm1.p, keep.p + s->ndof, (size_t)s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
+  return GMPNP_OK;
+}
+
+// model.inv_dt of the handle and of every coarse level below it (gmpnp_attach_coarse_level): the time term is the diagonal of the
+// species blocks
+int time_step_apply(gmpnp_solver* s, double inv_dt) {
+  for (gmpnp_solver* l = s; l; l = l->ml_coarse) {
+    HIP_TRY(hipSetDevice(l->opts.device_id));
+    HIP_TRY(hipStreamSynchronize(l->stream));
+    if (l->stream2) HIP_TRY(hipStreamSynchronize(l->stream2));
+    l->model.inv_dt = inv_dt;
+    HIP_TRY(hipMemcpy(l->d_model.p, &l->model, sizeof(gmpnp_model_t), hipMemcpyHostToDevice));
+    l->jacobian_valid = false; l->precond_valid = false;
+  }
   return GMPNP_OK;
 }
 
@@ -215,16 +233,8 @@ int gmpnp_set_time_step(gmpnp_solver* s, double inv_dt) {
   if (!s) return fail(GMPNP_ERR_INVALID, "NULL handle");
   if (s->partitioned) return fail(GMPNP_ERR_INVALID, "gmpnp_set_time_step: partition handles have no adaptive time stepping");
   if (!time_step_valid(inv_dt)) return fail(GMPNP_ERR_INVALID, "gmpnp_set_time_step: inv_dt must be finite and >= 0 (0 = steady form)");
-  // the handle and every coarse level below it (gmpnp_attach_coarse_level): the time term is the diagonal of the species blocks
-  for (gmpnp_solver* l = s; l; l = l->ml_coarse) {
-    HIP_TRY(hipSetDevice(l->opts.device_id));
-    HIP_TRY(hipStreamSynchronize(l->stream));
-    if (l->stream2) HIP_TRY(hipStreamSynchronize(l->stream2));
-    l->model.inv_dt = inv_dt;
-    HIP_TRY(hipMemcpy(l->d_model.p, &l->model, sizeof(gmpnp_model_t), hipMemcpyHostToDevice));
-    l->jacobian_valid = false; l->precond_valid = false;
-  }
-  return GMPNP_OK;
+  time_read_un(s);   // a backward Euler step: the time term reads u_n (it may have read u* since gmpnp_set_time_step_bdf2)
+  return time_step_apply(s, inv_dt);
 }
 
 int gmpnp_time_error(gmpnp_solver* s, double h, double h_prev, const gmpnp_time_tol_t* tol, gmpnp_time_error_t* out) {
@@ -246,8 +256,8 @@ int gmpnp_time_accept(gmpnp_solver* s) {
   if (!s) return fail(GMPNP_ERR_INVALID, "NULL handle");
   int rc = time_prepare(s, "gmpnp_time_accept"); if (rc) return rc;
   // stream-ordered like gmpnp_assign_previous: whatever reads u_n / u_nm1 next is launched behind the pass
-  rc = time_shift_launch(s); if (rc) return rc;
-  s->stepper->has_history = true;
+  rc = s->stepper->order == 2 ? time_shift3_launch(s) : time_shift_launch(s); if (rc) return rc;
+  s->stepper->accepted();
   return GMPNP_OK;
 }
 

@@ -190,7 +190,7 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action) {
   HIP_TRY(hipStreamSynchronize(e->stream));   // complete when it returns, like every ensemble call
   for (int k : list) {
     gmpnp_solver* s = e->m[k];
-    if (action[k] == 1) s->stepper->has_history = true;                    // gmpnp_time_accept
+    if (action[k] == 1) s->stepper->accepted();                            // gmpnp_time_accept
     else { s->state_jumped = true; s->jacobian_valid = false; }            // gmpnp_time_reject
   }
   return GMPNP_OK;

@@ -48,14 +48,16 @@ def output_root():
 
 class EDLRun:
     def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, adaptive_dt=False,
-                 dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0, max_steps=None, **kwargs):
+                 dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0, max_steps=None, dt_order=1,
+                 **kwargs):
         """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
         ``step_fraction`` = tau in (0, 1): the Newton updates go through the fraction-to-boundary step limiter
         (``newton_solver["step_fraction"]``, include/gmpnp.h; not a reference feature); 0 = off, the reference's plain Newton.
         ``adaptive_dt`` = True: the step size is the error controller's (gmpnp_amd/timestep.py; all times in the driver's scaled
         units): ``dt_rtol`` / ``dt_atol`` its weights, ``dt_init`` the first step (default: the reference step), ``dt_min`` /
         ``dt_max`` its bounds, ``t_end`` the end time (default: the end of the schedule), ``steady_tol`` > 0 the steady stop,
-        ``max_steps`` the largest number of attempted steps.  A rejected step leaves the clock, the history, the budget log and the
+        ``max_steps`` the largest number of attempted steps, ``dt_order`` = 2 variable-step BDF2 in backward Euler's place (after its
+        start-up; the log gets an ``order`` column and the metadata ``dt_order``).  A rejected step leaves the clock, the history, the budget log and the
         SUPG parameters as they were.  Not with ``H_OHP``: its multiplicative flux controller is calibrated per fixed step
         (ValueError, before anything touches the device).  Off: nothing changes."""
         self.adaptive = bool(adaptive_dt)
@@ -91,7 +93,7 @@ class EDLRun:
             L_D = ep.L_D
             self.stepping = DriverStepping(self.sys, self.solver_parameters, lambda h: 1.0 / (h * L_D), ep.dts[0], ep.stage_T[-1],
                                            dt_rtol=dt_rtol, dt_atol=dt_atol, dt_init=dt_init, dt_min=dt_min, dt_max=dt_max, t_end=t_end,
-                                           steady_tol=steady_tol, max_steps=max_steps)
+                                           steady_tol=steady_tol, max_steps=max_steps, dt_order=dt_order)
             self.stepper, self.times = self.stepping.stepper, self.stepping.times   # times: the actual times of the history rows
             self._supg_stale = True    # the SUPG parameters follow u_n: recomputed after an accepted step only
 

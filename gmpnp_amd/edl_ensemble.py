@@ -16,7 +16,7 @@ import itertools
 from . import backend
 from .edl1d import EDLRun, run_identifier
 from .params import edl_parameters
-from .timestep import member_adaptive_keywords
+from .timestep import member_adaptive_keywords, refuse_ensemble_order2
 
 # keyword surface of solve_EDL / EDLRun (reference 1D:66-79) and its defaults
 MEMBER_DEFAULTS = {"concentration_elec": 0.1, "model": "MPNP", "voltage_multiplier": -1.0, "H2_FE": 0.2,
@@ -133,6 +133,7 @@ class EDLEnsemble(AdaptiveRounds):
         members = [dict(m) for m in members]
         if any(m.get("adaptive_dt") for m in members):   # before anything touches the device
             raise ValueError(ADAPTIVE_REFUSAL)
+        refuse_ensemble_order2(members, adaptive)
         self.adaptive = bool(adaptive_dt)
         per_member = member_adaptive_keywords(len(members), adaptive)
         if self.adaptive and any(m.get("H_OHP") is not None for m in members):

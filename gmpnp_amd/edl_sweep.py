@@ -92,6 +92,9 @@ def main(argv=None):
     common = dict(model=a.model, mesh_structure=a.mesh_structure, H2_FE=a.H2_FE, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                   H_OHP=a.H_OHP, params_file=a.params_file, dry_run=not a.staged)
     members = sweep_members(a.voltage_multiplier, a.cation, a.concentration_elec, **common)
+    if a.dt_order != 1:   # (before anything touches the device)
+        from .timestep import ORDER2_ENSEMBLE_REFUSAL
+        raise ValueError("--" + ORDER2_ENSEMBLE_REFUSAL)
     rows, path = run_sweep(members, num_steps=a.num_steps, device_id=a.device_id, log=lambda s: print(s, flush=True), budget=a.budget, step_fraction=a.step_fraction,
                            **(adaptive_keywords(a) if a.adaptive_dt else {}))
     print(path)

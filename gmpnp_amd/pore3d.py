@@ -48,7 +48,7 @@ class PoreRun:
     def __init__(self, num_steps=None, as_published=False, device_kwargs=None, solver_parameters=None, refine=0,
                  partition=None, multilevel=False, ml_theta=2.0, ml_sweeps=4, glue="host", budget=False, step_fraction=0.0,
                  adaptive_dt=False, dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0,
-                 max_steps=None, **kwargs):
+                 max_steps=None, dt_order=1, **kwargs):
         """``partition`` = (nparts, rank): solve this ONE problem across `nparts` mesh partitions (rank None: all of them in
         this process on one GPU; rank r: this process is rank r of a ``torch.distributed`` job, RCCL inside the library).
         ``multilevel`` (with ``refine`` > 0): the preconditioner gets the geometric multilevel term over the nested meshes
@@ -68,7 +68,8 @@ class PoreRun:
         ``adaptive_dt`` = True: the step size is the error controller's (gmpnp_amd/timestep.py; not a reference feature), ``inv_dt`` =
         1/h in the driver's scaled time: ``dt_rtol`` / ``dt_atol`` its weights, ``dt_init`` the first step (default: the reference
         step), ``dt_min`` / ``dt_max`` its bounds, ``t_end`` the end time (default: the driver's T), ``steady_tol`` > 0 the steady
-        stop, ``max_steps`` the largest number of attempted steps.  A rejected step leaves the clock, the history, the budget log and
+        stop, ``max_steps`` the largest number of attempted steps, ``dt_order`` = 2 variable-step BDF2 in backward Euler's place
+        (after its start-up).  A rejected step leaves the clock, the history, the budget log and
         the CO2 Dirichlet value as they were.  Not with ``partition`` (ValueError, before anything touches the device).  Off: nothing
         changes."""
         if glue not in ("host", "device"):
@@ -124,7 +125,7 @@ class PoreRun:
         if self.adaptive:
             self.stepping = DriverStepping(self.sys, self.solver_parameters, lambda h: 1.0 / h, self.pp.dt, self.pp.T, dt_rtol=dt_rtol,
                                            dt_atol=dt_atol, dt_init=dt_init, dt_min=dt_min, dt_max=dt_max, t_end=t_end, steady_tol=steady_tol,
-                                           max_steps=max_steps)
+                                           max_steps=max_steps, dt_order=dt_order)
             self.stepper, self.times = self.stepping.stepper, self.stepping.times   # times: the actual times of the history rows
 
     def adaptive_step(self, verbose=True):

@@ -17,7 +17,7 @@ from . import backend
 from .edl_ensemble import ADAPTIVE_REFUSAL, AdaptiveRounds, error_text
 from .pore3d import SOLVER_PARAMETERS, PoreRun
 from .solver import column_medians
-from .timestep import member_adaptive_keywords
+from .timestep import member_adaptive_keywords, refuse_ensemble_order2
 
 # what may differ between the members of one ensemble (keywords of ``solveEDL``, reference 3D:96-113) and their defaults
 MEMBER_DEFAULTS = {"concentration_elec": 1.0, "voltage_multiplier": -1.0, "cation": "K", "H2_FE": 0.05, "current_rough": 3000.0,
@@ -76,6 +76,7 @@ class PoreEnsemble(AdaptiveRounds):
         members = [dict(m) for m in members]
         if any(m.get("adaptive_dt") for m in members):   # before anything touches the device
             raise ValueError(ADAPTIVE_REFUSAL)
+        refuse_ensemble_order2(members, adaptive)
         self.adaptive = bool(adaptive_dt)
         per_member = member_adaptive_keywords(len(members), adaptive)
         self.kwargs, steps = plan_members(members, num_steps)

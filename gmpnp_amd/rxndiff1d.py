@@ -136,7 +136,7 @@ class RxnDiffRun:
     def __init__(self, num_steps=None, device_kwargs=None, solver_parameters=None, budget=False, step_fraction=0.0, **kwargs):
         """``budget`` = True: every step records its species-budget table; ``write_outputs`` adds ``budget.npz`` (gmpnp_amd/budget.py).
         ``step_fraction``: tau of the step limiter of the Newton update (``newton_solver["step_fraction"]``), 0 = off.
-        ``adaptive_dt`` = True with ``dt_rtol``, ``dt_atol``, ``dt_init``, ``dt_min``, ``dt_max``, ``t_end``, ``steady_tol``, ``max_steps``
+        ``adaptive_dt`` = True with ``dt_rtol``, ``dt_atol``, ``dt_init``, ``dt_min``, ``dt_max``, ``t_end``, ``steady_tol``, ``max_steps``, ``dt_order``
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history and the budget log as they were.  Off: nothing changes."""
         adaptive = timestep.pop_adaptive(kwargs)

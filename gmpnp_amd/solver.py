@@ -101,6 +101,19 @@ class GMPNPSystem(_System):
     def time_reject(self):
         self.dev.time_reject()
 
+    # second order (variable-step BDF2)
+    def set_time_order(self, order):
+        self.dev.set_time_order(order)
+
+    def time_history_levels(self):
+        return self.dev.time_history_levels()
+
+    def set_time_step_bdf2(self, inv_dt, ratio):
+        self.dev.set_time_step_bdf2(inv_dt, ratio)
+
+    def time_error_bdf2(self, h, h_prev, h_prev2, rtol, atol):
+        return self.dev.time_error_bdf2(h, h_prev, h_prev2, rtol, atol)
+
     def owned_vertex_values(self):
         """[(vertex ids, (n, nf) values)] of the rows this process owns: here all of them."""
         return [(np.arange(self.nv), self.vertex_values())]
@@ -141,6 +154,7 @@ class PartitionedSystem(_System):
         raise ValueError("adaptive time stepping is not available on a partitioned system")
 
     set_time_step = time_error = time_accept = time_reject = _no_adaptive
+    set_time_order = time_history_levels = set_time_step_bdf2 = time_error_bdf2 = _no_adaptive   # (order 2 no more than order 1)
 
     def owned_vertex_values(self):
         """[(global vertex ids, (n_owned, nf) values)] of this process's partitions: one device-to-host copy each, no collective."""

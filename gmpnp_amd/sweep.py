@@ -163,6 +163,9 @@ def main(argv=None):
     if a.adaptive_dt and not a.ensemble:
         raise ValueError("--adaptive_dt: the sweep steps adaptively as a device ensemble only (add --ensemble); a single adaptive "
                          "run is gmpnp_amd.pore3d --adaptive_dt")
+    if a.dt_order != 1:   # (before anything touches the device)
+        from .timestep import ORDER2_ENSEMBLE_REFUSAL
+        raise ValueError("--" + ORDER2_ENSEMBLE_REFUSAL)
     adaptive = adaptive_keywords(a) if a.adaptive_dt else {}
     from .dist import init_process_group_from_env
     rank, world, local, dist = init_process_group_from_env(a.backend or "nccl")

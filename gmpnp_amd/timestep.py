@@ -1,5 +1,6 @@
 """Adaptive time stepping with error control and a steady-state stop (not a reference feature: the reference marches with the
-step of its YAML file).  Backward Euler; the step is chosen from the device's estimate of its local error (include/gmpnp.h,
+step of its YAML file).  Backward Euler, or with ``order`` = 2 variable-step BDF2 after a backward Euler start-up (DESIGN.md section
+5g; kernels: csrc/gmpnp_time_order.h); the step is chosen from the device's estimate of its local error (include/gmpnp.h,
 gmpnp_time_error; kernels: csrc/gmpnp_time_step.h).  ``next_time_step`` is the Python statement of the rule that
 csrc/gmpnp_host_rules.h states in C++ (``next_time_step`` there; tests/test_time_step_reference.py compiles that one with the host
 compiler and holds both against a NumPy restatement of its own).  ``AdaptiveStepper`` owns the loop body of one attempted step,
@@ -14,6 +15,21 @@ import numpy as np
 from . import backend
 
 REASONS = ("accepted", "error_too_large", "newton_failed", "nonfinite")
+
+
+def _c_cbrt():
+    """The C library's cbrt, the function std::cbrt of csrc/gmpnp_host_rules.h calls (``math.cbrt`` where Python has it; NumPy's
+    cube root is another implementation and differs from it in the last bit, e.g. at 0.125)."""
+    if hasattr(math, "cbrt"):
+        return math.cbrt
+    import ctypes
+    import ctypes.util
+    fn = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6").cbrt
+    fn.restype, fn.argtypes = ctypes.c_double, [ctypes.c_double]
+    return fn
+
+
+cbrt = _c_cbrt()
 
 
 @dataclass
@@ -41,17 +57,20 @@ class TimeStepDecision:
     steady_run: int      # the steady counter after this attempt (handed back in at the next one)
 
 
-def next_time_step(p: TimeStepPolicy, t, h, err, has_history, newton_failed, rate, steady_run) -> TimeStepDecision:
+def next_time_step(p: TimeStepPolicy, t, h, err, has_history, newton_failed, rate, steady_run, order=1) -> TimeStepDecision:
     """The accept / reject rule of one attempted step h at time t.  The exponent of the step factor is 1/2 because backward
-    Euler's LOCAL error is O(h^2): err(h') = err(h) (h'/h)^2 = 1 at h' = h err^(-1/2), times the safety factor."""
+    Euler's LOCAL error is O(h^2): err(h') = err(h) (h'/h)^2 = 1 at h' = h err^(-1/2), times the safety factor.  ``order`` = 2
+    (a BDF2 step, local error O(h^3)): the factor is safety err^(-1/3) and an accepted step grows by min(max_factor, 2) at most
+    (variable-step BDF2 is zero-stable only for h / h_prev < 1 + sqrt(2)); everything else is the same rule."""
     nan_err = err != err
 
     def factor(hi):
         if not has_history:
             return 1.0
         if err > 0.0:
-            return min(max(p.safety / math.sqrt(err), p.min_factor), hi)
+            return min(max(p.safety / (cbrt(err) if order == 2 else math.sqrt(err)), p.min_factor), hi)
         return hi
+    grow = min(p.max_factor, 2.0) if order == 2 else p.max_factor
 
     stop_steady = False
     if newton_failed or nan_err:
@@ -59,7 +78,7 @@ def next_time_step(p: TimeStepPolicy, t, h, err, has_history, newton_failed, rat
     elif has_history and err > 1.0:
         accept, reason, t_next, h_next, run = False, 1, t, h * factor(1.0), steady_run
     else:
-        accept, reason, t_next, h_next = True, 0, t + h, h * factor(p.max_factor)
+        accept, reason, t_next, h_next = True, 0, t + h, h * factor(grow)
         run = steady_run + 1 if (p.steady_tol > 0.0 and rate < p.steady_tol) else 0
         stop_steady = p.steady_tol > 0.0 and run >= p.steady_steps
     if h_next > p.h_max:
@@ -75,17 +94,51 @@ def next_time_step(p: TimeStepPolicy, t, h, err, has_history, newton_failed, rat
     return TimeStepDecision(accept, reason, t_next, h_next, stop_end, stop_steady, give_up, run)
 
 
+# ---- the coefficients of variable-step BDF2 (csrc/gmpnp_host_rules.h states them in C++, statement for statement) ---------------
+def bdf2_alpha0(omega):
+    return (1.0 + 2.0 * omega) / (1.0 + omega)
+
+
+def bdf2_history_weights(omega):
+    """(a, b) of u* = a u_n - b u_nm1."""
+    q = 1.0 + 2.0 * omega
+    return (1.0 + omega) * (1.0 + omega) / q, omega * omega / q
+
+
+def bdf2_predictor_weights(h, h1, h2):
+    """Lagrange weights (u_n, u_nm1, u_nm2) at t + h of the quadratic through (t - h1 - h2, u_nm2), (t - h1, u_nm1), (t, u_n)."""
+    wn = (h + h1 + h2) * (h + h1) / ((h1 + h2) * h1)
+    wm1 = -((h + h1 + h2) * h) / (h1 * h2)
+    wm2 = (h + h1) * h / (h2 * (h1 + h2))
+    return wn, wm1, wm2
+
+
+def bdf2_error_share(h, h1, h2):
+    """kappa: BDF2's local error as a share of u - p."""
+    c = h / bdf2_alpha0(h / h1)
+    return c / (h + h1 + h2 + c)
+
+
 class AdaptiveStepper:
     """The loop body of an adaptive run on a ``GMPNPSystem``: set the step, solve, estimate, decide, accept or reject.
     ``tol`` = (rtol, atol) with atol a scalar or one value per field; ``inv_dt_of_h(h)`` = the model's inv_dt for a step h in the
-    driver's time units (3D: 1/h, 1D: 1/(h L_D), L_D the scaled Debye length).  ``log`` holds one row per attempt."""
+    driver's time units (3D: 1/h, 1D: 1/(h L_D), L_D the scaled Debye length).  ``log`` holds one row per attempt.
+    ``order`` = 2: variable-step BDF2.  The order of each attempt follows the handle's history: backward Euler without an estimate,
+    backward Euler with its estimate, then BDF2 for as long as the handle holds three accepted states (``order`` in the row)."""
 
     COLUMNS = ("t", "h", "accepted", "reason", "err", "rate", "newton", "krylov", "worst_dof", "steric_excursion")
 
-    def __init__(self, system, policy: TimeStepPolicy, tol, inv_dt_of_h, h_init, t0=0.0, solver_parameters=None):
+    def __init__(self, system, policy: TimeStepPolicy, tol, inv_dt_of_h, h_init, t0=0.0, solver_parameters=None, order=1):
         from .solver import PartitionedSystem
         if isinstance(system, PartitionedSystem):
             raise ValueError("adaptive time stepping is not available on a partitioned system")
+        if order not in (1, 2):
+            raise ValueError("order is 1 (backward Euler) or 2 (variable-step BDF2)")
+        self.order = int(order)
+        self.h_prev2 = 0.0
+        self.columns = self.COLUMNS + (("order",) if self.order == 2 else ())
+        if self.order == 2:
+            system.set_time_order(2)
         self.sys, self.policy, self.inv_dt_of_h = system, policy, inv_dt_of_h
         self.rtol, self.atol = float(tol[0]), tol[1]
         self.solver_parameters = solver_parameters
@@ -113,22 +166,24 @@ class AdaptiveStepper:
             raise RuntimeError("the adaptive run has ended (%s)" % self.stop_reason)
         return self.t, self.h
 
-    def decide(self, t, h, st, failed, est):
+    def decide(self, t, h, st, failed, est, order=1):
         """The decision and the log row of the attempt (t, h): ``st`` = the Newton statistics (None: none came back), ``failed`` =
         Newton gave up (``RETRY_CODES``), ``est`` = the estimator's report of a converged solve, else None."""
         err = est["err"] if est else 0.0
         rate = est["rate"] if est else math.inf
-        d = next_time_step(self.policy, t, h, err, bool(est and est["has_history"]), failed, rate, self.steady_run)
+        d = next_time_step(self.policy, t, h, err, bool(est and est["has_history"]), failed, rate, self.steady_run, order)
         row = {"t": t, "h": h, "accepted": bool(d.accept), "reason": d.reason, "err": err if est else math.nan,
                "rate": rate if est else math.nan, "newton": st["iterations"] if st else -1,
                "krylov": st["krylov_iterations"] if st else -1, "worst_dof": est["worst_dof"] if est else -1,
                "steric_excursion": st["steric_excursion"] if st else -1}
+        if self.order == 2:
+            row["order"] = order
         return d, row
 
     def finish(self, d, row):
         """The clock, the controller's memory, the log and the stop reason after the attempt's accept / reject went to the device."""
         if d.accept:
-            self.h_prev = row["h"]
+            self.h_prev2, self.h_prev = self.h_prev, row["h"]
         self.t, self.h, self.steady_run = d.t_next, d.h_next, d.steady_run
         self.log.append(row)
         self.last_decision = d
@@ -145,7 +200,11 @@ class AdaptiveStepper:
         (budgets, history row, new Dirichlet values) — a rejected step calls neither it nor anything else of the driver.
         Returns the log row.  (``EnsembleStepper.round`` runs the same phases for many members at once.)"""
         t, h = self.start()
-        self.sys.set_time_step(self.inv_dt_of_h(h))
+        order = 2 if (self.order == 2 and self.sys.time_history_levels() >= 2) else 1
+        if order == 2:
+            self.sys.set_time_step_bdf2(self.inv_dt_of_h(h), h / self.h_prev)
+        else:
+            self.sys.set_time_step(self.inv_dt_of_h(h))
         if before_solve is not None:
             before_solve(t, h)
         st, failed = None, False
@@ -163,9 +222,11 @@ class AdaptiveStepper:
         if failed and st is not None:   # solve() accounts converged solves only
             self.sys.record(st)
         est = None
-        if not failed:
+        if not failed and order == 2:
+            est = self.sys.time_error_bdf2(h, self.h_prev, self.h_prev2, self.rtol, self.atol)
+        elif not failed:
             est = self.sys.time_error(h, self.h_prev, self.rtol, self.atol)
-        d, row = self.decide(t, h, st, failed, est)
+        d, row = self.decide(t, h, st, failed, est, order)
         if d.accept:
             if before_accept is not None:
                 before_accept(st)
@@ -178,16 +239,19 @@ class AdaptiveStepper:
     def log_arrays(self):
         """The log as arrays by column (what ``timestep_log.npz`` holds)."""
         out = {}
-        for c in self.COLUMNS:
+        for c in self.columns:
             kind = np.float64 if c in ("t", "h", "err", "rate") else (np.bool_ if c == "accepted" else np.int64)
             out[c] = np.array([r[c] for r in self.log], dtype=kind)
         return out
 
     def summary(self):
         """The keys an adaptive run adds to metadata.json."""
-        return {"adaptive_dt": True, "dt_rtol": self.rtol, "dt_atol": np.asarray(self.atol, dtype=float).tolist(),
-                "steps_accepted": self.accepted, "steps_rejected": self.rejected, "newton_failures": self.newton_failures,
-                "t_reached": self.t, "stop_reason": self.stop_reason}
+        out = {"adaptive_dt": True, "dt_rtol": self.rtol, "dt_atol": np.asarray(self.atol, dtype=float).tolist(),
+               "steps_accepted": self.accepted, "steps_rejected": self.rejected, "newton_failures": self.newton_failures,
+               "t_reached": self.t, "stop_reason": self.stop_reason}
+        if self.order == 2:
+            out["dt_order"] = 2
+        return out
 
 
 # a Newton solve that ends with one of these is a failed ATTEMPT (rejected and tried again with a smaller step), as in ``attempt``
@@ -290,7 +354,18 @@ class EnsembleStepper:
 
 # ---- what the four drivers share ----------------------------------------------------------------------------------------------------
 ADAPTIVE_KEYWORDS = dict(adaptive_dt=False, dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None, t_end=None, steady_tol=0.0,
-                         max_steps=None)
+                         max_steps=None, dt_order=1)
+ORDER2_ENSEMBLE_REFUSAL = ("dt_order=2: the device ensembles have no order 2 (variable-step BDF2) yet; an order-2 adaptive run is a "
+                           "single run (EDLRun / PoreRun / RxnDiffRun / RxnPoreRun with adaptive_dt=True, dt_order=2)")
+
+
+def refuse_ensemble_order2(members, adaptive):
+    """ValueError when a member dict or an adaptive-stepping keyword of an ensemble asks for order 2 (before anything touches the
+    device)."""
+    asked = [adaptive.get("dt_order", 1)] + [m.get("dt_order", 1) for m in members]
+    for v in asked:
+        if any(int(x) != 1 for x in (v if isinstance(v, (list, tuple, np.ndarray)) else [v])):
+            raise ValueError(ORDER2_ENSEMBLE_REFUSAL)
 
 
 def pop_adaptive(kwargs):
@@ -327,6 +402,8 @@ def add_adaptive_arguments(p):
     p.add_argument("--t_end", required=False, default=None, type=float, help="(addition) end time (default: the driver's own T)")
     p.add_argument("--steady_tol", required=False, default=0.0, type=float, help="(addition) stop when the rate of change stays below it; 0 = off")
     p.add_argument("--max_steps", required=False, default=None, type=int, help="(addition) largest number of attempted steps")
+    p.add_argument("--dt_order", required=False, default=1, type=int, choices=(1, 2),
+                   help="(addition) 1 = backward Euler, 2 = variable-step BDF2 after a backward Euler start-up")
 
 
 def adaptive_keywords(a):
@@ -339,11 +416,11 @@ class DriverStepping:
     ``T`` = the driver's own end time), the actual times of the history rows, the attempt loop and the outputs."""
 
     def __init__(self, system, solver_parameters, inv_dt_of_h, h_ref, T, dt_rtol=1e-2, dt_atol=1e-4, dt_init=None, dt_min=0.0, dt_max=None,
-                 t_end=None, steady_tol=0.0, max_steps=None, adaptive_dt=True):
+                 t_end=None, steady_tol=0.0, max_steps=None, adaptive_dt=True, dt_order=1):
         policy = TimeStepPolicy(h_min=float(dt_min), h_max=math.inf if dt_max is None else float(dt_max),
                                 t_end=float(T) if t_end is None else float(t_end), steady_tol=float(steady_tol))
         self.stepper = AdaptiveStepper(system, policy, (dt_rtol, dt_atol), inv_dt_of_h, h_ref if dt_init is None else float(dt_init),
-                                       solver_parameters=solver_parameters)
+                                       solver_parameters=solver_parameters, order=dt_order)
         self.max_steps = None if max_steps is None else int(max_steps)
         self.times = [0.0]
 

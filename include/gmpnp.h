@@ -271,6 +271,38 @@ int gmpnp_time_accept(gmpnp_solver* s);
 /* u <- u_n (device copy); the history stays.  The next Newton solve starts from a state set from outside (no coarse reuse). */
 int gmpnp_time_reject(gmpnp_solver* s);
 
+/* ---- second-order adaptive time stepping: variable-step BDF2 (opt-in; kernels: csrc/gmpnp_time_order.h) ----
+ * A handle that never calls gmpnp_set_time_order(s, 2) keeps the buffers, launches and results of the calls above.  With
+ * omega = h / h_prev the BDF2 time term is (alpha0 / h) M (u - u*), alpha0 = (1 + 2 omega)/(1 + omega),
+ * u* = ((1 + omega)^2 u_n - omega^2 u_nm1)/(1 + 2 omega): the shape of backward Euler's inv_dt M (u - u_n) with another scalar and
+ * another vector, so the residual, the Jacobian and the species budgets of an order-2 step come from the same kernels.  The handle
+ * counts the accepted states behind u_n (levels: 0, 1 = u_nm1, 2 = u_nm1 and u_nm2); gmpnp_time_accept raises the count,
+ * gmpnp_time_reject keeps it, a gmpnp_set_state that writes u_n and gmpnp_assign_previous reset it to 0.  has_history of the calls
+ * above is levels >= 1.  The estimator of an order-2 step, over the free dofs, h1 / h2 the two accepted steps before h:
+ *     p = the quadratic through (t - h1 - h2, u_nm2), (t - h1, u_nm1), (t, u_n) at t + h
+ *     d = (u - p) kappa,  kappa = c / (h + h1 + h2 + c),  c = h / alpha0        w, err_f, rate_f, worst_dof, nonfinite: as above
+ * (u_exact - p = u'''/6 h (h + h1)(h + h1 + h2) and BDF2's local error is u'''/6 h^2 (h + h1)(1 + omega)/(1 + 2 omega), the same sign:
+ * kappa is the second's share of their sum.)  The coefficients are host functions of csrc/gmpnp_host_rules.h, where the
+ * accept / reject rule of order 2 lives too (next_time_step with order = 2).  Partition handles are refused (GMPNP_ERR_INVALID), and
+ * so is every gmpnp_ensemble_* call that solves, estimates or advances while a member is at order 2. */
+/* order 1 (backward Euler, the default) or 2.  2 allocates u_nm2 and u* on the first call; from then on gmpnp_time_accept shifts
+ * three deep (u_nm2 <- u_nm1 <- u_n <- u, one launch) and counts up to 2 levels.  1 makes the time term read u_n again and caps the
+ * levels at 1. */
+int gmpnp_set_time_order(gmpnp_solver* s, int32_t order);
+int gmpnp_time_history_levels(gmpnp_solver* s, int32_t* levels);
+/* The set-up of a BDF2 step: u* is formed on the device (one launch), model.inv_dt becomes alpha0(ratio) * inv_dt on the host and the
+ * device of this handle and of every attached coarse level, the time term reads u* in u_n's place, the Jacobian and the
+ * preconditioner are invalidated.  inv_dt as gmpnp_set_time_step's; ratio = h / h_prev finite and > 0; the handle at order 2 with
+ * levels >= 1.  A later gmpnp_set_time_step is a backward Euler step again and reads u_n.  gmpnp_get_state, the estimators,
+ * gmpnp_time_reject and the rate of change always see the true u_n. */
+int gmpnp_set_time_step_bdf2(gmpnp_solver* s, double inv_dt, double ratio);
+/* The estimator above for the step u_n -> u of length h (h_prev, h_prev2: the two accepted steps before it).  With fewer than 2
+ * levels, or h_prev <= 0 or h_prev2 <= 0: has_history = 0 and the err values are 0, the rates are computed all the same.  Fixed-order
+ * reductions: two calls give the same bits. */
+int gmpnp_time_error_bdf2(gmpnp_solver* s, double h, double h_prev, double h_prev2, const gmpnp_time_tol_t* tol, gmpnp_time_error_t* out);
+/* u* of the last gmpnp_set_time_step_bdf2, file order [n_dofs] (for tests). */
+int gmpnp_get_time_history(gmpnp_solver* s, double* out);
+
 /* solve(F == 0, u, bcs, solver_parameters) (3D:789-799, 1D:737-742): damped Newton on the device state u.
  * Returns GMPNP_ERR_NOT_CONVERGED where DOLFIN raises RuntimeError; stats are filled either way. */
 int gmpnp_newton_solve(gmpnp_solver* s, const gmpnp_newton_options_t* opts, gmpnp_newton_stats_t* stats);
@@ -538,7 +570,9 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * and up; needs an assembled Jacobian), 19 = element kernel without J (with 3: one residual evaluation), 20 = the launch chain of one
  * gmpnp_species_budget call (element kernel without J, cell pass, row pass, final sums), 21 = the two launches of the step limiter
  * (k_step_limit + k_limited_update, on a zero correction: the state stays), 22 = the three launches of an accepted adaptive time step
- * (estimator + reduce + shift; u_n and u_nm1 are put back afterwards, the history flag stays). */
+ * (estimator + reduce + shift; u_n and u_nm1 are put back afterwards, the history flag stays), 23 = the four launches of an accepted
+ * order-2 step (u*, order-2 estimator, reduce, three-deep shift; u_n, u_nm1 and u_nm2 are put back, the order and the levels stay;
+ * allocates the order-2 vectors). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
