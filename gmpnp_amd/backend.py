@@ -41,6 +41,7 @@ EXPORTS = [
     "gmpnp_step_limit",
     "gmpnp_set_time_step", "gmpnp_time_error", "gmpnp_time_accept", "gmpnp_time_reject",
     "gmpnp_set_time_order", "gmpnp_time_history_levels", "gmpnp_set_time_step_bdf2", "gmpnp_time_error_bdf2", "gmpnp_get_time_history",
+    "gmpnp_set_stern", "gmpnp_stern_displacement",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -83,6 +84,14 @@ class CTimeError(ctypes.Structure):
     """gmpnp_time_error_t (include/gmpnp.h, adaptive time stepping)."""
     _fields_ = [("err", c_double), ("err_field", c_double * 9), ("rate", c_double), ("rate_field", c_double * 9),
                 ("worst_dof", c_int64), ("has_history", c_int32), ("nonfinite", c_int32)]
+
+
+class CStern(ctypes.Structure):
+    """ctypes image of ``gmpnp_stern_t`` (include/gmpnp.h)."""
+    _fields_ = [("model", c_int32), ("p_electrode", c_double), ("lam", c_double), ("eps_surface", c_double)]
+
+
+STERN_MODELS = {"linear": 1, "BDM": 2}   # gmpnp_stern_t.model (0 = off)
 
 
 class CLinearStats(ctypes.Structure):
@@ -221,6 +230,8 @@ def load_library(path: str = None):
     lib.gmpnp_ensemble_time_advance.argtypes = [c_void_p, POINTER(c_int32)]
     for name in ("gmpnp_species_budget", "gmpnp_group_species_budget"):
         getattr(lib, name).argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_set_stern.argtypes = [c_void_p, POINTER(CStern)]
+    lib.gmpnp_stern_displacement.argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -386,6 +397,8 @@ class DeviceSolver:
         self._h = h
         if len(problem.bc_dofs):
             self.set_dirichlet(problem.bc_dofs, problem.bc_vals)
+        if getattr(problem, "stern", None) is not None:
+            self.set_stern(problem.stern)
 
     # ------------------------------------------------------------------------------------------
     def _check(self, code):
@@ -541,6 +554,21 @@ class DeviceSolver:
         form): per field ``storage + reaction + wall + exit + point = dirichlet + closure``; ``dirichlet`` is the consistent flux
         the Dirichlet rows supply, ``closure`` the sum of the residual over the free rows.  Leaves the handle's state untouched."""
         return species_budget_call(self.lib.gmpnp_species_budget, self._h, self.nf, self._check)
+
+    def set_stern(self, stern=None):
+        """Stern-layer boundary condition of the potential (``gmpnp_set_stern``): a ``problem.SternLayer`` record, or None = off."""
+        c = CStern()
+        if stern is not None:
+            if stern.model not in STERN_MODELS:
+                raise ValueError("Stern model must be one of %s" % sorted(STERN_MODELS))
+            c.model, c.p_electrode, c.lam, c.eps_surface = STERN_MODELS[stern.model], float(stern.p_electrode), float(stern.lam), float(stern.eps_surface)
+        self._check(self.lib.gmpnp_set_stern(self._h, byref(c)))
+
+    def stern_displacement(self) -> float:
+        """The integrated Stern term int g (p_M - p) / lam ds at the current u, in the scaled units of the weak form."""
+        out = c_double()
+        self._check(self.lib.gmpnp_stern_displacement(self._h, byref(out)))
+        return float(out.value)
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

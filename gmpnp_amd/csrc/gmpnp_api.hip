@@ -122,6 +122,16 @@ struct gmpnp_time_stepper {
   ~gmpnp_time_stepper() { if (h_report) (void)hipHostFree(h_report); }
 };
 
+// device side of the Stern-layer boundary condition (gmpnp_stern.h), allocated by the first gmpnp_set_stern with model != 0: a handle
+// that never asks for it keeps the buffers, launches and pointers it had
+struct gmpnp_sterner {
+  gmpnp_stern_t opt{};
+  int n_nodes = 0, n_pairs = 0;
+  DevBuf<int32_t> node, nf_ptr, nf_ent, fnodes, pair_row, pf_ptr, pf_ent;
+  DevBuf<int64_t> addr;
+  DevBuf<double> area, bnd_dyn, sum;   // bnd_dyn: bndF + the Stern term, what Ctx::bndF points at while the option is on
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -194,6 +204,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_budgeter> budgeter;
   std::unique_ptr<gmpnp_step_limiter> limiter;
   std::unique_ptr<gmpnp_time_stepper> stepper;
+  std::unique_ptr<gmpnp_sterner> sterner;
   // geometric multilevel term (gmpnp_attach_coarse_level, gmpnp_multilevel.h): the link to the next-coarser level (tables in the
   // internal orders of both handles) and this handle's buffers when it serves as a coarse level itself
   gmpnp_solver* ml_coarse = nullptr; double ml_theta = 1.0; bool ml_is_coarse = false;
@@ -236,6 +247,13 @@ namespace {
   } while (0)
 
 int grid_for(int n, int block) { return (n + block - 1) / block; }
+
+// gmpnp_stern.h: the Stern term of the potential rows in front of a residual gather, its Jacobian entries behind the Jacobian gather
+inline bool stern_on(const gmpnp_solver* s) { return s->sterner && s->sterner->opt.model != 0; }
+int stern_rebind(gmpnp_solver* s);
+int stern_launch_residual(gmpnp_solver* s, int32_t* status);
+int stern_launch_jacobian(gmpnp_solver* s);
+int stern_launch_sum(gmpnp_solver* s, double* table_entry);
 
 size_t coarse_lds_bytes(int n, int nf) { return (size_t)(n * n + n * nf + 2 * nf * nf) * sizeof(double); }
 
@@ -296,6 +314,7 @@ int rebuild_boundary(gmpnp_solver* s) {
   HIP_TRY(s->rob_row.upload(rrow)); HIP_TRY(s->rob_val.upload(rval)); HIP_TRY(s->rob_addr.upload(raddr));
   s->c.bndF = s->bndF.p; s->c.robF_ptr = s->robF_ptr.p; s->c.rob_col = s->rob_col.p; s->c.rob_row = s->rob_row.p;
   s->c.rob_val = s->rob_val.p; s->c.rob_addr = s->rob_addr.p; s->c.n_robin = (int)rval.size();
+  if (s->sterner) return stern_rebind(s);   // the new constant vector under the Stern term
   return GMPNP_OK;
 }
 
@@ -342,6 +361,7 @@ int launch_jac_gather(gmpnp_solver* s) {
   hipLaunchKernelGGL((k_jac_gather<DIM, NF>), dim3(g), dim3(kVecBlock), 0, s->stream, s->c);
   if (s->c.n_robin > 0) hipLaunchKernelGGL(k_robin_add, dim3(grid_for(s->c.n_robin, 256)), dim3(256), 0, s->stream, s->c);
   HIP_TRY(hipGetLastError());
+  if (stern_on(s)) return stern_launch_jacobian(s);
   return GMPNP_OK;
 }
 
@@ -368,6 +388,7 @@ double sum_partials(const gmpnp_solver* s, int row) {
 template <int DIM, int NF>
 int residual(gmpnp_solver* s, bool want_j, double* norm, int* flags) {
   int rc = launch_element<DIM, NF>(s, want_j); if (rc) return rc;
+  if (stern_on(s)) { rc = stern_launch_residual(s, s->status.p); if (rc) return rc; }
   rc = launch_res_gather<DIM, NF>(s); if (rc) return rc;
   // the partials and the status word land in pinned host memory by the kernel's own stores: no copy in the stream
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1628,6 +1649,7 @@ int gmpnp_assemble(gmpnp_solver* s, int32_t want_jacobian, double* F_out, double
   if (norm_out) *norm_out = r;
   if (F_out) { rc = download_vec(s, s->F.p, F_out); if (rc) return rc; }
   if ((flags & 1) && s->cfg.strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+  if (flags & 32) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
   return GMPNP_OK;
 }
 
@@ -1720,6 +1742,7 @@ int gmpnp_linear_solve(gmpnp_solver* s, const double* b, double* x, int32_t mode
 int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const int32_t* parents, double theta, int32_t sweeps) {
   if (!fine || !coarse || !parents) return fail(GMPNP_ERR_INVALID, "NULL argument");
   if (fine == coarse || coarse->ml_is_coarse) return fail(GMPNP_ERR_INVALID, "a level handle serves one finer level");
+  if (stern_on(fine) || stern_on(coarse)) return fail(GMPNP_ERR_INVALID, "multilevel term: not with the Stern boundary condition on a level (gmpnp_set_stern)");
   if (fine->dim != 3 || coarse->dim != 3 || fine->nf != 9 || coarse->nf != 9) return fail(GMPNP_ERR_INVALID, "multilevel term: 3D pore problems (9 fields)");
   if (fine->partitioned != coarse->partitioned) return fail(GMPNP_ERR_INVALID, "multilevel term: both levels partitioned, or neither");
   if (fine->opts.device_id != coarse->opts.device_id) return fail(GMPNP_ERR_INVALID, "the levels live on one device");
@@ -1748,7 +1771,8 @@ int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const in
 
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us) {
   if (!s || !avg_us || launches < 1) return fail(GMPNP_ERR_INVALID, "bad arguments");
-  if ((kernel == 0 || kernel == 18) && !s->jacobian_valid)
+  if (kernel == 24 && !stern_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 24 is the Stern boundary condition: the option is off (gmpnp_set_stern)");
+  if ((kernel == 0 || kernel == 18 || kernel == 24) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
   hipEvent_t a, b; HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
@@ -1785,6 +1809,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
         GMPNP_DISPATCH(s, r = (step_launch<NF>(s, s->limiter->dx.p, s->limiter->dx.p, 1.0, 0.9, nullptr))); break;
       case 22: r = time_launch_any(s); break;   // k_time_error + k_time_reduce + k_time_shift
       case 23: r = time_launch_any2(s); break;  // k_time_history + k_time_error2 + k_time_reduce + k_time_shift3
+      case 24: r = stern_launch_residual(s, s->status.p); if (!r) r = stern_launch_jacobian(s); break;   // k_stern_residual + k_stern_jacobian
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -1820,6 +1845,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   if (rc) return rc;
   *avg_us = 1000.0 * ms / launches;
+  if (kernel == 24) { s->jacobian_valid = false; s->precond_valid = false; }   // every launch added the Stern entries once more
   return GMPNP_OK;
 }
 
@@ -1903,3 +1929,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_time_step.h"
 #include "gmpnp_time_step_ens.h"
 #include "gmpnp_time_order.h"
+#include "gmpnp_stern.h"

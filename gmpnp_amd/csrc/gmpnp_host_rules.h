@@ -16,7 +16,7 @@
 namespace gmpnp {
 
 // device status word: bit 1 = steric excursion (information, unless strict_steric), bits 2 / 4 / 8 = the linear solve failed,
-// bit 16 = the step limiter met a NaN / Inf in the correction (the update was not applied)
+// bit 16 = the step limiter met a NaN / Inf in the correction (the update was not applied), bit 32 = eps(u) <= 0 on the Stern boundary
 inline std::string status_message(int flags) {
   std::string m;
   if (flags & 1) m += "1 - sum_j a_j u_j <= 0 at a quadrature point; ";
@@ -24,7 +24,38 @@ inline std::string status_message(int flags) {
   if (flags & 4) m += "singular coarse operator; ";
   if (flags & 8) m += "in-launch hand-over timed out; ";
   if (flags & 16) m += "NaN / Inf in the Newton correction (step limiter); ";
+  if (flags & 32) m += "eps(u) <= 0 on the Stern boundary (BDM model); ";
   return m;
+}
+
+// ---- Stern-layer boundary condition (include/gmpnp.h "Stern-layer boundary condition"; kernels: gmpnp_stern.h) ----------------------
+// The Stern term of the potential row is g(eps) (p_M - p) / lam with eps = eps(u) at the outer Helmholtz plane:
+//     linear (model 1)   g = eps                                   the layer has the OHP permittivity (stern.py: Stern_linear)
+//     BDM    (model 2)   g = (eps - eps_s) / ln(eps / eps_s)       eps falls linearly to eps_s at the surface (stern.py: bdm_closed_form)
+// BDM is evaluated as eps_s (r - 1) / log(r), r = eps / eps_s; for |r - 1| < 1e-4 the series 1 + d/2 - d^2/12 (d = r - 1) takes over
+// (next term d^3/24 < 5e-14) and g' = 1/2 - d/6 + d^2/8.  eps <= 0 has no BDM layer: ok = 0, g = g' = 0, and the caller raises
+// status bit 32.  One function for the host and the device; gmpnp_amd/stern.py's coupled_g is its Python statement, operation for
+// operation (tests/test_stern_bc_reference.py compares the bits).
+#if defined(__HIPCC__)
+#define GMPNP_RULE_HD __host__ __device__
+#else
+#define GMPNP_RULE_HD
+#endif
+constexpr double kSternSeriesSwitch = 1.0e-4;
+struct SternG { double g, dg; int ok; };   // g(eps), dg / d eps
+GMPNP_RULE_HD inline SternG stern_g(int model, double eps, double eps_s) {
+  if (model != 2) return SternG{eps, 1.0, 1};
+  if (!(eps > 0.0)) return SternG{0.0, 0.0, 0};
+  const double r = eps / eps_s, d = r - 1.0;
+  if ((d < 0.0 ? -d : d) < kSternSeriesSwitch)
+    return SternG{eps_s * (1.0 + d / 2.0 - d * d / 12.0), 0.5 - d / 6.0 + d * d / 8.0, 1};
+  const double L = log(r);
+  return SternG{eps_s * (d / L), 1.0 / L - d / (r * L * L), 1};
+}
+inline bool stern_options_valid(const gmpnp_stern_t& o) {
+  if (o.model == 0) return true;
+  return (o.model == 1 || o.model == 2) && o.p_electrode == o.p_electrode && !std::isinf(o.p_electrode) && o.lam > 0.0 && !std::isinf(o.lam) &&
+         (o.model == 1 || (o.eps_surface > 0.0 && !std::isinf(o.eps_surface)));
 }
 
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every
@@ -45,6 +76,7 @@ struct NewtonJudge {
   // residual at the state the solve starts from (the status bits of a linear solve mean nothing yet)
   Verdict first(double r, int flags) {
     if (steric(flags)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+    if (flags & 32) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
     r0 = r;
     st.residuals[0] = r; st.n_residuals = 1;
     if (!(r == r)) return fail(GMPNP_ERR_NUMERIC, "residual is NaN before the first Newton iteration");
@@ -53,7 +85,7 @@ struct NewtonJudge {
   // residual after an update (st.iterations already counts it)
   Verdict next(double r, int flags) {
     if (steric(flags)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
-    if (flags & 16) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+    if (flags & (16 | 32)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
     if (flags & 14) return fail(GMPNP_ERR_LINEAR, status_message(flags));
     if (st.n_residuals < GMPNP_MAX_NEWTON_HISTORY) st.residuals[st.n_residuals++] = r;
     // NaN / Inf stay fatal (DOLFIN would iterate to its limit on a NaN residual and raise there)

@@ -263,6 +263,8 @@ class PartitionedSolver:
         ``levels`` (``problem.pore_hierarchy``, finest first; ``prob`` is its finest problem): the geometric multilevel term of the
         preconditioner across the partitions (``partition_hierarchy``; gmpnp_attach_coarse_level + gmpnp_group_attach_coarse_group),
         ``ml_theta`` / ``ml_sweeps`` as on one GPU.  Not over the peer transport (refused by the library)."""
+        if getattr(prob, "stern", None) is not None:
+            raise ValueError("partition: the Stern boundary condition is not available in a partitioned solve")
         from ctypes import c_void_p
         if rank is not None:
             # one rank per process: torch.distributed carries the set-up (mailbox handles, communicator id, host-staged collectives).

@@ -24,8 +24,8 @@ import numpy as np
 
 from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
-from .params import edl_parameters, utilities_dir
-from .problem import edl_problem
+from .params import _load_yaml, edl_parameters, utilities_dir
+from .problem import add_stern_arguments, edl_problem, pop_stern, stern_keywords
 from .solver import GMPNPSystem, supg_parameters
 from .timestep import adaptive_keywords, add_adaptive_arguments
 
@@ -59,7 +59,19 @@ class EDLRun:
         ``max_steps`` the largest number of attempted steps, ``dt_order`` = 2 variable-step BDF2 in backward Euler's place (after its
         start-up; the log gets an ``order`` column and the metadata ``dt_order``).  A rejected step leaves the clock, the history, the budget log and the
         SUPG parameters as they were.  Not with ``H_OHP``: its multiplicative flux controller is calibrated per fixed step
-        (ValueError, before anything touches the device).  Off: nothing changes."""
+        (ValueError, before anything touches the device).  Off: nothing changes.
+        ``electrode_voltage`` = X (thermal voltages; in place of ``voltage_multiplier``, giving both is a ValueError): the electrode
+        potential is applied through the Stern-layer boundary condition (``stern_model`` "BDM" or "linear",
+        ``stern_length`` 4e-10 m, ``stern_eps_surface`` 6): the OHP potential becomes a result.  Not with ``stabilization`` "Y" and not with
+        ``H_OHP`` (ValueError, before anything touches the device).  The metadata gains ``electrode_voltage``, ``stern_model``,
+        ``stern_length``, ``stern_displacement`` (the integrated Stern term g (p_M - p) / lam of the last state, scaled units) and
+        ``surface_charge`` [C/m2] = eps_0 thermal_voltage / L_n x stern_displacement: the displacement eps_0 eps_r E pointing from the
+        electrode into the electrolyte, i.e. the charge per area ON THE ELECTRODE (negative for a cathode, p_M < p_OHP)."""
+        self.stern = pop_stern(kwargs, kwargs.get("L_n", 50.0e-6))
+        if self.stern is not None and kwargs.get("stabilization", "N") == "Y":
+            raise ValueError("electrode_voltage: the Stern boundary condition is not available with stabilization Y")
+        if self.stern is not None and kwargs.get("H_OHP") is not None:
+            raise ValueError("electrode_voltage: the Stern boundary condition is not available with the H_OHP flux controller")
         self.adaptive = bool(adaptive_dt)
         if self.adaptive and kwargs.get("H_OHP") is not None:
             raise ValueError("adaptive_dt: the H_OHP flux controller is calibrated per fixed step")
@@ -72,7 +84,7 @@ class EDLRun:
         self.warn_stab = stab and ep.model_name != "PNP"   # "Warning:stabilization not implemented for MPNP!", 1D:724-727
         self.h_vertex = None
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), ep.mesh_name))
-        self.problem = edl_problem(ep, self.mesh)
+        self.problem = edl_problem(ep, self.mesh, stern=self.stern)
         self.model = copy.deepcopy(self.problem.model)
         self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
         self.solver_parameters = backend.with_step_fraction(solver_parameters or SOLVER_PARAMETERS, self.step_fraction)
@@ -214,11 +226,19 @@ class EDLRun:
         return {"field_OHP": float(field[0] * 1.0e-9), "eps_rel_OHP": float(ep.eps_rel * ((55 - w) / 55) + 6 * (w / 55)),
                 "potential_OHP": float(last[0, 6] * ep.thermal_voltage)}
 
+    def stern_summary(self):
+        """The metadata keys of a run with the Stern boundary condition (see ``__init__``), from the device's current state."""
+        ep, st = self.ep, self.stern
+        d = self.sys.dev.stern_displacement()
+        EPS_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
+        return {"electrode_voltage": st.p_electrode, "stern_model": st.model, "stern_length": st.lam * ep.L_n, "stern_displacement": d,
+                "surface_charge": EPS_0 * ep.thermal_voltage / ep.L_n * d}
+
     def write_outputs(self, stamp=None):
         ep, mesh, k = self.ep, self.mesh, self.kwargs
         stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         end_time = datetime.now().strftime("%y-%m-%d-%H-%M-%S")
-        identifier = run_identifier(ep, k)
+        identifier = run_identifier(ep, k, self.stern)
         newpath = os.path.join(output_root(), ep.model_name, stamp + "_experiment", identifier)
         os.makedirs(newpath, exist_ok=True)
         hist = np.stack(self.history)
@@ -270,6 +290,8 @@ class EDLRun:
             "num_steps_run": int(self.n)}
         if self.step_fraction:
             metadata_dict["step_fraction"] = self.step_fraction
+        if self.stern is not None:
+            metadata_dict.update(self.stern_summary())
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
@@ -279,18 +301,31 @@ class EDLRun:
         return newpath
 
 
-def run_identifier(ep, kwargs):
-    """Name of a run's output directory below ``<model>/<stamp>_experiment`` (reference 1D:862-866)."""
-    return ("voltage_" + str(ep.voltage_scaled) + "_H2_FE_" + str(kwargs.get("H2_FE", 0.2)) + "_current_"
+def run_identifier(ep, kwargs, stern=None):
+    """Name of a run's output directory below ``<model>/<stamp>_experiment`` (reference 1D:862-866; a run with the Stern boundary
+    condition is named by its electrode voltage and Stern model in the OHP voltage's place)."""
+    if stern is not None:
+        head = "electrode_" + str(stern.p_electrode) + "_" + stern.model
+    else:
+        head = "voltage_" + str(ep.voltage_scaled)
+    return (head + "_H2_FE_" + str(kwargs.get("H2_FE", 0.2)) + "_current_"
             + str(ep.current_OHP_ss) + "_H_OHP_" + str(ep.H_OHP) + "_cation_" + ep.cation)
 
 
-def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=-1.0, H2_FE=0.2, mesh_structure="variable",
+def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_FE=0.2, mesh_structure="variable",
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
-              dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, **adaptive):
+              dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM",
+              stern_length=4.0e-10, stern_eps_surface=6.0, **adaptive):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
-    adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps)."""
-    run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec, model=model,
+    adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
+    ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
+    ``stern_eps_surface``: the Stern boundary condition of ``EDLRun``) takes its place."""
+    stern = {}
+    if electrode_voltage is not None:
+        stern = dict(electrode_voltage=electrode_voltage, stern_model=stern_model, stern_length=stern_length, stern_eps_surface=stern_eps_surface)
+    elif voltage_multiplier is None:
+        voltage_multiplier = -1.0
+    run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, **stern, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
                  params_file=params_file, dry_run=dry_run)
@@ -306,7 +341,7 @@ def build_parser():
     p = argparse.ArgumentParser(description="experiment parameters")
     p.add_argument("--concentration_elec", required=False, default=0.1, type=float)
     p.add_argument("--model", required=False, default="MPNP", type=str)
-    p.add_argument("--voltage_multiplier", required=False, default=-1.0, type=float)
+    p.add_argument("--voltage_multiplier", required=False, default=None, type=float, help="default -1.0 (without --electrode_voltage)")
     p.add_argument("--mesh_structure", required=False, default="variable", type=str)
     p.add_argument("--H2_FE", required=False, default=0.2, type=float)
     p.add_argument("--current_OHP_ss", required=False, default=10.0, type=float)
@@ -320,6 +355,7 @@ def build_parser():
     p.add_argument("--budget", action="store_true", help="(addition) record the species budgets and consistent boundary fluxes of every step (budget.npz)")
     p.add_argument("--step_fraction", required=False, default=0.0, type=float, help="(addition) fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off")
     add_adaptive_arguments(p)
+    add_stern_arguments(p)
     return p
 
 
@@ -328,7 +364,7 @@ def main(argv=None):
     return solve_EDL(concentration_elec=a.concentration_elec, model=a.model, voltage_multiplier=a.voltage_multiplier,
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
-                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a))
+                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a))
 
 
 if __name__ == "__main__":

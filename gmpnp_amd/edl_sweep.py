@@ -20,6 +20,7 @@ from datetime import datetime
 
 from . import backend
 from .edl1d import output_root
+from .problem import refuse_stern
 from .edl_ensemble import EDLEnsemble, sweep_members
 from .timestep import adaptive_keywords, add_adaptive_arguments
 
@@ -48,6 +49,9 @@ def build_parser():
 def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget=False, step_fraction=0.0, **adaptive):
     """Run the members in ensembles of at most backend.MAX_ENSEMBLE; returns (summary rows, path of ensemble_summary.json).
     ``adaptive``: the adaptive-stepping keywords of ``EDLEnsemble`` (scalars: the same for every member)."""
+    for k, m in enumerate(members):
+        refuse_stern(m, "the ensemble sweep (member %d)" % k)
+    refuse_stern(adaptive, "the ensemble sweep")
     stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
     rows = []
     for c0 in range(0, len(members), backend.MAX_ENSEMBLE):

@@ -18,7 +18,7 @@ import numpy as np
 from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
-from .problem import pore_dirichlet, pore_problem
+from .problem import add_stern_arguments, pop_stern, pore_dirichlet, pore_problem, stern_keywords
 from .solver import GMPNPSystem, column_medians, device_medians_and_minima
 from .timestep import DriverStepping, adaptive_keywords, add_adaptive_arguments
 from .vtk import write_pvd
@@ -71,9 +71,20 @@ class PoreRun:
         stop, ``max_steps`` the largest number of attempted steps, ``dt_order`` = 2 variable-step BDF2 in backward Euler's place
         (after its start-up).  A rejected step leaves the clock, the history, the budget log and
         the CO2 Dirichlet value as they were.  Not with ``partition`` (ValueError, before anything touches the device).  Off: nothing
-        changes."""
+        changes.
+        ``electrode_voltage`` = X (thermal voltages; in place of ``voltage_multiplier``, giving both is a ValueError): the electrode
+        potential is applied on the wall through the Stern-layer boundary condition (``stern_model`` "BDM" or
+        "linear", ``stern_length`` 4e-10 m, ``stern_eps_surface`` 6); the wall potential becomes a result.  Not with ``partition`` or
+        ``multilevel`` (ValueError, before anything touches the device).  The metadata gains ``electrode_voltage``, ``stern_model``,
+        ``stern_length``, ``stern_displacement`` (the Stern term integrated over the wall, scaled units) and ``surface_charge``
+        [C/m2] = eps_0 thermal_voltage / L x stern_displacement / wall area (scaled): the mean charge per area on the electrode."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
+        self.stern = pop_stern(kwargs, kwargs.get("L", 100.0e-9))
+        if self.stern is not None and partition:
+            raise ValueError("electrode_voltage: the Stern boundary condition is not available in a partitioned solve")
+        if self.stern is not None and multilevel:
+            raise ValueError("electrode_voltage: the Stern boundary condition is not available with the geometric multilevel term")
         self.adaptive = bool(adaptive_dt)
         if self.adaptive and partition:
             raise ValueError("adaptive_dt: adaptive time stepping is not available in a partitioned solve")
@@ -91,7 +102,7 @@ class PoreRun:
             self._levels = pore_hierarchy(self.pp, self.mesh, refine)
             self.problem, self.bnd = self._levels[0][0], self._levels[0][1]
         else:
-            self.problem, self.bnd = pore_problem(self.pp, self.mesh, refine=refine)
+            self.problem, self.bnd = pore_problem(self.pp, self.mesh, refine=refine, stern=self.stern)
         if refine:  # uniformly refined copy of the reference mesh (not a reference feature: roofline studies)
             from .mesh import Mesh
             self.mesh = Mesh(dim=3, coords=self.problem.coords, cells=self.problem.cells)
@@ -175,7 +186,7 @@ class PoreRun:
         self.history.append(row)
         # medians of the scaled ion concentrations -> Sechenov -> new CO2 Dirichlet value at S1 (3D:817-838)
         self.co2_bc = self.pp.sechenov_co2_scaled(*meds)
-        self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, self.co2_bc))
+        self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, self.co2_bc, stern=self.stern is not None))
         self.CO2_min = co2_min
         if assign:
             self.sys.assign_previous()
@@ -214,6 +225,17 @@ class PoreRun:
             self.step(verbose)
         return self
 
+    def stern_summary(self):
+        """The metadata keys of a run with the Stern boundary condition (see ``__init__``), from the device's current state."""
+        from .params import _load_yaml
+        pp, st = self.pp, self.stern
+        X = self.problem.coords[self.problem.wall_facets]
+        area = float((0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)).sum())
+        d = self.sys.dev.stern_displacement()
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters_pore") + ".yaml"))["nat_const"]["eps_0"]
+        return {"electrode_voltage": st.p_electrode, "stern_model": st.model, "stern_length": st.lam * pp.L, "stern_displacement": d,
+                "surface_charge": eps_0 * pp.thermal_voltage / pp.L * d / area}
+
     # ---- outputs (3D:860-1085) -------------------------------------------------------------------
     def write_outputs(self, stamp=None):
         pp, mesh, k = self.pp, self.mesh, self.kwargs
@@ -231,7 +253,7 @@ class PoreRun:
         stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         end_time = datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         L, R = pp.L, pp.R
-        identifier = ("v_" + str(pp.voltage_scaled) + "_L_" + str(int(L * 1e+9)) + "_R_" + str(int(R * 1e+9))
+        identifier = (("v_" + str(pp.voltage_scaled) if self.stern is None else "electrode_" + str(self.stern.p_electrode) + "_" + self.stern.model) + "_L_" + str(int(L * 1e+9)) + "_R_" + str(int(R * 1e+9))
                       + "_P_g_" + str(k.get("press_gas", 1.0)) + "_D_eff_" + str(k.get("pore_geom_multiplier", 1.0))
                       + "_Re_" + str(k.get("electrolyte_flow_geom_multiplier", 1.0))
                       + "_rough_" + str(k.get("roughness_factor", 150.0)))
@@ -285,6 +307,8 @@ class PoreRun:
             "num_steps_run": int(self.n)}
         if self.step_fraction:
             metadata_dict["step_fraction"] = self.step_fraction
+        if self.stern is not None:
+            metadata_dict.update(self.stern_summary())
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
@@ -294,17 +318,25 @@ class PoreRun:
         return newpath
 
 
-def solveEDL(concentration_elec=1.0, voltage_multiplier=-1.0, H2_FE=0.05, current_rough=3000.0, L=100.0e-9,
+def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, current_rough=3000.0, L=100.0e-9,
              cation="K", R=5.0e-9, press_gas=1.0, pore_geom_multiplier=1.0, porosity_eff=0.5, tortuosity_eff=1.5,
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
-             device_kwargs=None, glue="host", budget=False, step_fraction=0.0, **adaptive):
+             device_kwargs=None, glue="host", budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM", stern_length=4.0e-10,
+             stern_eps_surface=6.0, **adaptive):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
     geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
     one rank per process only rank 0 writes and returns the directory; the others return None); ``adaptive``: the adaptive-stepping
-    keywords of ``PoreRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps)."""
-    run = PoreRun(num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
+    keywords of ``PoreRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
+    ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
+    ``stern_eps_surface``: the Stern boundary condition of ``PoreRun``) takes its place."""
+    stern = {}
+    if electrode_voltage is not None:
+        stern = dict(electrode_voltage=electrode_voltage, stern_model=stern_model, stern_length=stern_length, stern_eps_surface=stern_eps_surface)
+    elif voltage_multiplier is None:
+        voltage_multiplier = -1.0
+    run = PoreRun(**stern, num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
                   device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
                   R=R, press_gas=press_gas, pore_geom_multiplier=pore_geom_multiplier, porosity_eff=porosity_eff,
@@ -321,7 +353,7 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=-1.0, H2_FE=0.05, curren
 def build_parser():
     """Flags, defaults and types of reference 3D:1089-1233."""
     p = argparse.ArgumentParser(description="experiment parameters")
-    for name, default in (("concentration_elec", 1.0), ("voltage_multiplier", -1.0), ("H2_FE", 0.05),
+    for name, default in (("concentration_elec", 1.0), ("voltage_multiplier", None), ("H2_FE", 0.05),
                           ("current_rough", 3000.0), ("L", 100e-9), ("R", 5e-9)):
         p.add_argument("--" + name, required=False, default=default, type=float)
     p.add_argument("--cation", required=False, default="K", type=str)
@@ -343,6 +375,7 @@ def build_parser():
     p.add_argument("--step_fraction", required=False, default=0.0, type=float,
                    help="fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off (not with --partitions)")
     add_adaptive_arguments(p)   # (not with --partitions)
+    add_stern_arguments(p)      # (not with --partitions / --multilevel; --voltage_multiplier defaults to -1.0 without --electrode_voltage)
     return p
 
 
@@ -370,6 +403,10 @@ def main(argv=None):
     extra, tdist = {}, None
     if a.partitions and a.adaptive_dt:
         raise ValueError("--adaptive_dt: adaptive time stepping is not available with --partitions")
+    if a.partitions and a.electrode_voltage is not None:
+        raise ValueError("--electrode_voltage: the Stern boundary condition is not available with --partitions")
+    if a.electrode_voltage is not None and a.voltage_multiplier is not None:
+        raise ValueError("--electrode_voltage takes the place of --voltage_multiplier: give one of them")
     if a.partitions:
         partition, device_kwargs, tdist = partition_setup(a.partitions)
         extra = dict(partition=partition, device_kwargs=device_kwargs, glue="device", verbose=partition[1] in (None, 0))
@@ -381,7 +418,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

@@ -16,6 +16,69 @@ from .mesh import Mesh, mark_pore_boundaries, pore_wall_tolerance
 from .model import Model, Quadrature, default_quadrature
 
 
+L_STERN_DEFAULT = 4.0e-10  # [m] stern.py: L_STERN
+EPS_SURFACE_DEFAULT = 6.0
+
+
+@dataclass
+class SternLayer:
+    """Stern-layer boundary condition of the potential (include/gmpnp.h): on the Stern boundary (1D:
+    ``Problem.point_vertices``, 3D: ``Problem.wall_facets``) the potential's Dirichlet value is dropped and the row gains
+    ``int g(eps) (p_M - p) / lam v ds``.  ``model``: "linear" (g = eps) or "BDM" (g = (eps - eps_s) / ln(eps / eps_s))."""
+    model: str  # "linear" | "BDM"
+    p_electrode: float  # p_M [thermal voltages]
+    lam: float  # Stern length / length scale of the mesh
+    eps_surface: float = EPS_SURFACE_DEFAULT
+
+    def __post_init__(self):
+        if self.model not in ("linear", "BDM"):
+            raise ValueError("Stern model must be 'linear' or 'BDM', not %r" % (self.model,))
+        if not (self.lam > 0.0 and np.isfinite(self.lam) and np.isfinite(self.p_electrode)):
+            raise ValueError("Stern layer: lam > 0 and a finite electrode potential")
+        if not (self.eps_surface > 0.0 and np.isfinite(self.eps_surface)):
+            raise ValueError("Stern layer: eps_surface > 0")
+
+
+STERN_KEYWORDS = ("electrode_voltage", "stern_model", "stern_length", "stern_eps_surface")
+
+
+def pop_stern(kwargs, length_scale):
+    """Takes the Stern keywords of a driver (``electrode_voltage`` [thermal voltages], ``stern_model`` = "BDM", ``stern_length`` =
+    4e-10 m, ``stern_eps_surface`` = 6) out of ``kwargs``; returns the ``SternLayer`` with lam = stern_length / length_scale, or None
+    without an electrode voltage.  ``electrode_voltage`` takes the place of ``voltage_multiplier``: giving both is a ValueError."""
+    if "voltage_multiplier" in kwargs and kwargs["voltage_multiplier"] is None:   # a keyword surface's "not given"
+        kwargs.pop("voltage_multiplier")
+    v = kwargs.pop("electrode_voltage", None)
+    model = kwargs.pop("stern_model", "BDM")
+    length = kwargs.pop("stern_length", L_STERN_DEFAULT)
+    eps_s = kwargs.pop("stern_eps_surface", EPS_SURFACE_DEFAULT)
+    if v is None:
+        return None
+    if "voltage_multiplier" in kwargs:
+        raise ValueError("electrode_voltage takes the place of voltage_multiplier: give one of them")
+    return SternLayer(model=model, p_electrode=float(v), lam=float(length) / float(length_scale), eps_surface=float(eps_s))
+
+
+def refuse_stern(kwargs, what):
+    """ValueError if a keyword dict asks for the Stern boundary condition where it does not exist (before anything touches the device)."""
+    if kwargs.get("electrode_voltage") is not None:
+        raise ValueError("electrode_voltage: the Stern boundary condition is not available in %s" % what)
+
+
+def add_stern_arguments(p):
+    """The drivers' command-line flags of the Stern boundary condition (additions, not reference flags)."""
+    p.add_argument("--electrode_voltage", required=False, default=None, type=float,
+                   help="(addition) electrode potential in thermal voltages, applied through a Stern layer; takes the place of --voltage_multiplier")
+    p.add_argument("--stern_model", required=False, default="BDM", type=str, choices=("linear", "BDM"), help="(addition) Stern-layer model")
+    p.add_argument("--stern_length", required=False, default=L_STERN_DEFAULT, type=float, help="(addition) Stern-layer thickness [m]")
+    p.add_argument("--stern_eps_surface", required=False, default=EPS_SURFACE_DEFAULT, type=float, help="(addition) relative permittivity at the surface (BDM)")
+
+
+def stern_keywords(a):
+    """The Stern keywords of a parsed command line (``add_stern_arguments``)."""
+    return {k: getattr(a, k) for k in STERN_KEYWORDS}
+
+
 @dataclass
 class Problem:
     coords: np.ndarray  # (nv,d)
@@ -32,6 +95,7 @@ class Problem:
     # OH term, which takes grad(u_H): SURVEY Q7).  None = no stabilisation.
     supg_rho: np.ndarray = None
     supg_w: np.ndarray = None
+    stern: SternLayer = None  # Stern-layer boundary condition of the potential; None = the potential is prescribed (Dirichlet)
 
     def __post_init__(self):
         d = self.coords.shape[1]
@@ -73,17 +137,18 @@ def merge_dirichlet(bcs, nf):
     return uniq, rev_vals[first]
 
 
-def pore_dirichlet(pp, bnd, co2_value=None):
-    """bcs = [bc1..bc6] of reference 3D:460-467 (bc4 rebuilt every step, 3D:835-838)."""
+def pore_dirichlet(pp, bnd, co2_value=None, stern=False):
+    """bcs = [bc1..bc6] of reference 3D:460-467 (bc4 rebuilt every step, 3D:835-838).  ``stern``: the wall potential is not
+    prescribed (the (s2, ns, voltage) entry is dropped; wall vertices shared with S1 / S3 keep p = 0)."""
     ns = len(pp.species)
     co2 = pp.eq_conc_CO2_scaled if co2_value is None else co2_value
     s1, s2, s3 = bnd.dirichlet_vertices[1], bnd.dirichlet_vertices[2], bnd.dirichlet_vertices[3]
     # Only the CO2 value changes between time steps: the merged dof set and the positions of the bc4 entries in it are
     # kept on the boundary record (keyed by everything else that enters), so the per-step rebuild is one fill.
-    key = (ns, float(pp.voltage_scaled), float(pp.eq_conc_CO_scaled), float(pp.eq_conc_H2_scaled))
+    key = (ns, float(pp.voltage_scaled), float(pp.eq_conc_CO_scaled), float(pp.eq_conc_H2_scaled), bool(stern))
     cache = getattr(bnd, "_dirichlet_cache", None)
     if cache is None or cache[0] != key:
-        bcs = [(s1, ns, 0.0), (s3, ns, 0.0), (s2, ns, pp.voltage_scaled),
+        bcs = [(s1, ns, 0.0), (s3, ns, 0.0)] + ([] if stern else [(s2, ns, pp.voltage_scaled)]) + [
                (s1, 4, co2), (s1, 5, pp.eq_conc_CO_scaled), (s1, 6, pp.eq_conc_H2_scaled)]
         dofs, vals = merge_dirichlet(bcs, ns + 1)
         # field 4 appears in bc4 only, so "later bc wins" never touches these entries
@@ -99,7 +164,7 @@ def pore_dirichlet(pp, bnd, co2_value=None):
     return dofs, vals
 
 
-def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0):
+def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0, stern: SternLayer = None):
     """Problem + boundary record for the 3D pore (reference 3D:329-382,460-467).  ``refine`` > 0 applies that many
     uniform refinements with inherited markers (gmpnp_amd.mesh.refine_pore); returns (problem, boundaries) of the
     mesh actually used (``problem.coords/cells``)."""
@@ -107,9 +172,9 @@ def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0):
     for _ in range(refine):
         from .mesh import refine_pore
         mesh, bnd = refine_pore(mesh, bnd)
-    dofs, vals = pore_dirichlet(pp, bnd)
+    dofs, vals = pore_dirichlet(pp, bnd, stern=stern is not None)
     prob = Problem(coords=mesh.coords, cells=mesh.cells, model=pp.model, quad=quad,
-                   wall_facets=bnd.ds_facets[2], exit_facets=bnd.ds_facets[3], bc_dofs=dofs, bc_vals=vals)
+                   wall_facets=bnd.ds_facets[2], exit_facets=bnd.ds_facets[3], bc_dofs=dofs, bc_vals=vals, stern=stern)
     return prob, bnd
 
 
@@ -131,16 +196,17 @@ def pore_hierarchy(pp, mesh: Mesh, refine: int, quad: Quadrature = None):
     return out
 
 
-def edl_problem(ep, mesh: Mesh, quad: Quadrature = None):
+def edl_problem(ep, mesh: Mesh, quad: Quadrature = None, stern: SternLayer = None):
     """Problem for the 1D EDL (reference 1D:237-254,350-355): all 7 fields pinned to
-    (1,..,1,0) at x=1; p = voltage_multiplier at x=0; point fluxes at the x=0 vertex."""
+    (1,..,1,0) at x=1; p = voltage_multiplier at x=0; point fluxes at the x=0 vertex.  ``stern``: the OHP potential is not
+    prescribed (the (left, ns, voltage) entry is dropped) and the record travels with the problem."""
     tol = 1.0e-14
     x = mesh.coords[:, 0]
     _, ext, _ = mesh.facets()
     right = np.nonzero(ext & (np.abs(x - 1.0) < tol))[0]
     left = np.nonzero(ext & (np.abs(x - 0.0) < tol))[0]
     ns = len(ep.species)
-    bcs = [(right, f, 1.0) for f in range(ns)] + [(right, ns, 0.0), (left, ns, ep.voltage_scaled)]
+    bcs = [(right, f, 1.0) for f in range(ns)] + [(right, ns, 0.0)] + ([] if stern is not None else [(left, ns, ep.voltage_scaled)])
     dofs, vals = merge_dirichlet(bcs, ns + 1)
     return Problem(coords=mesh.coords, cells=mesh.cells, model=ep.model, quad=quad,
-                   point_vertices=left.astype(np.int32), bc_dofs=dofs, bc_vals=vals)
+                   point_vertices=left.astype(np.int32), bc_dofs=dofs, bc_vals=vals, stern=stern)

@@ -79,6 +79,8 @@ class GMPNPSystem(_System):
     def __init__(self, problem: Problem, levels=None, ml_theta: float = 2.0, ml_sweeps: int = 4, **device_kwargs):
         """``levels`` (``problem.pore_hierarchy``, finest first, ``problem`` its finest): the geometric multilevel term of the
         preconditioner; the coarser levels are ordinary handles of the parent meshes on the same device, owned by this system."""
+        if levels and getattr(problem, "stern", None) is not None:
+            raise ValueError("multilevel: the Stern boundary condition is not available with the geometric multilevel term")
         self.dev = backend.DeviceSolver(problem, **device_kwargs)
         super().__init__(problem, self.dev)
         self._coarse = [backend.DeviceSolver(lv[0], device_id=device_kwargs.get("device_id", 0), shared_device=1) for lv in (levels or [])[1:]]

@@ -18,6 +18,14 @@ Reference behaviour kept on purpose (``as_published=True``, the default; ``--as_
   S3  after defining everything ``main`` loops over the five recorded (voltage, field, permittivity) triples (:66-68,177-178) whatever
       the command line says; the flags only set defaults nobody uses.  Here: the same loop without arguments, ONE case when
       ``--field_OHP`` / ``--eps_rel_OHP`` / ``--from_run`` are given.
+
+The same ion-free layer also exists as a boundary condition INSIDE the solve (``--electrode_voltage`` of the 1D
+and 3D MPNP drivers, ``gmpnp_set_stern``): the electrode potential is applied through a Robin condition ``g(eps) (p_M - p) / lam`` on the
+potential, and no post-processing or hand iteration of the OHP voltage is needed.  Its ``linear`` model is ``Stern_linear`` here (constant
+field, OHP permittivity); its ``BDM`` model is ``BDM`` with ``as_published=False`` (permittivity linear from the OHP value to 6 at the surface:
+the potential drop of ``bdm_closed_form`` over the layer is ``f0 L ln(eps/eps_s) eps / (eps - eps_s)``, i.e. displacement = g (p_M - p) / L
+with g = (eps - eps_s) / ln(eps / eps_s)).  ``coupled_g`` below is the Python statement of that g, the mirror of ``stern_g`` in
+gmpnp_amd/csrc/gmpnp_host_rules.h.  Nothing in this module's published-quirk behaviour changes.
 """
 from __future__ import annotations
 
@@ -37,6 +45,30 @@ EPS_REL_SURFACE = 6.0      # rigid water at the catalyst surface, :79
 RECORDED = {-2.5: {"E": -0.08032108300135771, "eps": 74.56149297894756}, -5.0: {"E": -0.2524415478848975, "eps": 57.64572780716129},
             -7.5: {"E": -0.4612956299192668, "eps": 50.16243860179017}, -10.0: {"E": -0.6149631587776277, "eps": 49.311548142969336},
             -12.5: {"E": -0.7310301485096051, "eps": 49.2556833480052}}
+
+
+COUPLED_SERIES_SWITCH = 1.0e-4   # gmpnp_host_rules.h: kSternSeriesSwitch
+
+
+def coupled_g(model, eps, eps_s=EPS_REL_SURFACE):
+    """(g, dg/d eps) of the coupled Stern condition for one permittivity value: ``stern_g`` of gmpnp_host_rules.h, operation for
+    operation (tests/test_stern_bc_reference.py compares the bits).  ``model``: "linear" (g = eps) or "BDM"
+    (g = (eps - eps_s) / ln(eps / eps_s), evaluated as eps_s (r - 1) / log(r) with r = eps / eps_s, and by the series
+    1 + d/2 - d^2/12, d = r - 1, for |d| < 1e-4).  ValueError for eps <= 0 under BDM (the library raises status bit 32)."""
+    import math
+    eps = float(eps)
+    if model == "linear":
+        return eps, 1.0
+    if model != "BDM":
+        raise ValueError("model %r: linear or BDM" % (model,))
+    if not eps > 0.0:
+        raise ValueError("eps <= 0 on the Stern boundary: the BDM layer does not exist")
+    r = eps / eps_s
+    d = r - 1.0
+    if abs(d) < COUPLED_SERIES_SWITCH:
+        return eps_s * (1.0 + d / 2.0 - d * d / 12.0), 0.5 - d / 6.0 + d * d / 8.0
+    L = math.log(r)
+    return eps_s * (d / L), 1.0 / L - d / (r * L * L)
 
 
 def thermal_voltage(params_file="parameters"):

@@ -505,6 +505,30 @@ typedef enum {
 int gmpnp_species_budget(gmpnp_solver* s, double* out /* [n_fields][GMPNP_BUDGET_COLUMNS] */);
 int gmpnp_group_species_budget(gmpnp_group* g, double* out /* [n_fields][GMPNP_BUDGET_COLUMNS] */);
 
+/* ---- Stern-layer boundary condition (no reference counterpart: the reference prescribes the potential at the outer Helmholtz plane
+ * and 1D/Stern_CO2ER.py integrates the Stern layer afterwards) -----------------------------------------------------------------------
+ * On the Stern boundary Gamma_S (1D: the point vertices, the OHP vertex; 3D: the wall facets ds(2)) the potential row keeps the
+ * boundary term of its integration by parts, with displacement continuity across an ion-free layer of scaled thickness lam:
+ *     F_p += int_{Gamma_S} g(eps) (p_M - p) / lam  v ds        eps = eps0 + sum_j epsc_j u_j
+ * p_electrode = p_M in thermal voltages; model 1 (linear): g = eps; model 2 (BDM): g = (eps - eps_s) / ln(eps / eps_s) with
+ * eps_s = eps_surface (ignored by model 1).  1D takes eps at the vertex; 3D takes it per facet at the facet mean of u and (p_M - p) as
+ * P1 with the facet mass matrix |f| (1 + delta_ab) / 12.  The Jacobian holds the exact derivative, the permittivity's included.  A
+ * potential row that carries a Dirichlet value receives nothing (the caller leaves the OHP potential out of gmpnp_set_dirichlet).
+ * eps <= 0 on Gamma_S under model 2 raises status bit 32: the residual evaluation (gmpnp_assemble, gmpnp_newton_solve) returns
+ * GMPNP_ERR_NUMERIC.  gmpnp_species_budget reports the integrated term in the potential row's wall (3D) or point (1D) column.
+ * Setting the option invalidates the Jacobian and the preconditioner; model = 0 restores the handle as it was before the first call
+ * (no launch, no buffer read).  Refused (GMPNP_ERR_INVALID, the message names Stern): partition handles (and so groups), a handle with
+ * a coarse level attached or serving as one (and attaching one to a handle with the option on), every gmpnp_ensemble_* call with such a
+ * member.  gmpnp_stern_displacement: the integrated term int_{Gamma_S} g (p_M - p) / lam ds at the current u, scaled units. */
+typedef struct {
+  int32_t model;       /* 0 off, 1 linear, 2 BDM */
+  double p_electrode;  /* p_M [thermal voltages] */
+  double lam;          /* Stern length / length scale of the mesh, > 0 */
+  double eps_surface;  /* eps_s of the BDM model, > 0 */
+} gmpnp_stern_t;
+int gmpnp_set_stern(gmpnp_solver* s, const gmpnp_stern_t* stern);
+int gmpnp_stern_displacement(gmpnp_solver* s, double* out);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -572,7 +596,8 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * (k_step_limit + k_limited_update, on a zero correction: the state stays), 22 = the three launches of an accepted adaptive time step
  * (estimator + reduce + shift; u_n and u_nm1 are put back afterwards, the history flag stays), 23 = the four launches of an accepted
  * order-2 step (u*, order-2 estimator, reduce, three-deep shift; u_n, u_nm1 and u_nm2 are put back, the order and the levels stay;
- * allocates the order-2 vectors). */
+ * allocates the order-2 vectors), 24 = the two launches of the Stern boundary condition (k_stern_residual + k_stern_jacobian; needs
+ * gmpnp_set_stern with model != 0 and an assembled Jacobian, which the launches keep adding to). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
