@@ -13,7 +13,7 @@ from ctypes import POINTER, byref, c_double, c_int32, c_int64, c_void_p
 
 import numpy as np
 
-from .model import CModel, CQuadrature, Model, to_cmodel, to_cquadrature
+from .model import MAX_SPECIES, CModel, CQuadrature, Model, to_cmodel, to_cquadrature
 from .problem import Problem
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,6 +42,7 @@ EXPORTS = [
     "gmpnp_set_time_step", "gmpnp_time_error", "gmpnp_time_accept", "gmpnp_time_reject",
     "gmpnp_set_time_order", "gmpnp_time_history_levels", "gmpnp_set_time_step_bdf2", "gmpnp_time_error_bdf2", "gmpnp_get_time_history",
     "gmpnp_set_stern", "gmpnp_stern_displacement",
+    "gmpnp_set_kinetics", "gmpnp_kinetics_currents",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -92,6 +93,27 @@ class CStern(ctypes.Structure):
 
 
 STERN_MODELS = {"linear": 1, "BDM": 2}   # gmpnp_stern_t.model (0 = off)
+MAX_SURFACE_REACTIONS = 4                # GMPNP_MAX_SURFACE_REACTIONS
+
+
+class CKinetics(ctypes.Structure):
+    """ctypes image of ``gmpnp_kinetics_t`` (include/gmpnp.h)."""
+    _fields_ = [("n_reactions", c_int32), ("reactant", c_int32 * MAX_SURFACE_REACTIONS), ("k", c_double * MAX_SURFACE_REACTIONS),
+                ("alpha", c_double * MAX_SURFACE_REACTIONS), ("p_eq", c_double * MAX_SURFACE_REACTIONS),
+                ("nu", (c_double * MAX_SPECIES) * MAX_SURFACE_REACTIONS), ("p_electrode", c_double)]
+
+
+def to_ckinetics(kin, species) -> CKinetics:
+    """The C image of a ``problem.SurfaceKinetics`` record: species names resolved against ``species`` (the model's order)."""
+    c = CKinetics()
+    c.n_reactions = len(kin.reactions)
+    c.p_electrode = float(kin.p_electrode)
+    for r, rx in enumerate(kin.reactions):
+        c.reactant[r] = -1 if rx.reactant is None else species.index(rx.reactant)
+        c.k[r], c.alpha[r], c.p_eq[r] = float(rx.k), float(rx.alpha), float(rx.p_eq)
+        for name, v in rx.nu.items():
+            c.nu[r][species.index(name)] = float(v)
+    return c
 
 
 class CLinearStats(ctypes.Structure):
@@ -232,6 +254,8 @@ def load_library(path: str = None):
         getattr(lib, name).argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_set_stern.argtypes = [c_void_p, POINTER(CStern)]
     lib.gmpnp_stern_displacement.argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_set_kinetics.argtypes = [c_void_p, POINTER(CKinetics)]
+    lib.gmpnp_kinetics_currents.argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -399,6 +423,9 @@ class DeviceSolver:
             self.set_dirichlet(problem.bc_dofs, problem.bc_vals)
         if getattr(problem, "stern", None) is not None:
             self.set_stern(problem.stern)
+        self._n_reactions = 0
+        if getattr(problem, "kinetics", None) is not None:
+            self.set_kinetics(problem.kinetics)
 
     # ------------------------------------------------------------------------------------------
     def _check(self, code):
@@ -569,6 +596,21 @@ class DeviceSolver:
         out = c_double()
         self._check(self.lib.gmpnp_stern_displacement(self._h, byref(out)))
         return float(out.value)
+
+    def set_kinetics(self, kinetics=None):
+        """Potential-dependent surface kinetics on the Stern boundary (``gmpnp_set_kinetics``): a ``problem.SurfaceKinetics`` record
+        (species by name, resolved against the problem's model), or None = off."""
+        c = CKinetics()
+        if kinetics is not None:
+            c = to_ckinetics(kinetics, list(self.problem.model.species))
+        self._check(self.lib.gmpnp_set_kinetics(self._h, byref(c)))
+        self._n_reactions = int(c.n_reactions)
+
+    def kinetics_currents(self) -> np.ndarray:
+        """sum_I w_I rate_r at the current u, one entry per reaction (``gmpnp_kinetics_currents``)."""
+        out = (c_double * MAX_SURFACE_REACTIONS)()
+        self._check(self.lib.gmpnp_kinetics_currents(self._h, out))
+        return np.array(out[:self._n_reactions], dtype=np.float64)
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

@@ -129,7 +129,18 @@ struct gmpnp_sterner {
   int n_nodes = 0, n_pairs = 0;
   DevBuf<int32_t> node, nf_ptr, nf_ent, fnodes, pair_row, pf_ptr, pf_ent;
   DevBuf<int64_t> addr;
-  DevBuf<double> area, bnd_dyn, sum;   // bnd_dyn: bndF + the Stern term, what Ctx::bndF points at while the option is on
+  DevBuf<double> area, sum;
+};
+
+// device side of the surface kinetics (gmpnp_kinetics.h), allocated by the first gmpnp_set_kinetics with n_reactions != 0: a handle
+// that never asks for it keeps the buffers, launches and pointers it had
+struct gmpnp_kineticist {
+  gmpnp_kinetics_t opt{};
+  int n_nodes = 0;
+  DevBuf<gmpnp_kinetics_t> d_opt;
+  DevBuf<int32_t> node, status;   // status: the word of gmpnp_kinetics_currents' own launches
+  DevBuf<int64_t> addr;
+  DevBuf<double> w, sum;
 };
 
 struct gmpnp_solver {
@@ -205,6 +216,10 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_step_limiter> limiter;
   std::unique_ptr<gmpnp_time_stepper> stepper;
   std::unique_ptr<gmpnp_sterner> sterner;
+  std::unique_ptr<gmpnp_kineticist> kineticist;
+  // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
+  // (boundary_rebind); allocated by the first of them
+  DevBuf<double> bnd_dyn;
   // geometric multilevel term (gmpnp_attach_coarse_level, gmpnp_multilevel.h): the link to the next-coarser level (tables in the
   // internal orders of both handles) and this handle's buffers when it serves as a coarse level itself
   gmpnp_solver* ml_coarse = nullptr; double ml_theta = 1.0; bool ml_is_coarse = false;
@@ -250,10 +265,25 @@ int grid_for(int n, int block) { return (n + block - 1) / block; }
 
 // gmpnp_stern.h: the Stern term of the potential rows in front of a residual gather, its Jacobian entries behind the Jacobian gather
 inline bool stern_on(const gmpnp_solver* s) { return s->sterner && s->sterner->opt.model != 0; }
-int stern_rebind(gmpnp_solver* s);
 int stern_launch_residual(gmpnp_solver* s, int32_t* status);
 int stern_launch_jacobian(gmpnp_solver* s);
 int stern_launch_sum(gmpnp_solver* s, double* table_entry);
+// gmpnp_kinetics.h: the kinetic term of the species rows beside the Stern term, its Jacobian entries behind the Stern entries
+inline bool kinetics_on(const gmpnp_solver* s) { return s->kineticist && s->kineticist->opt.n_reactions != 0; }
+int kinetics_launch_residual(gmpnp_solver* s, int32_t* status);
+int kinetics_launch_jacobian(gmpnp_solver* s);
+int kinetics_launch_sum(gmpnp_solver* s, int32_t* status, double* table);
+
+// Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
+// rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
+int boundary_rebind(gmpnp_solver* s) {
+  if (!stern_on(s) && !kinetics_on(s)) { s->c.bndF = s->bndF.p; return GMPNP_OK; }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (s->bnd_dyn.n != (size_t)s->ndof) HIP_TRY(s->bnd_dyn.alloc((size_t)s->ndof, false));
+  HIP_TRY(hipMemcpy(s->bnd_dyn.p, s->bndF.p, (size_t)s->ndof * sizeof(double), hipMemcpyDeviceToDevice));
+  s->c.bndF = s->bnd_dyn.p;
+  return GMPNP_OK;
+}
 
 size_t coarse_lds_bytes(int n, int nf) { return (size_t)(n * n + n * nf + 2 * nf * nf) * sizeof(double); }
 
@@ -314,8 +344,7 @@ int rebuild_boundary(gmpnp_solver* s) {
   HIP_TRY(s->rob_row.upload(rrow)); HIP_TRY(s->rob_val.upload(rval)); HIP_TRY(s->rob_addr.upload(raddr));
   s->c.bndF = s->bndF.p; s->c.robF_ptr = s->robF_ptr.p; s->c.rob_col = s->rob_col.p; s->c.rob_row = s->rob_row.p;
   s->c.rob_val = s->rob_val.p; s->c.rob_addr = s->rob_addr.p; s->c.n_robin = (int)rval.size();
-  if (s->sterner) return stern_rebind(s);   // the new constant vector under the Stern term
-  return GMPNP_OK;
+  return boundary_rebind(s);   // the new constant vector under the Stern and kinetic terms (nothing to do with both off)
 }
 
 int check_model(const gmpnp_model_t* m, int dim) {
@@ -361,7 +390,8 @@ int launch_jac_gather(gmpnp_solver* s) {
   hipLaunchKernelGGL((k_jac_gather<DIM, NF>), dim3(g), dim3(kVecBlock), 0, s->stream, s->c);
   if (s->c.n_robin > 0) hipLaunchKernelGGL(k_robin_add, dim3(grid_for(s->c.n_robin, 256)), dim3(256), 0, s->stream, s->c);
   HIP_TRY(hipGetLastError());
-  if (stern_on(s)) return stern_launch_jacobian(s);
+  if (stern_on(s)) { int rc = stern_launch_jacobian(s); if (rc) return rc; }
+  if (kinetics_on(s)) return kinetics_launch_jacobian(s);
   return GMPNP_OK;
 }
 
@@ -389,6 +419,7 @@ template <int DIM, int NF>
 int residual(gmpnp_solver* s, bool want_j, double* norm, int* flags) {
   int rc = launch_element<DIM, NF>(s, want_j); if (rc) return rc;
   if (stern_on(s)) { rc = stern_launch_residual(s, s->status.p); if (rc) return rc; }
+  if (kinetics_on(s)) { rc = kinetics_launch_residual(s, s->status.p); if (rc) return rc; }
   rc = launch_res_gather<DIM, NF>(s); if (rc) return rc;
   // the partials and the status word land in pinned host memory by the kernel's own stores: no copy in the stream
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1522,6 +1553,7 @@ int gmpnp_set_supg(gmpnp_solver* s, const double* rho, const int32_t* w_index) {
   HIP_TRY(hipStreamSynchronize(s->stream));
   s->jacobian_valid = false;
   if (!rho) { s->c.supg_rho = nullptr; return GMPNP_OK; }
+  if (kinetics_on(s)) return fail(GMPNP_ERR_INVALID, "SUPG terms: not with the surface kinetics on (gmpnp_set_kinetics)");
   if (s->dim != 1) return fail(GMPNP_ERR_INVALID, "SUPG stabilisation exists for 1D meshes only (reference 1D:597-722)");
   const int ns = s->nf - 1, nv = s->t.nv;
   std::vector<double> tmp((size_t)nv * ns);
@@ -1649,7 +1681,7 @@ int gmpnp_assemble(gmpnp_solver* s, int32_t want_jacobian, double* F_out, double
   if (norm_out) *norm_out = r;
   if (F_out) { rc = download_vec(s, s->F.p, F_out); if (rc) return rc; }
   if ((flags & 1) && s->cfg.strict_steric) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
-  if (flags & 32) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+  if (flags & (32 | 64)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
   return GMPNP_OK;
 }
 
@@ -1743,6 +1775,7 @@ int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const in
   if (!fine || !coarse || !parents) return fail(GMPNP_ERR_INVALID, "NULL argument");
   if (fine == coarse || coarse->ml_is_coarse) return fail(GMPNP_ERR_INVALID, "a level handle serves one finer level");
   if (stern_on(fine) || stern_on(coarse)) return fail(GMPNP_ERR_INVALID, "multilevel term: not with the Stern boundary condition on a level (gmpnp_set_stern)");
+  if (kinetics_on(fine) || kinetics_on(coarse)) return fail(GMPNP_ERR_INVALID, "multilevel term: not with the surface kinetics on a level (gmpnp_set_kinetics)");
   if (fine->dim != 3 || coarse->dim != 3 || fine->nf != 9 || coarse->nf != 9) return fail(GMPNP_ERR_INVALID, "multilevel term: 3D pore problems (9 fields)");
   if (fine->partitioned != coarse->partitioned) return fail(GMPNP_ERR_INVALID, "multilevel term: both levels partitioned, or neither");
   if (fine->opts.device_id != coarse->opts.device_id) return fail(GMPNP_ERR_INVALID, "the levels live on one device");
@@ -1772,7 +1805,8 @@ int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const in
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us) {
   if (!s || !avg_us || launches < 1) return fail(GMPNP_ERR_INVALID, "bad arguments");
   if (kernel == 24 && !stern_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 24 is the Stern boundary condition: the option is off (gmpnp_set_stern)");
-  if ((kernel == 0 || kernel == 18 || kernel == 24) && !s->jacobian_valid)
+  if (kernel == 25 && !kinetics_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 25 is the surface kinetics: the option is off (gmpnp_set_kinetics)");
+  if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
   hipEvent_t a, b; HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
@@ -1810,6 +1844,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 22: r = time_launch_any(s); break;   // k_time_error + k_time_reduce + k_time_shift
       case 23: r = time_launch_any2(s); break;  // k_time_history + k_time_error2 + k_time_reduce + k_time_shift3
       case 24: r = stern_launch_residual(s, s->status.p); if (!r) r = stern_launch_jacobian(s); break;   // k_stern_residual + k_stern_jacobian
+      case 25: r = kinetics_launch_residual(s, s->status.p); if (!r) r = kinetics_launch_jacobian(s); break;   // k_kinetics_residual + k_kinetics_jacobian
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -1845,7 +1880,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   if (rc) return rc;
   *avg_us = 1000.0 * ms / launches;
-  if (kernel == 24) { s->jacobian_valid = false; s->precond_valid = false; }   // every launch added the Stern entries once more
+  if (kernel == 24 || kernel == 25) { s->jacobian_valid = false; s->precond_valid = false; }   // every launch added the Stern / kinetic entries once more
   return GMPNP_OK;
 }
 
@@ -1930,3 +1965,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_time_step_ens.h"
 #include "gmpnp_time_order.h"
 #include "gmpnp_stern.h"
+#include "gmpnp_kinetics.h"

@@ -15,6 +15,8 @@
 //   k_budget_final   one workgroup: the workgroup partials of both passes in a fixed order -> table[field][column]
 // With the Stern boundary condition on (gmpnp_stern.h) k_stern_residual refreshes the term at the current u in front of the row pass
 // (c.bndF is then bnd_dyn) and k_stern_sum writes the integrated term into the potential row's wall (3D) / point (1D) entry.
+// With the surface kinetics on (gmpnp_kinetics.h) k_kinetics_residual does the same for the species rows and k_kinetics_sum adds
+// the integrated kinetic flux of every species to its wall / point entry.
 // Reductions are fixed-order sums of per-workgroup partials (no floating-point atomics): two calls on one state give equal bits.
 // The element residual is evaluated at the current u by k_element<.., WANT_J = false> into a buffer of the budget's own, with a status
 // word of its own: u, u_n, F, EF, kr / kb, the Jacobian, the preconditioner and the device status stay what they were.
@@ -274,6 +276,7 @@ int budget_launch(gmpnp_solver* s) {
   hipLaunchKernelGGL((k_element<DIM, NF, false>), dim3(grid_for(s->t.nc, 64)), dim3(64), 0, s->stream, c);
   hipLaunchKernelGGL((k_budget_cells<DIM, NF>), dim3(b->nblk_c), dim3(kVecBlock), 0, s->stream, c, b->part_c.p);
   if (stern_on(s)) { int rc = stern_launch_residual(s, b->status.p); if (rc) return rc; }   // the Stern term at THIS u, for the row pass
+  if (kinetics_on(s)) { int rc = kinetics_launch_residual(s, b->status.p); if (rc) return rc; }   // and the kinetic term of the species rows
   BudgetGeo g{b->wall_w.p, b->exit_w.p, b->exit_ptr.p, b->exit_col.p, b->exit_val.p, b->point_w.p};
   hipLaunchKernelGGL((k_budget_rows<DIM, NF>), dim3(b->nblk_r), dim3(kVecBlock), 0, s->stream, c, (const double*)b->EF.p, g, b->part_r.p);
   hipLaunchKernelGGL((k_budget_final<NF>), dim3(1), dim3(kVecBlock), 0, s->stream, (const double*)b->part_c.p, b->nblk_c, (const double*)b->part_r.p,
@@ -281,6 +284,9 @@ int budget_launch(gmpnp_solver* s) {
   if (stern_on(s)) {   // the integrated Stern term: the potential row's wall (3D) / point (1D) entry, so that row still closes
     int rc = stern_launch_sum(s, b->table.p + (size_t)(NF - 1) * GMPNP_BUDGET_COLUMNS + (DIM == 3 ? GMPNP_BUDGET_WALL : GMPNP_BUDGET_POINT));
     if (rc) return rc;
+  }
+  if (kinetics_on(s)) {   // the integrated kinetic fluxes: added to the species rows' wall (3D) / point (1D) entries, so those rows still close
+    int rc = kinetics_launch_sum(s, b->status.p, b->table.p); if (rc) return rc;
   }
   HIP_TRY(hipGetLastError());
   return GMPNP_OK;

@@ -274,6 +274,7 @@ int ens_check_member(const gmpnp_solver* s, const gmpnp_solver* s0, int k) {
   if (s0 && s->dim != s0->dim) return bad("1D and 3D members cannot share an ensemble");
   if (s->partitioned) return bad("partitioned handles cannot join an ensemble");
   if (stern_on(s)) return bad("the Stern boundary condition is on (gmpnp_set_stern): ensembles do not apply it");
+  if (kinetics_on(s)) return bad("the surface kinetics are on (gmpnp_set_kinetics): ensembles do not apply them");
   if (s->stepper && s->stepper->order == 2) return bad("the handle steps at order 2 (gmpnp_set_time_order): ensembles have no second-order time stepping");
   if (is3d) {
     if (s->ml_coarse || s->ml_is_coarse) return bad("a multilevel coarse level is attached: not supported in an ensemble");
@@ -767,7 +768,7 @@ int gmpnp_ensemble_assign_previous(gmpnp_ensemble* e) {
   for (const gmpnp_solver* s : e->m)
     if (s->stepper && s->stepper->order == 2) return fail(GMPNP_ERR_INVALID, "gmpnp_ensemble_assign_previous: a member steps at order 2 (gmpnp_set_time_order): ensembles have no second-order time stepping");
   for (size_t k = 0; k < e->m.size(); ++k)
-    if (stern_on(e->m[k])) return ens_check_member(e->m[k], e->m[0], (int)k);   // (the Stern boundary condition was set after create)
+    if (stern_on(e->m[k]) || kinetics_on(e->m[k])) return ens_check_member(e->m[k], e->m[0], (int)k);   // (the Stern boundary condition or the surface kinetics were set after create)
   int rc = ens_drain_members(e); if (rc) return rc;
   // u / u_n of a handle are allocated once at create: the table of the last upload addresses them
   hipLaunchKernelGGL(k_ens_assign, dim3(grid_for(e->ndof, 256), (unsigned)e->m.size()), dim3(256), 0, e->stream, (const EnsMember*)e->tab.p, e->ndof);
@@ -780,7 +781,7 @@ int gmpnp_ensemble_get_state(gmpnp_ensemble* e, double* u_out) {
   if (!e || !u_out) return fail(GMPNP_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(e->device));
   for (size_t k = 0; k < e->m.size(); ++k)
-    if (stern_on(e->m[k])) return ens_check_member(e->m[k], e->m[0], (int)k);   // (the Stern boundary condition was set after create)
+    if (stern_on(e->m[k]) || kinetics_on(e->m[k])) return ens_check_member(e->m[k], e->m[0], (int)k);   // (the Stern boundary condition or the surface kinetics were set after create)
   int rc = ens_drain_members(e); if (rc) return rc;
   const int n = (int)e->m.size(), nf = e->m[0]->nf, nv = e->nv, ndof = e->ndof;
   hipLaunchKernelGGL(k_ens_gather_u, dim3(grid_for(ndof, 256), n), dim3(256), 0, e->stream, (const EnsMember*)e->tab.p, e->ustage.p, ndof);

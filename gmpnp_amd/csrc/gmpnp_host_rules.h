@@ -16,7 +16,8 @@
 namespace gmpnp {
 
 // device status word: bit 1 = steric excursion (information, unless strict_steric), bits 2 / 4 / 8 = the linear solve failed,
-// bit 16 = the step limiter met a NaN / Inf in the correction (the update was not applied), bit 32 = eps(u) <= 0 on the Stern boundary
+// bit 16 = the step limiter met a NaN / Inf in the correction (the update was not applied), bit 32 = eps(u) <= 0 on the Stern boundary,
+// bit 64 = a surface reaction rate that is not finite (kinetics on the Stern boundary)
 inline std::string status_message(int flags) {
   std::string m;
   if (flags & 1) m += "1 - sum_j a_j u_j <= 0 at a quadrature point; ";
@@ -25,6 +26,7 @@ inline std::string status_message(int flags) {
   if (flags & 8) m += "in-launch hand-over timed out; ";
   if (flags & 16) m += "NaN / Inf in the Newton correction (step limiter); ";
   if (flags & 32) m += "eps(u) <= 0 on the Stern boundary (BDM model); ";
+  if (flags & 64) m += "surface kinetics: a reaction rate on the Stern boundary is not finite; ";
   return m;
 }
 
@@ -58,6 +60,36 @@ inline bool stern_options_valid(const gmpnp_stern_t& o) {
          (o.model == 1 || (o.eps_surface > 0.0 && !std::isinf(o.eps_surface)));
 }
 
+// ---- surface kinetics (include/gmpnp.h "potential-dependent surface kinetics"; kernels: gmpnp_kinetics.h) --------------------------
+// Reaction r on the Stern boundary runs at  rate = k (u_reactant or 1) E,  E = exp(-alpha (p_M - p - p_eq)),  with p and u at the
+// boundary node.  d_u = d rate / d u_reactant = k E and d_p = d rate / d p = alpha rate are what the Jacobian takes.  The reactant
+// is not clamped (a negative u gives a negative rate: the derivative stays exact).  ok = 0 where rate or k E is not finite (the
+// exponent overflowed at a wild iterate): the caller raises status bit 64.  One function for the host and the device;
+// gmpnp_amd/kinetics.py's surface_rate is its Python statement, operation for operation.
+struct KinRate { double rate, d_u, d_p; int ok; };
+GMPNP_RULE_HD inline KinRate surface_rate(double k, double alpha, double p_eq, double p_M, double p, int has_reactant, double u_reactant) {
+  const double E = exp(-alpha * (p_M - p - p_eq));
+  const double kE = k * E;
+  const double rate = has_reactant ? kE * u_reactant : kE;
+  const double d_p = alpha * rate;
+  // finite: |x| <= DBL_MAX is false for Inf and NaN (x - x == 0 would not do: under FMA contraction the compiler may turn the
+  // difference of a product and its rounded value into the rounding error)
+  const double big = 1.7976931348623157e308;
+  const int ok = ((rate < 0.0 ? -rate : rate) <= big) && ((kE < 0.0 ? -kE : kE) <= big) && ((d_p < 0.0 ? -d_p : d_p) <= big);
+  return KinRate{rate, kE, d_p, ok};
+}
+inline bool kinetics_options_valid(const gmpnp_kinetics_t& o, int n_species) {
+  auto fin = [](double v) { return v == v && !std::isinf(v); };
+  if (o.n_reactions < 0 || o.n_reactions > GMPNP_MAX_SURFACE_REACTIONS) return false;
+  if (!fin(o.p_electrode)) return false;
+  for (int r = 0; r < o.n_reactions; ++r) {
+    if (!fin(o.k[r]) || !fin(o.alpha[r]) || !fin(o.p_eq[r])) return false;
+    if (o.reactant[r] < -1 || o.reactant[r] >= n_species) return false;
+    for (int i = 0; i < GMPNP_MAX_SPECIES; ++i) if (!fin(o.nu[r][i])) return false;
+  }
+  return true;
+}
+
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every
 // update.  A driver hands every residual norm (with the device status word of its evaluation) to first() / next() and does what
 // the verdict says; on `failed` and `limit` the error is (code, message).  Owns r0, steric_excursion, residuals[], n_residuals
@@ -76,7 +108,7 @@ struct NewtonJudge {
   // residual at the state the solve starts from (the status bits of a linear solve mean nothing yet)
   Verdict first(double r, int flags) {
     if (steric(flags)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
-    if (flags & 32) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+    if (flags & (32 | 64)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
     r0 = r;
     st.residuals[0] = r; st.n_residuals = 1;
     if (!(r == r)) return fail(GMPNP_ERR_NUMERIC, "residual is NaN before the first Newton iteration");
@@ -85,7 +117,7 @@ struct NewtonJudge {
   // residual after an update (st.iterations already counts it)
   Verdict next(double r, int flags) {
     if (steric(flags)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
-    if (flags & (16 | 32)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+    if (flags & (16 | 32 | 64)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
     if (flags & 14) return fail(GMPNP_ERR_LINEAR, status_message(flags));
     if (st.n_residuals < GMPNP_MAX_NEWTON_HISTORY) st.residuals[st.n_residuals++] = r;
     // NaN / Inf stay fatal (DOLFIN would iterate to its limit on a NaN residual and raise there)

@@ -16,6 +16,8 @@
 //   k_stern_sum        one workgroup: the integrated term, sum over the Stern nodes of bnd_dyn - bndF, fixed order
 // Every sum is a gather in list order (no floating-point atomics): two calls on one state give equal bits.  A potential row with a
 // Dirichlet flag is skipped by all three, as k_robin_add skips Dirichlet rows.  eps <= 0 (BDM): status bit 32, g = g' = 0.
+// bnd_dyn is the handle's one dynamic boundary vector (boundary_rebind, gmpnp_api.hip), shared with the surface kinetics
+// (gmpnp_kinetics.h), which write the species rows only.
 // Included at the end of gmpnp_api.hip.
 #pragma once
 
@@ -181,7 +183,7 @@ int stern_build(gmpnp_solver* s, gmpnp_sterner* S) {
   HIP_TRY(S->node.upload(node)); HIP_TRY(S->nf_ptr.upload(nf_ptr)); HIP_TRY(S->nf_ent.upload(nf_ent)); HIP_TRY(S->fnodes.upload(fnodes));
   HIP_TRY(S->area.upload(area)); HIP_TRY(S->pair_row.upload(pair_row)); HIP_TRY(S->pf_ptr.upload(pf_ptr)); HIP_TRY(S->pf_ent.upload(pf_ent));
   HIP_TRY(S->addr.upload(addr));
-  HIP_TRY(S->bnd_dyn.alloc((size_t)s->ndof)); HIP_TRY(S->sum.alloc(1));
+  HIP_TRY(S->sum.alloc(1));
   return GMPNP_OK;
 }
 
@@ -192,18 +194,8 @@ SternTab stern_tab(gmpnp_solver* s, int32_t* status) {
   t.p_M = S->opt.p_electrode; t.lam = S->opt.lam; t.eps_s = S->opt.eps_surface;
   t.node = S->node.p; t.nf_ptr = S->nf_ptr.p; t.nf_ent = S->nf_ent.p; t.fnodes = S->fnodes.p; t.area = S->area.p;
   t.pair_row = S->pair_row.p; t.pf_ptr = S->pf_ptr.p; t.pf_ent = S->pf_ent.p; t.addr = S->addr.p;
-  t.bndF = s->bndF.p; t.bnd_dyn = S->bnd_dyn.p; t.status = status;
+  t.bndF = s->bndF.p; t.bnd_dyn = s->bnd_dyn.p; t.status = status;
   return t;
-}
-
-// bnd_dyn <- bndF and the context reads bnd_dyn (option on); the context reads bndF (option off)
-int stern_rebind(gmpnp_solver* s) {
-  gmpnp_sterner* S = s->sterner.get();
-  if (!S || S->opt.model == 0) { s->c.bndF = s->bndF.p; return GMPNP_OK; }
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(S->bnd_dyn.p, s->bndF.p, (size_t)s->ndof * sizeof(double), hipMemcpyDeviceToDevice));
-  s->c.bndF = S->bnd_dyn.p;
-  return GMPNP_OK;
 }
 
 int stern_launch_residual(gmpnp_solver* s, int32_t* status) {
@@ -249,7 +241,7 @@ int gmpnp_set_stern(gmpnp_solver* s, const gmpnp_stern_t* o) {
   }
   s->sterner->opt = *o;
   s->jacobian_valid = false; s->precond_valid = false;
-  return stern_rebind(s);
+  return boundary_rebind(s);
 }
 
 int gmpnp_stern_displacement(gmpnp_solver* s, double* out) {

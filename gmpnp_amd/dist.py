@@ -265,6 +265,8 @@ class PartitionedSolver:
         ``ml_theta`` / ``ml_sweeps`` as on one GPU.  Not over the peer transport (refused by the library)."""
         if getattr(prob, "stern", None) is not None:
             raise ValueError("partition: the Stern boundary condition is not available in a partitioned solve")
+        if getattr(prob, "kinetics", None) is not None:
+            raise ValueError("partition: the surface kinetics are not available in a partitioned solve")
         from ctypes import c_void_p
         if rank is not None:
             # one rank per process: torch.distributed carries the set-up (mailbox handles, communicator id, host-staged collectives).

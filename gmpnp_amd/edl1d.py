@@ -25,7 +25,7 @@ import numpy as np
 from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import _load_yaml, edl_parameters, utilities_dir
-from .problem import add_stern_arguments, edl_problem, pop_stern, stern_keywords
+from .problem import add_kinetics_arguments, add_stern_arguments, edl_problem, kinetics_keywords, pop_kinetics, pop_stern, stern_keywords
 from .solver import GMPNPSystem, supg_parameters
 from .timestep import adaptive_keywords, add_adaptive_arguments
 
@@ -66,8 +66,22 @@ class EDLRun:
         ``H_OHP`` (ValueError, before anything touches the device).  The metadata gains ``electrode_voltage``, ``stern_model``,
         ``stern_length``, ``stern_displacement`` (the integrated Stern term g (p_M - p) / lam of the last state, scaled units) and
         ``surface_charge`` [C/m2] = eps_0 thermal_voltage / L_n x stern_displacement: the displacement eps_0 eps_r E pointing from the
-        electrode into the electrolyte, i.e. the charge per area ON THE ELECTRODE (negative for a cathode, p_M < p_OHP)."""
+        electrode into the electrolyte, i.e. the charge per area ON THE ELECTRODE (negative for a cathode, p_M < p_OHP).
+        ``kinetics`` = "tafel" (with ``electrode_voltage``; ``i0_CO`` / ``i0_H2`` [A/m2] required, ``alpha_CO`` / ``alpha_H2`` = 0.5,
+        ``p_eq_CO`` / ``p_eq_H2`` = 0 thermal voltages): the currents of CO2 -> CO and of the hydrogen evolution follow the potential
+        drop across the Stern layer and the CO2 concentration at the OHP (gmpnp_amd/kinetics.py) in place of the
+        prescribed ``current_OHP_ss`` / ``H2_FE``, which are then unused for the CO2, OH and H fluxes.  Not with ``stabilization`` "Y"
+        and not with ``H_OHP`` (ValueError, before anything touches the device).  Every step records ``i_CO``, ``i_H2`` [A/m2] and
+        ``FE_H2`` (arrays_unscaled.npz; the last values and the kinetic parameters in the metadata)."""
         self.stern = pop_stern(kwargs, kwargs.get("L_n", 50.0e-6))
+        self.kinetic_par = pop_kinetics(kwargs)
+        if self.kinetic_par is not None:
+            if self.stern is None:
+                raise ValueError("kinetics: the surface kinetics need an electrode potential (electrode_voltage)")
+            if kwargs.get("stabilization", "N") == "Y":
+                raise ValueError("kinetics: the surface kinetics are not available with stabilization Y")
+            if kwargs.get("H_OHP") is not None:
+                raise ValueError("kinetics: the surface kinetics are not available with the H_OHP flux controller")
         if self.stern is not None and kwargs.get("stabilization", "N") == "Y":
             raise ValueError("electrode_voltage: the Stern boundary condition is not available with stabilization Y")
         if self.stern is not None and kwargs.get("H_OHP") is not None:
@@ -84,7 +98,12 @@ class EDLRun:
         self.warn_stab = stab and ep.model_name != "PNP"   # "Warning:stabilization not implemented for MPNP!", 1D:724-727
         self.h_vertex = None
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), ep.mesh_name))
-        self.problem = edl_problem(ep, self.mesh, stern=self.stern)
+        self.kinetics, self.currents = None, []
+        if self.kinetic_par is not None:
+            from .kinetics import edl_tafel
+            self.kinetics, ep.model = edl_tafel(ep, self.kinetic_par, self.stern.p_electrode)
+            print("kinetics tafel: current_OHP_ss and H2_FE are not used for the CO2, OH and H fluxes at the OHP")
+        self.problem = edl_problem(ep, self.mesh, stern=self.stern, kinetics=self.kinetics)
         self.model = copy.deepcopy(self.problem.model)
         self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
         self.solver_parameters = backend.with_step_fraction(solver_parameters or SOLVER_PARAMETERS, self.step_fraction)
@@ -183,6 +202,8 @@ class EDLRun:
         1D:770-793) re-uploads the OHP fluxes.  u_n.assign(u) and the step count stay with the caller."""
         ep = self.ep
         self.history.append(vals)
+        if self.kinetics is not None:
+            self.currents.append(self.sys.dev.kinetics_currents())
         H_OHP_frac = vals[0, 0]
         H_OHP = ep.H_OHP
         if H_OHP is not None:  # reference 1D:770-793
@@ -234,6 +255,12 @@ class EDLRun:
         return {"electrode_voltage": st.p_electrode, "stern_model": st.model, "stern_length": st.lam * ep.L_n, "stern_displacement": d,
                 "surface_charge": EPS_0 * ep.thermal_voltage / ep.L_n * d}
 
+    def kinetics_summary(self):
+        """Per-step ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2`` of a run with the surface kinetics (the OHP is one point: w = 1)."""
+        from .kinetics import current_summary
+        rows = [current_summary(c, 1.0) for c in self.currents]
+        return {k: np.array([r[k] for r in rows]) for k in ("i_CO", "i_H2", "FE_H2")}
+
     def write_outputs(self, stamp=None):
         ep, mesh, k = self.ep, self.mesh, self.kwargs
         stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
@@ -255,7 +282,8 @@ class EDLRun:
             tau_array = np.concatenate((np.linspace(0, ep.stage_T[0], ep.stage_steps[0]),
                                         np.linspace(ep.stage_T[0] + ep.dts[1], ep.stage_T[1], ep.stage_steps[1])))
         np.savez(newpath + "/arrays_unscaled.npz", H=Hh["H"], OH=Hh["OH"], HCO3=Hh["HCO3"], CO32=Hh["CO32"],
-                 CO2=Hh["CO2"], cat=Hh["cat"], p=Hh["p"], coor=mesh.coords, tau=tau_array, field_values=field_values)
+                 CO2=Hh["CO2"], cat=Hh["cat"], p=Hh["p"], coor=mesh.coords, tau=tau_array, field_values=field_values,
+                 **(self.kinetics_summary() if self.kinetics is not None else {}))
         sc = {nme: scale(species=sp, tau=tau_array, C=Hh[nme], initial_conc=ep.initial_conc, diff_coeff=ep.diff_coeff,
                          L_n=ep.L_n, L_debye=ep.L_debye) for nme, sp in zip(names[:6], ep.species)}
         c = {nme: sc[nme][1] for nme in sc}
@@ -292,6 +320,10 @@ class EDLRun:
             metadata_dict["step_fraction"] = self.step_fraction
         if self.stern is not None:
             metadata_dict.update(self.stern_summary())
+        if self.kinetics is not None:
+            from .kinetics import tafel_parameters
+            metadata_dict.update(tafel_parameters(self.kinetic_par))
+            metadata_dict.update({key: (float(v[-1]) if len(v) else None) for key, v in self.kinetics_summary().items()})
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
@@ -315,7 +347,8 @@ def run_identifier(ep, kwargs, stern=None):
 def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_FE=0.2, mesh_structure="variable",
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
               dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM",
-              stern_length=4.0e-10, stern_eps_surface=6.0, **adaptive):
+              stern_length=4.0e-10, stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0,
+              p_eq_H2=0.0, **adaptive):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
     adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
     ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
@@ -325,6 +358,8 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
         stern = dict(electrode_voltage=electrode_voltage, stern_model=stern_model, stern_length=stern_length, stern_eps_surface=stern_eps_surface)
     elif voltage_multiplier is None:
         voltage_multiplier = -1.0
+    if kinetics is not None:   # (the surface kinetics of ``EDLRun``)
+        stern.update(kinetics=kinetics, i0_CO=i0_CO, i0_H2=i0_H2, alpha_CO=alpha_CO, alpha_H2=alpha_H2, p_eq_CO=p_eq_CO, p_eq_H2=p_eq_H2)
     run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, **stern, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
@@ -356,6 +391,7 @@ def build_parser():
     p.add_argument("--step_fraction", required=False, default=0.0, type=float, help="(addition) fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off")
     add_adaptive_arguments(p)
     add_stern_arguments(p)
+    add_kinetics_arguments(p)
     return p
 
 
@@ -364,7 +400,7 @@ def main(argv=None):
     return solve_EDL(concentration_elec=a.concentration_elec, model=a.model, voltage_multiplier=a.voltage_multiplier,
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
-                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a))
+                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a))
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@ import itertools
 
 from . import backend
 from .edl1d import EDLRun, run_identifier
-from .problem import refuse_stern
+from .problem import refuse_kinetics, refuse_stern
 from .params import edl_parameters
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
 
@@ -42,6 +42,7 @@ def plan_members(members, num_steps=None):
     full = []
     for k, m in enumerate(members):
         refuse_stern(m, "an ensemble (member %d)" % k)
+        refuse_kinetics(m, "an ensemble (member %d)" % k)
         unknown = set(m) - set(MEMBER_DEFAULTS) - {"num_steps"}
         if unknown:
             raise TypeError("member %d: unknown keyword(s) %s" % (k, sorted(unknown)))

@@ -20,7 +20,7 @@ from datetime import datetime
 
 from . import backend
 from .edl1d import output_root
-from .problem import refuse_stern
+from .problem import refuse_kinetics, refuse_stern
 from .edl_ensemble import EDLEnsemble, sweep_members
 from .timestep import adaptive_keywords, add_adaptive_arguments
 
@@ -51,7 +51,9 @@ def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget
     ``adaptive``: the adaptive-stepping keywords of ``EDLEnsemble`` (scalars: the same for every member)."""
     for k, m in enumerate(members):
         refuse_stern(m, "the ensemble sweep (member %d)" % k)
+        refuse_kinetics(m, "the ensemble sweep (member %d)" % k)
     refuse_stern(adaptive, "the ensemble sweep")
+    refuse_kinetics(adaptive, "the ensemble sweep")
     stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
     rows = []
     for c0 in range(0, len(members), backend.MAX_ENSEMBLE):

@@ -18,7 +18,8 @@ import numpy as np
 from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
-from .problem import add_stern_arguments, pop_stern, pore_dirichlet, pore_problem, stern_keywords
+from .problem import (add_kinetics_arguments, add_stern_arguments, kinetics_keywords, pop_kinetics, pop_stern, pore_dirichlet, pore_problem,
+                      stern_keywords)
 from .solver import GMPNPSystem, column_medians, device_medians_and_minima
 from .timestep import DriverStepping, adaptive_keywords, add_adaptive_arguments
 from .vtk import write_pvd
@@ -77,10 +78,24 @@ class PoreRun:
         "linear", ``stern_length`` 4e-10 m, ``stern_eps_surface`` 6); the wall potential becomes a result.  Not with ``partition`` or
         ``multilevel`` (ValueError, before anything touches the device).  The metadata gains ``electrode_voltage``, ``stern_model``,
         ``stern_length``, ``stern_displacement`` (the Stern term integrated over the wall, scaled units) and ``surface_charge``
-        [C/m2] = eps_0 thermal_voltage / L x stern_displacement / wall area (scaled): the mean charge per area on the electrode."""
+        [C/m2] = eps_0 thermal_voltage / L x stern_displacement / wall area (scaled): the mean charge per area on the electrode.
+        ``kinetics`` = "tafel" (with ``electrode_voltage``; ``i0_CO`` / ``i0_H2`` [A/m2] required, ``alpha_CO`` / ``alpha_H2`` = 0.5,
+        ``p_eq_CO`` / ``p_eq_H2`` = 0 thermal voltages): the wall fluxes of CO2, CO, H2 and OH follow the potential drop across the
+        Stern layer and the CO2 concentration at the wall (gmpnp_amd/kinetics.py) in place of the prescribed
+        ``current_rough`` / ``H2_FE``, which are then unused for them.  Not with ``partition`` or ``multilevel`` (ValueError, before
+        anything touches the device).  Every step records the wall means ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2``
+        (arrays_unscaled.npz; the last values and the kinetic parameters in the metadata)."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
         self.stern = pop_stern(kwargs, kwargs.get("L", 100.0e-9))
+        self.kinetic_par = pop_kinetics(kwargs)
+        if self.kinetic_par is not None:
+            if self.stern is None:
+                raise ValueError("kinetics: the surface kinetics need an electrode potential (electrode_voltage)")
+            if partition:
+                raise ValueError("kinetics: the surface kinetics are not available in a partitioned solve")
+            if multilevel:
+                raise ValueError("kinetics: the surface kinetics are not available with the geometric multilevel term")
         if self.stern is not None and partition:
             raise ValueError("electrode_voltage: the Stern boundary condition is not available in a partitioned solve")
         if self.stern is not None and multilevel:
@@ -97,12 +112,19 @@ class PoreRun:
         self.pp = pore_parameters(as_published=as_published, **kwargs)
         self.mesh = read_dolfin_xml(resolve_mesh_path(utilities_dir(), self.pp.mesh_name))
         self._levels = None
+        self.kinetics, self.currents = None, []
+        if self.kinetic_par is not None:
+            from .kinetics import pore_tafel
+            from .params import _load_yaml
+            farad = _load_yaml(os.path.join(utilities_dir(), kwargs.get("params_file", "parameters_pore") + ".yaml"))["nat_const"]["F"]
+            self.kinetics, self.pp.model = pore_tafel(self.pp, self.kinetic_par, self.stern.p_electrode, farad)
+            print("kinetics tafel: current_rough and H2_FE are not used for the CO2, CO, H2 and OH fluxes at the wall")
         if multilevel and refine > 0:
             from .problem import pore_hierarchy
             self._levels = pore_hierarchy(self.pp, self.mesh, refine)
             self.problem, self.bnd = self._levels[0][0], self._levels[0][1]
         else:
-            self.problem, self.bnd = pore_problem(self.pp, self.mesh, refine=refine, stern=self.stern)
+            self.problem, self.bnd = pore_problem(self.pp, self.mesh, refine=refine, stern=self.stern, kinetics=self.kinetics)
         if refine:  # uniformly refined copy of the reference mesh (not a reference feature: roofline studies)
             from .mesh import Mesh
             self.mesh = Mesh(dim=3, coords=self.problem.coords, cells=self.problem.cells)
@@ -184,6 +206,8 @@ class PoreRun:
         """What follows the Newton solve of a step: history row, Sechenov, new Dirichlet set, ``u_n.assign(u)``, counters.
         ``assign=False``: the caller assigns (``PoreEnsemble`` does it for all its members with one launch)."""
         self.history.append(row)
+        if self.kinetics is not None:
+            self.currents.append(self.sys.dev.kinetics_currents())
         # medians of the scaled ion concentrations -> Sechenov -> new CO2 Dirichlet value at S1 (3D:817-838)
         self.co2_bc = self.pp.sechenov_co2_scaled(*meds)
         self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, self.co2_bc, stern=self.stern is not None))
@@ -236,6 +260,17 @@ class PoreRun:
         return {"electrode_voltage": st.p_electrode, "stern_model": st.model, "stern_length": st.lam * pp.L, "stern_displacement": d,
                 "surface_charge": eps_0 * pp.thermal_voltage / pp.L * d / area}
 
+    def wall_area(self):
+        X = self.problem.coords[self.problem.wall_facets]
+        return float((0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)).sum())
+
+    def kinetics_summary(self):
+        """Per-step wall means ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2`` of a run with the surface kinetics (sum_I w_I = the wall area)."""
+        from .kinetics import current_summary
+        area = self.wall_area()
+        rows = [current_summary(c, area) for c in self.currents]
+        return {k: np.array([r[k] for r in rows]) for k in ("i_CO", "i_H2", "FE_H2")}
+
     # ---- outputs (3D:860-1085) -------------------------------------------------------------------
     def write_outputs(self, stamp=None):
         pp, mesh, k = self.pp, self.mesh, self.kwargs
@@ -273,7 +308,7 @@ class PoreRun:
                  CO=H["CO"], H2=H["H2"], cat=H["cat"], p=H["p"], coor=mesh.coords, tau=tau_array,
                  field_values=field_values, H_grad=grads["H"], OH_grad=grads["OH"], HCO3_grad=grads["HCO3"],
                  CO32_grad=grads["CO32"], CO2_grad=grads["CO2"], CO_grad=grads["CO"], H2_grad=grads["H2"],
-                 cat_grad=grads["cat"])
+                 cat_grad=grads["cat"], **(self.kinetics_summary() if self.kinetics is not None else {}))
         sc = {}
         for nme, sp in zip(names[:8], pp.species):
             sc[nme] = scale_conc_time(species=sp, C=H[nme], grad_c=grads[nme], bulk_conc=pp.bulk_conc, tau=tau_array,
@@ -309,6 +344,10 @@ class PoreRun:
             metadata_dict["step_fraction"] = self.step_fraction
         if self.stern is not None:
             metadata_dict.update(self.stern_summary())
+        if self.kinetics is not None:
+            from .kinetics import tafel_parameters
+            metadata_dict.update(tafel_parameters(self.kinetic_par))
+            metadata_dict.update({key: (float(v[-1]) if len(v) else None) for key, v in self.kinetics_summary().items()})
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
@@ -323,7 +362,7 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
              device_kwargs=None, glue="host", budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM", stern_length=4.0e-10,
-             stern_eps_surface=6.0, **adaptive):
+             stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0, p_eq_H2=0.0, **adaptive):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
     geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
@@ -336,6 +375,8 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
         stern = dict(electrode_voltage=electrode_voltage, stern_model=stern_model, stern_length=stern_length, stern_eps_surface=stern_eps_surface)
     elif voltage_multiplier is None:
         voltage_multiplier = -1.0
+    if kinetics is not None:   # (the surface kinetics of ``PoreRun``)
+        stern.update(kinetics=kinetics, i0_CO=i0_CO, i0_H2=i0_H2, alpha_CO=alpha_CO, alpha_H2=alpha_H2, p_eq_CO=p_eq_CO, p_eq_H2=p_eq_H2)
     run = PoreRun(**stern, num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
                   device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
@@ -376,6 +417,7 @@ def build_parser():
                    help="fraction-to-boundary step limiter of the Newton update: tau in (0, 1), 0 = off (not with --partitions)")
     add_adaptive_arguments(p)   # (not with --partitions)
     add_stern_arguments(p)      # (not with --partitions / --multilevel; --voltage_multiplier defaults to -1.0 without --electrode_voltage)
+    add_kinetics_arguments(p)   # (with --electrode_voltage; not with --partitions / --multilevel)
     return p
 
 
@@ -405,6 +447,8 @@ def main(argv=None):
         raise ValueError("--adaptive_dt: adaptive time stepping is not available with --partitions")
     if a.partitions and a.electrode_voltage is not None:
         raise ValueError("--electrode_voltage: the Stern boundary condition is not available with --partitions")
+    if a.partitions and a.kinetics is not None:
+        raise ValueError("--kinetics: the surface kinetics are not available with --partitions")
     if a.electrode_voltage is not None and a.voltage_multiplier is not None:
         raise ValueError("--electrode_voltage takes the place of --voltage_multiplier: give one of them")
     if a.partitions:
@@ -418,7 +462,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

@@ -16,7 +16,7 @@ import numpy as np
 from . import backend
 from .edl_ensemble import ADAPTIVE_REFUSAL, AdaptiveRounds, error_text
 from .pore3d import SOLVER_PARAMETERS, PoreRun
-from .problem import refuse_stern
+from .problem import refuse_kinetics, refuse_stern
 from .solver import column_medians
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
 
@@ -39,6 +39,7 @@ def plan_members(members, num_steps=None):
     full = []
     for k, m in enumerate(members):
         refuse_stern(m, "an ensemble (member %d)" % k)
+        refuse_kinetics(m, "an ensemble (member %d)" % k)
         for f in REFUSED:
             if m.get(f):
                 raise ValueError("member %d: %s is not supported in an ensemble" % (k, f))

@@ -8,7 +8,7 @@ boundary facet sets and the merged Dirichlet table, all in FILE vertex order wit
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -79,6 +79,89 @@ def stern_keywords(a):
     return {k: getattr(a, k) for k in STERN_KEYWORDS}
 
 
+MAX_SURFACE_REACTIONS = 4  # GMPNP_MAX_SURFACE_REACTIONS (include/gmpnp.h)
+
+
+@dataclass
+class SurfaceReaction:
+    """One reaction of ``SurfaceKinetics``: rate = k (u_reactant or 1) exp(-alpha (p_M - p - p_eq)); ``nu``: species name -> flux weight."""
+    k: float
+    alpha: float = 0.5
+    p_eq: float = 0.0  # [thermal voltages]
+    reactant: str = None  # species name, None = no reactant
+    nu: dict = field(default_factory=dict)
+
+
+@dataclass
+class SurfaceKinetics:
+    """Potential-dependent surface kinetics on the Stern boundary (include/gmpnp.h ``gmpnp_kinetics_t`` with the
+    species by name): the species rows of the boundary nodes gain ``w_I sum_r nu[r][i] rate_r``.  ``p_electrode``: the kinetics' own p_M."""
+    reactions: list
+    p_electrode: float
+
+    def __post_init__(self):
+        self.reactions = list(self.reactions)
+        if not 1 <= len(self.reactions) <= MAX_SURFACE_REACTIONS:
+            raise ValueError("surface kinetics: 1 ... %d reactions, not %d" % (MAX_SURFACE_REACTIONS, len(self.reactions)))
+        vals = [self.p_electrode] + [v for r in self.reactions for v in (r.k, r.alpha, r.p_eq, *r.nu.values())]
+        if not np.isfinite(np.asarray(vals, dtype=np.float64)).all():
+            raise ValueError("surface kinetics: k, alpha, p_eq, nu and the electrode potential must be finite")
+
+    def check_species(self, species):
+        """ValueError where a reactant or a flux weight names a species the model does not have."""
+        for r in self.reactions:
+            for name in ([] if r.reactant is None else [r.reactant]) + list(r.nu):
+                if name not in species:
+                    raise ValueError("surface kinetics: no species %r in the model (%s)" % (name, ", ".join(species)))
+
+
+KINETICS_KEYWORDS = ("kinetics", "i0_CO", "i0_H2", "alpha_CO", "alpha_H2", "p_eq_CO", "p_eq_H2")
+
+
+def pop_kinetics(kwargs):
+    """Takes the kinetics keywords of a driver (``kinetics`` = "tafel", ``i0_CO`` / ``i0_H2`` [A/m2], ``alpha_CO`` / ``alpha_H2`` = 0.5,
+    ``p_eq_CO`` / ``p_eq_H2`` = 0 thermal voltages) out of ``kwargs``; returns them as a dict, or None without ``kinetics``."""
+    kind = kwargs.pop("kinetics", None)
+    par = {k: kwargs.pop(k, None) for k in KINETICS_KEYWORDS[1:]}
+    if kind is None:
+        return None
+    if kind != "tafel":
+        raise ValueError("kinetics must be 'tafel', not %r" % (kind,))
+    if par["i0_CO"] is None or par["i0_H2"] is None:
+        raise ValueError("kinetics tafel: i0_CO and i0_H2 [A/m2] are required")
+    for k, default in (("alpha_CO", 0.5), ("alpha_H2", 0.5), ("p_eq_CO", 0.0), ("p_eq_H2", 0.0)):
+        par[k] = default if par[k] is None else par[k]
+    par = {k: float(v) for k, v in par.items()}
+    if not all(np.isfinite(v) for v in par.values()):
+        raise ValueError("kinetics tafel: the parameters must be finite")
+    return par
+
+
+def refuse_kinetics(kwargs, what):
+    """ValueError if a keyword dict asks for the surface kinetics where they do not exist (before anything touches the device)."""
+    if kwargs.get("kinetics") is not None:
+        raise ValueError("kinetics: the potential-dependent surface kinetics are not available in %s" % what)
+
+
+def add_kinetics_arguments(p):
+    """The drivers' command-line flags of the surface kinetics (additions, not reference flags)."""
+    p.add_argument("--kinetics", required=False, default=None, type=str, choices=("tafel",),
+                   help="(addition) potential-dependent Tafel currents at the OHP in place of the prescribed current; needs --electrode_voltage")
+    p.add_argument("--i0_CO", required=False, default=None, type=float, help="(addition) rate constant of CO2 -> CO [A/m2], required with --kinetics")
+    p.add_argument("--i0_H2", required=False, default=None, type=float, help="(addition) rate constant of the hydrogen evolution [A/m2], required with --kinetics")
+    p.add_argument("--alpha_CO", required=False, default=0.5, type=float, help="(addition) transfer coefficient of CO2 -> CO")
+    p.add_argument("--alpha_H2", required=False, default=0.5, type=float, help="(addition) transfer coefficient of the hydrogen evolution")
+    p.add_argument("--p_eq_CO", required=False, default=0.0, type=float, help="(addition) equilibrium offset of CO2 -> CO [thermal voltages]")
+    p.add_argument("--p_eq_H2", required=False, default=0.0, type=float, help="(addition) equilibrium offset of the hydrogen evolution [thermal voltages]")
+
+
+def kinetics_keywords(a):
+    """The kinetics keywords of a parsed command line (``add_kinetics_arguments``); empty without --kinetics."""
+    if a.kinetics is None:
+        return {}
+    return {k: getattr(a, k) for k in KINETICS_KEYWORDS}
+
+
 @dataclass
 class Problem:
     coords: np.ndarray  # (nv,d)
@@ -96,6 +179,7 @@ class Problem:
     supg_rho: np.ndarray = None
     supg_w: np.ndarray = None
     stern: SternLayer = None  # Stern-layer boundary condition of the potential; None = the potential is prescribed (Dirichlet)
+    kinetics: SurfaceKinetics = None  # potential-dependent surface kinetics on the Stern boundary; None = the constant fluxes alone
 
     def __post_init__(self):
         d = self.coords.shape[1]
@@ -164,7 +248,7 @@ def pore_dirichlet(pp, bnd, co2_value=None, stern=False):
     return dofs, vals
 
 
-def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0, stern: SternLayer = None):
+def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0, stern: SternLayer = None, kinetics: SurfaceKinetics = None):
     """Problem + boundary record for the 3D pore (reference 3D:329-382,460-467).  ``refine`` > 0 applies that many
     uniform refinements with inherited markers (gmpnp_amd.mesh.refine_pore); returns (problem, boundaries) of the
     mesh actually used (``problem.coords/cells``)."""
@@ -174,7 +258,7 @@ def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0, stern
         mesh, bnd = refine_pore(mesh, bnd)
     dofs, vals = pore_dirichlet(pp, bnd, stern=stern is not None)
     prob = Problem(coords=mesh.coords, cells=mesh.cells, model=pp.model, quad=quad,
-                   wall_facets=bnd.ds_facets[2], exit_facets=bnd.ds_facets[3], bc_dofs=dofs, bc_vals=vals, stern=stern)
+                   wall_facets=bnd.ds_facets[2], exit_facets=bnd.ds_facets[3], bc_dofs=dofs, bc_vals=vals, stern=stern, kinetics=kinetics)
     return prob, bnd
 
 
@@ -196,7 +280,7 @@ def pore_hierarchy(pp, mesh: Mesh, refine: int, quad: Quadrature = None):
     return out
 
 
-def edl_problem(ep, mesh: Mesh, quad: Quadrature = None, stern: SternLayer = None):
+def edl_problem(ep, mesh: Mesh, quad: Quadrature = None, stern: SternLayer = None, kinetics: SurfaceKinetics = None):
     """Problem for the 1D EDL (reference 1D:237-254,350-355): all 7 fields pinned to
     (1,..,1,0) at x=1; p = voltage_multiplier at x=0; point fluxes at the x=0 vertex.  ``stern``: the OHP potential is not
     prescribed (the (left, ns, voltage) entry is dropped) and the record travels with the problem."""
@@ -209,4 +293,4 @@ def edl_problem(ep, mesh: Mesh, quad: Quadrature = None, stern: SternLayer = Non
     bcs = [(right, f, 1.0) for f in range(ns)] + [(right, ns, 0.0)] + ([] if stern is not None else [(left, ns, ep.voltage_scaled)])
     dofs, vals = merge_dirichlet(bcs, ns + 1)
     return Problem(coords=mesh.coords, cells=mesh.cells, model=ep.model, quad=quad,
-                   point_vertices=left.astype(np.int32), bc_dofs=dofs, bc_vals=vals, stern=stern)
+                   point_vertices=left.astype(np.int32), bc_dofs=dofs, bc_vals=vals, stern=stern, kinetics=kinetics)

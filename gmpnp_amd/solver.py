@@ -81,6 +81,8 @@ class GMPNPSystem(_System):
         preconditioner; the coarser levels are ordinary handles of the parent meshes on the same device, owned by this system."""
         if levels and getattr(problem, "stern", None) is not None:
             raise ValueError("multilevel: the Stern boundary condition is not available with the geometric multilevel term")
+        if levels and getattr(problem, "kinetics", None) is not None:
+            raise ValueError("multilevel: the surface kinetics are not available with the geometric multilevel term")
         self.dev = backend.DeviceSolver(problem, **device_kwargs)
         super().__init__(problem, self.dev)
         self._coarse = [backend.DeviceSolver(lv[0], device_id=device_kwargs.get("device_id", 0), shared_device=1) for lv in (levels or [])[1:]]

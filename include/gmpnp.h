@@ -529,6 +529,39 @@ typedef struct {
 int gmpnp_set_stern(gmpnp_solver* s, const gmpnp_stern_t* stern);
 int gmpnp_stern_displacement(gmpnp_solver* s, double* out);
 
+/* ---- potential-dependent surface kinetics (no reference counterpart: the reference prescribes the current through the constant
+ * wall_flux / point_flux) ---------------------------------------------------------------------------------------------------------
+ * Up to GMPNP_MAX_SURFACE_REACTIONS reactions on the Stern boundary Gamma_S (the node set of gmpnp_set_stern: 1D the point vertices,
+ * 3D the vertices of the wall facets).  Reaction r has a rate constant k, a transfer coefficient alpha, an equilibrium offset p_eq
+ * (thermal voltages), an optional first-order reactant (species index, -1 = none) and flux weights nu[r][i] per species.  With
+ * p_M = p_electrode, at boundary node I:
+ *     E_r    = exp(-alpha_r (p_M - p_I - p_eq_r))            rate_r = k_r (reactant_r >= 0 ? u_{I,reactant_r} : 1) E_r
+ *     F[(I,i)]                += w_I sum_r nu[r][i] rate_r                  (species rows i only)
+ *     J[(I,i),(I,reactant_r)] += w_I nu[r][i] k_r E_r          J[(I,i),(I,p)] += w_I nu[r][i] alpha_r rate_r
+ * w_I = 1 in 1D; in 3D the sum over the wall facets holding I of |f| / 3 in facet list order (vertex quadrature, the weight the
+ * constant wall_flux enters with).  The sign is that of point_flux / wall_flux: one reaction with reactant -1, alpha 0, k 1 and
+ * nu = J is the constant flux J.  The reactant is not clamped.  A species row that carries a Dirichlet value receives nothing.  A
+ * rate that is not finite raises status bit 64: the residual evaluation (gmpnp_assemble, gmpnp_newton_solve) returns
+ * GMPNP_ERR_NUMERIC.  gmpnp_species_budget adds the integrated kinetic flux of species i to its wall (3D) / point (1D) column.
+ * Setting the option invalidates the Jacobian and the preconditioner; n_reactions = 0 on a handle that never had the option changes
+ * nothing, and after the option has been on it restores F and J bit for bit.  Independent of gmpnp_set_stern (a Dirichlet potential
+ * on Gamma_S makes E_r a constant); the two work together.  Refused (GMPNP_ERR_INVALID, the message names kinetics): partition
+ * handles (and so groups), a handle with a coarse level attached or serving as one (and attaching one to a handle with the option
+ * on), every gmpnp_ensemble_* call with such a member, a handle with SUPG terms set (and gmpnp_set_supg with the option on), a mesh
+ * without a Stern boundary.  gmpnp_kinetics_currents: out[r] = sum_I w_I rate_r at the current u. */
+#define GMPNP_MAX_SURFACE_REACTIONS 4
+typedef struct {
+  int32_t n_reactions;                                   /* 0 = off */
+  int32_t reactant[GMPNP_MAX_SURFACE_REACTIONS];         /* species index, -1 = none */
+  double k[GMPNP_MAX_SURFACE_REACTIONS];
+  double alpha[GMPNP_MAX_SURFACE_REACTIONS];
+  double p_eq[GMPNP_MAX_SURFACE_REACTIONS];              /* thermal voltages */
+  double nu[GMPNP_MAX_SURFACE_REACTIONS][GMPNP_MAX_SPECIES];
+  double p_electrode;                                    /* p_M [thermal voltages] */
+} gmpnp_kinetics_t;
+int gmpnp_set_kinetics(gmpnp_solver* s, const gmpnp_kinetics_t* kinetics);
+int gmpnp_kinetics_currents(gmpnp_solver* s, double* out /* [n_reactions] */);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -597,7 +630,9 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * (estimator + reduce + shift; u_n and u_nm1 are put back afterwards, the history flag stays), 23 = the four launches of an accepted
  * order-2 step (u*, order-2 estimator, reduce, three-deep shift; u_n, u_nm1 and u_nm2 are put back, the order and the levels stay;
  * allocates the order-2 vectors), 24 = the two launches of the Stern boundary condition (k_stern_residual + k_stern_jacobian; needs
- * gmpnp_set_stern with model != 0 and an assembled Jacobian, which the launches keep adding to). */
+ * gmpnp_set_stern with model != 0 and an assembled Jacobian, which the launches keep adding to), 25 = the two launches of the surface
+ * kinetics (k_kinetics_residual + k_kinetics_jacobian; needs gmpnp_set_kinetics with n_reactions > 0 and an assembled Jacobian, which
+ * the launches keep adding to). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
