@@ -43,6 +43,7 @@ EXPORTS = [
     "gmpnp_set_time_order", "gmpnp_time_history_levels", "gmpnp_set_time_step_bdf2", "gmpnp_time_error_bdf2", "gmpnp_get_time_history",
     "gmpnp_set_stern", "gmpnp_stern_displacement",
     "gmpnp_set_kinetics", "gmpnp_kinetics_currents",
+    "gmpnp_set_galvanostat", "gmpnp_galvanostat_report", "gmpnp_galvanostat_terms",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -114,6 +115,17 @@ def to_ckinetics(kin, species) -> CKinetics:
         for name, v in rx.nu.items():
             c.nu[r][species.index(name)] = float(v)
     return c
+
+
+class CGalvanostat(ctypes.Structure):
+    """ctypes image of ``gmpnp_galvanostat_t`` (include/gmpnp.h)."""
+    _fields_ = [("on", c_int32), ("target", c_double), ("weight", c_double * MAX_SURFACE_REACTIONS)]
+
+
+class CGalvanostatReport(ctypes.Structure):
+    """ctypes image of ``gmpnp_galvanostat_report_t`` (include/gmpnp.h)."""
+    _fields_ = [("p_electrode", c_double), ("p_electrode_n", c_double), ("I_r", c_double * MAX_SURFACE_REACTIONS), ("I", c_double), ("G", c_double),
+                ("cy", c_double), ("cz", c_double), ("d", c_double), ("dp", c_double), ("alpha", c_double)]
 
 
 class CLinearStats(ctypes.Structure):
@@ -256,6 +268,9 @@ def load_library(path: str = None):
     lib.gmpnp_stern_displacement.argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_set_kinetics.argtypes = [c_void_p, POINTER(CKinetics)]
     lib.gmpnp_kinetics_currents.argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_set_galvanostat.argtypes = [c_void_p, POINTER(CGalvanostat)]
+    lib.gmpnp_galvanostat_report.argtypes = [c_void_p, POINTER(CGalvanostatReport)]
+    lib.gmpnp_galvanostat_terms.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -426,6 +441,8 @@ class DeviceSolver:
         self._n_reactions = 0
         if getattr(problem, "kinetics", None) is not None:
             self.set_kinetics(problem.kinetics)
+        if getattr(problem, "galvanostat", None) is not None:
+            self.set_galvanostat(problem.galvanostat)
 
     # ------------------------------------------------------------------------------------------
     def _check(self, code):
@@ -611,6 +628,35 @@ class DeviceSolver:
         out = (c_double * MAX_SURFACE_REACTIONS)()
         self._check(self.lib.gmpnp_kinetics_currents(self._h, out))
         return np.array(out[:self._n_reactions], dtype=np.float64)
+
+    def set_galvanostat(self, galvanostat=None):
+        """Galvanostatic mode (``gmpnp_set_galvanostat``): a ``problem.Galvanostat`` record, or None = off (the potential that was
+        found stays in the Stern and kinetics options)."""
+        c = CGalvanostat()
+        if galvanostat is not None:
+            c.on, c.target = 1, float(galvanostat.target)
+            for r, w in enumerate(galvanostat.weights):
+                c.weight[r] = float(w)
+        self._check(self.lib.gmpnp_set_galvanostat(self._h, byref(c)))
+
+    def galvanostat_report(self) -> dict:
+        """``gmpnp_galvanostat_report``: p_electrode now and at u_n, the currents I_r, I and G at the current u, and the last
+        iteration's cy, cz, d, dp, alpha."""
+        r = CGalvanostatReport()
+        self._check(self.lib.gmpnp_galvanostat_report(self._h, byref(r)))
+        out = {k: float(getattr(r, k)) for k in ("p_electrode", "p_electrode_n", "I", "G", "cy", "cz", "d", "dp", "alpha")}
+        out["I_r"] = np.array(r.I_r[:self._n_reactions], dtype=np.float64)
+        return out
+
+    def galvanostat_terms(self, x=None):
+        """``gmpnp_galvanostat_terms`` at the current u and p_M: (b = dF/dp_M in file order, {G, d, I, cx}) with cx = c.x for ``x``
+        (file order; None: 0)."""
+        b = np.empty(self.ndof)
+        sc = (c_double * 4)()
+        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+        assert xx is None or xx.size == self.ndof
+        self._check(self.lib.gmpnp_galvanostat_terms(self._h, None if xx is None else _dptr(xx), _dptr(b), sc))
+        return b, {"G": float(sc[0]), "d": float(sc[1]), "I": float(sc[2]), "cx": float(sc[3])}
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

@@ -143,6 +143,19 @@ struct gmpnp_kineticist {
   DevBuf<double> w, sum;
 };
 
+// device side of the galvanostatic mode (gmpnp_galvanostat.h), allocated by the first gmpnp_set_galvanostat with on != 0: a handle
+// that never asks for it keeps the buffers, launches and pointers it had
+namespace gmpnp { struct GalvReport; }
+struct gmpnp_galvanostat {
+  gmpnp_galvanostat_t opt{};
+  DevBuf<double> scal;                  // [kGalvScalars]: p_M, its twin at u_n, dp and the verdict of the last reduce, the hook's own slots
+  DevBuf<double> b, y, z, x, zero;      // b = dF/dp_M, y = J^-1 F, z = J^-1 b (internal order); x: the hook's vector; zero: all zeros
+  DevBuf<int32_t> status;               // the word of the hooks' own launches
+  gmpnp::GalvReport* h_report = nullptr;   // pinned [2]: what k_galv_reduce / k_galv_potential write ([1]: the hooks')
+  gmpnp::GalvReport* d_report = nullptr;   // ... its device address
+  ~gmpnp_galvanostat() { if (h_report) (void)hipHostFree(h_report); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -217,6 +230,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_time_stepper> stepper;
   std::unique_ptr<gmpnp_sterner> sterner;
   std::unique_ptr<gmpnp_kineticist> kineticist;
+  std::unique_ptr<gmpnp_galvanostat> galvanostat;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
   // (boundary_rebind); allocated by the first of them
   DevBuf<double> bnd_dyn;
@@ -273,6 +287,13 @@ inline bool kinetics_on(const gmpnp_solver* s) { return s->kineticist && s->kine
 int kinetics_launch_residual(gmpnp_solver* s, int32_t* status);
 int kinetics_launch_jacobian(gmpnp_solver* s);
 int kinetics_launch_sum(gmpnp_solver* s, int32_t* status, double* table);
+// gmpnp_galvanostat.h: p_M as one more unknown; the Stern kernels read it through this pointer (nullptr: the option's own value)
+inline bool galvanostat_on(const gmpnp_solver* s) { return s->galvanostat && s->galvanostat->opt.on != 0; }
+inline const double* galvanostat_p_M(const gmpnp_solver* s) { return galvanostat_on(s) ? s->galvanostat->scal.p : nullptr; }
+int galvanostat_shift(gmpnp_solver* s, bool to_previous);
+int galvanostat_launch_iteration(gmpnp_solver* s);
+template <int DIM, int NF>
+int newton_galvanostat(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st);
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
@@ -1620,6 +1641,7 @@ int gmpnp_assign_previous(gmpnp_solver* s) {
   // stream-ordered: whatever reads u_n next is launched behind this copy, and every read-back synchronises the stream
   HIP_TRY(hipMemcpyAsync(s->un.p, s->u.p, s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   if (s->stepper) { s->stepper->dropped(); time_read_un(s); }   // adaptive time stepping: u_nm1 was not shifted (gmpnp_time_accept does both)
+  if (galvanostat_on(s)) return galvanostat_shift(s, true);
   return GMPNP_OK;
 }
 
@@ -1635,6 +1657,14 @@ int gmpnp_newton_solve(gmpnp_solver* s, const gmpnp_newton_options_t* o, gmpnp_n
   st = fresh_newton_stats();
   HIP_TRY(hipSetDevice(s->opts.device_id));
   int rc;
+  if (galvanostat_on(s)) {
+    if (o->linear_solver == GMPNP_LINEAR_BICGSTAB_TWOLEVEL || o->linear_solver == GMPNP_LINEAR_BICGSTAB_JACOBI)
+      return fail(GMPNP_ERR_INVALID, "galvanostat: the BiCGStab solvers are not available with the option on (1D: GMPNP_LINEAR_BLOCK_TRIDIAGONAL, 3D: GMPNP_LINEAR_BAND_LU)");
+    if ((s->dim == 1) != (o->linear_solver == GMPNP_LINEAR_BLOCK_TRIDIAGONAL))
+      return fail(GMPNP_ERR_INVALID, "galvanostat: 1D handles take GMPNP_LINEAR_BLOCK_TRIDIAGONAL, 3D handles GMPNP_LINEAR_BAND_LU");
+    GMPNP_DISPATCH(s, rc = (newton_galvanostat<DIM, NF>(s, *o, st)));
+    return rc;
+  }
   GMPNP_DISPATCH(s, rc = (newton<DIM, NF>(s, *o, st)));
   return rc;
 }
@@ -1776,6 +1806,7 @@ int gmpnp_attach_coarse_level(gmpnp_solver* fine, gmpnp_solver* coarse, const in
   if (fine == coarse || coarse->ml_is_coarse) return fail(GMPNP_ERR_INVALID, "a level handle serves one finer level");
   if (stern_on(fine) || stern_on(coarse)) return fail(GMPNP_ERR_INVALID, "multilevel term: not with the Stern boundary condition on a level (gmpnp_set_stern)");
   if (kinetics_on(fine) || kinetics_on(coarse)) return fail(GMPNP_ERR_INVALID, "multilevel term: not with the surface kinetics on a level (gmpnp_set_kinetics)");
+  if (galvanostat_on(fine) || galvanostat_on(coarse)) return fail(GMPNP_ERR_INVALID, "multilevel term: not with the galvanostat on a level (gmpnp_set_galvanostat)");
   if (fine->dim != 3 || coarse->dim != 3 || fine->nf != 9 || coarse->nf != 9) return fail(GMPNP_ERR_INVALID, "multilevel term: 3D pore problems (9 fields)");
   if (fine->partitioned != coarse->partitioned) return fail(GMPNP_ERR_INVALID, "multilevel term: both levels partitioned, or neither");
   if (fine->opts.device_id != coarse->opts.device_id) return fail(GMPNP_ERR_INVALID, "the levels live on one device");
@@ -1806,7 +1837,8 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (!s || !avg_us || launches < 1) return fail(GMPNP_ERR_INVALID, "bad arguments");
   if (kernel == 24 && !stern_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 24 is the Stern boundary condition: the option is off (gmpnp_set_stern)");
   if (kernel == 25 && !kinetics_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 25 is the surface kinetics: the option is off (gmpnp_set_kinetics)");
-  if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25) && !s->jacobian_valid)
+  if (kernel == 26 && !galvanostat_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 26 is the galvanostat: the option is off (gmpnp_set_galvanostat)");
+  if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
   hipEvent_t a, b; HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
@@ -1845,6 +1877,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 23: r = time_launch_any2(s); break;  // k_time_history + k_time_error2 + k_time_reduce + k_time_shift3
       case 24: r = stern_launch_residual(s, s->status.p); if (!r) r = stern_launch_jacobian(s); break;   // k_stern_residual + k_stern_jacobian
       case 25: r = kinetics_launch_residual(s, s->status.p); if (!r) r = kinetics_launch_jacobian(s); break;   // k_kinetics_residual + k_kinetics_jacobian
+      case 26: r = galvanostat_launch_iteration(s); break;   // k_galv_rhs + k_galv_reduce + k_galv_direction + k_galv_potential + k_galv_reduce (G alone)
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -1966,3 +1999,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_time_order.h"
 #include "gmpnp_stern.h"
 #include "gmpnp_kinetics.h"
+#include "gmpnp_galvanostat.h"

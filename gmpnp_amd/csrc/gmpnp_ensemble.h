@@ -273,6 +273,7 @@ int ens_check_member(const gmpnp_solver* s, const gmpnp_solver* s0, int k) {
   if (!is3d && (s->dim != 1 || s->nf != 7)) return bad("ensembles hold 1D problems (6 species + potential) or 3D problems (8 species + potential)");
   if (s0 && s->dim != s0->dim) return bad("1D and 3D members cannot share an ensemble");
   if (s->partitioned) return bad("partitioned handles cannot join an ensemble");
+  if (galvanostat_on(s)) return bad("the galvanostat is on (gmpnp_set_galvanostat): ensembles do not solve for the electrode potential");
   if (stern_on(s)) return bad("the Stern boundary condition is on (gmpnp_set_stern): ensembles do not apply it");
   if (kinetics_on(s)) return bad("the surface kinetics are on (gmpnp_set_kinetics): ensembles do not apply them");
   if (s->stepper && s->stepper->order == 2) return bad("the handle steps at order 2 (gmpnp_set_time_order): ensembles have no second-order time stepping");

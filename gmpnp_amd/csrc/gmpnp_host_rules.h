@@ -17,7 +17,8 @@ namespace gmpnp {
 
 // device status word: bit 1 = steric excursion (information, unless strict_steric), bits 2 / 4 / 8 = the linear solve failed,
 // bit 16 = the step limiter met a NaN / Inf in the correction (the update was not applied), bit 32 = eps(u) <= 0 on the Stern boundary,
-// bit 64 = a surface reaction rate that is not finite (kinetics on the Stern boundary)
+// bit 64 = a surface reaction rate that is not finite (kinetics on the Stern boundary), bit 128 = the galvanostat's constraint has no
+// step (total current <= 0, a term that is not finite, or a zero denominator)
 inline std::string status_message(int flags) {
   std::string m;
   if (flags & 1) m += "1 - sum_j a_j u_j <= 0 at a quadrature point; ";
@@ -27,6 +28,7 @@ inline std::string status_message(int flags) {
   if (flags & 16) m += "NaN / Inf in the Newton correction (step limiter); ";
   if (flags & 32) m += "eps(u) <= 0 on the Stern boundary (BDM model); ";
   if (flags & 64) m += "surface kinetics: a reaction rate on the Stern boundary is not finite; ";
+  if (flags & 128) m += "galvanostat: the total current is <= 0, a term of the constraint is not finite or d - c.z == 0; ";
   return m;
 }
 
@@ -90,6 +92,36 @@ inline bool kinetics_options_valid(const gmpnp_kinetics_t& o, int n_species) {
   return true;
 }
 
+// ---- galvanostatic mode (include/gmpnp.h "galvanostatic mode"; kernels: gmpnp_galvanostat.h) ---------------------------------------
+// The extra equation of the bordered Newton solve is G = ln(I / I_target) with I = sum_r weight_r I_r the total kinetic current, and
+// block elimination gives the potential's correction dp = (G - c.y) / (d - c.z) from y = J^-1 F, z = J^-1 b.  ok = 0 (status bit 128)
+// where I <= 0, where I, G, c.y, c.z or dp is not finite, or where d - c.z == 0; G and dp are then whatever the arithmetic gave and
+// the caller applies no update.  One function for the host and the device; gmpnp_amd/kinetics.py's galvanostat_step is its Python
+// statement, operation for operation.
+struct GalvStep { double G, dp; int ok; };
+GMPNP_RULE_HD inline bool rule_finite(double v) { return (v < 0.0 ? -v : v) <= 1.7976931348623157e308; }   // false for Inf and NaN (see surface_rate)
+GMPNP_RULE_HD inline GalvStep galvanostat_step(double I, double I_target, double cy, double cz, double d) {
+  const double G = I > 0.0 ? log(I / I_target) : 0.0;
+  const double den = d - cz;
+  const double dp = den != 0.0 ? (G - cy) / den : 0.0;
+  const int ok = (I > 0.0) && rule_finite(I) && rule_finite(G) && rule_finite(cy) && rule_finite(cz) && (den != 0.0) && rule_finite(den) && rule_finite(dp);
+  return GalvStep{G, dp, ok};
+}
+// G alone (the convergence test at a new state): ok = 0 where I <= 0 or I or G is not finite
+GMPNP_RULE_HD inline GalvStep galvanostat_constraint(double I, double I_target) {
+  const double G = I > 0.0 ? log(I / I_target) : 0.0;
+  const int ok = (I > 0.0) && rule_finite(I) && rule_finite(G);
+  return GalvStep{G, 0.0, ok};
+}
+inline bool galvanostat_options_valid(const gmpnp_galvanostat_t& o) {
+  if (!o.on) return true;
+  auto fin = [](double v) { return v == v && !std::isinf(v); };
+  if (!(o.target > 0.0) || !fin(o.target)) return false;
+  bool any = false;
+  for (int r = 0; r < GMPNP_MAX_SURFACE_REACTIONS; ++r) { if (!fin(o.weight[r])) return false; any = any || o.weight[r] != 0.0; }
+  return any;
+}
+
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every
 // update.  A driver hands every residual norm (with the device status word of its evaluation) to first() / next() and does what
 // the verdict says; on `failed` and `limit` the error is (code, message).  Owns r0, steric_excursion, residuals[], n_residuals
@@ -108,7 +140,7 @@ struct NewtonJudge {
   // residual at the state the solve starts from (the status bits of a linear solve mean nothing yet)
   Verdict first(double r, int flags) {
     if (steric(flags)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
-    if (flags & (32 | 64)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+    if (flags & (32 | 64 | 128)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
     r0 = r;
     st.residuals[0] = r; st.n_residuals = 1;
     if (!(r == r)) return fail(GMPNP_ERR_NUMERIC, "residual is NaN before the first Newton iteration");
@@ -117,7 +149,7 @@ struct NewtonJudge {
   // residual after an update (st.iterations already counts it)
   Verdict next(double r, int flags) {
     if (steric(flags)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
-    if (flags & (16 | 32 | 64)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
+    if (flags & (16 | 32 | 64 | 128)) return fail(GMPNP_ERR_NUMERIC, status_message(flags));
     if (flags & 14) return fail(GMPNP_ERR_LINEAR, status_message(flags));
     if (st.n_residuals < GMPNP_MAX_NEWTON_HISTORY) st.residuals[st.n_residuals++] = r;
     // NaN / Inf stay fatal (DOLFIN would iterate to its limit on a NaN residual and raise there)

@@ -229,6 +229,7 @@ int gmpnp_set_kinetics(gmpnp_solver* s, const gmpnp_kinetics_t* o) {
   if (!kinetics_options_valid(*o, s->nf - 1))
     return fail(GMPNP_ERR_INVALID, "surface kinetics: n_reactions in 0 ... 4, finite k, alpha, p_eq, nu and p_electrode, reactant in -1 ... n_species - 1");
   if (o->n_reactions == 0 && !s->kineticist) return GMPNP_OK;   // never on: the handle stays as it was
+  if (o->n_reactions == 0 && galvanostat_on(s)) return fail(GMPNP_ERR_INVALID, "surface kinetics: the galvanostat is on (gmpnp_set_galvanostat) and needs them; switch it off first");
   if (o->n_reactions != 0) {
     if (s->partitioned) return fail(GMPNP_ERR_INVALID, "surface kinetics: partition handles and groups are not supported");
     if (s->ml_coarse || s->ml_is_coarse) return fail(GMPNP_ERR_INVALID, "surface kinetics: not with a multilevel coarse level attached");
@@ -242,7 +243,9 @@ int gmpnp_set_kinetics(gmpnp_solver* s, const gmpnp_kinetics_t* o) {
     s->kineticist = std::move(K);
   }
   s->kineticist->opt = *o;
-  HIP_TRY(hipMemcpy(s->kineticist->d_opt.p, o, sizeof(gmpnp_kinetics_t), hipMemcpyHostToDevice));
+  if (galvanostat_on(s))   // the galvanostat's p_M stays (the stream is idle: its last update has landed)
+    HIP_TRY(hipMemcpy(&s->kineticist->opt.p_electrode, s->galvanostat->scal.p, sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(s->kineticist->d_opt.p, &s->kineticist->opt, sizeof(gmpnp_kinetics_t), hipMemcpyHostToDevice));
   s->jacobian_valid = false; s->precond_valid = false;
   return boundary_rebind(s);
 }

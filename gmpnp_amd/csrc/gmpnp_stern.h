@@ -26,6 +26,7 @@ namespace gmpnp {
 struct SternTab {
   int32_t n_nodes, n_pairs, model, pad_;
   double p_M, lam, eps_s;
+  const double* p_M_dev;    // the galvanostat's p_M on the device (gmpnp_galvanostat.h); nullptr: p_M above, by value
   const int32_t* node;      // [n_nodes] internal node
   const int32_t* nf_ptr;    // [n_nodes+1] CSR over the Stern nodes of (facet << 2 | local position)
   const int32_t* nf_ent;
@@ -44,7 +45,7 @@ struct SternTab {
 template <int DIM, int NF>
 struct SternFacet {
   static constexpr int FN = DIM == 3 ? 3 : 1;
-  double p[FN], psum, area;
+  double p[FN], psum, area, pM;
   SternG G;
   __device__ __forceinline__ SternFacet(const Ctx& c, const SternTab& t, int f) {
     constexpr int NS = NF - 1;
@@ -61,6 +62,7 @@ struct SternFacet {
       eps += m->epsc[j] * (us / FN);
     }
     area = t.area[f];
+    pM = t.p_M_dev ? *t.p_M_dev : t.p_M;
     G = stern_g(t.model, eps, t.eps_s);
     if (!G.ok) atomicOr(t.status, 32);
   }
@@ -68,8 +70,8 @@ struct SternFacet {
   __device__ __forceinline__ double w(const SternTab& t, int a) const {
     if constexpr (DIM == 3) {
       const double pa = a == 0 ? p[0] : a == 1 ? p[1] : p[2];   // (a select, not an index: the array stays in registers)
-      return area * (t.p_M / 3.0 - (psum + pa) / 12.0);
-    } else return t.p_M - p[0];
+      return area * (pM / 3.0 - (psum + pa) / 12.0);
+    } else return pM - p[0];
   }
   __device__ __forceinline__ double mass(int a, int b) const {
     if constexpr (DIM == 3) return area * (a == b ? 2.0 : 1.0) / 12.0;
@@ -192,6 +194,7 @@ SternTab stern_tab(gmpnp_solver* s, int32_t* status) {
   SternTab t{};
   t.n_nodes = S->n_nodes; t.n_pairs = S->n_pairs; t.model = S->opt.model;
   t.p_M = S->opt.p_electrode; t.lam = S->opt.lam; t.eps_s = S->opt.eps_surface;
+  t.p_M_dev = galvanostat_p_M(s);
   t.node = S->node.p; t.nf_ptr = S->nf_ptr.p; t.nf_ent = S->nf_ent.p; t.fnodes = S->fnodes.p; t.area = S->area.p;
   t.pair_row = S->pair_row.p; t.pf_ptr = S->pf_ptr.p; t.pf_ent = S->pf_ent.p; t.addr = S->addr.p;
   t.bndF = s->bndF.p; t.bnd_dyn = s->bnd_dyn.p; t.status = status;
@@ -239,7 +242,7 @@ int gmpnp_set_stern(gmpnp_solver* s, const gmpnp_stern_t* o) {
     int rc = stern_build(s, S.get()); if (rc) return rc;
     s->sterner = std::move(S);
   }
-  s->sterner->opt = *o;
+  s->sterner->opt = *o;   // (with the galvanostat on the kernels read ITS p_M: p_electrode is what on = 0 writes back)
   s->jacobian_valid = false; s->precond_valid = false;
   return boundary_rebind(s);
 }

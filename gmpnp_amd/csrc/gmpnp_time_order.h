@@ -147,6 +147,7 @@ int gmpnp_set_time_order(gmpnp_solver* s, int32_t order) {
   if (!s) return fail(GMPNP_ERR_INVALID, "NULL handle");
   if (order != 1 && order != 2) return fail(GMPNP_ERR_INVALID, "gmpnp_set_time_order: the order is 1 (backward Euler) or 2 (variable-step BDF2)");
   if (order == 1 && !s->stepper && !s->partitioned) return GMPNP_OK;   // nothing to undo: the handle stays as it was
+  if (order == 2 && galvanostat_on(s)) return fail(GMPNP_ERR_INVALID, "gmpnp_set_time_order: the galvanostat is on (gmpnp_set_galvanostat): p_M has no second-order history");
   int rc = order == 2 ? time_order_prepare(s, "gmpnp_set_time_order") : time_prepare(s, "gmpnp_set_time_order"); if (rc) return rc;
   gmpnp_time_stepper* T = s->stepper.get();
   T->order = order;

@@ -258,6 +258,7 @@ int gmpnp_time_accept(gmpnp_solver* s) {
   // stream-ordered like gmpnp_assign_previous: whatever reads u_n / u_nm1 next is launched behind the pass
   rc = s->stepper->order == 2 ? time_shift3_launch(s) : time_shift_launch(s); if (rc) return rc;
   s->stepper->accepted();
+  if (galvanostat_on(s)) return galvanostat_shift(s, true);
   return GMPNP_OK;
 }
 
@@ -266,6 +267,7 @@ int gmpnp_time_reject(gmpnp_solver* s) {
   int rc = time_prepare(s, "gmpnp_time_reject"); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(s->u.p, s->un.p, (size_t)s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   s->state_jumped = true; s->jacobian_valid = false;
+  if (galvanostat_on(s)) return galvanostat_shift(s, false);
   return GMPNP_OK;
 }
 

@@ -267,6 +267,8 @@ class PartitionedSolver:
             raise ValueError("partition: the Stern boundary condition is not available in a partitioned solve")
         if getattr(prob, "kinetics", None) is not None:
             raise ValueError("partition: the surface kinetics are not available in a partitioned solve")
+        if getattr(prob, "galvanostat", None) is not None:
+            raise ValueError("partition: the galvanostat is not available in a partitioned solve")
         from ctypes import c_void_p
         if rank is not None:
             # one rank per process: torch.distributed carries the set-up (mailbox handles, communicator id, host-staged collectives).

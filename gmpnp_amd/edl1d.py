@@ -25,7 +25,8 @@ import numpy as np
 from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import _load_yaml, edl_parameters, utilities_dir
-from .problem import add_kinetics_arguments, add_stern_arguments, edl_problem, kinetics_keywords, pop_kinetics, pop_stern, stern_keywords
+from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_arguments, add_stern_arguments, edl_problem, galvanostat_keywords, kinetics_keywords,
+                      pop_galvanostat, pop_kinetics, pop_stern, stern_keywords)
 from .solver import GMPNPSystem, supg_parameters
 from .timestep import adaptive_keywords, add_adaptive_arguments
 
@@ -72,9 +73,24 @@ class EDLRun:
         drop across the Stern layer and the CO2 concentration at the OHP (gmpnp_amd/kinetics.py) in place of the
         prescribed ``current_OHP_ss`` / ``H2_FE``, which are then unused for the CO2, OH and H fluxes.  Not with ``stabilization`` "Y"
         and not with ``H_OHP`` (ValueError, before anything touches the device).  Every step records ``i_CO``, ``i_H2`` [A/m2] and
-        ``FE_H2`` (arrays_unscaled.npz; the last values and the kinetic parameters in the metadata)."""
+        ``FE_H2`` (arrays_unscaled.npz; the last values and the kinetic parameters in the metadata).
+        ``target_current`` = X [A/m2] (with ``kinetics``): galvanostatic mode: every Newton solve also finds the
+        electrode potential at which i_CO + i_H2 = X; ``electrode_voltage`` is the starting guess.  Works with ``step_fraction``,
+        ``budget`` and ``adaptive_dt`` at order 1 (a rejected attempt restores the potential with the state); not with ``dt_order`` 2.
+        Every step records ``electrode_voltage`` beside the currents; the metadata gains ``target_current`` and reports the last
+        potential found as ``electrode_voltage``; the run directory is named by the target."""
         self.stern = pop_stern(kwargs, kwargs.get("L_n", 50.0e-6))
         self.kinetic_par = pop_kinetics(kwargs)
+        self.target_current = pop_galvanostat(kwargs)
+        if self.target_current is not None:
+            if self.kinetic_par is None:
+                raise ValueError("target_current: the galvanostat needs the surface kinetics (kinetics='tafel')")
+            if int(dt_order) == 2:
+                raise ValueError("target_current: the galvanostat is not available with dt_order 2")
+            if kwargs.get("stabilization", "N") == "Y":
+                raise ValueError("target_current: the galvanostat is not available with stabilization Y")
+            if kwargs.get("H_OHP") is not None:
+                raise ValueError("target_current: the galvanostat is not available with the H_OHP flux controller")
         if self.kinetic_par is not None:
             if self.stern is None:
                 raise ValueError("kinetics: the surface kinetics need an electrode potential (electrode_voltage)")
@@ -103,7 +119,10 @@ class EDLRun:
             from .kinetics import edl_tafel
             self.kinetics, ep.model = edl_tafel(ep, self.kinetic_par, self.stern.p_electrode)
             print("kinetics tafel: current_OHP_ss and H2_FE are not used for the CO2, OH and H fluxes at the OHP")
-        self.problem = edl_problem(ep, self.mesh, stern=self.stern, kinetics=self.kinetics)
+        self.galvanostat, self.potentials = None, []
+        if self.target_current is not None:
+            self.galvanostat = Galvanostat(self.target_current)   # the OHP is one point: sum_I w_I = 1
+        self.problem = edl_problem(ep, self.mesh, stern=self.stern, kinetics=self.kinetics, galvanostat=self.galvanostat)
         self.model = copy.deepcopy(self.problem.model)
         self.sys = GMPNPSystem(self.problem, **(device_kwargs or {}))
         self.solver_parameters = backend.with_step_fraction(solver_parameters or SOLVER_PARAMETERS, self.step_fraction)
@@ -204,6 +223,8 @@ class EDLRun:
         self.history.append(vals)
         if self.kinetics is not None:
             self.currents.append(self.sys.dev.kinetics_currents())
+        if self.galvanostat is not None:
+            self.potentials.append(self.sys.dev.galvanostat_report()["p_electrode"])
         H_OHP_frac = vals[0, 0]
         H_OHP = ep.H_OHP
         if H_OHP is not None:  # reference 1D:770-793
@@ -252,20 +273,24 @@ class EDLRun:
         ep, st = self.ep, self.stern
         d = self.sys.dev.stern_displacement()
         EPS_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
-        return {"electrode_voltage": st.p_electrode, "stern_model": st.model, "stern_length": st.lam * ep.L_n, "stern_displacement": d,
+        p_M = self.potentials[-1] if self.potentials else st.p_electrode   # galvanostatic mode: the potential that was found
+        return {"electrode_voltage": p_M, "stern_model": st.model, "stern_length": st.lam * ep.L_n, "stern_displacement": d,
                 "surface_charge": EPS_0 * ep.thermal_voltage / ep.L_n * d}
 
     def kinetics_summary(self):
         """Per-step ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2`` of a run with the surface kinetics (the OHP is one point: w = 1)."""
         from .kinetics import current_summary
         rows = [current_summary(c, 1.0) for c in self.currents]
-        return {k: np.array([r[k] for r in rows]) for k in ("i_CO", "i_H2", "FE_H2")}
+        out = {k: np.array([r[k] for r in rows]) for k in ("i_CO", "i_H2", "FE_H2")}
+        if self.galvanostat is not None:
+            out["electrode_voltage"] = np.array(self.potentials)
+        return out
 
     def write_outputs(self, stamp=None):
         ep, mesh, k = self.ep, self.mesh, self.kwargs
         stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         end_time = datetime.now().strftime("%y-%m-%d-%H-%M-%S")
-        identifier = run_identifier(ep, k, self.stern)
+        identifier = run_identifier(ep, k, self.stern, self.target_current)
         newpath = os.path.join(output_root(), ep.model_name, stamp + "_experiment", identifier)
         os.makedirs(newpath, exist_ok=True)
         hist = np.stack(self.history)
@@ -324,6 +349,8 @@ class EDLRun:
             from .kinetics import tafel_parameters
             metadata_dict.update(tafel_parameters(self.kinetic_par))
             metadata_dict.update({key: (float(v[-1]) if len(v) else None) for key, v in self.kinetics_summary().items()})
+        if self.galvanostat is not None:
+            metadata_dict["target_current"] = self.target_current
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
@@ -333,10 +360,12 @@ class EDLRun:
         return newpath
 
 
-def run_identifier(ep, kwargs, stern=None):
+def run_identifier(ep, kwargs, stern=None, target_current=None):
     """Name of a run's output directory below ``<model>/<stamp>_experiment`` (reference 1D:862-866; a run with the Stern boundary
-    condition is named by its electrode voltage and Stern model in the OHP voltage's place)."""
-    if stern is not None:
+    condition is named by its electrode voltage and Stern model in the OHP voltage's place, a galvanostatic run by its target)."""
+    if target_current is not None:
+        head = "target_current_" + str(target_current) + "_" + stern.model
+    elif stern is not None:
         head = "electrode_" + str(stern.p_electrode) + "_" + stern.model
     else:
         head = "voltage_" + str(ep.voltage_scaled)
@@ -348,7 +377,7 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
               dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM",
               stern_length=4.0e-10, stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0,
-              p_eq_H2=0.0, **adaptive):
+              p_eq_H2=0.0, target_current=None, **adaptive):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
     adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
     ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
@@ -360,6 +389,8 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
         voltage_multiplier = -1.0
     if kinetics is not None:   # (the surface kinetics of ``EDLRun``)
         stern.update(kinetics=kinetics, i0_CO=i0_CO, i0_H2=i0_H2, alpha_CO=alpha_CO, alpha_H2=alpha_H2, p_eq_CO=p_eq_CO, p_eq_H2=p_eq_H2)
+    if target_current is not None:   # (the galvanostatic mode of ``EDLRun``)
+        stern.update(target_current=target_current)
     run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, **stern, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
@@ -392,6 +423,7 @@ def build_parser():
     add_adaptive_arguments(p)
     add_stern_arguments(p)
     add_kinetics_arguments(p)
+    add_galvanostat_arguments(p)
     return p
 
 
@@ -400,7 +432,7 @@ def main(argv=None):
     return solve_EDL(concentration_elec=a.concentration_elec, model=a.model, voltage_multiplier=a.voltage_multiplier,
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
-                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a))
+                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a))
 
 
 if __name__ == "__main__":

@@ -35,6 +35,22 @@ def surface_rate(k, alpha, p_eq, p_M, p, has_reactant, u_reactant):
     return rate, kE, d_p, ok
 
 
+def galvanostat_step(I, I_target, cy, cz, d):
+    """(G, dp, ok) of the galvanostat's constraint G = ln(I / I_target) and the potential's correction dp = (G - c.y) / (d - c.z) of
+    the bordered Newton step: ``galvanostat_step`` of gmpnp_host_rules.h, operation for operation.  ok = False where I <= 0, where a
+    term is not finite or where d - c.z == 0 (the library raises status bit 128 and applies no update)."""
+    fin = math.isfinite
+    with np.errstate(all="ignore"):
+        G = 0.0
+        if I > 0.0:
+            q = float(np.float64(I) / np.float64(I_target))
+            G = math.log(q) if 0.0 < q < math.inf else (math.inf if q > 0.0 else -math.inf)     # C's log at Inf and at an underflowed 0
+        den = float(np.float64(d) - np.float64(cz))
+        dp = float((np.float64(G) - np.float64(cy)) / np.float64(den)) if den != 0.0 else 0.0
+    ok = bool(I > 0.0 and fin(I) and fin(G) and fin(cy) and fin(cz) and den != 0.0 and fin(den) and fin(dp))
+    return G, dp, ok
+
+
 def tafel_parameters(par):
     """The metadata keys that record the kinetic parameters of a run (``problem.pop_kinetics``)."""
     return {"kinetics": "tafel", **{k: par[k] for k in ("i0_CO", "i0_H2", "alpha_CO", "alpha_H2", "p_eq_CO", "p_eq_H2")}}

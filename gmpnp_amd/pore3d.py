@@ -18,8 +18,8 @@ import numpy as np
 from . import backend
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
-from .problem import (add_kinetics_arguments, add_stern_arguments, kinetics_keywords, pop_kinetics, pop_stern, pore_dirichlet, pore_problem,
-                      stern_keywords)
+from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_arguments, add_stern_arguments, galvanostat_keywords, kinetics_keywords,
+                      pop_galvanostat, pop_kinetics, pop_stern, pore_dirichlet, pore_problem, stern_keywords)
 from .solver import GMPNPSystem, column_medians, device_medians_and_minima
 from .timestep import DriverStepping, adaptive_keywords, add_adaptive_arguments
 from .vtk import write_pvd
@@ -84,11 +84,29 @@ class PoreRun:
         Stern layer and the CO2 concentration at the wall (gmpnp_amd/kinetics.py) in place of the prescribed
         ``current_rough`` / ``H2_FE``, which are then unused for them.  Not with ``partition`` or ``multilevel`` (ValueError, before
         anything touches the device).  Every step records the wall means ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2``
-        (arrays_unscaled.npz; the last values and the kinetic parameters in the metadata)."""
+        (arrays_unscaled.npz; the last values and the kinetic parameters in the metadata).
+        ``target_current`` = X [A/m2] (with ``kinetics``): galvanostatic mode: every Newton solve also finds the
+        electrode potential at which the wall mean of i_CO + i_H2 is X; ``electrode_voltage`` is the starting guess.  The linear solver
+        is the block-banded LU (a ``solver_parameters`` that names bicgstab is a ValueError); the first solve starts from the bulk state.  Works with ``step_fraction``, ``budget``
+        and ``adaptive_dt`` at order 1; not with ``dt_order`` 2, ``partition`` or ``multilevel``.  Every step records
+        ``electrode_voltage``; the metadata gains ``target_current`` and reports the last potential found."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
         self.stern = pop_stern(kwargs, kwargs.get("L", 100.0e-9))
         self.kinetic_par = pop_kinetics(kwargs)
+        self.target_current = pop_galvanostat(kwargs)
+        if self.target_current is not None:
+            if self.kinetic_par is None:
+                raise ValueError("target_current: the galvanostat needs the surface kinetics (kinetics='tafel')")
+            if int(dt_order) == 2:
+                raise ValueError("target_current: the galvanostat is not available with dt_order 2")
+            if partition:
+                raise ValueError("target_current: the galvanostat is not available in a partitioned solve")
+            if multilevel:
+                raise ValueError("target_current: the galvanostat is not available with the geometric multilevel term")
+            lin = dict((solver_parameters or SOLVER_PARAMETERS).get("newton_solver", {})).get("linear_solver", "default")
+            if lin == "bicgstab":
+                raise ValueError("target_current: the galvanostat solves with the block-banded LU, not with bicgstab")
         if self.kinetic_par is not None:
             if self.stern is None:
                 raise ValueError("kinetics: the surface kinetics need an electrode potential (electrode_voltage)")
@@ -125,6 +143,12 @@ class PoreRun:
             self.problem, self.bnd = self._levels[0][0], self._levels[0][1]
         else:
             self.problem, self.bnd = pore_problem(self.pp, self.mesh, refine=refine, stern=self.stern, kinetics=self.kinetics)
+        self.galvanostat, self.potentials = None, []
+        if self.target_current is not None:   # the library's target is the integrated current: X times sum_I w_I, the wall area
+            self.galvanostat = Galvanostat(self.target_current * self.wall_area())
+            self.problem.galvanostat = self.galvanostat
+            solver_parameters = dict(solver_parameters or SOLVER_PARAMETERS)
+            solver_parameters["newton_solver"] = dict(solver_parameters.get("newton_solver", {}), linear_solver="band_lu")
         if refine:  # uniformly refined copy of the reference mesh (not a reference feature: roofline studies)
             from .mesh import Mesh
             self.mesh = Mesh(dim=3, coords=self.problem.coords, cells=self.problem.cells)
@@ -138,6 +162,11 @@ class PoreRun:
         self.tot_num_steps = self.pp.tot_num_steps if num_steps is None else int(num_steps)
         nv = self.mesh.num_vertices
         self.sys.initialise([1.0] * 8 + [0.0])
+        if self.galvanostat is not None:
+            # The first Newton solve starts from the bulk state, not from u = 0: at u = 0 the CO2 current (first order in u_CO2) is
+            # exactly 0, the constraint ln(I / target) is linearised where I is the hydrogen current alone, and with i_CO >> i_H2 its
+            # first correction of p_M overshoots out of the admissible set (the 1D driver's first step keeps u = 0).
+            self.sys.set_state(np.tile(np.r_[np.ones(8), 0.0], nv), None)
         # history rows: initial ones/zeros (3D:771-779), one row appended per step (3D:842-850); "device" glue: the rows this process
         # owns, one array per local partition (vertex ids in self.owned_ids)
         if glue == "device":
@@ -208,6 +237,8 @@ class PoreRun:
         self.history.append(row)
         if self.kinetics is not None:
             self.currents.append(self.sys.dev.kinetics_currents())
+        if self.galvanostat is not None:
+            self.potentials.append(self.sys.dev.galvanostat_report()["p_electrode"])
         # medians of the scaled ion concentrations -> Sechenov -> new CO2 Dirichlet value at S1 (3D:817-838)
         self.co2_bc = self.pp.sechenov_co2_scaled(*meds)
         self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, self.co2_bc, stern=self.stern is not None))
@@ -257,7 +288,8 @@ class PoreRun:
         area = float((0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)).sum())
         d = self.sys.dev.stern_displacement()
         eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters_pore") + ".yaml"))["nat_const"]["eps_0"]
-        return {"electrode_voltage": st.p_electrode, "stern_model": st.model, "stern_length": st.lam * pp.L, "stern_displacement": d,
+        p_M = self.potentials[-1] if self.potentials else st.p_electrode   # galvanostatic mode: the potential that was found
+        return {"electrode_voltage": p_M, "stern_model": st.model, "stern_length": st.lam * pp.L, "stern_displacement": d,
                 "surface_charge": eps_0 * pp.thermal_voltage / pp.L * d / area}
 
     def wall_area(self):
@@ -269,7 +301,10 @@ class PoreRun:
         from .kinetics import current_summary
         area = self.wall_area()
         rows = [current_summary(c, area) for c in self.currents]
-        return {k: np.array([r[k] for r in rows]) for k in ("i_CO", "i_H2", "FE_H2")}
+        out = {k: np.array([r[k] for r in rows]) for k in ("i_CO", "i_H2", "FE_H2")}
+        if self.galvanostat is not None:
+            out["electrode_voltage"] = np.array(self.potentials)
+        return out
 
     # ---- outputs (3D:860-1085) -------------------------------------------------------------------
     def write_outputs(self, stamp=None):
@@ -288,7 +323,10 @@ class PoreRun:
         stamp = stamp or datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         end_time = datetime.now().strftime("%y-%m-%d-%H-%M-%S")
         L, R = pp.L, pp.R
-        identifier = (("v_" + str(pp.voltage_scaled) if self.stern is None else "electrode_" + str(self.stern.p_electrode) + "_" + self.stern.model) + "_L_" + str(int(L * 1e+9)) + "_R_" + str(int(R * 1e+9))
+        head = "v_" + str(pp.voltage_scaled) if self.stern is None else "electrode_" + str(self.stern.p_electrode) + "_" + self.stern.model
+        if self.target_current is not None:   # a galvanostatic run is named by its target: no collision with a potentiostatic run's directory
+            head = "target_current_" + str(self.target_current) + "_" + self.stern.model
+        identifier = (head + "_L_" + str(int(L * 1e+9)) + "_R_" + str(int(R * 1e+9))
                       + "_P_g_" + str(k.get("press_gas", 1.0)) + "_D_eff_" + str(k.get("pore_geom_multiplier", 1.0))
                       + "_Re_" + str(k.get("electrolyte_flow_geom_multiplier", 1.0))
                       + "_rough_" + str(k.get("roughness_factor", 150.0)))
@@ -348,6 +386,8 @@ class PoreRun:
             from .kinetics import tafel_parameters
             metadata_dict.update(tafel_parameters(self.kinetic_par))
             metadata_dict.update({key: (float(v[-1]) if len(v) else None) for key, v in self.kinetics_summary().items()})
+        if self.galvanostat is not None:
+            metadata_dict["target_current"] = self.target_current
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
@@ -362,7 +402,8 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
              device_kwargs=None, glue="host", budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM", stern_length=4.0e-10,
-             stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0, p_eq_H2=0.0, **adaptive):
+             stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0, p_eq_H2=0.0, target_current=None,
+             **adaptive):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
     geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
@@ -377,6 +418,8 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
         voltage_multiplier = -1.0
     if kinetics is not None:   # (the surface kinetics of ``PoreRun``)
         stern.update(kinetics=kinetics, i0_CO=i0_CO, i0_H2=i0_H2, alpha_CO=alpha_CO, alpha_H2=alpha_H2, p_eq_CO=p_eq_CO, p_eq_H2=p_eq_H2)
+    if target_current is not None:   # (the galvanostatic mode of ``PoreRun``)
+        stern.update(target_current=target_current)
     run = PoreRun(**stern, num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
                   device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
@@ -418,6 +461,7 @@ def build_parser():
     add_adaptive_arguments(p)   # (not with --partitions)
     add_stern_arguments(p)      # (not with --partitions / --multilevel; --voltage_multiplier defaults to -1.0 without --electrode_voltage)
     add_kinetics_arguments(p)   # (with --electrode_voltage; not with --partitions / --multilevel)
+    add_galvanostat_arguments(p)   # (with --kinetics tafel; not with --partitions / --multilevel / --dt_order 2)
     return p
 
 
@@ -449,6 +493,8 @@ def main(argv=None):
         raise ValueError("--electrode_voltage: the Stern boundary condition is not available with --partitions")
     if a.partitions and a.kinetics is not None:
         raise ValueError("--kinetics: the surface kinetics are not available with --partitions")
+    if a.partitions and a.target_current is not None:
+        raise ValueError("--target_current: the galvanostat is not available with --partitions")
     if a.electrode_voltage is not None and a.voltage_multiplier is not None:
         raise ValueError("--electrode_voltage takes the place of --voltage_multiplier: give one of them")
     if a.partitions:
@@ -462,7 +508,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a), **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

@@ -163,6 +163,55 @@ def kinetics_keywords(a):
 
 
 @dataclass
+class Galvanostat:
+    """Galvanostatic mode (include/gmpnp.h ``gmpnp_galvanostat_t``): the electrode potential is an unknown and
+    ``sum_r weights[r] sum_I w_I rate_r = target`` the extra equation.  ``target`` is in the units of the integrated rates."""
+    target: float
+    weights: tuple = (1.0, 1.0)
+
+    def __post_init__(self):
+        self.weights = tuple(float(w) for w in self.weights)
+        if not (np.isfinite(self.target) and self.target > 0.0):
+            raise ValueError("galvanostat: the target current must be positive and finite, not %r" % (self.target,))
+        if not 1 <= len(self.weights) <= MAX_SURFACE_REACTIONS or not np.isfinite(self.weights).all() or not any(self.weights):
+            raise ValueError("galvanostat: 1 ... %d finite weights, not all zero" % MAX_SURFACE_REACTIONS)
+
+
+GALVANOSTAT_KEYWORDS = ("target_current",)
+
+
+def pop_galvanostat(kwargs):
+    """Takes ``target_current`` [A/m2, the area mean of i_CO + i_H2] of a driver out of ``kwargs``; returns it as a float, or None."""
+    x = kwargs.pop("target_current", None)
+    if x is None:
+        return None
+    x = float(x)
+    if not (np.isfinite(x) and x > 0.0):
+        raise ValueError("target_current: the galvanostat's target must be positive and finite, not %r" % (x,))
+    return x
+
+
+def refuse_galvanostat(kwargs, what):
+    """ValueError if a keyword dict asks for the galvanostat where it does not exist (before anything touches the device)."""
+    if kwargs.get("target_current") is not None:
+        raise ValueError("target_current: the galvanostat is not available in %s" % what)
+
+
+def add_galvanostat_arguments(p):
+    """The drivers' command-line flag of the galvanostatic mode (an addition, not a reference flag)."""
+    p.add_argument("--target_current", required=False, default=None, type=float,
+                   help="(addition) total current density i_CO + i_H2 [A/m2] to hold: the electrode potential is solved for, "
+                        "--electrode_voltage is its starting guess; needs --kinetics tafel")
+
+
+def galvanostat_keywords(a):
+    """The galvanostat keyword of a parsed command line (``add_galvanostat_arguments``); empty without --target_current."""
+    if a.target_current is None:
+        return {}
+    return {"target_current": a.target_current}
+
+
+@dataclass
 class Problem:
     coords: np.ndarray  # (nv,d)
     cells: np.ndarray  # (nc,d+1)
@@ -180,6 +229,7 @@ class Problem:
     supg_w: np.ndarray = None
     stern: SternLayer = None  # Stern-layer boundary condition of the potential; None = the potential is prescribed (Dirichlet)
     kinetics: SurfaceKinetics = None  # potential-dependent surface kinetics on the Stern boundary; None = the constant fluxes alone
+    galvanostat: Galvanostat = None  # the electrode potential as an unknown at a set total current (needs kinetics); None = potentiostatic
 
     def __post_init__(self):
         d = self.coords.shape[1]
@@ -248,7 +298,8 @@ def pore_dirichlet(pp, bnd, co2_value=None, stern=False):
     return dofs, vals
 
 
-def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0, stern: SternLayer = None, kinetics: SurfaceKinetics = None):
+def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0, stern: SternLayer = None, kinetics: SurfaceKinetics = None,
+                 galvanostat: Galvanostat = None):
     """Problem + boundary record for the 3D pore (reference 3D:329-382,460-467).  ``refine`` > 0 applies that many
     uniform refinements with inherited markers (gmpnp_amd.mesh.refine_pore); returns (problem, boundaries) of the
     mesh actually used (``problem.coords/cells``)."""
@@ -258,7 +309,7 @@ def pore_problem(pp, mesh: Mesh, quad: Quadrature = None, refine: int = 0, stern
         mesh, bnd = refine_pore(mesh, bnd)
     dofs, vals = pore_dirichlet(pp, bnd, stern=stern is not None)
     prob = Problem(coords=mesh.coords, cells=mesh.cells, model=pp.model, quad=quad,
-                   wall_facets=bnd.ds_facets[2], exit_facets=bnd.ds_facets[3], bc_dofs=dofs, bc_vals=vals, stern=stern, kinetics=kinetics)
+                   wall_facets=bnd.ds_facets[2], exit_facets=bnd.ds_facets[3], bc_dofs=dofs, bc_vals=vals, stern=stern, kinetics=kinetics, galvanostat=galvanostat)
     return prob, bnd
 
 
@@ -280,7 +331,7 @@ def pore_hierarchy(pp, mesh: Mesh, refine: int, quad: Quadrature = None):
     return out
 
 
-def edl_problem(ep, mesh: Mesh, quad: Quadrature = None, stern: SternLayer = None, kinetics: SurfaceKinetics = None):
+def edl_problem(ep, mesh: Mesh, quad: Quadrature = None, stern: SternLayer = None, kinetics: SurfaceKinetics = None, galvanostat: Galvanostat = None):
     """Problem for the 1D EDL (reference 1D:237-254,350-355): all 7 fields pinned to
     (1,..,1,0) at x=1; p = voltage_multiplier at x=0; point fluxes at the x=0 vertex.  ``stern``: the OHP potential is not
     prescribed (the (left, ns, voltage) entry is dropped) and the record travels with the problem."""
@@ -293,4 +344,4 @@ def edl_problem(ep, mesh: Mesh, quad: Quadrature = None, stern: SternLayer = Non
     bcs = [(right, f, 1.0) for f in range(ns)] + [(right, ns, 0.0)] + ([] if stern is not None else [(left, ns, ep.voltage_scaled)])
     dofs, vals = merge_dirichlet(bcs, ns + 1)
     return Problem(coords=mesh.coords, cells=mesh.cells, model=ep.model, quad=quad,
-                   point_vertices=left.astype(np.int32), bc_dofs=dofs, bc_vals=vals, stern=stern, kinetics=kinetics)
+                   point_vertices=left.astype(np.int32), bc_dofs=dofs, bc_vals=vals, stern=stern, kinetics=kinetics, galvanostat=galvanostat)

@@ -25,7 +25,7 @@ from . import backend, timestep
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
-from .problem import KINETICS_KEYWORDS, pore_dirichlet, pore_problem, refuse_kinetics, refuse_stern
+from .problem import GALVANOSTAT_KEYWORDS, KINETICS_KEYWORDS, pore_dirichlet, pore_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem, column_medians
 from .vtk import write_pvd
 
@@ -60,6 +60,7 @@ class RxnPoreRun:
         ``adaptive_dt`` = True with ``dt_rtol``, ``dt_atol``, ``dt_init``, ``dt_min``, ``dt_max``, ``t_end``, ``steady_tol``, ``max_steps``, ``dt_order``
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history, the budget log and the CO2 Dirichlet value as they were.  Off: nothing changes."""
+        refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         adaptive = timestep.pop_adaptive(kwargs)
@@ -207,7 +208,7 @@ def build_parser():
     p = pore_parser()  # same flags as the MPNP pore script ...
     for act in list(p._actions):
         if ({"--voltage_multiplier", "--as_published", "--electrode_voltage", "--stern_model", "--stern_length", "--stern_eps_surface"}
-                | {"--" + k for k in KINETICS_KEYWORDS}) & set(act.option_strings):
+                | {"--" + k for k in KINETICS_KEYWORDS + GALVANOSTAT_KEYWORDS}) & set(act.option_strings):
             p._remove_action(act)  # ... minus the voltage (reference :788-942 has none)
             for s in act.option_strings:
                 p._option_string_actions.pop(s, None)

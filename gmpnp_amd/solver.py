@@ -83,7 +83,9 @@ class GMPNPSystem(_System):
             raise ValueError("multilevel: the Stern boundary condition is not available with the geometric multilevel term")
         if levels and getattr(problem, "kinetics", None) is not None:
             raise ValueError("multilevel: the surface kinetics are not available with the geometric multilevel term")
-        self.dev = backend.DeviceSolver(problem, **device_kwargs)
+        if levels and getattr(problem, "galvanostat", None) is not None:
+            raise ValueError("multilevel: the galvanostat is not available with the geometric multilevel term")
+        self.dev = backend.DeviceSolver(problem, **device_kwargs)   # (hands problem.stern, .kinetics and .galvanostat to the handle)
         super().__init__(problem, self.dev)
         self._coarse = [backend.DeviceSolver(lv[0], device_id=device_kwargs.get("device_id", 0), shared_device=1) for lv in (levels or [])[1:]]
         backend.attach_level_chain([self.dev] + self._coarse, [lv[2] for lv in levels or []], ml_theta, ml_sweeps)

@@ -562,6 +562,50 @@ typedef struct {
 int gmpnp_set_kinetics(gmpnp_solver* s, const gmpnp_kinetics_t* kinetics);
 int gmpnp_kinetics_currents(gmpnp_solver* s, double* out /* [n_reactions] */);
 
+/* ---- galvanostatic mode (no reference counterpart: the reference prescribes the current through constant fluxes; with the surface
+ * kinetics the current follows the potential, and this option solves the inverse problem) ------------------------------------------
+ * The electrode potential p_M becomes one extra scalar unknown of the handle and one extra equation fixes the total kinetic current.
+ * With I_r(u, p_M) = sum_I w_I rate_r (gmpnp_kinetics_currents) and I = sum_r weight[r] I_r:
+ *     G(u, p_M) = ln(I / target) = 0                                     target > 0, I > 0
+ *     c = dG/du   at boundary node I: column reactant_r: weight_r w_I k_r E_r / I,  column p: weight_r w_I alpha_r rate_r / I
+ *     d = dG/dp_M = -sum_r weight_r alpha_r I_r / I
+ *     b = dF/dp_M  Stern rows: 1D g / lam, 3D sum over the node's Stern facets in list order of g(eps_f) |f| / (3 lam);
+ *                  kinetic rows: -w_I sum_r nu[r][i] alpha_r rate_r;  0 on every Dirichlet row and everywhere else
+ * gmpnp_newton_solve then runs a bordered Newton iteration by block elimination:
+ *     J y = F,  J z = b,  dp = (G - c.y) / (d - c.z),  dx = y - dp z,  u -= omega alpha dx,  p_M -= omega alpha dp
+ * (alpha: the step limiter's factor, 1 without it; the limiter looks at u only).  The residual the convergence test sees is
+ * sqrt(||F||^2 + G^2), before the first iteration and after every update.  I <= 0, a value of I, G, c.y, c.z or dp that is not finite
+ * or d - c.z == 0 raise status bit 128: the update is not applied and the solve ends GMPNP_ERR_NUMERIC.  The logarithm makes the
+ * Tafel law linear in p_M; the difference form (I - target) / target leaves the admissible set from ordinary starts.
+ * 1D handles take GMPNP_LINEAR_BLOCK_TRIDIAGONAL (two solves per iteration), 3D handles GMPNP_LINEAR_BAND_LU (one factorisation, two
+ * substitutions); the BiCGStab solvers are refused with the option on.
+ * gmpnp_set_galvanostat needs the kinetics on, a finite target > 0 and finite weights that are not all zero.  p_M starts at the
+ * kinetics' p_electrode; with the Stern option on, its p_electrode must be equal to it.  on = 0 on a handle that never had the option
+ * is a no-op; after the option has been on it writes the current p_M into both options' p_electrode, and from then on F and J are
+ * bit for bit those of a handle that had that p_electrode set directly.  While the option is on gmpnp_set_kinetics and
+ * gmpnp_set_stern keep the galvanostat's p_M (their p_electrode is not read) and n_reactions = 0 is refused.  gmpnp_assign_previous
+ * and gmpnp_time_accept copy p_M to its twin at u_n, gmpnp_time_reject copies it back.  gmpnp_species_budget,
+ * gmpnp_kinetics_currents and gmpnp_stern_displacement see the current p_M.  Refused (GMPNP_ERR_INVALID, the message names the
+ * galvanostat): partition handles (and so groups), a handle with a coarse level attached or serving as one, every gmpnp_ensemble_*
+ * call with such a member, order-2 time stepping.
+ * gmpnp_galvanostat_report: p_M now and at u_n, the currents and G at the current u, and c.y, c.z, d, dp, alpha of the last
+ * iteration of the last solve (zeros before one).  gmpnp_galvanostat_terms: parity hook; at the current u and p_M, b in file order
+ * (b_out[n_dofs], may be NULL) and scalars[4] = {G, d, I, c.x} for the caller's x (file order; NULL: c.x = 0). */
+typedef struct {
+  int32_t on;                                    /* 0 = off */
+  double target;                                 /* I_target > 0, in the units of sum_I w_I rate_r */
+  double weight[GMPNP_MAX_SURFACE_REACTIONS];    /* weight_r of reaction r in the total current */
+} gmpnp_galvanostat_t;
+typedef struct {
+  double p_electrode, p_electrode_n;             /* p_M now and at u_n */
+  double I_r[GMPNP_MAX_SURFACE_REACTIONS];       /* sum_I w_I rate_r at the current u */
+  double I, G;
+  double cy, cz, d, dp, alpha;                   /* the last iteration's c.y, c.z, d, dp and step factor */
+} gmpnp_galvanostat_report_t;
+int gmpnp_set_galvanostat(gmpnp_solver* s, const gmpnp_galvanostat_t* galvanostat);
+int gmpnp_galvanostat_report(gmpnp_solver* s, gmpnp_galvanostat_report_t* out);
+int gmpnp_galvanostat_terms(gmpnp_solver* s, const double* x /* [n_dofs] or NULL */, double* b_out /* [n_dofs] or NULL */, double* scalars /* [4] */);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -632,7 +676,9 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * allocates the order-2 vectors), 24 = the two launches of the Stern boundary condition (k_stern_residual + k_stern_jacobian; needs
  * gmpnp_set_stern with model != 0 and an assembled Jacobian, which the launches keep adding to), 25 = the two launches of the surface
  * kinetics (k_kinetics_residual + k_kinetics_jacobian; needs gmpnp_set_kinetics with n_reactions > 0 and an assembled Jacobian, which
- * the launches keep adding to). */
+ * the launches keep adding to), 26 = the galvanostat's launches of one Newton iteration apart from the two linear solves (k_galv_rhs,
+ * k_galv_reduce, k_galv_direction, k_galv_potential on a zero step, k_galv_reduce for G alone; needs gmpnp_set_galvanostat with on != 0
+ * and an assembled Jacobian; the state and p_M stay). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
