@@ -44,6 +44,7 @@ EXPORTS = [
     "gmpnp_set_stern", "gmpnp_stern_displacement",
     "gmpnp_set_kinetics", "gmpnp_kinetics_currents",
     "gmpnp_set_galvanostat", "gmpnp_galvanostat_report", "gmpnp_galvanostat_terms",
+    "gmpnp_frequency_response",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -126,6 +127,16 @@ class CGalvanostatReport(ctypes.Structure):
     """ctypes image of ``gmpnp_galvanostat_report_t`` (include/gmpnp.h)."""
     _fields_ = [("p_electrode", c_double), ("p_electrode_n", c_double), ("I_r", c_double * MAX_SURFACE_REACTIONS), ("I", c_double), ("G", c_double),
                 ("cy", c_double), ("cz", c_double), ("d", c_double), ("dp", c_double), ("alpha", c_double)]
+
+
+class CResponse(ctypes.Structure):
+    """ctypes image of ``gmpnp_response_t`` (include/gmpnp.h): C and dI are (re, im) pairs."""
+    _fields_ = [("sigma", c_double), ("C", c_double * 2), ("dI", (c_double * 2) * MAX_SURFACE_REACTIONS), ("residual", c_double),
+                ("status", c_int32)]
+
+
+RESPONSE_MAX_FREQUENCIES = 4096   # gmpnp_frequency_response: n in 1 ... 4096
+RESPONSE_SINGULAR, RESPONSE_NONFINITE = 256, 512   # bits of gmpnp_response_t.status
 
 
 class CLinearStats(ctypes.Structure):
@@ -271,6 +282,7 @@ def load_library(path: str = None):
     lib.gmpnp_set_galvanostat.argtypes = [c_void_p, POINTER(CGalvanostat)]
     lib.gmpnp_galvanostat_report.argtypes = [c_void_p, POINTER(CGalvanostatReport)]
     lib.gmpnp_galvanostat_terms.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    lib.gmpnp_frequency_response.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(CResponse), POINTER(c_double)]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -657,6 +669,24 @@ class DeviceSolver:
         assert xx is None or xx.size == self.ndof
         self._check(self.lib.gmpnp_galvanostat_terms(self._h, None if xx is None else _dptr(xx), _dptr(b), sc))
         return b, {"G": float(sc[0]), "d": float(sc[1]), "I": float(sc[2]), "cx": float(sc[3])}
+
+    def frequency_response(self, sigmas, want_x=False) -> dict:
+        """``gmpnp_frequency_response`` at the current u and p_M: the small-signal response per unit of p_M at the time-term
+        multipliers ``sigmas`` (>= 0, i sigma in the place of inv_dt).  Returns sigma (n,), C (n,) complex, dI (n, n_reactions)
+        complex, residual (n,), status (n,) and, with ``want_x``, x (n, ndof) complex in file order."""
+        sg = np.ascontiguousarray(sigmas, dtype=np.float64).ravel()
+        n = int(sg.size)
+        out = (CResponse * max(n, 1))()
+        x = np.empty((n, self.ndof, 2)) if want_x else None
+        self._check(self.lib.gmpnp_frequency_response(self._h, n, _dptr(sg), out, None if x is None else _dptr(x)))
+        rec = np.frombuffer(out, dtype=np.dtype([("sigma", "f8"), ("C", "f8", 2), ("dI", "f8", (MAX_SURFACE_REACTIONS, 2)), ("residual", "f8"),
+                                                 ("status", "i4"), ("pad", "i4")]), count=n)
+        res = {"sigma": rec["sigma"].copy(), "C": rec["C"][:, 0] + 1j * rec["C"][:, 1],
+               "dI": (rec["dI"][:, :, 0] + 1j * rec["dI"][:, :, 1])[:, :self._n_reactions], "residual": rec["residual"].copy(),
+               "status": rec["status"].copy()}
+        if want_x:
+            res["x"] = x[:, :, 0] + 1j * x[:, :, 1]
+        return res
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

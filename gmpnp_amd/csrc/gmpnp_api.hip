@@ -156,6 +156,23 @@ struct gmpnp_galvanostat {
   ~gmpnp_galvanostat() { if (h_report) (void)hipHostFree(h_report); }
 };
 
+// device side of gmpnp_frequency_response (gmpnp_response.h), allocated by the first call: a handle that never asks for it keeps the
+// buffers and launches it had
+namespace gmpnp { struct RespOut; }
+struct gmpnp_responder {
+  DevBuf<double> blocks;               // L, D, U [NF*NF][nv] and b [NF][nv]: level 0 of the response's own (K at inv_dt = 0, b = dF/dp_M)
+  DevBuf<double> b, mass, sigma;       // b in internal order; [3][nv] mass entries of a species row; the chunk's sigma
+  DevBuf<double2> ws, x;               // [chunk][nv][8][8] eliminated blocks and right-hand sides; [chunk][nv][8] the solution
+  DevBuf<int32_t> fstat, status;       // per-frequency word of the solve; the word of the set-up's own launches
+  DevBuf<gmpnp::RespOut> out;
+  size_t cap_freq = 0;                 // frequencies ws / x / sigma / fstat / out hold
+  int last_chunk = 0;                  // frequencies of the last chunk solved (gmpnp_time_kernel 27)
+  gmpnp::RespOut* h_out = nullptr;     // pinned [cap_freq]
+  double* h_x = nullptr;               // pinned [h_x_freq][nv][8][2], allocated when x is asked for
+  size_t h_x_freq = 0;
+  ~gmpnp_responder() { if (h_out) (void)hipHostFree(h_out); if (h_x) (void)hipHostFree(h_x); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -231,6 +248,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_sterner> sterner;
   std::unique_ptr<gmpnp_kineticist> kineticist;
   std::unique_ptr<gmpnp_galvanostat> galvanostat;
+  std::unique_ptr<gmpnp_responder> responder;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
   // (boundary_rebind); allocated by the first of them
   DevBuf<double> bnd_dyn;
@@ -294,6 +312,9 @@ int galvanostat_shift(gmpnp_solver* s, bool to_previous);
 int galvanostat_launch_iteration(gmpnp_solver* s);
 template <int DIM, int NF>
 int newton_galvanostat(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st);
+// gmpnp_response.h: the two launches of the last chunk of the last gmpnp_frequency_response (gmpnp_time_kernel 27)
+bool response_has_chunk(const gmpnp_solver* s);
+int response_time_chunk(gmpnp_solver* s);
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
@@ -1838,6 +1859,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (kernel == 24 && !stern_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 24 is the Stern boundary condition: the option is off (gmpnp_set_stern)");
   if (kernel == 25 && !kinetics_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 25 is the surface kinetics: the option is off (gmpnp_set_kinetics)");
   if (kernel == 26 && !galvanostat_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 26 is the galvanostat: the option is off (gmpnp_set_galvanostat)");
+  if (kernel == 27 && !response_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 27 is one chunk of the frequency response: no call has been made (gmpnp_frequency_response)");
   if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
@@ -1878,6 +1900,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 24: r = stern_launch_residual(s, s->status.p); if (!r) r = stern_launch_jacobian(s); break;   // k_stern_residual + k_stern_jacobian
       case 25: r = kinetics_launch_residual(s, s->status.p); if (!r) r = kinetics_launch_jacobian(s); break;   // k_kinetics_residual + k_kinetics_jacobian
       case 26: r = galvanostat_launch_iteration(s); break;   // k_galv_rhs + k_galv_reduce + k_galv_direction + k_galv_potential + k_galv_reduce (G alone)
+      case 27: r = response_time_chunk(s); break;   // k_response_solve + k_response_functional on the last chunk's frequencies
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -2000,3 +2023,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_stern.h"
 #include "gmpnp_kinetics.h"
 #include "gmpnp_galvanostat.h"
+#include "gmpnp_response.h"

@@ -18,7 +18,9 @@ namespace gmpnp {
 // device status word: bit 1 = steric excursion (information, unless strict_steric), bits 2 / 4 / 8 = the linear solve failed,
 // bit 16 = the step limiter met a NaN / Inf in the correction (the update was not applied), bit 32 = eps(u) <= 0 on the Stern boundary,
 // bit 64 = a surface reaction rate that is not finite (kinetics on the Stern boundary), bit 128 = the galvanostat's constraint has no
-// step (total current <= 0, a term that is not finite, or a zero denominator)
+// step (total current <= 0, a term that is not finite, or a zero denominator).  Bits 256 / 512 belong to the per-frequency status of
+// gmpnp_frequency_response (gmpnp_response_t.status), not to the handle's word: a pivot of the complex block elimination that is (all
+// but) zero, a value of the response that is not finite
 inline std::string status_message(int flags) {
   std::string m;
   if (flags & 1) m += "1 - sum_j a_j u_j <= 0 at a quadrature point; ";
@@ -29,6 +31,8 @@ inline std::string status_message(int flags) {
   if (flags & 32) m += "eps(u) <= 0 on the Stern boundary (BDM model); ";
   if (flags & 64) m += "surface kinetics: a reaction rate on the Stern boundary is not finite; ";
   if (flags & 128) m += "galvanostat: the total current is <= 0, a term of the constraint is not finite or d - c.z == 0; ";
+  if (flags & 256) m += "frequency response: a pivot of the complex block elimination is (all but) zero at this frequency; ";
+  if (flags & 512) m += "frequency response: a value of the response at this frequency is not finite; ";
   return m;
 }
 
@@ -120,6 +124,54 @@ inline bool galvanostat_options_valid(const gmpnp_galvanostat_t& o) {
   bool any = false;
   for (int r = 0; r < GMPNP_MAX_SURFACE_REACTIONS; ++r) { if (!fin(o.weight[r])) return false; any = any || o.weight[r] != 0.0; }
   return any;
+}
+
+// ---- frequency response (include/gmpnp.h "small-signal frequency response"; kernels: gmpnp_response.h) ---------------------------------
+// The response of the 1D handle per unit of p_M at time-term multiplier sigma solves (K + i sigma M) x = -b with K = J at inv_dt = 0,
+// M the consistent P1 mass on the species rows that carry no Dirichlet value, b = dF/dp_M.  Its functionals at a Stern node (g, g' at
+// the node's permittivity, p the node's potential, x_p and x_j the node's entries of x) and at a kinetic node of weight w:
+//     C    += g / lam (1 - x_p) + g' (p_M - p) / lam  sum_j epsc_j x_j          (dD/dp_M + the Stern row of J applied to x, g' included)
+//     dI_r += w (d_u x_reactant + d_p (x_p - 1))                                (d_p = alpha rate: dI_r/dp_M = -alpha_r I_r)
+// The complex numbers are pairs (re, im); the operations below are written out so that the host, the device and the Python statement
+// (gmpnp_amd/impedance.py) perform the same roundings.  The pivot search of the complex block elimination compares |re| + |im|.
+// Every product and sum below is rounded on its own (no fused multiply-add: GMPNP_RULE_NO_CONTRACT), so the device's elimination and
+// tests/response_reference.py's model of it perform the same operations on the same numbers.
+#if defined(__clang__)
+#define GMPNP_RULE_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define GMPNP_RULE_NO_CONTRACT
+#endif
+struct Cx { double re, im; };
+GMPNP_RULE_HD inline Cx cx_mul(Cx a, Cx b) { GMPNP_RULE_NO_CONTRACT return Cx{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+GMPNP_RULE_HD inline Cx cx_sub(Cx a, Cx b) { return Cx{a.re - b.re, a.im - b.im}; }
+GMPNP_RULE_HD inline Cx cx_add(Cx a, Cx b) { return Cx{a.re + b.re, a.im + b.im}; }
+GMPNP_RULE_HD inline Cx cx_inv(Cx a) { GMPNP_RULE_NO_CONTRACT const double n = a.re * a.re + a.im * a.im; return Cx{a.re / n, -a.im / n}; }
+GMPNP_RULE_HD inline double response_pivot_key(Cx a) { return (a.re < 0.0 ? -a.re : a.re) + (a.im < 0.0 ? -a.im : a.im); }
+// the Stern node's share of C; s = sum_j epsc_j x_j
+GMPNP_RULE_HD inline Cx response_capacitance_term(double g, double dg, double lam, double p_M, double p, Cx x_p, Cx s) {
+  GMPNP_RULE_NO_CONTRACT
+  const double a = g / lam, c = dg * (p_M - p) / lam;
+  return Cx{a * (1.0 - x_p.re) + c * s.re, c * s.im - a * x_p.im};
+}
+// reaction r's share of dI_r at a kinetic node of weight w (x_u = 0 for a reaction without a reactant)
+GMPNP_RULE_HD inline Cx response_current_term(double w, double d_u, double d_p, Cx x_u, Cx x_p) {
+  GMPNP_RULE_NO_CONTRACT
+  return Cx{w * (d_u * x_u.re + d_p * (x_p.re - 1.0)), w * (d_u * x_u.im + d_p * x_p.im)};
+}
+constexpr int kResponseMaxFrequencies = 4096;
+constexpr int kResponseSingular = 256, kResponseNonFinite = 512;   // gmpnp_response_t.status
+inline bool response_sigma_valid(double sigma) { return sigma >= 0.0 && !std::isinf(sigma); }
+inline bool response_count_valid(int n) { return n >= 1 && n <= kResponseMaxFrequencies; }
+// bytes of workspace one frequency takes on nv vertices: the eliminated blocks [nv][8 columns][8 lanes] complex and x [nv][8] complex
+inline double response_bytes_per_frequency(int nv) { return (double)nv * (8.0 * 8.0 + 8.0) * 16.0; }
+// frequencies per chunk under a memory cap: at least one, at most n, a whole number of 8-frequency waves where that fits
+inline int response_chunk(int n, int nv, double cap_bytes) {
+  const double per = response_bytes_per_frequency(nv);
+  double k = std::floor(cap_bytes / per);
+  if (!(k >= 1.0)) k = 1.0;
+  int c = k >= (double)n ? n : (int)k;
+  if (c < n && c >= 8) c -= c % 8;
+  return c;
 }
 
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every

@@ -23,6 +23,7 @@ from datetime import datetime
 import numpy as np
 
 from . import backend
+from .impedance import add_impedance_arguments, impedance_keywords
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import _load_yaml, edl_parameters, utilities_dir
 from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_arguments, add_stern_arguments, edl_problem, galvanostat_keywords, kinetics_keywords,
@@ -78,7 +79,23 @@ class EDLRun:
         electrode potential at which i_CO + i_H2 = X; ``electrode_voltage`` is the starting guess.  Works with ``step_fraction``,
         ``budget`` and ``adaptive_dt`` at order 1 (a rejected attempt restores the potential with the state); not with ``dt_order`` 2.
         Every step records ``electrode_voltage`` beside the currents; the metadata gains ``target_current`` and reports the last
-        potential found as ``electrode_voltage``; the run directory is named by the target."""
+        potential found as ``electrode_voltage``; the run directory is named by the target.
+        ``impedance`` = dict(freq_min=1e-2, freq_max=1e8, per_decade=10) [Hz] (with ``electrode_voltage``): ``write_outputs`` computes the
+        impedance spectrum of the interface at the run's last state (gmpnp_amd/impedance.py; ``impedance()``
+        does the same at any time) and adds ``impedance.npz`` (frequency, sigma, capacitance [F/m2], admittance [S/m2], impedance
+        [Ohm m2], dI_CO, dI_H2 [S/m2], residual); the metadata gains ``impedance_points``, ``capacitance_low`` / ``capacitance_high``
+        (the real part of C at the lowest / highest frequency), ``capacitance_high_closed_form`` (the Stern capacitor in series with
+        the elements'), ``R_ct`` [Ohm m2] (None without kinetics) and ``impedance_last_step_change`` = max |u - u_n| of the last step:
+        how steady the operating point was."""
+        self.impedance_par = kwargs.pop("impedance", None) or None
+        if self.impedance_par is not None:
+            from .impedance import frequency_grid
+            if kwargs.get("electrode_voltage") is None:
+                raise ValueError("impedance: the frequency response needs an electrode potential (electrode_voltage)")
+            if kwargs.get("stabilization", "N") == "Y":
+                raise ValueError("impedance: the frequency response is not available with stabilization Y")
+            self.impedance_par = dict(self.impedance_par)
+            frequency_grid(**self.impedance_par)   # a bad grid is refused before anything touches the device
         self.stern = pop_stern(kwargs, kwargs.get("L_n", 50.0e-6))
         self.kinetic_par = pop_kinetics(kwargs)
         self.target_current = pop_galvanostat(kwargs)
@@ -277,6 +294,49 @@ class EDLRun:
         return {"electrode_voltage": p_M, "stern_model": st.model, "stern_length": st.lam * ep.L_n, "stern_displacement": d,
                 "surface_charge": EPS_0 * ep.thermal_voltage / ep.L_n * d}
 
+    def impedance(self, frequencies):
+        """The impedance spectrum of the interface at the run's CURRENT state and electrode potential, at ``frequencies`` [Hz]
+        (gmpnp_amd/impedance.py: ``spectrum``; one ``gmpnp_frequency_response`` call).  A galvanostatic run switches its galvanostat
+        off for the call (that keeps the potential it found) and on again with the same target."""
+        from . import impedance as imp
+        if self.stern is None:
+            raise ValueError("impedance: the frequency response needs an electrode potential (electrode_voltage)")
+        if self.supg:
+            raise ValueError("impedance: the frequency response is not available with stabilization Y")
+        f = np.atleast_1d(np.asarray(frequencies, dtype=np.float64))
+        if not imp.count_valid(f.size) or not np.all(np.isfinite(f)) or np.any(f < 0.0):
+            raise ValueError("impedance: 1 ... %d finite frequencies >= 0" % imp.MAX_FREQUENCIES)
+        dev = self.sys.dev
+        if self.galvanostat is not None:
+            dev.set_galvanostat(None)
+        try:
+            res = dev.frequency_response(imp.sigma_from_frequency(self.ep, f))
+        finally:
+            if self.galvanostat is not None:
+                dev.set_galvanostat(self.galvanostat)
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
+        return imp.spectrum(self.ep, eps_0, f, res)
+
+    def impedance_outputs(self, newpath):
+        """``impedance.npz`` of the last state and the metadata keys that go with it (see ``__init__``)."""
+        from . import impedance as imp
+        sp = self.impedance(imp.frequency_grid(**self.impedance_par))
+        nr = sp["dI_dV"].shape[1]
+        zero = np.zeros(len(sp["frequency"]), dtype=complex)
+        np.savez(newpath + "/impedance.npz", frequency=sp["frequency"], sigma=sp["sigma"], capacitance=sp["capacitance"], admittance=sp["admittance"],
+                 impedance=sp["impedance"], dI_CO=sp["dI_dV"][:, 0] if nr > 0 else zero, dI_H2=sp["dI_dV"][:, 1] if nr > 1 else zero,
+                 residual=sp["residual"])
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
+        p_M = self.potentials[-1] if self.potentials else self.stern.p_electrode
+        stern = type(self.stern)(self.stern.model, p_M, self.stern.lam, self.stern.eps_surface)
+        c_inf = imp.high_frequency_capacitance(self.mesh.coords, self.history[-1], self.problem.model, stern) * eps_0 / self.ep.L_n
+        g_ct = -float(sp["dI_dV"][0].sum().real) if nr else 0.0
+        change = float(np.abs(self.history[-1] - self.history[-2]).max()) if len(self.history) > 1 else None
+        return {"impedance_points": int(len(sp["frequency"])), "capacitance_low": float(sp["capacitance"][0].real),
+                "capacitance_high": float(sp["capacitance"][-1].real), "capacitance_high_closed_form": float(c_inf),
+                "R_ct": (1.0 / g_ct) if g_ct != 0.0 else None, "impedance_last_step_change": change,
+                "impedance_worst_residual": float(np.max(sp["residual"])), "impedance_status": int(np.bitwise_or.reduce(sp["status"]))}
+
     def kinetics_summary(self):
         """Per-step ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2`` of a run with the surface kinetics (the OHP is one point: w = 1)."""
         from .kinetics import current_summary
@@ -351,6 +411,8 @@ class EDLRun:
             metadata_dict.update({key: (float(v[-1]) if len(v) else None) for key, v in self.kinetics_summary().items()})
         if self.galvanostat is not None:
             metadata_dict["target_current"] = self.target_current
+        if self.impedance_par is not None:
+            metadata_dict.update(self.impedance_outputs(newpath))
         if self.budget is not None:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
@@ -377,7 +439,7 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
               dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM",
               stern_length=4.0e-10, stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0,
-              p_eq_H2=0.0, target_current=None, **adaptive):
+              p_eq_H2=0.0, target_current=None, impedance=None, **adaptive):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
     adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
     ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
@@ -391,6 +453,8 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
         stern.update(kinetics=kinetics, i0_CO=i0_CO, i0_H2=i0_H2, alpha_CO=alpha_CO, alpha_H2=alpha_H2, p_eq_CO=p_eq_CO, p_eq_H2=p_eq_H2)
     if target_current is not None:   # (the galvanostatic mode of ``EDLRun``)
         stern.update(target_current=target_current)
+    if impedance:   # (the impedance spectrum of ``EDLRun``, after the last step)
+        stern.update(impedance=impedance)
     run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, **stern, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
@@ -424,6 +488,7 @@ def build_parser():
     add_stern_arguments(p)
     add_kinetics_arguments(p)
     add_galvanostat_arguments(p)
+    add_impedance_arguments(p)
     return p
 
 
@@ -432,7 +497,8 @@ def main(argv=None):
     return solve_EDL(concentration_elec=a.concentration_elec, model=a.model, voltage_multiplier=a.voltage_multiplier,
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
-                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a))
+                     dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a),
+                     **impedance_keywords(a))
 
 
 if __name__ == "__main__":

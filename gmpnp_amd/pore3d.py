@@ -92,6 +92,8 @@ class PoreRun:
         ``electrode_voltage``; the metadata gains ``target_current`` and reports the last potential found."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
+        from .impedance import refuse_impedance
+        refuse_impedance(kwargs, "the 3D pore driver (it needs a complex band LU)")
         self.stern = pop_stern(kwargs, kwargs.get("L", 100.0e-9))
         self.kinetic_par = pop_kinetics(kwargs)
         self.target_current = pop_galvanostat(kwargs)

@@ -16,6 +16,7 @@ import numpy as np
 from . import backend
 from .edl_ensemble import ADAPTIVE_REFUSAL, AdaptiveRounds, error_text
 from .pore3d import SOLVER_PARAMETERS, PoreRun
+from .impedance import refuse_impedance
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import column_medians
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -38,6 +39,7 @@ def plan_members(members, num_steps=None):
         raise ValueError("an ensemble holds 1 ... %d members, not %d" % (backend.MAX_ENSEMBLE, len(members)))
     full = []
     for k, m in enumerate(members):
+        refuse_impedance(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

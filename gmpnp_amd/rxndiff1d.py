@@ -27,6 +27,7 @@ from . import backend, timestep
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .model import Model
 from .params import _load_yaml, _reaction_tables, utilities_dir
+from .impedance import refuse_impedance
 from .problem import edl_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem
 
@@ -139,6 +140,7 @@ class RxnDiffRun:
         ``adaptive_dt`` = True with ``dt_rtol``, ``dt_atol``, ``dt_init``, ``dt_min``, ``dt_max``, ``t_end``, ``steady_tol``, ``max_steps``, ``dt_order``
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history and the budget log as they were.  Off: nothing changes."""
+        refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

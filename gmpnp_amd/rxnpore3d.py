@@ -25,6 +25,7 @@ from . import backend, timestep
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
+from .impedance import refuse_impedance
 from .problem import GALVANOSTAT_KEYWORDS, KINETICS_KEYWORDS, pore_dirichlet, pore_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem, column_medians
 from .vtk import write_pvd
@@ -60,6 +61,7 @@ class RxnPoreRun:
         ``adaptive_dt`` = True with ``dt_rtol``, ``dt_atol``, ``dt_init``, ``dt_min``, ``dt_max``, ``t_end``, ``steady_tol``, ``max_steps``, ``dt_order``
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history, the budget log and the CO2 Dirichlet value as they were.  Off: nothing changes."""
+        refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

@@ -606,6 +606,37 @@ int gmpnp_set_galvanostat(gmpnp_solver* s, const gmpnp_galvanostat_t* galvanosta
 int gmpnp_galvanostat_report(gmpnp_solver* s, gmpnp_galvanostat_report_t* out);
 int gmpnp_galvanostat_terms(gmpnp_solver* s, const double* x /* [n_dofs] or NULL */, double* b_out /* [n_dofs] or NULL */, double* scalars /* [4] */);
 
+/* ---- small-signal frequency response (no reference counterpart: impedance spectroscopy of the double layer) ------------------------
+ * 1D handles with the Stern option on.  The linearisation is taken at the handle's current u and p_M: K = J(u) at inv_dt = 0 with
+ * every Stern and kinetic term and the Dirichlet identity rows, M = the consistent P1 mass on the species rows that carry no Dirichlet
+ * value (J is affine in inv_dt: J = K + inv_dt M), b = dF/dp_M as the galvanostatic mode defines it.  Per unit of p_M (thermal
+ * voltages), at time-term multiplier sigma >= 0 with i sigma in the place of inv_dt:
+ *     (K + i sigma M) x = -b
+ *     C(sigma)    = dD/dp_M + (dD/du).x        D = gmpnp_stern_displacement; 1D: dD/dp_M = g / lam, dD/dp_v = -g / lam, dD/du_{v,j} =
+ *                                              g' epsc_j (p_M - p_v) / lam (the Stern row of J)
+ *     dI_r(sigma) = dI_r/dp_M + (dI_r/du).x    I_r = gmpnp_kinetics_currents; = -alpha_r I_r + sum_I w_I (k_r E_r x_reactant + alpha_r rate_r x_p)
+ * Nothing depends on u_n or on model.inv_dt.  out[k] holds sigma[k], C and dI_r as (re, im) pairs (dI = 0 with the kinetics off), the
+ * residual max |(K + i sigma M) x + b| / max |b| and a status word of that frequency alone: bit 256 = a pivot of the complex block
+ * elimination was (all but) zero, bit 512 = a value that is not finite; the other frequencies are not affected.  x_out, where given,
+ * receives x as (re, im) pairs in file order.  The n systems are solved by a complex block Thomas elimination with partial pivoting
+ * inside the 7 x 7 blocks (pivot key |re| + |im|), eight lanes per frequency, in chunks of frequencies sized from a memory cap
+ * (1024 MB of workspace; the environment variable GMPNP_RESPONSE_CAP_MB overrides it) with one host synchronisation per chunk; the
+ * result of a frequency does not depend on n or on the chunking, and two calls give equal bits.  Afterwards F, the Jacobian and the
+ * validity flags of the handle are what they were before the call, bit for bit (a following gmpnp_newton_solve is not affected).
+ * Refused (GMPNP_ERR_INVALID, the message names the frequency response): 3D handles, partition handles, SUPG terms set, a coarse
+ * level attached or serving as one, the Stern option off, the galvanostat on (switch it off first: that keeps the potential it
+ * found), Stern and kinetic options with different p_electrode, n outside 1 ... 4096, a sigma that is negative or not finite.
+ * eps <= 0 on the Stern boundary or a rate that is not finite at the current state: GMPNP_ERR_NUMERIC. */
+typedef struct {
+  double sigma;
+  double C[2];                                   /* (re, im), scaled units */
+  double dI[GMPNP_MAX_SURFACE_REACTIONS][2];     /* (re, im) per reaction */
+  double residual;
+  int32_t status;                                /* 0, or bits 256 / 512 */
+} gmpnp_response_t;
+int gmpnp_frequency_response(gmpnp_solver* s, int32_t n, const double* sigma /* [n] */, gmpnp_response_t* out /* [n] */,
+                             double* x_out /* [n][n_dofs][2] in file order, or NULL */);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -678,7 +709,8 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * kinetics (k_kinetics_residual + k_kinetics_jacobian; needs gmpnp_set_kinetics with n_reactions > 0 and an assembled Jacobian, which
  * the launches keep adding to), 26 = the galvanostat's launches of one Newton iteration apart from the two linear solves (k_galv_rhs,
  * k_galv_reduce, k_galv_direction, k_galv_potential on a zero step, k_galv_reduce for G alone; needs gmpnp_set_galvanostat with on != 0
- * and an assembled Jacobian; the state and p_M stay). */
+ * and an assembled Jacobian; the state and p_M stay), 27 = the two launches of one chunk of the frequency response (k_response_solve +
+ * k_response_functional on the frequencies of the last chunk of the last gmpnp_frequency_response call, which it needs). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
