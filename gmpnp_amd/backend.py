@@ -45,6 +45,7 @@ EXPORTS = [
     "gmpnp_set_kinetics", "gmpnp_kinetics_currents",
     "gmpnp_set_galvanostat", "gmpnp_galvanostat_report", "gmpnp_galvanostat_terms",
     "gmpnp_frequency_response",
+    "gmpnp_electrode_tangent", "gmpnp_tangent_columns", "gmpnp_electrode_advance",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -135,6 +136,13 @@ class CResponse(ctypes.Structure):
                 ("status", c_int32)]
 
 
+class CTangent(ctypes.Structure):
+    """ctypes image of ``gmpnp_tangent_t`` (include/gmpnp.h)."""
+    _fields_ = [("param", c_int32), ("dD", c_double), ("dI", c_double * MAX_SURFACE_REACTIONS), ("dp_boundary", c_double),
+                ("residual", c_double), ("status", c_int32)]
+
+
+TANGENT_MAX_COLUMNS = 10          # GMPNP_TANGENT_MAX_COLUMNS
 RESPONSE_MAX_FREQUENCIES = 4096   # gmpnp_frequency_response: n in 1 ... 4096
 RESPONSE_SINGULAR, RESPONSE_NONFINITE = 256, 512   # bits of gmpnp_response_t.status
 
@@ -283,6 +291,9 @@ def load_library(path: str = None):
     lib.gmpnp_galvanostat_report.argtypes = [c_void_p, POINTER(CGalvanostatReport)]
     lib.gmpnp_galvanostat_terms.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
     lib.gmpnp_frequency_response.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(CResponse), POINTER(c_double)]
+    lib.gmpnp_electrode_tangent.argtypes = [c_void_p, c_int32, POINTER(c_int32), POINTER(CTangent), POINTER(c_double)]
+    lib.gmpnp_tangent_columns.argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_electrode_advance.argtypes = [c_void_p, c_double, c_double, POINTER(c_double)]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -687,6 +698,37 @@ class DeviceSolver:
         if want_x:
             res["x"] = x[:, :, 0] + 1j * x[:, :, 1]
         return res
+
+    def electrode_tangent(self, params, want_z=False) -> dict:
+        """``gmpnp_electrode_tangent`` at the current u, p_M and inv_dt: the tangents z_k = du/dtheta_k for the parameter codes
+        ``params`` (``polarisation.PARAM_*``).  Returns param (n,), dD (n,), dI (n, n_reactions), dp_boundary (n,), residual (n,),
+        status (n,) and, with ``want_z``, z (n, ndof) in file order."""
+        pr = np.ascontiguousarray(params, dtype=np.int32).ravel()
+        n = int(pr.size)
+        out = (CTangent * max(n, 1))()
+        z = np.empty((n, self.ndof)) if want_z else None
+        self._check(self.lib.gmpnp_electrode_tangent(self._h, n, _iptr(pr), out, None if z is None else _dptr(z)))
+        rec = np.frombuffer(out, dtype=np.dtype([("param", "i4"), ("pad0", "i4"), ("dD", "f8"), ("dI", "f8", MAX_SURFACE_REACTIONS),
+                                                 ("dp_boundary", "f8"), ("residual", "f8"), ("status", "i4"), ("pad", "i4")]), count=n)
+        res = {"param": rec["param"].copy(), "dD": rec["dD"].copy(), "dI": rec["dI"][:, :self._n_reactions].copy(),
+               "dp_boundary": rec["dp_boundary"].copy(), "residual": rec["residual"].copy(), "status": rec["status"].copy()}
+        if want_z:
+            res["z"] = z
+        return res
+
+    def tangent_columns(self, n) -> np.ndarray:
+        """``gmpnp_tangent_columns``: the columns c_k = dF/dtheta_k of the last ``electrode_tangent`` call of ``n`` columns, (n, ndof)
+        in file order."""
+        c = np.empty((int(n), self.ndof))
+        self._check(self.lib.gmpnp_tangent_columns(self._h, _dptr(c)))
+        return c
+
+    def electrode_advance(self, dp, tau=0.0) -> float:
+        """``gmpnp_electrode_advance``: p_electrode += dp in the Stern and kinetic options, u += alpha dp z_0 with the p_M tangent of
+        the last ``electrode_tangent`` (which must belong to the present state).  Returns alpha (1 with ``tau`` = 0)."""
+        alpha = c_double()
+        self._check(self.lib.gmpnp_electrode_advance(self._h, float(dp), float(tau), byref(alpha)))
+        return float(alpha.value)
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

@@ -173,6 +173,22 @@ struct gmpnp_responder {
   ~gmpnp_responder() { if (h_out) (void)hipHostFree(h_out); if (h_x) (void)hipHostFree(h_x); }
 };
 
+// device side of gmpnp_electrode_tangent / gmpnp_electrode_advance (gmpnp_tangent.h), allocated by the first call: a handle that never
+// asks for it keeps the buffers and launches it had
+namespace gmpnp { struct TanOut; }
+struct gmpnp_tangenter {
+  DevBuf<double> c, z, Jz;             // [10][ndof] internal order: the columns dF/dtheta_k, the tangents, J z_k
+  DevBuf<double> cols_store;           // per level of the cyclic-reduction pyramid: b, bi, x with 8 columns each
+  DevBuf<double> alpha;                // the advance's step factor
+  DevBuf<int32_t> status;              // the word of the column and functional launches
+  DevBuf<gmpnp::TanOut> out;
+  gmpnp::TanOut* h_out = nullptr;      // pinned [10]
+  int last_n = 0;                      // columns of the last call (gmpnp_time_kernel 28, gmpnp_tangent_columns)
+  int col_pM = -1;                     // where the p_M column of the last call sits
+  bool fresh = false;                  // z[col_pM] belongs to the present u, p_M and options: gmpnp_electrode_advance may use it
+  ~gmpnp_tangenter() { if (h_out) (void)hipHostFree(h_out); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -249,6 +265,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_kineticist> kineticist;
   std::unique_ptr<gmpnp_galvanostat> galvanostat;
   std::unique_ptr<gmpnp_responder> responder;
+  std::unique_ptr<gmpnp_tangenter> tangenter;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
   // (boundary_rebind); allocated by the first of them
   DevBuf<double> bnd_dyn;
@@ -315,6 +332,11 @@ int newton_galvanostat(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_n
 // gmpnp_response.h: the two launches of the last chunk of the last gmpnp_frequency_response (gmpnp_time_kernel 27)
 bool response_has_chunk(const gmpnp_solver* s);
 int response_time_chunk(gmpnp_solver* s);
+// gmpnp_tangent.h: the multi-column chain(s) of the last gmpnp_electrode_tangent (gmpnp_time_kernel 28); whatever changes u, p_M or an
+// option drops the tangent the advance would use
+bool tangent_has_chain(const gmpnp_solver* s);
+int tangent_time_chain(gmpnp_solver* s);
+inline void tangent_drop(gmpnp_solver* s) { if (s->tangenter) s->tangenter->fresh = false; }
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
@@ -1581,6 +1603,7 @@ int gmpnp_set_model(gmpnp_solver* s, const gmpnp_model_t* model) {
   if (!s) return fail(GMPNP_ERR_INVALID, "NULL handle");
   int rc = check_model(model, s->dim); if (rc) return rc;
   if (model->n_species + 1 != s->nf) return fail(GMPNP_ERR_INVALID, "n_species cannot change after create");
+  tangent_drop(s);
   HIP_TRY(hipSetDevice(s->opts.device_id));
   HIP_TRY(hipStreamSynchronize(s->stream));
   s->model = *model;
@@ -1591,6 +1614,7 @@ int gmpnp_set_model(gmpnp_solver* s, const gmpnp_model_t* model) {
 
 int gmpnp_set_supg(gmpnp_solver* s, const double* rho, const int32_t* w_index) {
   if (!s) return fail(GMPNP_ERR_INVALID, "NULL handle");
+  tangent_drop(s);
   HIP_TRY(hipSetDevice(s->opts.device_id));
   HIP_TRY(hipStreamSynchronize(s->stream));
   s->jacobian_valid = false;
@@ -1617,6 +1641,7 @@ int gmpnp_set_supg(gmpnp_solver* s, const double* rho, const int32_t* w_index) {
 
 int gmpnp_set_dirichlet(gmpnp_solver* s, int64_t n, const int64_t* dofs, const double* values) {
   if (!s || n < 0 || (n > 0 && (!dofs || !values))) return fail(GMPNP_ERR_INVALID, "bad arguments");
+  tangent_drop(s);
   HIP_TRY(hipSetDevice(s->opts.device_id));
   HIP_TRY(hipStreamSynchronize(s->stream));   // the pinned value buffer may still be in flight
   std::fill(s->h_bcflag.begin(), s->h_bcflag.end(), 0);
@@ -1639,6 +1664,7 @@ int gmpnp_set_dirichlet(gmpnp_solver* s, int64_t n, const int64_t* dofs, const d
 
 int gmpnp_set_state(gmpnp_solver* s, const double* u, const double* u_n) {
   if (!s) return fail(GMPNP_ERR_INVALID, "NULL handle");
+  tangent_drop(s);
   HIP_TRY(hipSetDevice(s->opts.device_id));
   HIP_TRY(hipStreamSynchronize(s->stream));
   if (u) { int rc = upload_vec(s, u, s->u.p); if (rc) return rc; s->state_jumped = true; }
@@ -1673,6 +1699,7 @@ int gmpnp_newton_solve(gmpnp_solver* s, const gmpnp_newton_options_t* o, gmpnp_n
   if (o->linear_solver == GMPNP_LINEAR_BLOCK_TRIDIAGONAL && !s->tri_ok)
     return fail(GMPNP_ERR_INVALID, "block-tridiagonal solver needs a 1D mesh in path order");
   if (!step_fraction_valid(o->step_fraction)) return fail(GMPNP_ERR_INVALID, "step_fraction must be 0 (off) or lie in (0, 1)");
+  tangent_drop(s);
   gmpnp_newton_stats_t local{};
   gmpnp_newton_stats_t& st = stats ? *stats : local;
   st = fresh_newton_stats();
@@ -1860,6 +1887,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (kernel == 25 && !kinetics_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 25 is the surface kinetics: the option is off (gmpnp_set_kinetics)");
   if (kernel == 26 && !galvanostat_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 26 is the galvanostat: the option is off (gmpnp_set_galvanostat)");
   if (kernel == 27 && !response_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 27 is one chunk of the frequency response: no call has been made (gmpnp_frequency_response)");
+  if (kernel == 28 && !tangent_has_chain(s)) return fail(GMPNP_ERR_INVALID, "kernel 28 is the multi-column chain of the electrode tangent: no call has been made on this Jacobian (gmpnp_electrode_tangent, 1D)");
   if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
@@ -1901,6 +1929,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 25: r = kinetics_launch_residual(s, s->status.p); if (!r) r = kinetics_launch_jacobian(s); break;   // k_kinetics_residual + k_kinetics_jacobian
       case 26: r = galvanostat_launch_iteration(s); break;   // k_galv_rhs + k_galv_reduce + k_galv_direction + k_galv_potential + k_galv_reduce (G alone)
       case 27: r = response_time_chunk(s); break;   // k_response_solve + k_response_functional on the last chunk's frequencies
+      case 28: r = tangent_time_chain(s); break;    // extraction, k_bcr_forward_cols / k_bcr_tail_cols / k_bcr_backward_cols, application
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -2024,3 +2053,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_kinetics.h"
 #include "gmpnp_galvanostat.h"
 #include "gmpnp_response.h"
+#include "gmpnp_tangent.h"

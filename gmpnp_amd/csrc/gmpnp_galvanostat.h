@@ -349,6 +349,7 @@ extern "C" {
 int gmpnp_set_galvanostat(gmpnp_solver* s, const gmpnp_galvanostat_t* o) {
   if (!s || !o) return fail(GMPNP_ERR_INVALID, "galvanostat: NULL argument");
   if (!o->on && !s->galvanostat) return GMPNP_OK;   // never on: the handle stays as it was
+  tangent_drop(s);
   HIP_TRY(hipSetDevice(s->opts.device_id));
   if (!o->on) {
     if (!galvanostat_on(s)) return GMPNP_OK;

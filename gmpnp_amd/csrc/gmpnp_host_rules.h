@@ -174,6 +174,99 @@ inline int response_chunk(int n, int nv, double cap_bytes) {
   return c;
 }
 
+// ---- electrode tangent and polarisation curves (include/gmpnp.h "electrode tangent"; kernels: gmpnp_tangent.h) ----------------------
+// The tangent z = du/dtheta of F(u; theta) = 0 solves J z = -dF/dtheta.  Parameter codes: 0 = p_M, 16 + r = ln k_r, 32 + r = alpha_r,
+// 48 = ln lam; kinds 0 ... 3 in that order, -1 = unknown.  The explicit derivatives at a boundary node, per unit weight:
+//     rate_r     p_M: -alpha_r rate_r (= -d_p)    ln k_s: delta_rs rate_r    alpha_s: -delta_rs rate_r (p_M - p - p_eq_r)    ln lam: 0
+//     Stern term p_M: g M / lam (`slope`)         ln lam: -term              otherwise 0
+// and the functionals take  dI_r += w (d_u z_reactant + d_p z_p + explicit),  dD += explicit + (Stern row of J).z.  Every product and sum
+// is rounded on its own (GMPNP_RULE_NO_CONTRACT); gmpnp_amd/polarisation.py states the same operations in Python.
+constexpr int kTangentMaxColumns = 10;
+constexpr int kTangentNonFinite = 1;   // gmpnp_tangent_t.status
+GMPNP_RULE_HD inline int tangent_param_kind(int param) {
+  if (param == 0) return 0;
+  if (param >= 16 && param < 16 + GMPNP_MAX_SURFACE_REACTIONS) return 1;
+  if (param >= 32 && param < 32 + GMPNP_MAX_SURFACE_REACTIONS) return 2;
+  if (param == 48) return 3;
+  return -1;
+}
+GMPNP_RULE_HD inline int tangent_param_reaction(int param) { const int k = tangent_param_kind(param); return k == 1 ? param - 16 : k == 2 ? param - 32 : -1; }
+// valid for a handle with n_reactions reactions (0: the kinetics are off)
+GMPNP_RULE_HD inline bool tangent_param_valid(int param, int n_reactions) {
+  const int k = tangent_param_kind(param);
+  if (k < 0) return false;
+  return (k == 0 || k == 3) ? true : tangent_param_reaction(param) < n_reactions;
+}
+inline bool tangent_count_valid(int n) { return n >= 1 && n <= kTangentMaxColumns; }
+// d rate_r / d theta at fixed u; eta = p_M - p - p_eq_r
+GMPNP_RULE_HD inline double tangent_rate_explicit(int param, int r, double rate, double d_p, double eta) {
+  GMPNP_RULE_NO_CONTRACT
+  const int k = tangent_param_kind(param);
+  if (k == 0) return -d_p;
+  if (k == 1) return tangent_param_reaction(param) == r ? rate : 0.0;
+  if (k == 2) return tangent_param_reaction(param) == r ? -(rate * eta) : 0.0;
+  return 0.0;
+}
+// d (Stern term) / d theta at fixed u; slope = d term / d p_M
+GMPNP_RULE_HD inline double tangent_stern_explicit(int param, double slope, double term) {
+  const int k = tangent_param_kind(param);
+  return k == 0 ? slope : k == 3 ? -term : 0.0;
+}
+// reaction r's share of dI_r at a kinetic node of weight w (z_u = 0 for a reaction without a reactant)
+GMPNP_RULE_HD inline double tangent_current_term(double w, double d_u, double d_p, double z_u, double z_p, double explicit_part) {
+  GMPNP_RULE_NO_CONTRACT
+  return w * ((d_u * z_u + d_p * z_p) + explicit_part);
+}
+// The continuation rule of a polarisation curve.  Targets are the grid v_start + k v_step up to v_end, which is landed on exactly; an
+// attempt goes from the last converged point `at` towards the next target with step `dp`; a failed attempt halves the step, a success
+// tries the whole remainder to the target again; a step below |v_step| / 1024 ends the curve (stop = 1, "dp_min").
+struct Continuation {
+  double v_start, v_end, v_step;
+  double at;        // the last converged potential
+  int k;            // grid points reached so far (the start is point 0)
+  double dp;        // the step of the next attempt
+  int stop;         // 0 running, 1 dp_min, 2 the end was reached
+};
+inline bool continuation_valid(double v_start, double v_end, double v_step) {
+  return rule_finite(v_start) && rule_finite(v_end) && rule_finite(v_step) && v_step != 0.0 && (v_end - v_start) * v_step >= 0.0;
+}
+inline double continuation_target(const Continuation& c) {
+  const double t = c.v_start + (c.k + 1) * c.v_step;
+  return (c.v_step > 0.0 ? t >= c.v_end : t <= c.v_end) ? c.v_end : t;
+}
+inline Continuation continuation_begin(double v_start, double v_end, double v_step) {
+  Continuation c{v_start, v_end, v_step, v_start, 0, 0.0, 0};
+  if (v_start == v_end) c.stop = 2;
+  else c.dp = continuation_target(c) - c.at;
+  return c;
+}
+// the potential of the next attempt: the target itself where the attempt lands on it
+inline double continuation_attempt(const Continuation& c) {
+  const double next = c.at + c.dp, t = continuation_target(c);
+  return (c.v_step > 0.0 ? next >= t : next <= t) ? t : next;
+}
+// after an attempt of step c.dp: returns 1 where a grid point was reached (c.k counts it), else 0
+inline int continuation_advance(Continuation& c, bool success) {
+  const double target = continuation_target(c);
+  const double dp_min = (c.v_step < 0.0 ? -c.v_step : c.v_step) / 1024.0;
+  if (!success) {
+    c.dp = c.dp / 2.0;
+    if ((c.dp < 0.0 ? -c.dp : c.dp) < dp_min) c.stop = 1;
+    return 0;
+  }
+  const double next = c.at + c.dp;
+  const bool landed = c.v_step > 0.0 ? next >= target : next <= target;
+  if (landed) {
+    c.at = target; c.k += 1;
+    if (target == c.v_end) { c.stop = 2; c.dp = 0.0; }
+    else c.dp = continuation_target(c) - c.at;
+    return 1;
+  }
+  c.at = next;
+  c.dp = target - c.at;
+  return 0;
+}
+
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every
 // update.  A driver hands every residual norm (with the device status word of its evaluation) to first() / next() and does what
 // the verdict says; on `failed` and `limit` the error is (code, message).  Owns r0, steric_excursion, residuals[], n_residuals

@@ -242,6 +242,7 @@ int gmpnp_set_kinetics(gmpnp_solver* s, const gmpnp_kinetics_t* o) {
     int rc = kinetics_build(s, K.get()); if (rc) return rc;
     s->kineticist = std::move(K);
   }
+  tangent_drop(s);
   s->kineticist->opt = *o;
   if (galvanostat_on(s))   // the galvanostat's p_M stays (the stream is idle: its last update has landed)
     HIP_TRY(hipMemcpy(&s->kineticist->opt.p_electrode, s->galvanostat->scal.p, sizeof(double), hipMemcpyDeviceToHost));

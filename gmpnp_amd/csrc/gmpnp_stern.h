@@ -242,6 +242,7 @@ int gmpnp_set_stern(gmpnp_solver* s, const gmpnp_stern_t* o) {
     int rc = stern_build(s, S.get()); if (rc) return rc;
     s->sterner = std::move(S);
   }
+  tangent_drop(s);
   s->sterner->opt = *o;   // (with the galvanostat on the kernels read ITS p_M: p_electrode is what on = 0 writes back)
   s->jacobian_valid = false; s->precond_valid = false;
   return boundary_rebind(s);

@@ -190,6 +190,7 @@ int time_step_apply(gmpnp_solver* s, double inv_dt) {
     l->model.inv_dt = inv_dt;
     HIP_TRY(hipMemcpy(l->d_model.p, &l->model, sizeof(gmpnp_model_t), hipMemcpyHostToDevice));
     l->jacobian_valid = false; l->precond_valid = false;
+    tangent_drop(l);
   }
   return GMPNP_OK;
 }
@@ -267,6 +268,7 @@ int gmpnp_time_reject(gmpnp_solver* s) {
   int rc = time_prepare(s, "gmpnp_time_reject"); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(s->u.p, s->un.p, (size_t)s->ndof * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   s->state_jumped = true; s->jacobian_valid = false;
+  tangent_drop(s);
   if (galvanostat_on(s)) return galvanostat_shift(s, false);
   return GMPNP_OK;
 }

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import copy
+import dataclasses
 import json
 import math
 import os
@@ -24,6 +25,7 @@ import numpy as np
 
 from . import backend
 from .impedance import add_impedance_arguments, impedance_keywords
+from .polarisation import add_polarisation_arguments, polarisation_keywords
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import _load_yaml, edl_parameters, utilities_dir
 from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_arguments, add_stern_arguments, edl_problem, galvanostat_keywords, kinetics_keywords,
@@ -35,6 +37,7 @@ SOLVER_PARAMETERS = {  # reference 1D:357-364
     "nonlinear_solver": "newton",
     "newton_solver": {"maximum_iterations": 50, "relative_tolerance": 1.0e-4, "absolute_tolerance": 1.0e-4},
 }
+from .polarisation import NEWTON as POLARISATION_NEWTON  # noqa: E402 (the Newton solves of a polarisation curve)
 
 
 def scale(species="H", tau=None, C=None, initial_conc=None, diff_coeff=None, L_n=0.0, L_debye=0.0):
@@ -86,7 +89,19 @@ class EDLRun:
         [Ohm m2], dI_CO, dI_H2 [S/m2], residual); the metadata gains ``impedance_points``, ``capacitance_low`` / ``capacitance_high``
         (the real part of C at the lowest / highest frequency), ``capacitance_high_closed_form`` (the Stern capacitor in series with
         the elements'), ``R_ct`` [Ohm m2] (None without kinetics) and ``impedance_last_step_change`` = max |u - u_n| of the last step:
-        how steady the operating point was."""
+        how steady the operating point was.
+        ``polarisation`` = dict(v_end=X, v_step=Y[, params=(0, ...)]) (thermal voltages; with ``electrode_voltage``): ``write_outputs``
+        walks the steady-state polarisation curve from the run's last state and potential to ``v_end`` (DESIGN.md section 5l,
+        gmpnp_amd/polarisation.py; ``polarisation()`` does the same at any time) and adds ``polarisation.npz``; the metadata gains
+        ``polarisation_points``, ``polarisation_v_end``, ``polarisation_v_step``, ``polarisation_stop_reason``,
+        ``polarisation_newton_iterations``, ``polarisation_substeps``, ``polarisation_worst_residual`` and ``polarisation_params``.
+        Not with ``target_current``, ``stabilization`` "Y", ``H_OHP`` or ``dt_order`` 2 (ValueError, before anything touches the
+        device).  The run should have reached its steady state (``adaptive_dt`` with ``steady_tol``): the first point is one Newton
+        solve at inv_dt = 0 from the last state."""
+        self.polarisation_par = kwargs.pop("polarisation", None) or None
+        if self.polarisation_par is not None:
+            from .polarisation import check_polarisation
+            self.polarisation_par = check_polarisation(self.polarisation_par, kwargs, dt_order)
         self.impedance_par = kwargs.pop("impedance", None) or None
         if self.impedance_par is not None:
             from .impedance import frequency_grid
@@ -337,6 +352,49 @@ class EDLRun:
                 "R_ct": (1.0 / g_ct) if g_ct != 0.0 else None, "impedance_last_step_change": change,
                 "impedance_worst_residual": float(np.max(sp["residual"])), "impedance_status": int(np.bitwise_or.reduce(sp["status"]))}
 
+    def polarisation(self, v_end, v_step, params=(0,), predictor=True, solver_parameters=None):
+        """The steady-state polarisation curve from the run's LAST state and electrode potential to ``v_end`` on the grid
+        electrode_voltage + k ``v_step`` (thermal voltages; gmpnp_amd/polarisation.py: ``run_continuation``).  The time term is
+        switched off (``set_time_step(0)``) and put back afterwards; one Newton solve finds the first point (RuntimeError where it
+        fails: run to the steady stop first), then per point: tangent (``gmpnp_electrode_tangent`` for the parameter codes
+        ``params``, p_M among them), predictor (``gmpnp_electrode_advance`` with the run's ``step_fraction``), Newton at inv_dt = 0
+        (``solver_parameters``, default ``polarisation.NEWTON``-like tight tolerances, with the run's ``step_fraction``).  A failed
+        attempt returns to the last converged point, kept in u_n.  The handle and the run's Stern / kinetics records end at the last
+        converged potential.  Returns the arrays of ``polarisation.npz`` plus ``stop_reason``."""
+        from . import polarisation as pol
+        if self.stern is None:
+            raise ValueError("polarisation: the curve needs an electrode potential (electrode_voltage)")
+        if self.galvanostat is not None:
+            raise ValueError("polarisation: the curve is not available with target_current (the galvanostat)")
+        if self.supg:
+            raise ValueError("polarisation: the curve is not available with stabilization Y")
+        par = pol.check_polarisation(dict(v_end=v_end, v_step=v_step, params=params),
+                                     dict(electrode_voltage=self.stern.p_electrode, kinetics=self.kinetic_par))
+        sp = backend.with_step_fraction(solver_parameters or POLARISATION_NEWTON, self.step_fraction)
+        ops = pol.DeviceOps(self, backend.newton_options(sp, dim=1), par["params"], lambda u: float(u[self.problem.nf - 1]))
+
+        inv_dt = float(self.sys.problem.model.inv_dt)
+        self.sys.set_time_step(0.0)
+        try:
+            records, substeps, newton, stop = pol.run_continuation(ops, self.stern.p_electrode, par["v_end"], par["v_step"], predictor)
+        finally:
+            self.sys.set_time_step(inv_dt)
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
+        out = pol.curve_arrays(self.ep, eps_0, 1.0, records, par["params"], substeps, newton)
+        out["stop_reason"] = stop
+        return out
+
+    def polarisation_outputs(self, newpath):
+        """``polarisation.npz`` of the curve from the last state and the metadata keys that go with it (see ``__init__``)."""
+        out = self.polarisation(**self.polarisation_par)
+        stop = out.pop("stop_reason")
+        np.savez(newpath + "/polarisation.npz", **out)
+        return {"polarisation_points": int(len(out["electrode_voltage"])), "polarisation_v_end": float(self.polarisation_par["v_end"]),
+                "polarisation_v_step": float(self.polarisation_par["v_step"]), "polarisation_stop_reason": stop,
+                "polarisation_newton_iterations": int(out["newton_iterations"].sum()), "polarisation_substeps": int(out["substeps"].sum()),
+                "polarisation_worst_residual": float(np.max(out["tangent_residual"])),
+                "polarisation_params": [int(q) for q in out["sensitivity_params"]]}
+
     def kinetics_summary(self):
         """Per-step ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2`` of a run with the surface kinetics (the OHP is one point: w = 1)."""
         from .kinetics import current_summary
@@ -417,6 +475,8 @@ class EDLRun:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
             self.stepping.save(newpath, metadata_dict)
+        if self.polarisation_par is not None:   # last: the handle leaves the run's operating point
+            metadata_dict.update(self.polarisation_outputs(newpath))
         with open(newpath + "/metadata.json", "w") as fh:
             fh.write(json.dumps(metadata_dict, indent=0))
         return newpath
@@ -439,7 +499,7 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
               dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM",
               stern_length=4.0e-10, stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0,
-              p_eq_H2=0.0, target_current=None, impedance=None, **adaptive):
+              p_eq_H2=0.0, target_current=None, impedance=None, polarisation=None, **adaptive):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
     adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
     ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
@@ -455,6 +515,8 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
         stern.update(target_current=target_current)
     if impedance:   # (the impedance spectrum of ``EDLRun``, after the last step)
         stern.update(impedance=impedance)
+    if polarisation:   # (the polarisation curve of ``EDLRun``, after the last step)
+        stern.update(polarisation=polarisation)
     run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, **stern, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
@@ -489,6 +551,7 @@ def build_parser():
     add_kinetics_arguments(p)
     add_galvanostat_arguments(p)
     add_impedance_arguments(p)
+    add_polarisation_arguments(p)
     return p
 
 
@@ -498,7 +561,7 @@ def main(argv=None):
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
                      dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a),
-                     **impedance_keywords(a))
+                     **impedance_keywords(a), **polarisation_keywords(a))
 
 
 if __name__ == "__main__":

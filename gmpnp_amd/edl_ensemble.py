@@ -16,6 +16,7 @@ import itertools
 from . import backend
 from .edl1d import EDLRun, run_identifier
 from .impedance import refuse_impedance
+from .polarisation import refuse_polarisation
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .params import edl_parameters
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -43,6 +44,7 @@ def plan_members(members, num_steps=None):
     full = []
     for k, m in enumerate(members):
         refuse_impedance(m, "an ensemble (member %d)" % k)
+        refuse_polarisation(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

@@ -22,6 +22,7 @@ from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_argum
                       pop_galvanostat, pop_kinetics, pop_stern, pore_dirichlet, pore_problem, stern_keywords)
 from .solver import GMPNPSystem, column_medians, device_medians_and_minima
 from .timestep import DriverStepping, adaptive_keywords, add_adaptive_arguments
+from .polarisation import add_polarisation_arguments, polarisation_keywords
 from .vtk import write_pvd
 
 SOLVER_PARAMETERS = {  # reference 3D:789-798
@@ -89,11 +90,23 @@ class PoreRun:
         electrode potential at which the wall mean of i_CO + i_H2 is X; ``electrode_voltage`` is the starting guess.  The linear solver
         is the block-banded LU (a ``solver_parameters`` that names bicgstab is a ValueError); the first solve starts from the bulk state.  Works with ``step_fraction``, ``budget``
         and ``adaptive_dt`` at order 1; not with ``dt_order`` 2, ``partition`` or ``multilevel``.  Every step records
-        ``electrode_voltage``; the metadata gains ``target_current`` and reports the last potential found."""
+        ``electrode_voltage``; the metadata gains ``target_current`` and reports the last potential found.
+        ``polarisation`` = dict(v_end=X, v_step=Y[, params=(0, ...)]) (thermal voltages; with ``electrode_voltage``): ``write_outputs``
+        walks the steady-state polarisation curve from the run's last state and potential (``polarisation()``)
+        and adds ``polarisation.npz`` and the ``polarisation_*`` metadata keys.  Not with ``target_current``, ``dt_order`` 2,
+        ``partition`` or ``multilevel`` (ValueError, before anything touches the device)."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
         from .impedance import refuse_impedance
         refuse_impedance(kwargs, "the 3D pore driver (it needs a complex band LU)")
+        self.polarisation_par = kwargs.pop("polarisation", None) or None
+        if self.polarisation_par is not None:
+            from .polarisation import check_polarisation
+            if partition:
+                raise ValueError("polarisation: the curve is not available in a partitioned solve")
+            if multilevel:
+                raise ValueError("polarisation: the curve is not available with the geometric multilevel term")
+            self.polarisation_par = check_polarisation(self.polarisation_par, kwargs, dt_order)
         self.stern = pop_stern(kwargs, kwargs.get("L", 100.0e-9))
         self.kinetic_par = pop_kinetics(kwargs)
         self.target_current = pop_galvanostat(kwargs)
@@ -294,6 +307,65 @@ class PoreRun:
         return {"electrode_voltage": p_M, "stern_model": st.model, "stern_length": st.lam * pp.L, "stern_displacement": d,
                 "surface_charge": eps_0 * pp.thermal_voltage / pp.L * d / area}
 
+    def polarisation(self, v_end, v_step, params=(0,), predictor=True, solver_parameters=None):
+        """The steady-state polarisation curve from the run's LAST state and electrode potential to ``v_end`` on the grid
+        electrode_voltage + k ``v_step`` (gmpnp_amd/polarisation.py: ``run_continuation``, ``DeviceOps``), as ``EDLRun.polarisation``
+        walks it, with the block-banded LU.  At every point the Sechenov update of the CO2 Dirichlet value (as ``accept_solution``
+        forms it from the medians of the ion concentrations) and the Newton solve are repeated until the value changes by less than
+        1e-10 relative, for at most 10 rounds (recorded as ``sechenov_rounds``).  The tangent is taken at the final Dirichlet values:
+        the slopes (capacitance, dI/dV, Tafel slopes, sensitivities) do NOT include the feedback of the potential on the CO2 value.
+        Currents and charges are wall means (divided by ``wall_area``)."""
+        from types import SimpleNamespace
+        from . import polarisation as pol
+        from .params import _load_yaml
+        if self.stern is None:
+            raise ValueError("polarisation: the curve needs an electrode potential (electrode_voltage)")
+        if self.galvanostat is not None:
+            raise ValueError("polarisation: the curve is not available with target_current (the galvanostat)")
+        if self.glue != "host" or self._levels is not None or self.rank is not None:
+            raise ValueError("polarisation: the curve runs on one unpartitioned handle without the multilevel term (host glue)")
+        par = pol.check_polarisation(dict(v_end=v_end, v_step=v_step, params=params),
+                                     dict(electrode_voltage=self.stern.p_electrode, kinetics=self.kinetic_par))
+        sp = dict(solver_parameters or pol.NEWTON)
+        sp["newton_solver"] = dict(sp.get("newton_solver", {}), linear_solver="band_lu")
+        sp = backend.with_step_fraction(sp, self.step_fraction)
+        wall = np.unique(np.asarray(self.problem.wall_facets, dtype=np.int64))
+        nf = self.problem.nf
+
+        def after_solve():
+            new = self.pp.sechenov_co2_scaled(*column_medians(self.sys.vertex_values(), (1, 2, 3, 7)))
+            old, self.co2_bc = self.co2_bc, new
+            if old is not None and abs(new - old) <= 1e-10 * abs(new):
+                return False
+            self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, new, stern=True))
+            return True
+
+        ops = pol.DeviceOps(self, backend.newton_options(sp, dim=3), par["params"],
+                            lambda u: float(u.reshape(-1, nf)[wall, nf - 1].mean()), after_solve=after_solve)
+        inv_dt = float(self.sys.problem.model.inv_dt)
+        self.sys.set_time_step(0.0)
+        try:
+            records, substeps, newton, stop = pol.run_continuation(ops, self.stern.p_electrode, par["v_end"], par["v_step"], predictor)
+        finally:
+            self.sys.set_time_step(inv_dt)
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters_pore") + ".yaml"))["nat_const"]["eps_0"]
+        out = pol.curve_arrays(SimpleNamespace(thermal_voltage=self.pp.thermal_voltage, L_n=self.pp.L), eps_0, self.wall_area(), records,
+                               par["params"], substeps, newton)
+        out["stop_reason"] = stop
+        return out
+
+    def polarisation_outputs(self, newpath):
+        """``polarisation.npz`` of the curve from the last state and the metadata keys that go with it."""
+        out = self.polarisation(**self.polarisation_par)
+        stop = out.pop("stop_reason")
+        np.savez(os.path.join(newpath, "polarisation.npz"), **out)
+        return {"polarisation_points": int(len(out["electrode_voltage"])), "polarisation_v_end": float(self.polarisation_par["v_end"]),
+                "polarisation_v_step": float(self.polarisation_par["v_step"]), "polarisation_stop_reason": stop,
+                "polarisation_newton_iterations": int(out["newton_iterations"].sum()), "polarisation_substeps": int(out["substeps"].sum()),
+                "polarisation_worst_residual": float(np.max(out["tangent_residual"])),
+                "polarisation_params": [int(q) for q in out["sensitivity_params"]],
+                "polarisation_sechenov_rounds": int(out["sechenov_rounds"].max())}
+
     def wall_area(self):
         X = self.problem.coords[self.problem.wall_facets]
         return float((0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)).sum())
@@ -394,6 +466,8 @@ class PoreRun:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
             self.stepping.save(newpath, metadata_dict)
+        if self.polarisation_par is not None:   # last: the handle leaves the run's operating point
+            metadata_dict.update(self.polarisation_outputs(newpath))
         with open(newpath + "metadata.json", "w") as fh:
             fh.write(json.dumps(metadata_dict, indent=0))
         return newpath
@@ -404,7 +478,7 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
              constrictivity_eff=0.9, params_file="parameters_pore", y_CO2=0.95, electrolyte_flow_geom_multiplier=1.0,
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
              device_kwargs=None, glue="host", budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM", stern_length=4.0e-10,
-             stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0, p_eq_H2=0.0, target_current=None,
+             stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0, p_eq_H2=0.0, target_current=None, polarisation=None,
              **adaptive):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
@@ -422,6 +496,8 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
         stern.update(kinetics=kinetics, i0_CO=i0_CO, i0_H2=i0_H2, alpha_CO=alpha_CO, alpha_H2=alpha_H2, p_eq_CO=p_eq_CO, p_eq_H2=p_eq_H2)
     if target_current is not None:   # (the galvanostatic mode of ``PoreRun``)
         stern.update(target_current=target_current)
+    if polarisation:   # (the polarisation curve of ``PoreRun``, after the last step)
+        stern.update(polarisation=polarisation)
     run = PoreRun(**stern, num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
                   device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
@@ -463,6 +539,7 @@ def build_parser():
     add_adaptive_arguments(p)   # (not with --partitions)
     add_stern_arguments(p)      # (not with --partitions / --multilevel; --voltage_multiplier defaults to -1.0 without --electrode_voltage)
     add_kinetics_arguments(p)   # (with --electrode_voltage; not with --partitions / --multilevel)
+    add_polarisation_arguments(p)  # (with --electrode_voltage; not with --partitions / --multilevel / --target_current / --dt_order 2)
     add_galvanostat_arguments(p)   # (with --kinetics tafel; not with --partitions / --multilevel / --dt_order 2)
     return p
 
@@ -510,7 +587,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a), **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a), **polarisation_keywords(a), **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

@@ -17,6 +17,7 @@ from . import backend
 from .edl_ensemble import ADAPTIVE_REFUSAL, AdaptiveRounds, error_text
 from .pore3d import SOLVER_PARAMETERS, PoreRun
 from .impedance import refuse_impedance
+from .polarisation import refuse_polarisation
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import column_medians
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -40,6 +41,7 @@ def plan_members(members, num_steps=None):
     full = []
     for k, m in enumerate(members):
         refuse_impedance(m, "an ensemble (member %d)" % k)
+        refuse_polarisation(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

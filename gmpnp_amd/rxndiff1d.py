@@ -28,6 +28,7 @@ from .mesh import read_dolfin_xml, resolve_mesh_path
 from .model import Model
 from .params import _load_yaml, _reaction_tables, utilities_dir
 from .impedance import refuse_impedance
+from .polarisation import refuse_polarisation
 from .problem import edl_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem
 
@@ -141,6 +142,7 @@ class RxnDiffRun:
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history and the budget log as they were.  Off: nothing changes."""
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

@@ -26,6 +26,7 @@ from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
 from .impedance import refuse_impedance
+from .polarisation import refuse_polarisation
 from .problem import GALVANOSTAT_KEYWORDS, KINETICS_KEYWORDS, pore_dirichlet, pore_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem, column_medians
 from .vtk import write_pvd
@@ -62,6 +63,7 @@ class RxnPoreRun:
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history, the budget log and the CO2 Dirichlet value as they were.  Off: nothing changes."""
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")
@@ -210,7 +212,7 @@ def build_parser():
     p = pore_parser()  # same flags as the MPNP pore script ...
     for act in list(p._actions):
         if ({"--voltage_multiplier", "--as_published", "--electrode_voltage", "--stern_model", "--stern_length", "--stern_eps_surface"}
-                | {"--" + k for k in KINETICS_KEYWORDS + GALVANOSTAT_KEYWORDS}) & set(act.option_strings):
+                | {"--" + k for k in KINETICS_KEYWORDS + GALVANOSTAT_KEYWORDS} | {"--polarisation", "--v_end", "--v_step"}) & set(act.option_strings):
             p._remove_action(act)  # ... minus the voltage (reference :788-942 has none)
             for s in act.option_strings:
                 p._option_string_actions.pop(s, None)

@@ -56,8 +56,10 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
     if adaptive.get("adaptive_dt") and ramp_steps > 0:
         raise ValueError("--adaptive_dt: the voltage ramp (--ramp_steps) counts fixed steps")
     from .impedance import refuse_impedance
+    from .polarisation import refuse_polarisation
     from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
     refuse_impedance(adaptive, "the pore sweep")
+    refuse_polarisation(adaptive, "the pore sweep")
     refuse_galvanostat(adaptive, "the pore sweep")
     refuse_stern(adaptive, "the pore sweep")
     refuse_kinetics(adaptive, "the pore sweep")

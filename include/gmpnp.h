@@ -637,6 +637,54 @@ typedef struct {
 int gmpnp_frequency_response(gmpnp_solver* s, int32_t n, const double* sigma /* [n] */, gmpnp_response_t* out /* [n] */,
                              double* x_out /* [n][n_dofs][2] in file order, or NULL */);
 
+/* ---- electrode tangent (no reference counterpart: polarisation curves by continuation in the electrode potential) --------------------
+ * 1D and 3D handles with the Stern option on.  With p_M and the other electrode parameters theta_k as parameters of F(u; theta) = 0, the
+ * tangent z_k = du/dtheta_k at the handle's current u, p_M and model.inv_dt solves
+ *     J z_k = -c_k,   c_k = dF/dtheta_k
+ * (inv_dt = 0: the tangent of the steady state; otherwise the tangent of one implicit step with u_n frozen).  Parameter codes:
+ * 0 = p_M, 16 + r = ln k_r, 32 + r = alpha_r, 48 = ln lam (the Stern thickness).  The columns:
+ *     p_M     gmpnp_galvanostat_terms' b, bit for bit (Stern rows g / lam, kinetic rows -w_I sum_r nu[r][i] alpha_r rate_r)
+ *     ln k_r  +w_I nu[r][i] rate_r on the species rows            alpha_r  -w_I nu[r][i] rate_r (p_M - p_I - p_eq_r)
+ *     ln lam  minus the Stern term of the potential rows (3D: per facet, in list order)          every Dirichlet row: 0
+ * out[k] holds, for column k,
+ *     dD = dD/dtheta + (dD/du).z       explicit part: g / lam for p_M, -D for ln lam, 0 otherwise (D = gmpnp_stern_displacement)
+ *     dI_r = dI_r/dtheta + (dI_r/du).z explicit part: -alpha_r I_r for p_M, delta_rs I_r for ln k_s, -sum_I w_I rate_r (p_M - p_I - p_eq_r)
+ *                                      for alpha_r, 0 for ln lam (I_r = gmpnp_kinetics_currents; 0 with the kinetics off)
+ *     dp_boundary                      the w-weighted mean of z's potential entry over the Stern nodes
+ *     residual                         max |J z + c| / max |c|
+ *     status                           a word of that column alone: bit 1 = a value that is not finite
+ * and z_out, where given, receives the tangents in file order.  F and J are assembled as the first iteration of gmpnp_newton_solve
+ * assembles them; afterwards u, u_n, p_M and the model are untouched, F and J are those of the current u as after
+ * gmpnp_assemble(want_jacobian = 1), and a following gmpnp_newton_solve gives the bits of a handle that never made the call.  3D: one
+ * block-banded LU factorisation and n substitutions, each refined as the galvanostat's second column is, under band_lu_max_gb.  1D: the n
+ * systems are solved by ONE block cyclic reduction of J that carries several right-hand sides (two or eight per chain): column k has
+ * the bits of gmpnp_linear_solve(-c_k, GMPNP_LINEAR_BLOCK_TRIDIAGONAL), they do not depend on which other columns were asked for,
+ * and two calls give equal bits.  eps <= 0 on the Stern boundary or a rate that is not finite at the state: GMPNP_ERR_NUMERIC.
+ * gmpnp_tangent_columns: parity hook; the columns c_k of the last call, c_out[n][n_dofs] in file order.
+ * gmpnp_electrode_advance is the predictor of a continuation in p_M: it needs a tangent whose p_M column was computed at the present
+ * u, p_M and options (any call that changes one of them, a Newton solve included, invalidates it and the advance is refused), adds dp
+ * to p_electrode of the Stern option and of the kinetic option, and sets u += alpha dp z_0 in one launch, compiled without fused
+ * multiply-add (u + (alpha dp) z in IEEE double).  tau = 0: alpha = 1; otherwise alpha is the fraction-to-boundary factor of
+ * gmpnp_step_limit for the direction -dp z_0, so that the state guess is damped while the potential takes the whole dp.  It marks the
+ * Jacobian and the preconditioner invalid.
+ * Refused (GMPNP_ERR_INVALID, the message names the electrode tangent): partition handles, a coarse level attached or
+ * serving as one, SUPG terms set, the Stern option off, the galvanostat on, Stern and kinetic options with different p_electrode, a
+ * kinetic parameter with the kinetics off or with r >= n_reactions, n outside 1 ... 10, a repeated or unknown parameter, a 1D handle
+ * whose mesh does not serve the block-tridiagonal solver. */
+#define GMPNP_TANGENT_MAX_COLUMNS 10
+typedef struct {
+  int32_t param;
+  double dD;
+  double dI[GMPNP_MAX_SURFACE_REACTIONS];
+  double dp_boundary;
+  double residual;
+  int32_t status;                                /* 0, or bit 1 */
+} gmpnp_tangent_t;
+int gmpnp_electrode_tangent(gmpnp_solver* s, int32_t n, const int32_t* param /* [n] */, gmpnp_tangent_t* out /* [n] */,
+                            double* z_out /* [n][n_dofs] in file order, or NULL */);
+int gmpnp_tangent_columns(gmpnp_solver* s, double* c_out /* [n][n_dofs] in file order */);
+int gmpnp_electrode_advance(gmpnp_solver* s, double dp, double tau, double* alpha_out /* or NULL */);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -710,7 +758,9 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * the launches keep adding to), 26 = the galvanostat's launches of one Newton iteration apart from the two linear solves (k_galv_rhs,
  * k_galv_reduce, k_galv_direction, k_galv_potential on a zero step, k_galv_reduce for G alone; needs gmpnp_set_galvanostat with on != 0
  * and an assembled Jacobian; the state and p_M stay), 27 = the two launches of one chunk of the frequency response (k_response_solve +
- * k_response_functional on the frequencies of the last chunk of the last gmpnp_frequency_response call, which it needs). */
+ * k_response_functional on the frequencies of the last chunk of the last gmpnp_frequency_response call, which it needs), 28 = the
+ * multi-column cyclic-reduction chain(s) of the last gmpnp_electrode_tangent call with extraction and application (needs such a call
+ * and the Jacobian it left). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
