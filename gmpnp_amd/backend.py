@@ -46,6 +46,7 @@ EXPORTS = [
     "gmpnp_set_galvanostat", "gmpnp_galvanostat_report", "gmpnp_galvanostat_terms",
     "gmpnp_frequency_response",
     "gmpnp_electrode_tangent", "gmpnp_tangent_columns", "gmpnp_electrode_advance",
+    "gmpnp_parameter_advance", "gmpnp_get_electrode_options",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -294,6 +295,8 @@ def load_library(path: str = None):
     lib.gmpnp_electrode_tangent.argtypes = [c_void_p, c_int32, POINTER(c_int32), POINTER(CTangent), POINTER(c_double)]
     lib.gmpnp_tangent_columns.argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_electrode_advance.argtypes = [c_void_p, c_double, c_double, POINTER(c_double)]
+    lib.gmpnp_parameter_advance.argtypes = [c_void_p, c_int32, POINTER(c_int32), POINTER(c_double), c_double, POINTER(c_double)]
+    lib.gmpnp_get_electrode_options.argtypes = [c_void_p, POINTER(CStern), POINTER(CKinetics)]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -729,6 +732,37 @@ class DeviceSolver:
         alpha = c_double()
         self._check(self.lib.gmpnp_electrode_advance(self._h, float(dp), float(tau), byref(alpha)))
         return float(alpha.value)
+
+    def parameter_advance(self, params, dtheta, tau=0.0) -> float:
+        """``gmpnp_parameter_advance``: the parameters ``params`` (codes of the last ``electrode_tangent`` call) move by ``dtheta`` in
+        the Stern and kinetic options, u += alpha sum_k dtheta_k z_k.  Returns alpha (1 with ``tau`` = 0)."""
+        pr = np.ascontiguousarray(params, dtype=np.int32).ravel()
+        dt = np.ascontiguousarray(dtheta, dtype=np.float64).ravel()
+        if pr.size != dt.size:
+            raise ValueError("parameter advance: %d parameters and %d steps" % (pr.size, dt.size))
+        alpha = c_double()
+        self._check(self.lib.gmpnp_parameter_advance(self._h, int(pr.size), _iptr(pr), _dptr(dt), float(tau), byref(alpha)))
+        return float(alpha.value)
+
+    def electrode_options(self):
+        """``gmpnp_get_electrode_options``: (stern, kinetics) as the handle holds them now, each a dict of the fields of
+        ``problem.SternLayer`` / ``problem.SurfaceKinetics`` (reactions as dicts of ``problem.SurfaceReaction``'s fields, species by
+        name), or None while the option is off."""
+        cs, ck = CStern(), CKinetics()
+        self._check(self.lib.gmpnp_get_electrode_options(self._h, byref(cs), byref(ck)))
+        stern = kinetics = None
+        if cs.model != 0:
+            model = {v: k for k, v in STERN_MODELS.items()}[int(cs.model)]
+            stern = {"model": model, "p_electrode": float(cs.p_electrode), "lam": float(cs.lam), "eps_surface": float(cs.eps_surface)}
+        if ck.n_reactions != 0:
+            species = list(self.problem.model.species)
+            reactions = []
+            for r in range(int(ck.n_reactions)):
+                nu = {name: float(ck.nu[r][i]) for i, name in enumerate(species) if ck.nu[r][i] != 0.0}
+                reactions.append({"k": float(ck.k[r]), "alpha": float(ck.alpha[r]), "p_eq": float(ck.p_eq[r]),
+                                  "reactant": None if ck.reactant[r] < 0 else species[ck.reactant[r]], "nu": nu})
+            kinetics = {"reactions": reactions, "p_electrode": float(ck.p_electrode)}
+        return stern, kinetics
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

@@ -186,6 +186,8 @@ struct gmpnp_tangenter {
   int last_n = 0;                      // columns of the last call (gmpnp_time_kernel 28, gmpnp_tangent_columns)
   int col_pM = -1;                     // where the p_M column of the last call sits
   bool fresh = false;                  // z[col_pM] belongs to the present u, p_M and options: gmpnp_electrode_advance may use it
+  bool cols_fresh = false;             // every z of the last call does: gmpnp_parameter_advance may use the columns whose status is 0
+  int32_t param[GMPNP_TANGENT_MAX_COLUMNS] = {}, col_status[GMPNP_TANGENT_MAX_COLUMNS] = {};   // the last call's parameters and the status words of their columns
   ~gmpnp_tangenter() { if (h_out) (void)hipHostFree(h_out); }
 };
 
@@ -336,7 +338,7 @@ int response_time_chunk(gmpnp_solver* s);
 // option drops the tangent the advance would use
 bool tangent_has_chain(const gmpnp_solver* s);
 int tangent_time_chain(gmpnp_solver* s);
-inline void tangent_drop(gmpnp_solver* s) { if (s->tangenter) s->tangenter->fresh = false; }
+inline void tangent_drop(gmpnp_solver* s) { if (s->tangenter) { s->tangenter->fresh = false; s->tangenter->cols_fresh = false; } }
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.

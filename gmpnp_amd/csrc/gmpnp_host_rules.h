@@ -217,6 +217,40 @@ GMPNP_RULE_HD inline double tangent_current_term(double w, double d_u, double d_
   GMPNP_RULE_NO_CONTRACT
   return w * ((d_u * z_u + d_p * z_p) + explicit_part);
 }
+// gmpnp_parameter_advance: how the options move along a step dtheta in the parameters of `param` (the state takes alpha of the step,
+// the parameters the whole of it).  p_M: p_electrode += dtheta in both options; ln k_r: k_r *= exp(dtheta); alpha_r += dtheta; ln lam:
+// lam *= exp(dtheta).  The moved options are validated by the setters' own rules BEFORE anything is changed: `stern` and `kinetics` are
+// the caller's copies, and false leaves the handle as it was.  n_reactions = 0: the kinetics are off (a kinetic parameter is then
+// refused by parameter_advance_refusal).  gmpnp_amd/fit.py's moved_options is its Python statement.
+inline bool parameter_move(gmpnp_stern_t& stern, gmpnp_kinetics_t& kinetics, int n_species, int n, const int32_t* param, const double* dtheta) {
+  for (int k = 0; k < n; ++k) {
+    const int kind = tangent_param_kind(param[k]), r = tangent_param_reaction(param[k]);
+    if (kind == 0) stern.p_electrode += dtheta[k];
+    else if (kind == 1) kinetics.k[r] *= std::exp(dtheta[k]);
+    else if (kind == 2) kinetics.alpha[r] += dtheta[k];
+    else if (kind == 3) stern.lam *= std::exp(dtheta[k]);
+    else return false;
+  }
+  if (kinetics.n_reactions != 0) kinetics.p_electrode = stern.p_electrode;
+  return stern_options_valid(stern) && (kinetics.n_reactions == 0 || kinetics_options_valid(kinetics, n_species));
+}
+// the arguments of gmpnp_parameter_advance against the parameters of the last tangent call (last[n_last], status 0 = computed):
+// nullptr = fine, otherwise what is wrong
+inline const char* parameter_advance_refusal(int n, const int32_t* param, const double* dtheta, double tau, int n_last, const int32_t* last,
+                                             const int32_t* last_status) {
+  if (!tangent_count_valid(n)) return "n must lie in 1 ... 10";
+  for (int k = 0; k < n; ++k) {
+    for (int q = 0; q < k; ++q)
+      if (param[q] == param[k]) return "a parameter is repeated";
+    int at = -1;
+    for (int q = 0; q < n_last; ++q) at = (last[q] == param[k]) ? q : at;
+    if (at < 0) return "a parameter is not among those of the last gmpnp_electrode_tangent call";
+    if (last_status[at] != 0) return "a requested column of the last gmpnp_electrode_tangent call is not finite";
+    if (!rule_finite(dtheta[k])) return "every dtheta must be finite";
+  }
+  if (!(tau == 0.0 || (tau > 0.0 && tau < 1.0))) return "tau must be 0 (no damping) or lie in (0, 1)";
+  return nullptr;
+}
 // The continuation rule of a polarisation curve.  Targets are the grid v_start + k v_step up to v_end, which is landed on exactly; an
 // attempt goes from the last converged point `at` towards the next target with step `dp`; a failed attempt halves the step, a success
 // tries the whole remainder to the target again; a step below |v_step| / 1024 ends the curve (stop = 1, "dp_min").

@@ -1,4 +1,5 @@
-// Electrode tangent on the device: gmpnp_electrode_tangent / gmpnp_electrode_advance / gmpnp_tangent_columns (include/gmpnp.h), rule in
+// Electrode tangent on the device: gmpnp_electrode_tangent / gmpnp_electrode_advance / gmpnp_parameter_advance / gmpnp_tangent_columns /
+// gmpnp_get_electrode_options (include/gmpnp.h), rule in
 // gmpnp_host_rules.h (tangent_param_kind, tangent_rate_explicit, tangent_stern_explicit, tangent_current_term).
 //
 // At the handle's current u, p_M and model.inv_dt, for up to ten parameters theta_k (p_M, ln k_r, alpha_r, ln lam):
@@ -20,6 +21,8 @@
 //                     weighted mean of z's potential entry from the boundary nodes (block_sum, fixed order), the column's status word.
 //   k_tan_scale / k_step_limit / k_tan_advance     gmpnp_electrode_advance: u += alpha dp z_0 without FMA contraction; with tau != 0 the
 //                     step limiter's partials of the direction -dp z_0 come first and every workgroup re-reduces them to alpha.
+//   k_par_advance     gmpnp_parameter_advance: the same in several columns at once (pointers and coefficients by value), both passes: the
+//                     direction -(dtheta_0 z_0 + ...) for the step limiter, and u += (alpha dtheta_0) z_0 + ... with k_tan_advance's reduction.
 // Every sum is a gather in a fixed order (no floating-point atomics): two calls on one state give equal bits.  The reactant's entry and
 // the rate of a column's reaction are picked by selects out of unrolled loops, not by indexing a register array.
 // Included at the end of gmpnp_api.hip.
@@ -421,11 +424,63 @@ __global__ __launch_bounds__(kVecBlock) void k_tan_advance(double* __restrict__ 
   if (i < n) u[i] = u[i] + (alpha * dp) * z[i];
 }
 
+// gmpnp_parameter_advance: the columns of a step in several parameters and their coefficients, by value
+struct ParCols {
+  int32_t n, pad_;
+  const double* z[kTangentMaxColumns];
+  double dtheta[kTangentMaxColumns];
+};
+
+// Both passes of gmpnp_parameter_advance, sums left to right in the order of `pc`, every product and sum rounded on its own:
+//   dx != nullptr   dx = -(dtheta_0 z_0 + dtheta_1 z_1 + ...): the direction the step limiter looks at
+//   dx == nullptr   u += (alpha dtheta_0) z_0 + (alpha dtheta_1) z_1 + ...; alpha as k_tan_advance finds it (part != nullptr: every
+//                   workgroup re-reduces the step limiter's partials; a NaN / Inf in the direction: nothing is applied, alpha = NaN)
+// One column is k_tan_scale's and k_tan_advance's expression.
+__global__ __launch_bounds__(kVecBlock) void k_par_advance(double* __restrict__ u, double* __restrict__ dx, const ParCols pc, double tau,
+                                                           const double* __restrict__ part, const int32_t* __restrict__ part_node, int nblk,
+                                                           double* __restrict__ alpha_out, int n) {
+  GMPNP_RULE_NO_CONTRACT
+  __shared__ double s_lam;
+  __shared__ int s_bad;
+  const int i = blockIdx.x * kVecBlock + threadIdx.x;
+  if (dx) {
+    if (i >= n) return;
+    double d = pc.dtheta[0] * pc.z[0][i];
+    for (int k = 1; k < pc.n; ++k) d = d + pc.dtheta[k] * pc.z[k][i];
+    dx[i] = -d;
+    return;
+  }
+  double alpha = 1.0;
+  int bad = 0;
+  if (part) {
+    if (threadIdx.x < kWave) {
+      double lam = INFINITY; int node = -1, b = 0;
+      for (int q = threadIdx.x; q < nblk; q += kWave) {
+        const double v = part[q];
+        const int nd = part_node[q];
+        if (nd == kStepBad) b = 1;
+        else if (v < lam) { lam = v; node = nd; }
+      }
+      wave_min_index(lam, node);
+      const int any_bad = __ballot(b) != 0 ? 1 : 0;
+      if (threadIdx.x == 0) { s_lam = lam; s_bad = any_bad; }
+    }
+    __syncthreads();
+    alpha = s_lam < 1.0 ? tau * s_lam : 1.0;
+    bad = s_bad;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = bad ? NAN : alpha;
+  if (bad || i >= n) return;
+  double d = (alpha * pc.dtheta[0]) * pc.z[0][i];
+  for (int k = 1; k < pc.n; ++k) d = d + (alpha * pc.dtheta[k]) * pc.z[k][i];
+  u[i] = u[i] + d;
+}
+
 }  // namespace gmpnp
 
 namespace {
 
-constexpr int kTanChainMax = 8;   // columns of the widest chain
+constexpr int kTanChainMax = 8;  // columns of the widest chain
 
 // the tangent's right-hand-side levels (the storage holds kTanChainMax columns per level; a chain of M columns uses the first M)
 std::vector<TriCols> tangent_levels(gmpnp_solver* s) {
@@ -555,7 +610,7 @@ int gmpnp_electrode_tangent(gmpnp_solver* s, int32_t n, const int32_t* param, gm
     s->tangenter = std::move(T);
   }
   gmpnp_tangenter* T = s->tangenter.get();
-  T->fresh = false; T->last_n = 0;
+  T->fresh = false; T->cols_fresh = false; T->last_n = 0;
   // F and J at the current u, as the first iteration of gmpnp_newton_solve assembles them
   HIP_TRY(hipMemsetAsync(s->status.p, 0, sizeof(int32_t), s->stream));
   HIP_TRY(hipMemsetAsync(T->status.p, 0, sizeof(int32_t), s->stream));
@@ -610,6 +665,8 @@ int gmpnp_electrode_tangent(gmpnp_solver* s, int32_t n, const int32_t* param, gm
   if (z_out)
     for (int k = 0; k < n; ++k) { rc = download_vec(s, T->z.p + (size_t)k * ndof, z_out + (size_t)k * ndof); if (rc) return rc; }
   if (col_pM >= 0 && out[col_pM].status == 0) { T->fresh = true; T->col_pM = col_pM; }
+  for (int k = 0; k < n; ++k) { T->param[k] = param[k]; T->col_status[k] = out[k].status; }
+  T->cols_fresh = true;
   return GMPNP_OK;
 }
 
@@ -648,7 +705,7 @@ int gmpnp_electrode_advance(gmpnp_solver* s, double dp, double tau, double* alph
   HIP_TRY(hipMemcpyAsync(s->h_stage, T->alpha.p, sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   alpha = s->h_stage[0];
-  T->fresh = false;
+  tangent_drop(s);
   if (!(alpha == alpha)) return fail(GMPNP_ERR_NUMERIC, "electrode tangent: " + status_message(16));
   // the potential takes the whole dp
   s->sterner->opt.p_electrode += dp;
@@ -659,6 +716,82 @@ int gmpnp_electrode_advance(gmpnp_solver* s, double dp, double tau, double* alph
   s->state_jumped = true;
   s->jacobian_valid = false; s->precond_valid = false;
   if (alpha_out) *alpha_out = alpha;
+  return GMPNP_OK;
+}
+
+int gmpnp_parameter_advance(gmpnp_solver* s, int32_t n, const int32_t* param, const double* dtheta, double tau, double* alpha_out) {
+  if (!s || !param || !dtheta) return fail(GMPNP_ERR_INVALID, "parameter advance: NULL argument");
+  if (const char* why = tangent_refusal(s)) return fail(GMPNP_ERR_INVALID, std::string("parameter advance: ") + why);
+  gmpnp_tangenter* T = s->tangenter.get();
+  if (!T || !T->cols_fresh)
+    return fail(GMPNP_ERR_INVALID, "parameter advance: it needs a tangent computed at the present state, potential and options (gmpnp_electrode_tangent)");
+  if (const char* why = parameter_advance_refusal(n, param, dtheta, tau, T->last_n, T->param, T->col_status))
+    return fail(GMPNP_ERR_INVALID, std::string("parameter advance: ") + why);
+  // the moved options, validated before anything is changed
+  const bool kin = kinetics_on(s);
+  gmpnp_stern_t stern = s->sterner->opt;
+  gmpnp_kinetics_t kinetics{};
+  if (kin) kinetics = s->kineticist->opt;
+  if (!parameter_move(stern, kinetics, s->nf - 1, n, param, dtheta))
+    return fail(GMPNP_ERR_INVALID, "parameter advance: the moved parameters are not valid options (a finite p_electrode, k and alpha, lam > 0)");
+  HIP_TRY(hipSetDevice(s->opts.device_id));
+  const int ndof = (int)s->ndof;
+  ParCols pc{};
+  pc.n = n;
+  for (int k = 0; k < n; ++k) {
+    int at = 0;
+    for (int q = 0; q < T->last_n; ++q) at = (T->param[q] == param[k]) ? q : at;
+    pc.z[k] = T->z.p + (size_t)at * s->ndof;
+    pc.dtheta[k] = dtheta[k];
+  }
+  const double* part = nullptr; const int32_t* part_node = nullptr; int nblk = 0;
+  if (tau != 0.0) {
+    int rc = step_prepare(s); if (rc) return rc;
+    gmpnp_step_limiter* L = s->limiter.get();
+    hipLaunchKernelGGL(k_par_advance, dim3(grid_for(ndof, kVecBlock)), dim3(kVecBlock), 0, s->stream, (double*)nullptr, L->dx.p, pc, tau, part, part_node, 0,
+                       (double*)nullptr, ndof);
+    GMPNP_DISPATCH(s, hipLaunchKernelGGL((k_step_limit<NF>), dim3(L->nblk), dim3(kVecBlock), 0, s->stream, step_limit_io(s, L->dx.p)));
+    part = L->part.p; part_node = L->part_node.p; nblk = L->nblk;
+  }
+  hipLaunchKernelGGL(k_par_advance, dim3(grid_for(ndof, kVecBlock)), dim3(kVecBlock), 0, s->stream, s->u.p, (double*)nullptr, pc, tau, part, part_node, nblk,
+                     T->alpha.p, ndof);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(s->h_stage, T->alpha.p, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  const double alpha = s->h_stage[0];
+  tangent_drop(s);
+  if (!(alpha == alpha)) return fail(GMPNP_ERR_NUMERIC, "parameter advance: " + status_message(16));
+  // the parameters take the whole step
+  s->sterner->opt = stern;
+  if (kin) {
+    s->kineticist->opt = kinetics;
+    HIP_TRY(hipMemcpy(s->kineticist->d_opt.p, &s->kineticist->opt, sizeof(gmpnp_kinetics_t), hipMemcpyHostToDevice));
+  }
+  s->state_jumped = true;
+  s->jacobian_valid = false; s->precond_valid = false;
+  if (alpha_out) *alpha_out = alpha;
+  return GMPNP_OK;
+}
+
+int gmpnp_get_electrode_options(gmpnp_solver* s, gmpnp_stern_t* stern_out, gmpnp_kinetics_t* kinetics_out) {
+  if (!s) return fail(GMPNP_ERR_INVALID, "electrode options: NULL handle");
+  double p_M = 0.0;
+  const bool galv = galvanostat_on(s);
+  if (galv) {   // the galvanostat holds p_M on the device
+    HIP_TRY(hipSetDevice(s->opts.device_id));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(&p_M, s->galvanostat->scal.p, sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (stern_out) {
+    gmpnp_stern_t o{};
+    if (stern_on(s)) { o = s->sterner->opt; if (galv) o.p_electrode = p_M; }
+    *stern_out = o;
+  }
+  if (kinetics_out) {
+    gmpnp_kinetics_t o{};
+    if (kinetics_on(s)) { o = s->kineticist->opt; if (galv) o.p_electrode = p_M; }
+    *kinetics_out = o;
+  }
   return GMPNP_OK;
 }
 

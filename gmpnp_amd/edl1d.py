@@ -26,6 +26,7 @@ import numpy as np
 from . import backend
 from .impedance import add_impedance_arguments, impedance_keywords
 from .polarisation import add_polarisation_arguments, polarisation_keywords
+from .fit import add_fit_arguments, fit_keywords
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import _load_yaml, edl_parameters, utilities_dir
 from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_arguments, add_stern_arguments, edl_problem, galvanostat_keywords, kinetics_keywords,
@@ -97,7 +98,16 @@ class EDLRun:
         ``polarisation_newton_iterations``, ``polarisation_substeps``, ``polarisation_worst_residual`` and ``polarisation_params``.
         Not with ``target_current``, ``stabilization`` "Y", ``H_OHP`` or ``dt_order`` 2 (ValueError, before anything touches the
         device).  The run should have reached its steady state (``adaptive_dt`` with ``steady_tol``): the first point is one Newton
-        solve at inv_dt = 0 from the last state."""
+        solve at inv_dt = 0 from the last state.
+        ``fit`` = dict(data=path[, params=("i0_CO", "i0_H2", "alpha_CO", "alpha_H2")]) (with ``kinetics``): ``write_outputs`` fits the named
+        electrode parameters (also ``stern_length``) to the polarisation data of the file (DESIGN.md section 5m, gmpnp_amd/fit.py;
+        ``fit()`` does the same at any time), after the impedance and before the polarisation curve, which is then the fitted one;
+        it adds ``fit.npz`` and the metadata keys ``fit_*``.  Afterwards the run stands at ``electrode_voltage`` with the fitted
+        parameters at the steady state there.  Refused as ``polarisation`` is, and without ``kinetics``."""
+        self.fit_par = kwargs.pop("fit", None) or None
+        if self.fit_par is not None:
+            from .fit import check_fit
+            self.fit_par = check_fit(self.fit_par, kwargs, dt_order)
         self.polarisation_par = kwargs.pop("polarisation", None) or None
         if self.polarisation_par is not None:
             from .polarisation import check_polarisation
@@ -395,6 +405,52 @@ class EDLRun:
                 "polarisation_worst_residual": float(np.max(out["tangent_residual"])),
                 "polarisation_params": [int(q) for q in out["sensitivity_params"]]}
 
+    def fit(self, data, params=None, predictor=True):
+        """Fits the electrode parameters ``params`` (names of ``fit.PARAMETERS``; default the four kinetic ones) to the polarisation
+        data ``data`` (a path, or a dict of the columns) by Levenberg-Marquardt on the log currents (and the surface charge, where
+        given) with the tangent's exact sensitivities (gmpnp_amd/fit.py: ``LevenbergMarquardt`` over ``DeviceCurve``).  Afterwards
+        the run and the handle stand at ``electrode_voltage`` with the FITTED parameters (``kinetics``, ``stern`` and the problem's
+        records replaced) at the steady state there, with the run's own inv_dt put back.  Returns the arrays of ``fit.npz`` plus
+        ``metadata`` (the ``fit_*`` keys) and ``result`` (``LevenbergMarquardt.run``'s)."""
+        from . import fit as ft
+        if self.stern is None or self.kinetics is None:
+            raise ValueError("fit: the fit needs an electrode potential and the surface kinetics (electrode_voltage, kinetics='tafel')")
+        if self.galvanostat is not None:
+            raise ValueError("fit: the fit is not available with target_current (the galvanostat)")
+        if self.supg:
+            raise ValueError("fit: the fit is not available with stabilization Y")
+        names = tuple(params or ft.DEFAULT_PARAMS)
+        codes = ft.param_codes(names)
+        V0 = float(self.stern.p_electrode)
+        table = ft.check_data(ft.load_data(data) if not isinstance(data, dict) else data, V0, len(codes))
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
+        curve = ft.DeviceCurve(self, table, codes, eps_0 * self.ep.thermal_voltage / self.ep.L_n, predictor=predictor)
+        inv_dt = float(self.sys.problem.model.inv_dt)
+        try:
+            curve.prepare()
+            theta0 = ft.theta_of(curve.kept["stern"], curve.kept["kinetics"], codes)
+            res = ft.LevenbergMarquardt(curve, [ft.is_log(c) for c in codes]).run(theta0)
+            res["theta"] = ft.theta_of(curve.kept["stern"], curve.kept["kinetics"], codes)   # the numbers the handle holds
+            curve.finish(V0, inv_dt)
+        except BaseException:
+            self.sys.set_time_step(inv_dt)
+            raise
+        self.stern, self.kinetics = ft.records_of(curve.kept["stern"], curve.kept["kinetics"], V0)
+        self.problem.stern, self.problem.kinetics = self.stern, self.kinetics
+        rx = self.kinetics.reactions
+        self.kinetic_par = dict(self.kinetic_par, i0_CO=rx[0].k, i0_H2=rx[1].k, alpha_CO=rx[0].alpha, alpha_H2=rx[1].alpha)
+        out = ft.fit_arrays(names, codes, table, theta0, res, [p[0] for p in curve.kept["points"]], self.ep.L_n)
+        out["metadata"], out["result"] = ft.fit_metadata(names, out, res), res
+        return out
+
+    def fit_outputs(self, newpath):
+        """``fit.npz`` and the metadata keys that go with it (see ``__init__``)."""
+        out = self.fit(**self.fit_par)
+        meta = out.pop("metadata")
+        out.pop("result")
+        np.savez(newpath + "/fit.npz", **out)
+        return meta
+
     def kinetics_summary(self):
         """Per-step ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2`` of a run with the surface kinetics (the OHP is one point: w = 1)."""
         from .kinetics import current_summary
@@ -475,6 +531,8 @@ class EDLRun:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
             self.stepping.save(newpath, metadata_dict)
+        if self.fit_par is not None:   # before the curve, which is then the fitted one; the handle ends at the run's operating point
+            metadata_dict.update(self.fit_outputs(newpath))
         if self.polarisation_par is not None:   # last: the handle leaves the run's operating point
             metadata_dict.update(self.polarisation_outputs(newpath))
         with open(newpath + "/metadata.json", "w") as fh:
@@ -499,7 +557,7 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
               dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM",
               stern_length=4.0e-10, stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0,
-              p_eq_H2=0.0, target_current=None, impedance=None, polarisation=None, **adaptive):
+              p_eq_H2=0.0, target_current=None, impedance=None, polarisation=None, fit=None, **adaptive):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
     adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
     ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
@@ -517,6 +575,8 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
         stern.update(impedance=impedance)
     if polarisation:   # (the polarisation curve of ``EDLRun``, after the last step)
         stern.update(polarisation=polarisation)
+    if fit:   # (the fit of the electrode kinetics of ``EDLRun``, after the last step and before the curve)
+        stern.update(fit=fit)
     run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, **stern, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
@@ -552,6 +612,7 @@ def build_parser():
     add_galvanostat_arguments(p)
     add_impedance_arguments(p)
     add_polarisation_arguments(p)
+    add_fit_arguments(p)
     return p
 
 
@@ -561,7 +622,7 @@ def main(argv=None):
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
                      dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a),
-                     **impedance_keywords(a), **polarisation_keywords(a))
+                     **impedance_keywords(a), **polarisation_keywords(a), **fit_keywords(a))
 
 
 if __name__ == "__main__":

@@ -17,6 +17,7 @@ from . import backend
 from .edl1d import EDLRun, run_identifier
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
+from .fit import refuse_fit
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .params import edl_parameters
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -45,6 +46,7 @@ def plan_members(members, num_steps=None):
     for k, m in enumerate(members):
         refuse_impedance(m, "an ensemble (member %d)" % k)
         refuse_polarisation(m, "an ensemble (member %d)" % k)
+        refuse_fit(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

@@ -99,6 +99,8 @@ class PoreRun:
             raise ValueError("glue must be 'host' or 'device'")
         from .impedance import refuse_impedance
         refuse_impedance(kwargs, "the 3D pore driver (it needs a complex band LU)")
+        from .fit import refuse_fit
+        refuse_fit(kwargs, "the 3D pore driver (the library's parameter advance works there, the fit's host glue is 1D)")
         self.polarisation_par = kwargs.pop("polarisation", None) or None
         if self.polarisation_par is not None:
             from .polarisation import check_polarisation

@@ -18,6 +18,7 @@ from .edl_ensemble import ADAPTIVE_REFUSAL, AdaptiveRounds, error_text
 from .pore3d import SOLVER_PARAMETERS, PoreRun
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
+from .fit import refuse_fit
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import column_medians
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -42,6 +43,7 @@ def plan_members(members, num_steps=None):
     for k, m in enumerate(members):
         refuse_impedance(m, "an ensemble (member %d)" % k)
         refuse_polarisation(m, "an ensemble (member %d)" % k)
+        refuse_fit(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

@@ -29,6 +29,7 @@ from .model import Model
 from .params import _load_yaml, _reaction_tables, utilities_dir
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
+from .fit import refuse_fit
 from .problem import edl_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem
 
@@ -143,6 +144,7 @@ class RxnDiffRun:
         leaves the clock, the history and the budget log as they were.  Off: nothing changes."""
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

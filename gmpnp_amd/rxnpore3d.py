@@ -27,6 +27,7 @@ from .params import pore_parameters, utilities_dir
 from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
+from .fit import refuse_fit
 from .problem import GALVANOSTAT_KEYWORDS, KINETICS_KEYWORDS, pore_dirichlet, pore_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem, column_medians
 from .vtk import write_pvd
@@ -64,6 +65,7 @@ class RxnPoreRun:
         leaves the clock, the history, the budget log and the CO2 Dirichlet value as they were.  Off: nothing changes."""
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

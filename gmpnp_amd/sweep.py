@@ -57,9 +57,11 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
         raise ValueError("--adaptive_dt: the voltage ramp (--ramp_steps) counts fixed steps")
     from .impedance import refuse_impedance
     from .polarisation import refuse_polarisation
+    from .fit import refuse_fit
     from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
     refuse_impedance(adaptive, "the pore sweep")
     refuse_polarisation(adaptive, "the pore sweep")
+    refuse_fit(adaptive, "the pore sweep")
     refuse_galvanostat(adaptive, "the pore sweep")
     refuse_stern(adaptive, "the pore sweep")
     refuse_kinetics(adaptive, "the pore sweep")

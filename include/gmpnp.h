@@ -685,6 +685,29 @@ int gmpnp_electrode_tangent(gmpnp_solver* s, int32_t n, const int32_t* param /* 
 int gmpnp_tangent_columns(gmpnp_solver* s, double* c_out /* [n][n_dofs] in file order */);
 int gmpnp_electrode_advance(gmpnp_solver* s, double dp, double tau, double* alpha_out /* or NULL */);
 
+/* ---- parameter advance (no reference counterpart: the predictor of a fit of the electrode parameters to polarisation data) -----------
+ * gmpnp_parameter_advance moves a 1D or 3D handle along several of the tangent's columns at once.  It needs a tangent computed at the
+ * present u, p_M and options (whatever invalidates gmpnp_electrode_advance's tangent invalidates this one), every param[k] among the
+ * parameters of that gmpnp_electrode_tangent call, its column's status 0.  A tangent call without a p_M column permits it in the columns
+ * it did compute (gmpnp_electrode_advance stays refused after such a call).  Without fused multiply-add, every product and sum rounded
+ * on its own, sums left to right in the order of THIS call's param:
+ *     d = dtheta_0 z_0 + dtheta_1 z_1 + ...
+ *     alpha = 1 (tau = 0), otherwise gmpnp_step_limit's factor for the direction -d
+ *     u += (alpha dtheta_0) z_0 + (alpha dtheta_1) z_1 + ...
+ * in one launch (tau = 0) or three (the direction, the limiter's partials, the update) and one host synchronisation; n = 1, param = {0}
+ * gives gmpnp_electrode_advance's bits.  The parameters take the WHOLE step whatever alpha is: p_electrode += dtheta in both options,
+ * k_r *= exp(dtheta), alpha_r += dtheta, lam *= exp(dtheta) (exp of the host's C library); the moved options are validated by the rules
+ * of gmpnp_set_stern and gmpnp_set_kinetics before anything is changed.  On success the Jacobian and the preconditioner are marked
+ * invalid and the tangent is dropped.  A direction that is not finite (tau != 0): nothing is applied, GMPNP_ERR_NUMERIC, the tangent is
+ * dropped.  Refused (GMPNP_ERR_INVALID, the message names the parameter advance; u, the options and the tangent stay as they were):
+ * everything gmpnp_electrode_tangent refuses of a handle, n outside 1 ... 10, a repeated parameter, a parameter not in the last tangent
+ * call, a dtheta that is not finite, tau outside {0} and (0, 1), a stale or missing tangent, moved options that are not valid.
+ * gmpnp_get_electrode_options: the handle's current option structs (p_electrode is the galvanostat's p_M while it is on; model = 0 /
+ * n_reactions = 0 and zeros while an option is off).  It launches nothing and changes nothing. */
+int gmpnp_parameter_advance(gmpnp_solver* s, int32_t n, const int32_t* param /* [n] */, const double* dtheta /* [n] */,
+                            double tau, double* alpha_out /* or NULL */);
+int gmpnp_get_electrode_options(gmpnp_solver* s, gmpnp_stern_t* stern_out /* or NULL */, gmpnp_kinetics_t* kinetics_out /* or NULL */);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
