@@ -47,6 +47,8 @@ EXPORTS = [
     "gmpnp_frequency_response",
     "gmpnp_electrode_tangent", "gmpnp_tangent_columns", "gmpnp_electrode_advance",
     "gmpnp_parameter_advance", "gmpnp_get_electrode_options",
+    "gmpnp_set_electrode_potential", "gmpnp_electrode_trace_open", "gmpnp_electrode_trace_append", "gmpnp_electrode_trace_read",
+    "gmpnp_electrode_trace_close",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -143,6 +145,17 @@ class CTangent(ctypes.Structure):
                 ("residual", c_double), ("status", c_int32)]
 
 
+class CElectrodeRecord(ctypes.Structure):
+    """ctypes image of ``gmpnp_electrode_record_t`` (include/gmpnp.h)."""
+    _fields_ = [("t", c_double), ("h", c_double), ("p_M", c_double), ("p_boundary", c_double), ("D", c_double), ("dD_dt", c_double),
+                ("I", c_double * MAX_SURFACE_REACTIONS), ("Q", c_double * MAX_SURFACE_REACTIONS), ("Q_D", c_double),
+                ("u_boundary", c_double * MAX_SPECIES), ("status", c_int32), ("pad_", c_int32)]
+
+
+ELECTRODE_RECORD_DTYPE = np.dtype([("t", "f8"), ("h", "f8"), ("p_M", "f8"), ("p_boundary", "f8"), ("D", "f8"), ("dD_dt", "f8"),
+                                   ("I", "f8", MAX_SURFACE_REACTIONS), ("Q", "f8", MAX_SURFACE_REACTIONS), ("Q_D", "f8"),
+                                   ("u_boundary", "f8", MAX_SPECIES), ("status", "i4"), ("pad_", "i4")])
+ELECTRODE_RECORD_NONFINITE = 1    # bit of gmpnp_electrode_record_t.status
 TANGENT_MAX_COLUMNS = 10          # GMPNP_TANGENT_MAX_COLUMNS
 RESPONSE_MAX_FREQUENCIES = 4096   # gmpnp_frequency_response: n in 1 ... 4096
 RESPONSE_SINGULAR, RESPONSE_NONFINITE = 256, 512   # bits of gmpnp_response_t.status
@@ -297,6 +310,11 @@ def load_library(path: str = None):
     lib.gmpnp_electrode_advance.argtypes = [c_void_p, c_double, c_double, POINTER(c_double)]
     lib.gmpnp_parameter_advance.argtypes = [c_void_p, c_int32, POINTER(c_int32), POINTER(c_double), c_double, POINTER(c_double)]
     lib.gmpnp_get_electrode_options.argtypes = [c_void_p, POINTER(CStern), POINTER(CKinetics)]
+    lib.gmpnp_set_electrode_potential.argtypes = [c_void_p, c_double]
+    lib.gmpnp_electrode_trace_open.argtypes = [c_void_p, c_int32]
+    lib.gmpnp_electrode_trace_append.argtypes = [c_void_p, c_double, c_double]
+    lib.gmpnp_electrode_trace_read.argtypes = [c_void_p, c_int32, c_int32, POINTER(CElectrodeRecord)]
+    lib.gmpnp_electrode_trace_close.argtypes = [c_void_p]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -763,6 +781,32 @@ class DeviceSolver:
                                   "reactant": None if ck.reactant[r] < 0 else species[ck.reactant[r]], "nu": nu})
             kinetics = {"reactions": reactions, "p_electrode": float(ck.p_electrode)}
         return stern, kinetics
+
+    def set_electrode_potential(self, p):
+        """``gmpnp_set_electrode_potential``: p_electrode of the Stern option and, where they are on, of the kinetics becomes ``p`` in
+        one call (the bits ``set_stern`` followed by ``set_kinetics`` with that value leave)."""
+        self._check(self.lib.gmpnp_set_electrode_potential(self._h, float(p)))
+
+    def electrode_trace_open(self, capacity):
+        """``gmpnp_electrode_trace_open``: a trace of ``capacity`` records; D at the current u becomes D_prev, Q and Q_D start at 0."""
+        self._check(self.lib.gmpnp_electrode_trace_open(self._h, int(capacity)))
+
+    def electrode_trace_append(self, t, h):
+        """``gmpnp_electrode_trace_append``: the record of the step of length ``h`` that ends at ``t`` with the current u, formed and
+        stored on the device (no synchronisation, no copy)."""
+        self._check(self.lib.gmpnp_electrode_trace_append(self._h, float(t), float(h)))
+
+    def electrode_trace_read(self, first, n) -> np.ndarray:
+        """``gmpnp_electrode_trace_read``: records ``first`` ... ``first + n - 1`` as a structured array (``ELECTRODE_RECORD_DTYPE``;
+        I and Q hold ``MAX_SURFACE_REACTIONS`` entries, u_boundary ``MAX_SPECIES``)."""
+        n = int(n)
+        out = (CElectrodeRecord * max(n, 1))()
+        self._check(self.lib.gmpnp_electrode_trace_read(self._h, int(first), n, out))
+        return np.frombuffer(out, dtype=ELECTRODE_RECORD_DTYPE, count=max(n, 0)).copy()
+
+    def electrode_trace_close(self):
+        """``gmpnp_electrode_trace_close``."""
+        self._check(self.lib.gmpnp_electrode_trace_close(self._h))
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

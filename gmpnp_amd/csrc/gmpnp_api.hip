@@ -191,6 +191,17 @@ struct gmpnp_tangenter {
   ~gmpnp_tangenter() { if (h_out) (void)hipHostFree(h_out); }
 };
 
+// device side of the electrode trace (gmpnp_trace.h), allocated by the first gmpnp_electrode_trace_open: a handle that never asks for it
+// keeps the buffers and launches it had
+struct gmpnp_tracer {
+  DevBuf<gmpnp_electrode_record_t> rec;   // [capacity + 1]: the slot behind the buffer is gmpnp_time_kernel(29)'s
+  DevBuf<ElectrodeAccum> acc;             // [2]: D_prev, Q, Q_D of the trace; the hook's own
+  DevBuf<double> w;                       // [n_nodes] w_I of the Stern nodes (read while the kinetics, which hold the same, are off)
+  DevBuf<int32_t> status;                 // the word of the Stern and kinetic launches of an open / append (not the solver's)
+  int capacity = 0, count = 0;
+  bool open = false;
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -268,6 +279,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_galvanostat> galvanostat;
   std::unique_ptr<gmpnp_responder> responder;
   std::unique_ptr<gmpnp_tangenter> tangenter;
+  std::unique_ptr<gmpnp_tracer> tracer;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
   // (boundary_rebind); allocated by the first of them
   DevBuf<double> bnd_dyn;
@@ -339,6 +351,9 @@ int response_time_chunk(gmpnp_solver* s);
 bool tangent_has_chain(const gmpnp_solver* s);
 int tangent_time_chain(gmpnp_solver* s);
 inline void tangent_drop(gmpnp_solver* s) { if (s->tangenter) { s->tangenter->fresh = false; s->tangenter->cols_fresh = false; } }
+// gmpnp_trace.h: the launches of one gmpnp_electrode_trace_append into a slot and accumulators of the hook's own (gmpnp_time_kernel 29)
+bool trace_is_open(const gmpnp_solver* s);
+int trace_time_append(gmpnp_solver* s);
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
@@ -1890,6 +1905,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (kernel == 26 && !galvanostat_on(s)) return fail(GMPNP_ERR_INVALID, "kernel 26 is the galvanostat: the option is off (gmpnp_set_galvanostat)");
   if (kernel == 27 && !response_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 27 is one chunk of the frequency response: no call has been made (gmpnp_frequency_response)");
   if (kernel == 28 && !tangent_has_chain(s)) return fail(GMPNP_ERR_INVALID, "kernel 28 is the multi-column chain of the electrode tangent: no call has been made on this Jacobian (gmpnp_electrode_tangent, 1D)");
+  if (kernel == 29 && !trace_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 29 is one append of the electrode trace: no trace is open (gmpnp_electrode_trace_open)");
   if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
@@ -1932,6 +1948,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 26: r = galvanostat_launch_iteration(s); break;   // k_galv_rhs + k_galv_reduce + k_galv_direction + k_galv_potential + k_galv_reduce (G alone)
       case 27: r = response_time_chunk(s); break;   // k_response_solve + k_response_functional on the last chunk's frequencies
       case 28: r = tangent_time_chain(s); break;    // extraction, k_bcr_forward_cols / k_bcr_tail_cols / k_bcr_backward_cols, application
+      case 29: r = trace_time_append(s); break;     // k_stern_residual + k_kinetics_residual (kinetics on) + k_electrode_record
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -2056,3 +2073,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_galvanostat.h"
 #include "gmpnp_response.h"
 #include "gmpnp_tangent.h"
+#include "gmpnp_trace.h"

@@ -301,6 +301,127 @@ inline int continuation_advance(Continuation& c, bool success) {
   return 0;
 }
 
+// ---- potential programmes (include/gmpnp.h "potential programmes"; kernels: gmpnp_trace.h; gmpnp_amd/programme.py states the same in
+// Python, operation for operation) ------------------------------------------------------------------------------------------------------
+// A programme is a list of segments (t0, t1, p0, p1), t1 > t0, contiguous in time, p linear inside a segment.  A breakpoint where
+// p1 of a segment equals p0 of the next is a corner, otherwise a jump.  Times are the driver's scaled time, potentials thermal voltages.
+struct ProgrammeSegment { double t0, t1, p0, p1; };
+using Programme = std::vector<ProgrammeSegment>;
+inline bool programme_valid(const Programme& s) {
+  if (s.empty()) return false;
+  for (size_t k = 0; k < s.size(); ++k) {
+    if (!(rule_finite(s[k].t0) && rule_finite(s[k].t1) && rule_finite(s[k].p0) && rule_finite(s[k].p1))) return false;
+    if (!(s[k].t1 > s[k].t0)) return false;
+    if (k > 0 && s[k].t0 != s[k - 1].t1) return false;
+  }
+  return true;
+}
+// the breakpoint behind segment k is a jump (the end of the programme is neither)
+inline bool programme_jump(const Programme& s, int k) { return k + 1 < (int)s.size() && s[k].p1 != s[k + 1].p0; }
+// The potential of an implicit step that ENDS at t_end inside the segment: p1 itself at t_end == t1 (landed values are exact, as
+// Continuation lands on its targets), else the interpolated sum.  A step never straddles a breakpoint.
+inline double programme_value(const ProgrammeSegment& s, double t_end) {
+  GMPNP_RULE_NO_CONTRACT
+  if (t_end >= s.t1) return s.p1;
+  return s.p0 + (s.p1 - s.p0) * ((t_end - s.t0) / (s.t1 - s.t0));
+}
+// pulse: `cycles` times the holds levels[k] for durations[k], from t = 0.  rise_time > 0 replaces each jump by a ramp of that length
+// taken from the following hold (which must be longer).  Empty where the arguments are not valid.
+inline Programme programme_pulse(const std::vector<double>& levels, const std::vector<double>& durations, int cycles, double rise_time) {
+  Programme out;
+  const size_t n = levels.size();
+  if (n == 0 || durations.size() != n || cycles < 1 || !(rise_time >= 0.0) || !rule_finite(rise_time)) return out;
+  for (size_t k = 0; k < n; ++k)
+    if (!rule_finite(levels[k]) || !rule_finite(durations[k]) || !(durations[k] > rise_time)) return Programme();
+  double t = 0.0, last = levels[0];
+  for (int c = 0; c < cycles; ++c)
+    for (size_t k = 0; k < n; ++k) {
+      const double end = t + durations[k];
+      double t_hold = t;
+      if (rise_time > 0.0 && levels[k] != last) { t_hold = t + rise_time; out.push_back({t, t_hold, last, levels[k]}); }
+      out.push_back({t_hold, end, levels[k], levels[k]});
+      t = end; last = levels[k];
+    }
+  return out;
+}
+// triangle: `cycles` times v_start -> v_vertex -> v_start at scan_rate > 0 (potential per time), from t = 0; every breakpoint a corner
+inline Programme programme_triangle(double v_start, double v_vertex, double scan_rate, int cycles) {
+  Programme out;
+  if (!rule_finite(v_start) || !rule_finite(v_vertex) || !rule_finite(scan_rate) || !(scan_rate > 0.0) || cycles < 1 || v_start == v_vertex)
+    return out;
+  const double span = v_vertex - v_start, leg = (span < 0.0 ? -span : span) / scan_rate;
+  if (!(leg > 0.0) || !rule_finite(leg)) return out;
+  double t = 0.0;
+  for (int c = 0; c < cycles; ++c) {
+    const double mid = t + leg, end = mid + leg;
+    out.push_back({t, mid, v_start, v_vertex});
+    out.push_back({mid, end, v_vertex, v_start});
+    t = end;
+  }
+  return out;
+}
+// table: straight lines through (times[k], potentials[k]); a time given twice in a row is a jump there (never three times)
+inline Programme programme_table(const std::vector<double>& times, const std::vector<double>& potentials) {
+  Programme out;
+  const size_t n = times.size();
+  if (n < 2 || potentials.size() != n) return out;
+  for (size_t k = 0; k < n; ++k) if (!rule_finite(times[k]) || !rule_finite(potentials[k])) return out;
+  for (size_t k = 0; k + 1 < n; ++k) {
+    if (times[k + 1] == times[k]) {
+      if (k == 0 || k + 2 >= n || times[k + 2] == times[k]) return Programme();
+      continue;
+    }
+    if (!(times[k + 1] > times[k])) return Programme();
+    out.push_back({times[k], times[k + 1], potentials[k], potentials[k + 1]});
+  }
+  return out;
+}
+// The walk.  Every attempt is judged by next_time_step with a copy of the policy whose t_end is programme_break: the smaller of the
+// segment's end and the run's end.  programme_after moves the walk on from that decision: a stop_end at a breakpoint that is not the
+// end moves to the next segment and does not stop; behind a jump the next attempt is a first step (h = dt_restart, h_prev = 0: the
+// estimator reports no history, so the step is not judged against an extrapolation across the jump); behind a corner nothing is reset.
+// A failed or rejected attempt stays in its segment with the controller's smaller step.  programme_clip is next_time_step's landing
+// applied to a step that starts a segment: cut, or stretched by at most 1 %, to end on the breakpoint.
+struct ProgrammeWalk {
+  int seg = 0;
+  double t = 0.0, h = 0.0, h_prev = 0.0;
+  int steady_run = 0;
+  int stop = 0;        // 0 running, 1 the end was reached, 2 h_min
+};
+inline double programme_break(const Programme& s, int seg, double run_end) { return s[seg].t1 < run_end ? s[seg].t1 : run_end; }
+inline double programme_clip(double h, double t, double t_break) {
+  const double left = t_break - t;
+  return left <= 1.01 * h ? left : h;
+}
+// where the attempt (t, h) ends: the breakpoint itself where next_time_step will say the step landed on it.  The attempt's potential is
+// programme_value there, so a landed step is solved at the segment's p1 exactly.
+inline double programme_step_end(double t, double h, double t_break) {
+  const double next = t + h, left = t_break - next;
+  return left > 1e-12 * std::fabs(t_break) ? next : t_break;
+}
+inline ProgrammeWalk programme_begin(const Programme& s, double dt_init, double run_end) {
+  ProgrammeWalk w;
+  w.t = s[0].t0;
+  w.h = programme_clip(dt_init, w.t, programme_break(s, 0, run_end));
+  return w;
+}
+// (programme_after, which reads the decision of next_time_step, stands behind it below)
+// fixed mode (steps_per_segment = n, no estimator): every step of a segment is (t1 - t0) / n long and the last one lands on t1
+inline double programme_fixed_step(const ProgrammeSegment& s, int n) { return (s.t1 - s.t0) / n; }
+
+// The combine step of one electrode record (gmpnp_electrode_trace_append): the host, the device and the Python statement perform the
+// same operations, every product, quotient and sum rounded on its own.  The state keeps D_prev and the accumulated charges.
+struct ElectrodeAccum { double D_prev, Q[GMPNP_MAX_SURFACE_REACTIONS], Q_D; };
+GMPNP_RULE_HD inline double electrode_record_combine(ElectrodeAccum& a, double h, double D, const double (&I)[GMPNP_MAX_SURFACE_REACTIONS]) {
+  GMPNP_RULE_NO_CONTRACT
+  const double dD_dt = (D - a.D_prev) / h;
+  a.Q[0] = a.Q[0] + h * I[0]; a.Q[1] = a.Q[1] + h * I[1]; a.Q[2] = a.Q[2] + h * I[2]; a.Q[3] = a.Q[3] + h * I[3];
+  a.Q_D = a.Q_D + h * dD_dt;
+  a.D_prev = D;
+  return dD_dt;
+}
+inline bool electrode_trace_step_valid(double t, double h) { return rule_finite(t) && rule_finite(h) && h > 0.0; }
+
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every
 // update.  A driver hands every residual norm (with the device status word of its evaluation) to first() / next() and does what
 // the verdict says; on `failed` and `limit` the error is (code, message).  Owns r0, steric_excursion, residuals[], n_residuals
@@ -428,6 +549,24 @@ inline TimeStepDecision next_time_step(const TimeStepPolicy& p, double t, double
   }
   if (!d.stop_end && !d.stop_steady && !lands && d.h_next < p.h_min) d.give_up = true;
   return d;
+}
+// The walk of a potential programme after the decision of an attempt (its policy's t_end was programme_break; h_done: the step just
+// judged).  Returns 1 where the accepted step landed on a breakpoint or on the end.
+inline int programme_after(const Programme& s, ProgrammeWalk& w, const TimeStepDecision& d, double h_done, double dt_restart, double run_end) {
+  w.steady_run = d.steady_run;
+  w.t = d.t_next; w.h = d.h_next;
+  if (!d.accept || !d.stop_end) {
+    if (d.accept) w.h_prev = h_done;
+    if (d.give_up) w.stop = 2;
+    return 0;
+  }
+  w.h_prev = h_done;
+  if (w.seg + 1 >= (int)s.size() || !(s[w.seg].t1 < run_end)) { w.stop = 1; return 1; }
+  const bool jump = programme_jump(s, w.seg);
+  w.seg += 1;
+  if (jump) { w.h = dt_restart; w.h_prev = 0.0; }
+  w.h = programme_clip(w.h, w.t, programme_break(s, w.seg, run_end));
+  return 1;
 }
 
 // ---- second order: variable-step BDF2 (include/gmpnp.h "second-order adaptive time stepping"; kernels: gmpnp_time_order.h) ----------

@@ -153,12 +153,11 @@ __global__ __launch_bounds__(kVecBlock) void k_kinetics_sum(const Ctx c, const K
 
 namespace {
 
-// the boundary nodes in ascending internal order, their weights and the addresses of their diagonal blocks: geometry only
-int kinetics_build(gmpnp_solver* s, gmpnp_kineticist* K) {
+// w_I of every vertex (0 off the Stern boundary) and the flags of the boundary's vertices: geometry only (also gmpnp_trace.h)
+void boundary_weights(const gmpnp_solver* s, std::vector<double>& wv, std::vector<uint8_t>& on) {
   const Topology& t = s->t;
-  const int nf = s->nf;
-  std::vector<double> wv((size_t)t.nv, 0.0);
-  std::vector<uint8_t> on((size_t)t.nv, 0);
+  wv.assign((size_t)t.nv, 0.0);
+  on.assign((size_t)t.nv, 0);
   if (s->dim == 3) {
     for (size_t k = 0; k + 2 < s->wall_f.size(); k += 3) {
       const int32_t* f = &s->wall_f[k];
@@ -171,6 +170,15 @@ int kinetics_build(gmpnp_solver* s, gmpnp_kineticist* K) {
   } else {
     for (int v : s->point_v) { wv[v] += 1.0; on[v] = 1; }
   }
+}
+
+// the boundary nodes in ascending internal order, their weights and the addresses of their diagonal blocks: geometry only
+int kinetics_build(gmpnp_solver* s, gmpnp_kineticist* K) {
+  const Topology& t = s->t;
+  const int nf = s->nf;
+  std::vector<double> wv;
+  std::vector<uint8_t> on;
+  boundary_weights(s, wv, on);
   std::vector<int32_t> node; std::vector<double> w; std::vector<int64_t> addr;
   for (int I = 0; I < t.nv; ++I) {
     if (!on[I]) continue;

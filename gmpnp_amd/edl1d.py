@@ -27,6 +27,7 @@ from . import backend
 from .impedance import add_impedance_arguments, impedance_keywords
 from .polarisation import add_polarisation_arguments, polarisation_keywords
 from .fit import add_fit_arguments, fit_keywords
+from .programme import add_programme_arguments, programme_keywords
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import _load_yaml, edl_parameters, utilities_dir
 from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_arguments, add_stern_arguments, edl_problem, galvanostat_keywords, kinetics_keywords,
@@ -103,7 +104,26 @@ class EDLRun:
         electrode parameters (also ``stern_length``) to the polarisation data of the file (DESIGN.md section 5m, gmpnp_amd/fit.py;
         ``fit()`` does the same at any time), after the impedance and before the polarisation curve, which is then the fitted one;
         it adds ``fit.npz`` and the metadata keys ``fit_*``.  Afterwards the run stands at ``electrode_voltage`` with the fitted
-        parameters at the steady state there.  Refused as ``polarisation`` is, and without ``kinetics``."""
+        parameters at the steady state there.  Refused as ``polarisation`` is, and without ``kinetics``.
+        ``programme`` = dict(kind="pulse", v_levels=[A, B], durations=[s, s], cycles=n[, rise_time=s]) | dict(kind="triangle", v_vertex=X,
+        scan_rate=V/s, cycles=n) | dict(kind="table", time_s=[...], electrode_voltage=[...]) (potentials in thermal voltages; with
+        ``electrode_voltage``; also dt_init, dt_restart [scaled time], steps_per_segment, capacity): ``write_outputs`` marches the
+        electrode potential through the waveform AFTER the run's own schedule, from its last state, on a clock of its own that starts
+        at 0 (gmpnp_amd/programme.py; ``programme()`` does the same at any time); it is meant to follow
+        ``adaptive_dt`` with ``steady_tol``.  Steps land on the corners and jumps of the waveform; the error controller (the run's
+        ``dt_rtol`` / ``dt_atol`` / ``dt_min`` / ``dt_max``) starts again behind a jump.  Per accepted step the device forms one record
+        of the interface (``gmpnp_electrode_trace_append``); full states are kept at the breakpoints only.  Adds ``programme.npz``
+        (``programme.OUTPUT_KEYS``), ``programme_states.npz``, the attempts as ``programme_*`` arrays of ``timestep_log.npz`` and the
+        metadata keys ``programme_*``; works with ``kinetics``, ``step_fraction`` and ``budget`` (a row per accepted step).  Afterwards
+        the run stands at the programme's last potential (``stern``, ``kinetics``, the metadata's ``electrode_voltage``), and
+        ``impedance`` is taken there.  Not with ``target_current``, ``polarisation``, ``fit``, ``stabilization`` "Y", ``H_OHP`` or
+        ``dt_order`` 2 (ValueError, before anything touches the device)."""
+        self.programme_par = kwargs.pop("programme", None) or None
+        if self.programme_par is not None:
+            from .programme import check_programme
+            self.programme_par = check_programme(self.programme_par, kwargs, dt_order)
+        self.programme_state = None   # the state a programme ended at (impedance_outputs reads it in the place of the history's last row)
+        self.dt_tol, self.dt_bounds, self.max_steps = (dt_rtol, dt_atol), (dt_min, dt_max), max_steps
         self.fit_par = kwargs.pop("fit", None) or None
         if self.fit_par is not None:
             from .fit import check_fit
@@ -354,7 +374,8 @@ class EDLRun:
         eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
         p_M = self.potentials[-1] if self.potentials else self.stern.p_electrode
         stern = type(self.stern)(self.stern.model, p_M, self.stern.lam, self.stern.eps_surface)
-        c_inf = imp.high_frequency_capacitance(self.mesh.coords, self.history[-1], self.problem.model, stern) * eps_0 / self.ep.L_n
+        last = self.history[-1] if self.programme_state is None else self.programme_state
+        c_inf = imp.high_frequency_capacitance(self.mesh.coords, last, self.problem.model, stern) * eps_0 / self.ep.L_n
         g_ct = -float(sp["dI_dV"][0].sum().real) if nr else 0.0
         change = float(np.abs(self.history[-1] - self.history[-2]).max()) if len(self.history) > 1 else None
         return {"impedance_points": int(len(sp["frequency"])), "capacitance_low": float(sp["capacitance"][0].real),
@@ -451,6 +472,71 @@ class EDLRun:
         np.savez(newpath + "/fit.npz", **out)
         return meta
 
+    def programme(self, verbose=False, **par):
+        """Marches the electrode potential through the programme ``par`` (the ``programme`` keyword of ``__init__``) from the run's
+        CURRENT state, on a clock of its own from 0 (gmpnp_amd/programme.py: ``run_programme`` over ``DeviceProgrammeOps``).  The
+        run's own inv_dt is put back afterwards; the run, its records and the handle end at the programme's last potential.  Where the
+        loop raises (a Newton failure in fixed mode, a library error) the handle goes back to the last accepted state, the trace is
+        closed and the run stands at the potential of the failed attempt; the exception goes on to the caller.  Returns
+        the arrays of ``programme.npz`` plus ``log`` (the attempts, by column), ``states`` (segment, time_s, (nv, nf) values at the
+        breakpoints) and ``metadata`` (the ``programme_*`` keys)."""
+        from . import programme as prg
+        from .timestep import TimeStepPolicy
+        if self.stern is None:
+            raise ValueError("programme: a potential programme needs an electrode potential (electrode_voltage)")
+        if self.galvanostat is not None:
+            raise ValueError("programme: not available with target_current (the galvanostat owns the potential)")
+        if self.supg:
+            raise ValueError("programme: not available with stabilization Y")
+        par = prg.check_programme(par, dict(electrode_voltage=self.stern.p_electrode))
+        ep = self.ep
+        segs = prg.build(par, float(self.stern.p_electrode), ep.time_constant, ep.thermal_voltage)
+        L_D = ep.L_D
+        ops = prg.DeviceProgrammeOps(self, self.solver_parameters, lambda h: 1.0 / (h * L_D), self.dt_tol, par.get("capacity") or 4096)
+        policy = TimeStepPolicy(h_min=float(self.dt_bounds[0]), h_max=math.inf if self.dt_bounds[1] is None else float(self.dt_bounds[1]))
+        inv_dt = float(self.sys.problem.model.inv_dt)
+        try:
+            res = prg.run_programme(ops, segs, policy, dt_init=par.get("dt_init") or ep.dts[0], dt_restart=par.get("dt_restart"),
+                                    steps_per_segment=par.get("steps_per_segment"), max_attempts=self.max_steps)
+            rec = ops.records()
+            last = self.sys.vertex_values()
+        except BaseException:   # (a Newton failure in fixed mode, a library error): back to the last accepted state, no trace left open
+            ops.abort()
+            raise
+        finally:
+            self.sys.set_time_step(inv_dt)
+        self.programme_state, self.programme_residuals = last, np.array(ops.residuals)
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
+        out = prg.output_arrays(ep, eps_0, rec, ops.segments, segs, par.get("cycles", 1))
+        if verbose:
+            print("programme %s: %d accepted steps, %d attempts, %s" % (par["kind"], len(rec), len(res["log"]), res["stop_reason"]))
+        states = list(ops.states)
+        t_last = res["times"][-1] if res["times"] else 0.0
+        if not states or states[-1][1] != t_last:   # the run ended between two breakpoints (max_steps, h_min): its last state is kept too
+            states.append((ops.segments[-1] if ops.segments else 0, t_last, last))
+        meta = {"programme_kind": par["kind"], "programme_cycles": int(par.get("cycles", 1)), "programme_segments": len(segs),
+                "programme_steps_accepted": int(len(rec)), "programme_steps_rejected": int(len(res["log"]) - len(rec)),
+                "programme_stop_reason": res["stop_reason"], "programme_t_reached": float(res["times"][-1] * ep.time_constant) if res["times"] else 0.0,
+                "programme_newton_iterations": int(ops.newton_iterations),
+                "programme_charge_closure": float(rec["Q_D"][-1] - (rec["D"][-1] - ops.D_first)) if len(rec) else 0.0,
+                "programme_status": int(np.bitwise_or.reduce(rec["status"])) if len(rec) else 0,
+                # the interface where the programme ended, as one consistent set (potential_OHP, field_OHP, eps_rel_OHP and the run's
+                # arrays describe the end of the schedule)
+                "programme_electrode_voltage": float(self.stern.p_electrode),
+                "programme_potential_OHP": float(out["potential_OHP"][-1]) if len(rec) else None,
+                "programme_surface_charge": float(out["surface_charge"][-1]) if len(rec) else None}
+        out.update(log=prg.log_arrays(res["log"]), states=[(k, t * ep.time_constant, v) for k, t, v in states], metadata=meta)
+        return out
+
+    def programme_outputs(self, newpath):
+        """``programme.npz``, ``programme_states.npz`` and the attempts for ``timestep_log.npz``; returns (metadata keys, log arrays)."""
+        out = self.programme(**self.programme_par)
+        meta, log, states = out.pop("metadata"), out.pop("log"), out.pop("states")
+        np.savez(newpath + "/programme.npz", **out)
+        np.savez(newpath + "/programme_states.npz", segment=np.array([k for k, _, _ in states], dtype=np.int64),
+                 time_s=np.array([t for _, t, _ in states]), states=np.stack([v for _, _, v in states]), coor=self.mesh.coords)
+        return meta, {"programme_" + k: v for k, v in log.items()}
+
     def kinetics_summary(self):
         """Per-step ``i_CO``, ``i_H2`` [A/m2] and ``FE_H2`` of a run with the surface kinetics (the OHP is one point: w = 1)."""
         from .kinetics import current_summary
@@ -467,6 +553,7 @@ class EDLRun:
         identifier = run_identifier(ep, k, self.stern, self.target_current)
         newpath = os.path.join(output_root(), ep.model_name, stamp + "_experiment", identifier)
         os.makedirs(newpath, exist_ok=True)
+        programme = self.programme_outputs(newpath) if self.programme_par is not None else None   # first: the metadata reports the state it ends at
         hist = np.stack(self.history)
         names = ["H", "OH", "HCO3", "CO32", "CO2", "cat", "p"]
         Hh = {nme: hist[:, :, i] for i, nme in enumerate(names)}
@@ -531,6 +618,12 @@ class EDLRun:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
             self.stepping.save(newpath, metadata_dict)
+        if programme is not None:
+            metadata_dict.update(programme[0])
+            log_path = os.path.join(newpath, "timestep_log.npz")
+            with_schedule = dict(np.load(log_path)) if os.path.exists(log_path) else {}
+            np.savez(log_path, **with_schedule, **programme[1])
+            metadata_dict["timestep_log"] = "timestep_log.npz"
         if self.fit_par is not None:   # before the curve, which is then the fitted one; the handle ends at the run's operating point
             metadata_dict.update(self.fit_outputs(newpath))
         if self.polarisation_par is not None:   # last: the handle leaves the run's operating point
@@ -557,7 +650,7 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
               current_OHP_ss=10.0, L_n=50.0e-6, stabilization="N", H_OHP=None, cation="K", params_file="parameters",
               dry_run=True, num_steps=None, verbose=True, budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM",
               stern_length=4.0e-10, stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0,
-              p_eq_H2=0.0, target_current=None, impedance=None, polarisation=None, fit=None, **adaptive):
+              p_eq_H2=0.0, target_current=None, impedance=None, polarisation=None, fit=None, programme=None, **adaptive):
     """Same keyword surface as the reference's ``solve_EDL`` (1D:66-79); returns the output directory.  ``adaptive``: the
     adaptive-stepping keywords of ``EDLRun`` (adaptive_dt, dt_rtol, dt_atol, dt_init, dt_min, dt_max, t_end, steady_tol, max_steps).
     ``voltage_multiplier`` = None is the reference's default -1.0, unless ``electrode_voltage`` (with ``stern_model``, ``stern_length``,
@@ -577,6 +670,8 @@ def solve_EDL(concentration_elec=0.1, model="MPNP", voltage_multiplier=None, H2_
         stern.update(polarisation=polarisation)
     if fit:   # (the fit of the electrode kinetics of ``EDLRun``, after the last step and before the curve)
         stern.update(fit=fit)
+    if programme:   # (the potential programme of ``EDLRun``, after the last step)
+        stern.update(programme=programme)
     run = EDLRun(num_steps=num_steps, budget=budget, step_fraction=step_fraction, **adaptive, **stern, concentration_elec=concentration_elec, model=model,
                  voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, mesh_structure=mesh_structure,
                  current_OHP_ss=current_OHP_ss, L_n=L_n, stabilization=stabilization, H_OHP=H_OHP, cation=cation,
@@ -613,6 +708,7 @@ def build_parser():
     add_impedance_arguments(p)
     add_polarisation_arguments(p)
     add_fit_arguments(p)
+    add_programme_arguments(p)
     return p
 
 
@@ -622,7 +718,7 @@ def main(argv=None):
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
                      dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a),
-                     **impedance_keywords(a), **polarisation_keywords(a), **fit_keywords(a))
+                     **impedance_keywords(a), **polarisation_keywords(a), **fit_keywords(a), **programme_keywords(a))
 
 
 if __name__ == "__main__":

@@ -18,6 +18,7 @@ from .edl1d import EDLRun, run_identifier
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
+from .programme import refuse_programme
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .params import edl_parameters
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -47,6 +48,7 @@ def plan_members(members, num_steps=None):
         refuse_impedance(m, "an ensemble (member %d)" % k)
         refuse_polarisation(m, "an ensemble (member %d)" % k)
         refuse_fit(m, "an ensemble (member %d)" % k)
+        refuse_programme(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

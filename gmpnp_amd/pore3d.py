@@ -100,7 +100,9 @@ class PoreRun:
         from .impedance import refuse_impedance
         refuse_impedance(kwargs, "the 3D pore driver (it needs a complex band LU)")
         from .fit import refuse_fit
+        from .programme import refuse_programme
         refuse_fit(kwargs, "the 3D pore driver (the library's parameter advance works there, the fit's host glue is 1D)")
+        refuse_programme(kwargs, "the 3D pore driver (potential programmes are 1D)")
         self.polarisation_par = kwargs.pop("polarisation", None) or None
         if self.polarisation_par is not None:
             from .polarisation import check_polarisation

@@ -19,6 +19,7 @@ from .pore3d import SOLVER_PARAMETERS, PoreRun
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
+from .programme import refuse_programme
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import column_medians
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -44,6 +45,7 @@ def plan_members(members, num_steps=None):
         refuse_impedance(m, "an ensemble (member %d)" % k)
         refuse_polarisation(m, "an ensemble (member %d)" % k)
         refuse_fit(m, "an ensemble (member %d)" % k)
+        refuse_programme(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

@@ -30,6 +30,7 @@ from .params import _load_yaml, _reaction_tables, utilities_dir
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
+from .programme import refuse_programme
 from .problem import edl_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem
 
@@ -145,6 +146,7 @@ class RxnDiffRun:
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

@@ -28,6 +28,7 @@ from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
 from .impedance import refuse_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
+from .programme import refuse_programme
 from .problem import GALVANOSTAT_KEYWORDS, KINETICS_KEYWORDS, pore_dirichlet, pore_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem, column_medians
 from .vtk import write_pvd
@@ -66,6 +67,7 @@ class RxnPoreRun:
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

@@ -58,10 +58,12 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
     from .impedance import refuse_impedance
     from .polarisation import refuse_polarisation
     from .fit import refuse_fit
+    from .programme import refuse_programme
     from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
     refuse_impedance(adaptive, "the pore sweep")
     refuse_polarisation(adaptive, "the pore sweep")
     refuse_fit(adaptive, "the pore sweep")
+    refuse_programme(adaptive, "the pore sweep")
     refuse_galvanostat(adaptive, "the pore sweep")
     refuse_stern(adaptive, "the pore sweep")
     refuse_kinetics(adaptive, "the pore sweep")

@@ -708,6 +708,51 @@ int gmpnp_parameter_advance(gmpnp_solver* s, int32_t n, const int32_t* param /* 
                             double tau, double* alpha_out /* or NULL */);
 int gmpnp_get_electrode_options(gmpnp_solver* s, gmpnp_stern_t* stern_out /* or NULL */, gmpnp_kinetics_t* kinetics_out /* or NULL */);
 
+/* ---- potential programmes (no reference counterpart: the electrode potential follows a waveform in time; rule: "potential programmes"
+ * in csrc/gmpnp_host_rules.h and gmpnp_amd/programme.py; kernels: csrc/gmpnp_trace.h) -------------------------------------------------
+ * gmpnp_set_electrode_potential: p_electrode of the Stern option and, where the kinetics are on, of the kinetic option become p, in one
+ * call with one synchronisation.  It drops the tangent, marks the Jacobian and the preconditioner invalid and rebinds the boundary
+ * vector once; afterwards F, J and gmpnp_get_electrode_options hold the bits that gmpnp_set_stern followed by gmpnp_set_kinetics with
+ * that value give.  Refused (GMPNP_ERR_INVALID, the message names the electrode potential): the Stern option off, the galvanostat on,
+ * p not finite.
+ *
+ * The electrode trace is a per-handle buffer of records that the device fills, one per accepted time step, allocated by the first
+ * gmpnp_electrode_trace_open (a handle that never asks keeps the buffers and launches it had).
+ *   open(capacity)    allocates `capacity` slots, resets the count, evaluates D at the current u as D_prev and zeroes Q and Q_D
+ *                     (one synchronisation)
+ *   append(t, h)      k_stern_residual, k_kinetics_residual (kinetics on) and k_electrode_record at the current u, which writes the
+ *                     next slot: no host synchronisation and no copy.  With w_I the weights of the kinetics (1D: 1, 3D: the wall
+ *                     weights) over the nodes of the Stern boundary:
+ *                         D            the bits of gmpnp_stern_displacement          I[r]   the bits of gmpnp_kinetics_currents
+ *                         p_boundary   sum_I w_I p_I / sum_I w_I                            (0 with the kinetics off)
+ *                         u_boundary   sum_I w_I u_{I,f} / sum_I w_I per species (0 behind the handle's species)
+ *                         dD_dt = (D - D_prev) / h     Q[r] += h I[r]     Q_D += h dD_dt     D_prev = D
+ *                     every product, quotient and sum of the last line rounded on its own (electrode_record_combine of the rule; the
+ *                     device keeps D_prev, Q and Q_D).  status bit 1: a value of the record is not finite.  A full buffer is refused
+ *                     and nothing is overwritten: read the records and open again, or open with more room.
+ *   read(first, n)    records first ... first + n - 1 with one synchronisation and one copy
+ *   close()           the trace is closed (the buffer stays with the handle); append, read and hook 29 are refused until the next open
+ * Refused (GMPNP_ERR_INVALID, the message names the electrode trace): the Stern option off, partition handles, a multilevel coarse
+ * level attached or the handle serving as one, the galvanostat on, capacity < 1, h <= 0 or not finite, t not finite, append / read /
+ * close without an open trace, a read outside the records written. */
+typedef struct {
+  double t, h;                                /* the arguments of the append */
+  double p_M;                                 /* p_electrode of the Stern option */
+  double p_boundary;
+  double D, dD_dt;
+  double I[GMPNP_MAX_SURFACE_REACTIONS];
+  double Q[GMPNP_MAX_SURFACE_REACTIONS];
+  double Q_D;
+  double u_boundary[GMPNP_MAX_SPECIES];
+  int32_t status;                             /* bit 1: a value that is not finite */
+  int32_t pad_;
+} gmpnp_electrode_record_t;
+int gmpnp_set_electrode_potential(gmpnp_solver* s, double p);
+int gmpnp_electrode_trace_open(gmpnp_solver* s, int32_t capacity);
+int gmpnp_electrode_trace_append(gmpnp_solver* s, double t, double h);
+int gmpnp_electrode_trace_read(gmpnp_solver* s, int32_t first, int32_t n, gmpnp_electrode_record_t* out /* [n] */);
+int gmpnp_electrode_trace_close(gmpnp_solver* s);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -783,7 +828,9 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * and an assembled Jacobian; the state and p_M stay), 27 = the two launches of one chunk of the frequency response (k_response_solve +
  * k_response_functional on the frequencies of the last chunk of the last gmpnp_frequency_response call, which it needs), 28 = the
  * multi-column cyclic-reduction chain(s) of the last gmpnp_electrode_tangent call with extraction and application (needs such a call
- * and the Jacobian it left). */
+ * and the Jacobian it left), 29 = the launches of one gmpnp_electrode_trace_append (k_stern_residual, k_kinetics_residual with the
+ * kinetics on, k_electrode_record; needs an open trace, whose records, count, D_prev, Q and Q_D stay: the hook's launches write a slot
+ * and accumulators of their own). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
