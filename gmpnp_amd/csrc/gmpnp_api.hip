@@ -222,6 +222,7 @@ struct gmpnp_solver {
       slice_node0, slice_nn, node_slice, sell_cols, sell_blk, wl_slice, wl_kpos, tile_slice0, tile_agg, tile_slot,
       tile_aggs, tile_nagg, tile_cols, tile_colslot, sell_lcol, agg, agg_start, row_aggs, status;
   DevBuf<int64_t> rob_addr, slice_off;
+  DevBuf<int32_t> rob_blk; DevBuf<double> rob_blk_val; DevBuf<uint32_t> rob_blk_mask;   // the Robin entries by node block
   DevBuf<uint8_t> bcflag, sell_aggslot;
   DevBuf<KrylovScalars> scal; DevBuf<TileRec> tile_rec;
   std::vector<uint8_t> h_bcflag, h_bcflag_dev;   // flags being built / flags the device holds
@@ -257,6 +258,16 @@ struct gmpnp_solver {
   hipStream_t stream2 = nullptr; hipEvent_t ev_mat = nullptr, ev_chain = nullptr, ev_jac = nullptr, ev_dots = nullptr;
   DevBuf<double> Aci2; double* aci_buf[2] = {nullptr, nullptr}; int aci_cur = 0;
   bool chain_in_flight = false;
+  // Jacobian gather beside Newton's convergence test (newton(), launch_jac_gather_ahead): the gather of the NEXT iteration's
+  // matrix runs on the side stream behind k_element, into the value buffer the context does not point at, while the main
+  // stream forms the residual norm and the host judges it.  `go_on` adopts both: c.vals and vals_spare change places, and
+  // so do `stream` and `stream2` — the iteration carries on in the stream that holds the gather, behind it, and the stream
+  // the host has just synchronised becomes the side stream (a way back through an event costs about what the overlap
+  // gains).  Any other verdict leaves c.vals, and with it every reader of the Jacobian, as it was.
+  DevBuf<double> vals2; double* vals_spare = nullptr;
+  hipEvent_t ev_elem = nullptr, ev_gather = nullptr;
+  int chain_level = 0;           // GMPNP_NEWTON_CHAIN: 0 the serial chain, 1 the gather beside the test, 2 (default) with the folded launches
+  bool gather_pending = false;   // a gather into vals_spare is in flight on the side stream (ev_gather)
   int direct_solves = 0;        // band LU solves since create (factorisations)
   hipEvent_t ev_phase[6] = {};
   hipEvent_t ev_poll[2] = {};
@@ -305,11 +316,13 @@ struct gmpnp_solver {
     if (h_part) (void)hipHostFree(h_part);
     if (h_status) (void)hipHostFree(h_status);
     if (h_red) (void)hipHostFree(h_red);
-    if (stream2) { (void)hipStreamSynchronize(stream2); (void)hipStreamDestroy(stream2); }
+    if (stream2) { if (stream) (void)hipStreamSynchronize(stream); (void)hipStreamSynchronize(stream2); (void)hipStreamDestroy(stream2); }   // (the two change roles: newton())
     if (ev_mat) (void)hipEventDestroy(ev_mat);
     if (ev_chain) (void)hipEventDestroy(ev_chain);
     if (ev_jac) (void)hipEventDestroy(ev_jac);
     if (ev_dots) (void)hipEventDestroy(ev_dots);
+    if (ev_elem) (void)hipEventDestroy(ev_elem);
+    if (ev_gather) (void)hipEventDestroy(ev_gather);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -407,14 +420,23 @@ int rebuild_boundary(gmpnp_solver* s) {
   // merge duplicates (stable order of first appearance => deterministic)
   std::stable_sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.row != b.row ? a.row < b.row : a.col < b.col; });
   std::vector<int32_t> rrow, rcol, rptr((size_t)s->ndof + 1, 0); std::vector<double> rval; std::vector<int64_t> raddr;
+  // ... and by node block (an entry couples species i of two nodes: it sits on the diagonal of its block)
+  std::vector<int32_t> rblk(t.cols.size(), -1); std::vector<double> rbval; std::vector<uint32_t> rbmask;
+  bool blk_ok = true;
   for (size_t k = 0; k < ents.size();) {
     size_t j = k; double v = 0.0;
     while (j < ents.size() && ents[j].row == ents[k].row && ents[j].col == ents[k].col) v += ents[j++].v;
     const int row = ents[k].row, col = ents[k].col;
     const int I = row / nf, i = row % nf, J = col / nf, jf = col % nf;
     const int32_t* b = t.cols.data() + t.rowptr[I]; const int32_t* e = t.cols.data() + t.rowptr[I + 1];
-    const int kpos = t.sellk[(int)(std::lower_bound(b, e, J) - t.cols.data())];
+    const int blk = (int)(std::lower_bound(b, e, J) - t.cols.data());
+    const int kpos = t.sellk[blk];
     const int sl = t.node_slice[I], il = I - t.slice_node0[sl];
+    if (i != jf || i >= ns) blk_ok = false;
+    else {
+      if (rblk[blk] < 0) { rblk[blk] = (int32_t)rbmask.size(); rbmask.push_back(0u); rbval.resize(rbval.size() + ns, 0.0); }
+      rbmask[rblk[blk]] |= 1u << i; rbval[(size_t)rblk[blk] * ns + i] = v;
+    }
     rrow.push_back(row); rcol.push_back(col); rval.push_back(v);
     raddr.push_back(t.slice_off[sl] + (int64_t)(kpos * nf + jf) * kWave + il * nf + i);
     rptr[row + 1]++;
@@ -425,6 +447,11 @@ int rebuild_boundary(gmpnp_solver* s) {
   HIP_TRY(s->rob_row.upload(rrow)); HIP_TRY(s->rob_val.upload(rval)); HIP_TRY(s->rob_addr.upload(raddr));
   s->c.bndF = s->bndF.p; s->c.robF_ptr = s->robF_ptr.p; s->c.rob_col = s->rob_col.p; s->c.rob_row = s->rob_row.p;
   s->c.rob_val = s->rob_val.p; s->c.rob_addr = s->rob_addr.p; s->c.n_robin = (int)rval.size();
+  s->c.rob_blk = nullptr;   // (entries off a block's diagonal: none today; the gather would leave them to k_robin_add)
+  if (blk_ok && !rval.empty()) {
+    HIP_TRY(s->rob_blk.upload(rblk)); HIP_TRY(s->rob_blk_val.upload(rbval)); HIP_TRY(s->rob_blk_mask.upload(rbmask));
+    s->c.rob_blk = s->rob_blk.p; s->c.rob_blk_val = s->rob_blk_val.p; s->c.rob_blk_mask = s->rob_blk_mask.p;
+  }
   return boundary_rebind(s);   // the new constant vector under the Stern and kinetic terms (nothing to do with both off)
 }
 
@@ -466,15 +493,36 @@ int launch_res_gather(gmpnp_solver* s) {
 }
 
 template <int DIM, int NF>
-int launch_jac_gather(gmpnp_solver* s) {
+int launch_jac_gather(gmpnp_solver* s, bool fold_robin = false) {
   const int g = grid_for(s->c.n_work * kWave, kVecBlock);   // n_work = 8 equal runs, each a whole number of workgroups
-  hipLaunchKernelGGL((k_jac_gather<DIM, NF>), dim3(g), dim3(kVecBlock), 0, s->stream, s->c);
-  if (s->c.n_robin > 0) hipLaunchKernelGGL(k_robin_add, dim3(grid_for(s->c.n_robin, 256)), dim3(256), 0, s->stream, s->c);
+  if (fold_robin && s->c.n_robin > 0 && s->c.rob_blk) {   // Newton's chain: one launch
+    hipLaunchKernelGGL((k_jac_gather<DIM, NF, true>), dim3(g), dim3(kVecBlock), 0, s->stream, s->c);
+  } else {
+    hipLaunchKernelGGL((k_jac_gather<DIM, NF>), dim3(g), dim3(kVecBlock), 0, s->stream, s->c);
+    if (s->c.n_robin > 0) hipLaunchKernelGGL(k_robin_add, dim3(grid_for(s->c.n_robin, 256)), dim3(256), 0, s->stream, s->c);
+  }
   HIP_TRY(hipGetLastError());
   if (stern_on(s)) { int rc = stern_launch_jacobian(s); if (rc) return rc; }
   if (kinetics_on(s)) return kinetics_launch_jacobian(s);
   return GMPNP_OK;
 }
+
+// The same launches on the side stream, into vals_spare, behind `ev_elem` (recorded in the main stream where the element
+// records and the dynamic boundary vector of this state are complete).  Nothing in the main stream waits for them here.
+template <int DIM, int NF>
+int launch_jac_gather_ahead(gmpnp_solver* s) {
+  HIP_TRY(hipStreamWaitEvent(s->stream2, s->ev_elem, 0));
+  hipStream_t keep = s->stream; double* cur = s->c.vals;
+  s->stream = s->stream2; s->c.vals = s->vals_spare;   // (as ml_setup lends a stream: every launch below takes both from the handle)
+  const int rc = launch_jac_gather<DIM, NF>(s, s->chain_level >= 2);
+  s->stream = keep; s->c.vals = cur;
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(s->ev_gather, s->stream2));
+  s->gather_pending = true;
+  return GMPNP_OK;
+}
+// where newton() may do so: the handle got the second value buffer at create and no multilevel level holds a copy of its context
+inline bool gather_ahead_ok(const gmpnp_solver* s) { return s->vals_spare && s->stream2 && !s->ml_coarse && !s->ml_is_coarse; }
 
 int drain_spmv_events(gmpnp_solver* s);
 int budget_launch_any(gmpnp_solver* s);   // gmpnp_budget.h: the launch chain of one species-budget call
@@ -497,11 +545,13 @@ double sum_partials(const gmpnp_solver* s, int row) {
 
 // residual at the current u: returns ||b||_2 and the device status flags
 template <int DIM, int NF>
-int residual(gmpnp_solver* s, bool want_j, double* norm, int* flags) {
+int residual(gmpnp_solver* s, bool want_j, double* norm, int* flags, bool gather_ahead = false) {
   int rc = launch_element<DIM, NF>(s, want_j); if (rc) return rc;
   if (stern_on(s)) { rc = stern_launch_residual(s, s->status.p); if (rc) return rc; }
   if (kinetics_on(s)) { rc = kinetics_launch_residual(s, s->status.p); if (rc) return rc; }
+  if (gather_ahead) HIP_TRY(hipEventRecord(s->ev_elem, s->stream));
   rc = launch_res_gather<DIM, NF>(s); if (rc) return rc;
+  if (gather_ahead) { rc = launch_jac_gather_ahead<DIM, NF>(s); if (rc) return rc; }   // (enqueued behind the main stream's own work)
   // the partials and the status word land in pinned host memory by the kernel's own stores: no copy in the stream
   HIP_TRY(hipStreamSynchronize(s->stream));
   rc = drain_spmv_events(s); if (rc) return rc;
@@ -738,14 +788,15 @@ int krylov_verdict(const KrylovScalars& res, double bnorm, gmpnp_linear_stats_t*
 // Solve J dx = rhs (rhs already in c.kr on the device, ||rhs|| = bnorm) with the fused right-preconditioned BiCGStab;
 // leaves y in c.ky; the caller applies M^{-1} (apply_minv).
 template <int NF>
-int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, int maxit, gmpnp_linear_stats_t* st, bool restart = false) {
+int krylov(gmpnp_solver* s, int mode, double bnorm, double rtol, double atol, int maxit, gmpnp_linear_stats_t* st, bool restart = false,
+           const double* warm_w = nullptr) {
   const int use_coarse = (mode == GMPNP_LINEAR_BICGSTAB_TWOLEVEL) ? 1 : 0;
   s->c.use_coarse = use_coarse;
   s->fused_seq = 0;
   const KrylovScalars init = krylov_start(s->shadow_src ? s->shadow_rho0 : bnorm * bnorm, bnorm, rtol, atol, maxit);
   // one launch: shadow vector (r_0, or a pseudo-random vector after a breakdown), y = 0, P^T r_0 partials
   // where A(0) expects them, hand-over flags cleared, scalars from the kernel argument
-  hipLaunchKernelGGL((k_krylov_init<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c, s->shadow_src, init, s->cpart_v1.p);
+  hipLaunchKernelGGL((k_krylov_init<NF>), dim3(s->t.own_ntiles), dim3(kVecBlock), 0, s->stream, s->c, s->shadow_src, init, s->cpart_v1.p, warm_w);
   if (s->prereduce && use_coarse) hipLaunchKernelGGL(k_dist_reduce, dim3(s->ncoarse), dim3(256), 0, s->stream, s->c, 0, 0, s->red_i.p);
   // the previous solve wrote its verdict before the host left its loop and nothing of it writes the mirror afterwards
   volatile HostPoll* hp = s->h_poll;
@@ -878,7 +929,7 @@ int krylov_verified(gmpnp_solver* s, gmpnp_linear_stats_t* st, KrylovRequest& q)
   q.upd_done = false;
   gmpnp_linear_stats_t total{}; total.rhs_norm = q.bnorm;
   double rhs_norm = q.bnorm;
-  bool warm = false;
+  bool warm = false, fold_start = false;
   if (q.warm_scale != 0.0 && q.bnorm > 0.0) {
     // x0 = warm_scale * kx + warm_prev * kxp (left in kx by the previous Newton update when `x0_ready`); accepted when
     // it removes at least half of the residual: one plain SpMV, three dots, one host round trip
@@ -894,9 +945,11 @@ int krylov_verified(gmpnp_solver* s, gmpnp_linear_stats_t* st, KrylovRequest& q)
     }
     // The predicted correction is taken as it is.  (Scaling it by the minimal-residual multiple (w,b)/(w,w) makes |r0|
     // smaller every time and BiCGStab slower all the same: 18.8k instead of 17.3k iterations over the bench, round 1.)
+    // r0 = b - w: formed by the first pass's k_krylov_init where one follows (fold_start), by a launch of its own otherwise
     if (accept_predicted_start(sum_partials(s, 0), sum_partials(s, 1), sum_partials(s, 2), &rhs_norm)) {
-      hipLaunchKernelGGL(k_start_residual, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p,
-                         (const double*)s->kt.p, n);
+      fold_start = s->chain_level >= 2 && !s->partitioned && rhs_norm > tol;
+      if (!fold_start) hipLaunchKernelGGL(k_start_residual, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, s->kr.p, (const double*)s->kb.p,
+                                          (const double*)s->kt.p, n);
       warm = true;
     }  // else: kr still holds b, cold start
   }
@@ -925,7 +978,8 @@ int krylov_verified(gmpnp_solver* s, gmpnp_linear_stats_t* st, KrylovRequest& q)
         s->shadow_src = s->krand.p; s->shadow_rho0 = sum_partials(s, 0);
       }
       const bool first_cold = (pass == 0 && !warm);
-      rc = krylov<NF>(s, q.mode, rhs_norm, first_cold ? q.rtol : 0.0, first_cold ? q.atol : tol, cap, &ls, pass > 0);
+      rc = krylov<NF>(s, q.mode, rhs_norm, first_cold ? q.rtol : 0.0, first_cold ? q.atol : tol, cap, &ls, pass > 0,
+                      pass == 0 && fold_start ? (const double*)s->kt.p : nullptr);
       s->shadow_src = nullptr;
     }
     total.iterations += ls.iterations; total.converged = ls.converged; total.residual_norm = ls.residual_norm;
@@ -1309,7 +1363,15 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
   // Every residual evaluation also leaves the element Jacobian records (k_element<.., true>, 43 us instead of 27): the
   // state only changes in the update, so the records of the convergence test ARE those of the next iteration's
   // Jacobian, and the separate element pass per iteration (another 43 us) is gone.  Wasted only on the last test of a solve.
-  int rc = residual<DIM, NF>(s, true, &r, &flags); if (rc) return rc;
+  // ... and where the handle allows it, the gather of those records runs beside the test (gmpnp_solver::vals2).  A gather
+  // that no iteration adopts (converged, limit, failed, an error) is awaited by the main stream in stream order when this
+  // function returns: whatever follows may write u, the element records or the spare buffer.
+  const bool ahead = gather_ahead_ok(s);
+  struct Orphan {
+    gmpnp_solver* s;
+    ~Orphan() { if (s->gather_pending) { (void)hipStreamWaitEvent(s->stream, s->ev_gather, 0); s->gather_pending = false; } }
+  } orphan{s};
+  int rc = residual<DIM, NF>(s, true, &r, &flags, ahead); if (rc) return rc;
   st.ms_assemble += now_ms() - ta;
   NewtonJudge judge(o, st, s->cfg.strict_steric != 0);
   NewtonJudge::Verdict v = judge.first(r, flags);
@@ -1317,8 +1379,18 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
   const bool limited = o.step_fraction != 0.0;
   if (limited) { rc = step_prepare(s); if (rc) return rc; }
   while (v == NewtonJudge::go_on) {
-    rc = mark_phase(s, 0); if (rc) return rc;
-    rc = launch_jac_gather<DIM, NF>(s); if (rc) return rc;   // element records: left by the last residual evaluation
+    if (s->gather_pending && s->cfg.phase_timing) HIP_TRY(hipEventRecord(s->ev_phase[0], s->stream));
+    else { rc = mark_phase(s, 0); if (rc) return rc; }
+    if (s->gather_pending) {
+      // started behind k_element: adopt its buffer and its stream.  The stream left behind is idle (residual() synchronised it),
+      // and what the other one holds in front of the gather, the coarse chain of the previous iteration, is awaited through
+      // ev_chain as before.  (Phase 0 was stamped there: assembly time counts from the verdict to the end of the gather.)
+      std::swap(s->c.vals, s->vals_spare);
+      std::swap(s->stream, s->stream2);
+      s->gather_pending = false;
+    } else {
+      rc = launch_jac_gather<DIM, NF>(s); if (rc) return rc;   // element records: left by the last residual evaluation
+    }
     s->jacobian_valid = true;
     rc = mark_phase(s, 1); if (rc) return rc;
     if (o.linear_solver == GMPNP_LINEAR_BLOCK_TRIDIAGONAL) rc = tridiagonal_step<DIM, NF>(s, o, st, r);
@@ -1328,7 +1400,12 @@ int newton(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_
     if (limited) { rc = step_launch<NF>(s, s->kx.p, s->kxp.p, o.relaxation_parameter, o.step_fraction, s->status.p); if (rc) return rc; }
     rc = mark_phase(s, 3); if (rc) return rc;
     st.iterations++;
-    rc = residual<DIM, NF>(s, true, &r, &flags); if (rc) return rc;  // synchronises the stream
+    // (no gather beside a test that is expected to end the solve: last_test_expected, gmpnp_host_rules.h)
+    const int nr = st.n_residuals;
+    const bool last = nr >= 2 && nr < GMPNP_MAX_NEWTON_HISTORY &&
+                      last_test_expected(st.residuals[nr - 2], st.residuals[nr - 1], judge.r0, o.relative_tolerance, o.absolute_tolerance,
+                                         st.iterations, o.maximum_iterations);
+    rc = residual<DIM, NF>(s, true, &r, &flags, ahead && !last); if (rc) return rc;  // synchronises the stream
     if (limited) record_step(st, st.iterations - 1, s->limiter->h_report->alpha);   // written by the update, in front of that synchronisation
     rc = collect_phases(s, st); if (rc) return rc;
     v = judge.next(r, flags);
@@ -1476,10 +1553,23 @@ static int create_impl(const gmpnp_mesh_t* mesh, const gmpnp_model_t* model, con
   HIP_TRY(s->Ac.alloc((size_t)s->ncoarse * s->ncoarse)); HIP_TRY(s->Aci.alloc((size_t)s->ncoarse * s->ncoarse));
   HIP_TRY(s->Aci2.alloc((size_t)s->ncoarse * s->ncoarse));
   const gmpnp_options_t& po = s->opts;
+  s->chain_level = GMPNP_NEWTON_CHAIN_DEFAULT;
+  if (const char* env = std::getenv("GMPNP_NEWTON_CHAIN")) s->chain_level = std::atoi(env);
   if (s->cfg.coarse_async || s->cfg.warm_async) {   // the side stream exists only when something uses it
-    HIP_TRY(hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking));
+    // The second value buffer of the gather beside Newton's test: unpartitioned 3D handles with the side stream, where it is cheap
+    // (matrix up to kGatherAheadCapBytes).  GMPNP_NEWTON_CHAIN=0 in the environment keeps the serial chain (A/B runs, tests).
+    // The two streams of such a handle change roles (newton()), so the side stream is created like the main one.
+    const size_t vbytes = ((size_t)t.slice_off[t.nslices] + (size_t)kRowPad * nf * kWave) * sizeof(double);
+    const bool chain = s->chain_level >= 1 && !part && mesh->dim == 3 && vbytes <= kGatherAheadCapBytes;
+    if (chain) HIP_TRY(hipStreamCreate(&s->stream2));
+    else HIP_TRY(hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&s->ev_mat, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->ev_chain, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&s->ev_jac, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->ev_dots, hipEventDisableTiming));
+    if (chain) {
+      HIP_TRY(s->vals2.alloc((size_t)t.slice_off[t.nslices], true, (size_t)kRowPad * nf * kWave));   // zero padding as in vals
+      s->vals_spare = s->vals2.p;
+      HIP_TRY(hipEventCreateWithFlags(&s->ev_elem, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->ev_gather, hipEventDisableTiming));
+    }
   }
   for (DevBuf<double>* b : {&s->kr, &s->krhat, &s->kp0, &s->kp1, &s->kv0, &s->kv1, &s->ks, &s->kt, &s->ky, &s->kx, &s->kxp, &s->kb}) HIP_TRY(b->alloc(ndof));
   HIP_TRY(s->yc.alloc((size_t)kMaxCoarse * 32));  // [nagg <= 16][ncoarse] column-block products (+ development stamps)
@@ -1787,7 +1877,7 @@ int gmpnp_get_jacobian_csr(gmpnp_solver* s, int32_t* indptr, int32_t* indices, d
   const Topology& t = s->t; const int nf = s->nf;
   std::vector<double> v((size_t)t.slice_off[t.nslices]);
   HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(v.data(), s->vals.p, v.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(v.data(), s->c.vals, v.size() * sizeof(double), hipMemcpyDeviceToHost));   // (c.vals: either of vals / vals2)
   int64_t pos = 0; indptr[0] = 0;
   std::vector<std::pair<int, int>> order;  // (file column node, kpos)
   for (int vf = 0; vf < t.nv; ++vf) {
@@ -2026,7 +2116,7 @@ int gmpnp_debug_read(gmpnp_solver* s, int which, double* out, int64_t n) {
     case 1: src = s->vals_s.p; cap = (int64_t)s->vals_s.n; break;
     case 2: src = s->Dinv.p; cap = (int64_t)s->Dinv.n; break;
     case 3: src = s->c.Aci; cap = (int64_t)s->Aci.n; break;
-    case 4: src = s->vals.p; cap = (int64_t)s->vals.n; break;
+    case 4: src = s->c.vals; cap = (int64_t)s->vals.n; break;
     case 5: src = s->Ac.p; cap = (int64_t)s->Ac.n; break;
     case 6: src = s->kr.p; cap = s->ndof; break;
     case 7: src = s->ky.p; cap = s->ndof; break;

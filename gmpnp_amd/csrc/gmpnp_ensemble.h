@@ -40,6 +40,7 @@ __global__ __launch_bounds__(kVecBlock) void k_res_gather_ens(const EnsMember* _
 template <int DIM, int NF>
 __global__ __launch_bounds__(kVecBlock) void k_jac_gather_ens(const EnsMember* __restrict__ tab, const int32_t* __restrict__ act) {
   const Ctx c = tab[act[blockIdx.y]].c;
+  constexpr bool ROBIN = false;   // members keep k_robin_add_ens
 #include "gmpnp_jac_gather_body.inc"
 }
 template <int NF>

@@ -614,6 +614,20 @@ inline bool accept_predicted_start(double wb, double ww, double bb, double* rnor
   return true;
 }
 
+// Whether the convergence test that follows the update of an iteration is expected to END the solve.  newton() starts the gather
+// of the next Jacobian beside that test; one started for a solve that ends there is thrown away and holds up whatever the caller
+// launches next, so it is not started where the end can be seen coming.  Newton's residual contracts by a near-constant factor from
+// one iteration to the next ((1 - omega) under damping), so the factor observed last is applied once more: r_next = r_now^2 / r_prev,
+// judged by NewtonJudge's own test (rel < rtol or res < atol; r0 = the solve's first residual).  `iterations` counts the update
+// just made: at the limit the verdict cannot be go_on whatever the residual.  No contraction seen, a NaN, no history: no
+// prediction (false).  A wrong answer costs time, never a result: the gather then runs behind the verdict, or is dropped.
+inline bool last_test_expected(double r_prev, double r_now, double r0, double rtol, double atol, int iterations, int maximum_iterations) {
+  if (iterations >= maximum_iterations) return true;
+  if (!(r_prev > 0.0) || !(r_now >= 0.0) || !(r_now < r_prev)) return false;
+  const double r_next = r_now * (r_now / r_prev);
+  return r_next / r0 < rtol || r_next < atol;
+}
+
 // ---- policies of the linear solves inside Newton: each owns its state; newton() / group_newton() ask and report, nothing else --------
 
 // kx holds the predicted start of the next linear solve (left by the previous Newton update).  (The previous time step's total

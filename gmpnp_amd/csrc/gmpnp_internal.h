@@ -41,6 +41,10 @@ constexpr int kSlicePad = 16;       // per-(slice,kpos) column-index record leng
 constexpr int kRowPreMax = GMPNP_ROW_PRELOAD_B > GMPNP_ROW_PRELOAD_A ? (GMPNP_ROW_PRELOAD_B > GMPNP_ROW_PRELOAD ? GMPNP_ROW_PRELOAD_B : GMPNP_ROW_PRELOAD)
                                                                      : (GMPNP_ROW_PRELOAD_A > GMPNP_ROW_PRELOAD ? GMPNP_ROW_PRELOAD_A : GMPNP_ROW_PRELOAD);
 constexpr int kRowPad = GMPNP_KRYLOV_WAVES * kRowPreMax;  // block positions of zero padding behind the last slice
+#ifndef GMPNP_NEWTON_CHAIN_DEFAULT
+#define GMPNP_NEWTON_CHAIN_DEFAULT 2  // Newton's launch chain between two solves: 0 serial, 1 Jacobian gather beside the convergence test, 2 also the folded launches (GMPNP_NEWTON_CHAIN in the environment overrides)
+#endif
+constexpr size_t kGatherAheadCapBytes = (size_t)256 << 20;  // largest matrix that gets the second value buffer of that gather
 
 // Device scalars of one BiCGStab solve.  Each field has ONE writer kernel and is read only by later launches
 // (fields written by kernel A are read by B and vice versa; rho is double-buffered by iteration parity).
@@ -106,6 +110,10 @@ struct Ctx {
   const double* rob_val;     // [n_robin]
   const int64_t* rob_addr;   // [n_robin] address in vals
   const int32_t* rob_row;    // [n_robin] row dof
+  // the same entries by node block, for the gather that adds them itself (k_jac_gather<.., ROBIN>)
+  const int32_t* rob_blk;       // [nb] index of the block's entry set, -1: none
+  const double* rob_blk_val;    // [sets][NF - 1] entry of species row i (column i of the block)
+  const uint32_t* rob_blk_mask; // [sets] bit i: the set holds an entry for species i
   // element intermediates
   double* EF;   // [nc][NN*NF]
   double* EJ;   // [nc][EJ_STRIDE]

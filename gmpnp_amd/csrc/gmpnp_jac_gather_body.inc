@@ -11,6 +11,8 @@
   if (k < 0) return;  // padding stays zero (set at create)
   const int J = c.cols[k];
   const int qb = c.cptr[k], qend = c.cptr[k + 1];
+  int rob = -1;
+  if constexpr (ROBIN) rob = c.rob_blk[k];   // requested with the block's other table entries, used behind the element sum
   const int bc = c.bcflag[I * NF + i];
   double* out = c.vals + c.slice_off[s] + (size_t)kpos * NF * kWave + lane;
   const gmpnp_model_t& m = *c.model;
@@ -89,6 +91,15 @@
 #pragma unroll
         for (int j = 0; j < NF; ++j) acc[j] += row[j];
       }
+    }
+  }
+  if constexpr (ROBIN) {
+    // the block's Robin entries (species rows, diagonal of the block): the one addition k_robin_add makes, on the same operands
+    if (rob >= 0 && !isp) {
+      const double rv = c.rob_blk_val[(size_t)rob * NS + is];
+      const bool has = (c.rob_blk_mask[rob] >> is) & 1;
+#pragma unroll
+      for (int j = 0; j < NS; ++j) if (j == is && has) acc[j] += rv;
     }
   }
   if (bc) {  // [3P] DirichletBC.apply(A): identity row

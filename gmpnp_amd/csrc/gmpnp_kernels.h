@@ -193,7 +193,9 @@ __device__ __forceinline__ int xcd_run_wave(const Ctx& c) {
   const int run = x + kXcds * (j / c.wl_run_blocks), off = j - (j / c.wl_run_blocks) * c.wl_run_blocks;
   return ((run * c.wl_run_blocks + off) * kVecBlock + (int)threadIdx.x) >> 6;
 }
-template <int DIM, int NF>
+// ROBIN: the wave that forms a block also adds the block's Robin entries (rob_blk / rob_blk_val, rebuild_boundary) behind its
+// element sum: what k_robin_add would add to the stored value, without the launch (Newton's chain; every other caller keeps both)
+template <int DIM, int NF, bool ROBIN = false>
 __global__ __launch_bounds__(kVecBlock) void k_jac_gather(const Ctx c) {
 #include "gmpnp_jac_gather_body.inc"   // (textual for the same reason as k_element's)
 }
@@ -1648,9 +1650,10 @@ __global__ void k_axpy(double* __restrict__ y, const double* __restrict__ x, dou
 // Start of a BiCGStab solve in ONE launch (was: copy, two memsets, k_restrict and a host-to-device copy of the scalars):
 // rhat = shadow vector (r_0 unless given), y = 0, restriction partials of r_0 where A(0) expects them, hand-over flags
 // cleared, scalars set from the kernel argument.  One workgroup per tile, as k_restrict.
+// `warm_w` = J x0 of an accepted predicted start: r_0 = b - w is formed here (what k_start_residual leaves) instead of read.
 template <int NF>
 __device__ __forceinline__ void krylov_init_body(const Ctx& c, const double* __restrict__ shadow, const KrylovScalars& init,
-                                                 double* __restrict__ part) {
+                                                 double* __restrict__ part, const double* __restrict__ warm_w = nullptr) {
   __shared__ double lv[kSlicesPerTile * 64];
   const int tile = c.tile0 + blockIdx.x, t = threadIdx.x;
   if (t < kSlicesPerTile * 64) {
@@ -1660,7 +1663,8 @@ __device__ __forceinline__ void krylov_init_body(const Ctx& c, const double* __r
     double v = 0.0;
     if (active) {
       const int idx = (c.slice_node0[s] + Iloc) * NF + i;
-      v = c.kr[idx];
+      if (warm_w) { v = c.kb[idx] - warm_w[idx]; c.kr[idx] = v; }
+      else v = c.kr[idx];
       c.krhat[idx] = shadow ? shadow[idx] : v;
       c.ky[idx] = 0.0;
     }
@@ -1680,8 +1684,8 @@ __device__ __forceinline__ void krylov_init_body(const Ctx& c, const double* __r
 }
 template <int NF>
 __global__ __launch_bounds__(kVecBlock) void k_krylov_init(const Ctx c, const double* __restrict__ shadow, const KrylovScalars init,
-                                                           double* __restrict__ part) {
-  krylov_init_body<NF>(c, shadow, init, part);
+                                                           double* __restrict__ part, const double* __restrict__ warm_w = nullptr) {
+  krylov_init_body<NF>(c, shadow, init, part, warm_w);
 }
 __global__ void k_copy2(double* __restrict__ a, double* __restrict__ b, const double* __restrict__ src, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
