@@ -45,6 +45,7 @@ EXPORTS = [
     "gmpnp_set_kinetics", "gmpnp_kinetics_currents",
     "gmpnp_set_galvanostat", "gmpnp_galvanostat_report", "gmpnp_galvanostat_terms",
     "gmpnp_frequency_response",
+    "gmpnp_frequency_response_3d", "gmpnp_band_lu_shape",
     "gmpnp_electrode_tangent", "gmpnp_tangent_columns", "gmpnp_electrode_advance",
     "gmpnp_parameter_advance", "gmpnp_get_electrode_options",
     "gmpnp_set_electrode_potential", "gmpnp_electrode_trace_open", "gmpnp_electrode_trace_append", "gmpnp_electrode_trace_read",
@@ -305,6 +306,8 @@ def load_library(path: str = None):
     lib.gmpnp_galvanostat_report.argtypes = [c_void_p, POINTER(CGalvanostatReport)]
     lib.gmpnp_galvanostat_terms.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
     lib.gmpnp_frequency_response.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(CResponse), POINTER(c_double)]
+    lib.gmpnp_frequency_response_3d.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(CResponse), POINTER(c_double)]
+    lib.gmpnp_band_lu_shape.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_int32)]
     lib.gmpnp_electrode_tangent.argtypes = [c_void_p, c_int32, POINTER(c_int32), POINTER(CTangent), POINTER(c_double)]
     lib.gmpnp_tangent_columns.argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_electrode_advance.argtypes = [c_void_p, c_double, c_double, POINTER(c_double)]
@@ -706,11 +709,25 @@ class DeviceSolver:
         """``gmpnp_frequency_response`` at the current u and p_M: the small-signal response per unit of p_M at the time-term
         multipliers ``sigmas`` (>= 0, i sigma in the place of inv_dt).  Returns sigma (n,), C (n,) complex, dI (n, n_reactions)
         complex, residual (n,), status (n,) and, with ``want_x``, x (n, ndof) complex in file order."""
+        return self._frequency_response(self.lib.gmpnp_frequency_response, sigmas, want_x)
+
+    def frequency_response_3d(self, sigmas, want_x=False) -> dict:
+        """``gmpnp_frequency_response_3d``: the same response of a 3D handle by the complex block-banded LU; the dictionary of
+        ``frequency_response``.  C and dI are sums over the wall (``electrode_tangent``'s dD and dI at sigma = 0, inv_dt = 0)."""
+        return self._frequency_response(self.lib.gmpnp_frequency_response_3d, sigmas, want_x)
+
+    def band_lu_shape(self):
+        """(node blocks, stored band width) of a 3D handle's block-banded LU (``gmpnp_band_lu_shape``)."""
+        n, band = c_int32(), c_int32()
+        self._check(self.lib.gmpnp_band_lu_shape(self._h, byref(n), byref(band)))
+        return int(n.value), int(band.value)
+
+    def _frequency_response(self, entry, sigmas, want_x) -> dict:
         sg = np.ascontiguousarray(sigmas, dtype=np.float64).ravel()
         n = int(sg.size)
         out = (CResponse * max(n, 1))()
         x = np.empty((n, self.ndof, 2)) if want_x else None
-        self._check(self.lib.gmpnp_frequency_response(self._h, n, _dptr(sg), out, None if x is None else _dptr(x)))
+        self._check(entry(self._h, n, _dptr(sg), out, None if x is None else _dptr(x)))
         rec = np.frombuffer(out, dtype=np.dtype([("sigma", "f8"), ("C", "f8", 2), ("dI", "f8", (MAX_SURFACE_REACTIONS, 2)), ("residual", "f8"),
                                                  ("status", "i4"), ("pad", "i4")]), count=n)
         res = {"sigma": rec["sigma"].copy(), "C": rec["C"][:, 0] + 1j * rec["C"][:, 1],

@@ -173,6 +173,24 @@ struct gmpnp_responder {
   ~gmpnp_responder() { if (h_out) (void)hipHostFree(h_out); if (h_x) (void)hipHostFree(h_x); }
 };
 
+// device side of gmpnp_frequency_response_3d (gmpnp_response_band.h), allocated by the first call: a handle that never asks for it keeps
+// the buffers and launches it had.  The complex band is storage of the response's own; the handle's real BandLU is not touched.
+namespace gmpnp { struct CBandState; }
+struct gmpnp_band_responder {
+  DevBuf<double> mass, rhs, kvals;     // [nb] mass per node block; b = dF/dp_M (internal order); the SELL values of K = J at inv_dt = 0
+  DevBuf<double> sigma, rmax;          // the chunk's sigma; [chunk][nslices] residual maxima
+  DevBuf<double2> band, dinv;          // [chunk][n][2b+1][81], [chunk][n][81]
+  DevBuf<double2> x, r, dx, y, part;   // [chunk][ndof] each; [chunk][16][4][9] partial sums of the substitution
+  DevBuf<int32_t> pos, node, fstat, status;   // elimination order; per-frequency word of the pivots; the word of the set-up's own launches
+  DevBuf<gmpnp::CBandState> st;
+  DevBuf<gmpnp::RespOut> out;
+  int n = 0, b = 0;
+  size_t cap_freq = 0;                 // frequencies the chunk storage holds
+  int last_chunk = 0;                  // frequencies of the last chunk solved (gmpnp_time_kernel 30)
+  gmpnp::RespOut* h_out = nullptr;     // pinned [cap_freq]
+  ~gmpnp_band_responder() { if (h_out) (void)hipHostFree(h_out); }
+};
+
 // device side of gmpnp_electrode_tangent / gmpnp_electrode_advance (gmpnp_tangent.h), allocated by the first call: a handle that never
 // asks for it keeps the buffers and launches it had
 namespace gmpnp { struct TanOut; }
@@ -289,6 +307,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_kineticist> kineticist;
   std::unique_ptr<gmpnp_galvanostat> galvanostat;
   std::unique_ptr<gmpnp_responder> responder;
+  std::unique_ptr<gmpnp_band_responder> band_responder;
   std::unique_ptr<gmpnp_tangenter> tangenter;
   std::unique_ptr<gmpnp_tracer> tracer;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
@@ -359,6 +378,9 @@ int newton_galvanostat(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_n
 // gmpnp_response.h: the two launches of the last chunk of the last gmpnp_frequency_response (gmpnp_time_kernel 27)
 bool response_has_chunk(const gmpnp_solver* s);
 int response_time_chunk(gmpnp_solver* s);
+// gmpnp_response_band.h: every launch of the last chunk of the last gmpnp_frequency_response_3d (gmpnp_time_kernel 30)
+bool response_band_has_chunk(const gmpnp_solver* s);
+int response_band_time_chunk(gmpnp_solver* s);
 // gmpnp_tangent.h: the multi-column chain(s) of the last gmpnp_electrode_tangent (gmpnp_time_kernel 28); whatever changes u, p_M or an
 // option drops the tangent the advance would use
 bool tangent_has_chain(const gmpnp_solver* s);
@@ -1996,6 +2018,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (kernel == 27 && !response_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 27 is one chunk of the frequency response: no call has been made (gmpnp_frequency_response)");
   if (kernel == 28 && !tangent_has_chain(s)) return fail(GMPNP_ERR_INVALID, "kernel 28 is the multi-column chain of the electrode tangent: no call has been made on this Jacobian (gmpnp_electrode_tangent, 1D)");
   if (kernel == 29 && !trace_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 29 is one append of the electrode trace: no trace is open (gmpnp_electrode_trace_open)");
+  if (kernel == 30 && !response_band_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 30 is one chunk of the 3D frequency response: no call has been made (gmpnp_frequency_response_3d), or the Stern option is off");
   if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
@@ -2039,6 +2062,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 27: r = response_time_chunk(s); break;   // k_response_solve + k_response_functional on the last chunk's frequencies
       case 28: r = tangent_time_chain(s); break;    // extraction, k_bcr_forward_cols / k_bcr_tail_cols / k_bcr_backward_cols, application
       case 29: r = trace_time_append(s); break;     // k_stern_residual + k_kinetics_residual (kinetics on) + k_electrode_record
+      case 30: r = response_band_time_chunk(s); break;   // scatter, k_cband_step per pivot, the solve and three refinement rounds, k_cband_functional
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -2164,3 +2188,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_response.h"
 #include "gmpnp_tangent.h"
 #include "gmpnp_trace.h"
+#include "gmpnp_response_band.h"

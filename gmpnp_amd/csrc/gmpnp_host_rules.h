@@ -174,6 +174,55 @@ inline int response_chunk(int n, int nv, double cap_bytes) {
   return c;
 }
 
+// ---- frequency response of the 3D pore (include/gmpnp.h "frequency response, 3D"; kernels: gmpnp_response_band.h) -------------------
+// The same system on the block band of the 3D handle: (K + i sigma M) x = -b by a complex block-banded LU.  C and dI_r are the tangent's
+// facet-wise functionals (tangent_current_term above all) applied to Re x and Im x separately; the explicit d/dp_M part (the slope of
+// the Stern term, -d_p of a rate) goes to the real part alone.  One facet's share of (Stern row of J).x towards its node a from its
+// node b: se_fn = sum_j epsc_j x_{b,j} / FN, m_ab the facet's P1 mass entry, w_a = int (p_M - p) phi_a ds:
+GMPNP_RULE_HD inline double response_facet_term(double g, double dg, double lam, double w_a, double m_ab, double se_fn, double x_p) {
+  GMPNP_RULE_NO_CONTRACT
+  return dg * se_fn * w_a / lam - g * m_ab / lam * x_p;
+}
+// bytes of complex band one frequency takes: n (2 b + 1) blocks of nf x nf (re, im) pairs
+inline double response_band_bytes_per_frequency(int n, int b, int nf) { return (double)n * (2.0 * b + 1.0) * nf * nf * 16.0; }
+// frequencies per chunk under the band LU's memory cap: at least one, at most n (a band above the cap for ONE frequency is refused by
+// the caller before this rule is asked)
+inline int response_band_chunk(int n, int n_blocks, int b, int nf, double cap_bytes) {
+  double k = std::floor(cap_bytes / response_band_bytes_per_frequency(n_blocks, b, nf));
+  if (!(k >= 1.0)) k = 1.0;
+  return k >= (double)n ? n : (int)k;
+}
+// Gauss-Jordan inverse of one complex NF x NF block with partial pivoting inside the block: the statement of what the device's 16-lane
+// group does (group16_inverse_cx).  Column k's pivot is the row r >= k with the largest |re| + |im| (ties: the lower row), which changes
+// places with row k.  pivot_row[k] = that row; returns true where a pivot column was all zero or not a number.  A and inv: row major.
+template <int NF>
+inline bool response_block_inverse(const Cx* A, Cx* inv, int* pivot_row) {
+  Cx row[NF][2 * NF];
+  for (int r = 0; r < NF; ++r)
+    for (int j = 0; j < NF; ++j) { row[r][j] = A[r * NF + j]; row[r][NF + j] = Cx{j == r ? 1.0 : 0.0, 0.0}; }
+  bool bad = false;
+  for (int k = 0; k < NF; ++k) {
+    int idx = k; double v = response_pivot_key(row[k][k]);
+    for (int r = k + 1; r < NF; ++r) { const double o = response_pivot_key(row[r][k]); if (o > v) { v = o; idx = r; } }
+    if (!(v > 0.0)) bad = true;   // (the block's status says so; what the inverse then holds is not used)
+    pivot_row[k] = idx;
+    const Cx ip = cx_inv(row[idx][k]);
+    Cx piv[2 * NF], oldk[2 * NF];
+    for (int j = 0; j < 2 * NF; ++j) { piv[j] = row[idx][j]; oldk[j] = row[k][j]; }
+    for (int r = 0; r < NF; ++r) {
+      const Cx* mine = (r == idx) ? oldk : row[r];
+      const Cx f = cx_mul(mine[k], ip);
+      Cx out[2 * NF];
+      for (int j = k + 1; j < 2 * NF; ++j) out[j] = (r == k) ? cx_mul(piv[j], ip) : cx_sub(mine[j], cx_mul(f, piv[j]));
+      for (int j = k + 1; j < 2 * NF; ++j) row[r][j] = out[j];
+      row[r][k] = Cx{r == k ? 1.0 : 0.0, 0.0};
+    }
+  }
+  for (int r = 0; r < NF; ++r)
+    for (int j = 0; j < NF; ++j) inv[r * NF + j] = row[r][NF + j];
+  return bad;
+}
+
 // ---- electrode tangent and polarisation curves (include/gmpnp.h "electrode tangent"; kernels: gmpnp_tangent.h) ----------------------
 // The tangent z = du/dtheta of F(u; theta) = 0 solves J z = -dF/dtheta.  Parameter codes: 0 = p_M, 16 + r = ln k_r, 32 + r = alpha_r,
 // 48 = ln lam; kinds 0 ... 3 in that order, -1 = unknown.  The explicit derivatives at a boundary node, per unit weight:

@@ -132,6 +132,8 @@ class EDLRun:
         if self.polarisation_par is not None:
             from .polarisation import check_polarisation
             self.polarisation_par = check_polarisation(self.polarisation_par, kwargs, dt_order)
+        from .impedance import refuse_pore_impedance
+        refuse_pore_impedance(kwargs, "the 1D double-layer driver", hint=": its spectrum is the keyword impedance (--impedance)")
         self.impedance_par = kwargs.pop("impedance", None) or None
         if self.impedance_par is not None:
             from .impedance import frequency_grid

@@ -15,7 +15,7 @@ import itertools
 
 from . import backend
 from .edl1d import EDLRun, run_identifier
-from .impedance import refuse_impedance
+from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
 from .programme import refuse_programme
@@ -46,6 +46,7 @@ def plan_members(members, num_steps=None):
     full = []
     for k, m in enumerate(members):
         refuse_impedance(m, "an ensemble (member %d)" % k)
+        refuse_pore_impedance(m, "an ensemble (member %d)" % k)
         refuse_polarisation(m, "an ensemble (member %d)" % k)
         refuse_fit(m, "an ensemble (member %d)" % k)
         refuse_programme(m, "an ensemble (member %d)" % k)

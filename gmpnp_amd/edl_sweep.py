@@ -20,7 +20,7 @@ from datetime import datetime
 
 from . import backend
 from .edl1d import output_root
-from .impedance import refuse_impedance
+from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
 from .programme import refuse_programme
@@ -55,6 +55,7 @@ def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget
     ``adaptive``: the adaptive-stepping keywords of ``EDLEnsemble`` (scalars: the same for every member)."""
     for k, m in enumerate(members):
         refuse_impedance(m, "the ensemble sweep (member %d)" % k)
+        refuse_pore_impedance(m, "the ensemble sweep (member %d)" % k)
         refuse_polarisation(m, "the ensemble sweep (member %d)" % k)
         refuse_fit(m, "the ensemble sweep (member %d)" % k)
         refuse_programme(m, "the ensemble sweep (member %d)" % k)
@@ -62,6 +63,7 @@ def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget
         refuse_stern(m, "the ensemble sweep (member %d)" % k)
         refuse_kinetics(m, "the ensemble sweep (member %d)" % k)
     refuse_impedance(adaptive, "the ensemble sweep")
+    refuse_pore_impedance(adaptive, "the ensemble sweep")
     refuse_polarisation(adaptive, "the ensemble sweep")
     refuse_fit(adaptive, "the ensemble sweep")
     refuse_programme(adaptive, "the ensemble sweep")

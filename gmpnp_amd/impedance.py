@@ -117,6 +117,138 @@ def high_frequency_capacitance(coords, u2d, model, stern):
     return 1.0 / (stern.lam / g + float(np.sum(h / eps_e)))
 
 
+# ---- the 3D pore (gmpnp_frequency_response_3d) ----------------------------------------------------------------------
+def facet_term(g, dg, lam, w_a, m_ab, se_fn, x_p):
+    """One facet's share of (Stern row of J).x towards its node a from its node b (``response_facet_term``), applied to the real and
+    to the imaginary part of x: g' se_fn w_a / lam - g m_ab / lam x_p, se_fn = sum_j epsc_j x_{b,j} / 3."""
+    g, dg, lam = np.float64(g), np.float64(dg), np.float64(lam)
+    return float(dg * np.float64(se_fn) * np.float64(w_a) / lam - g * np.float64(m_ab) / lam * np.float64(x_p))
+
+
+def band_bytes_per_frequency(n_blocks, band, nf=9):
+    """Bytes of complex band one frequency takes (``response_band_bytes_per_frequency``): n (2 b + 1) blocks of nf x nf pairs."""
+    return float(n_blocks) * (2.0 * band + 1.0) * nf * nf * 16.0
+
+
+def band_chunk(n, n_blocks, band, nf, cap_bytes):
+    """Frequencies per chunk under the band LU's memory cap (``response_band_chunk``): at least one, at most n."""
+    k = math.floor(cap_bytes / band_bytes_per_frequency(n_blocks, band, nf)) if math.isfinite(cap_bytes) else float("inf")
+    if not k >= 1.0:
+        k = 1.0
+    return n if k >= n else int(k)
+
+
+def block_inverse(A):
+    """(inverse, pivot rows, bad) of one complex block by the rule's Gauss-Jordan (``response_block_inverse``): column k's pivot is the
+    row r >= k with the largest |re| + |im|, ties to the lower row, and changes places with row k."""
+    A = np.asarray(A, dtype=np.complex128)
+    n = A.shape[0]
+    row = np.concatenate([A, np.eye(n, dtype=np.complex128)], axis=1)
+    piv, bad = [], False
+    for k in range(n):
+        idx, v = k, pivot_key(row[k, k])
+        for r in range(k + 1, n):
+            o = pivot_key(row[r, k])
+            if o > v:
+                idx, v = r, o
+        bad = bad or not v > 0.0
+        piv.append(idx)
+        with np.errstate(all="ignore"):
+            ip = 1.0 / row[idx, k]
+            pr, old = row[idx].copy(), row[k].copy()
+            for r in range(n):
+                mine = old if r == idx else row[r].copy()
+                row[r] = pr * ip if r == k else mine - (mine[k] * ip) * pr
+                row[r, k] = 1.0 if r == k else 0.0
+    return row[:, n:], piv, bad
+
+
+def pore_sigma_from_frequency(pp, frequency):
+    """sigma of a harmonic perturbation of ``frequency`` [Hz] on the pore driver's scaling: ``PoreParameters`` builds
+    ``model.inv_dt`` = 1 / dt with dt = time_step / time_constant, so sigma = 2 pi f time_constant."""
+    return 2.0 * math.pi * np.asarray(frequency, dtype=np.float64) * pp.time_constant
+
+
+def pore_spectrum(pp, eps_0, wall_area, frequency, response):
+    """The physical spectrum of one ``DeviceSolver.frequency_response_3d`` result, per wall area: the library's C and dI are sums over
+    the wall, ``wall_area`` = sum_I w_I (scaled) makes them wall means as the polarisation curve reports its currents and capacitance.
+    capacitance = eps_0 / L C / area [F/m2], dI_dV = dI / area / thermal_voltage [S/m2], Y = i omega C - sum_r dI_r/dV, Z = 1 / Y."""
+    f = np.asarray(frequency, dtype=np.float64)
+    cap = eps_0 / pp.L * np.asarray(response["C"]) / wall_area
+    dI = np.asarray(response["dI"]).reshape(len(f), -1) / wall_area / pp.thermal_voltage
+    Y = 1j * 2.0 * math.pi * f * cap - dI.sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Z = 1.0 / Y
+    return {"frequency": f, "sigma": np.asarray(response["sigma"]), "capacitance": cap, "dI_dV": dI, "admittance": Y, "impedance": Z,
+            "residual": np.asarray(response["residual"]), "status": np.asarray(response["status"])}
+
+
+def potential_block_capacitance(K, b, potential_rows, functional):
+    """The high-frequency reference of C, scaled units: with the concentrations frozen (sigma -> infinity) x keeps its potential
+    entries alone, and they solve the potential block of K: K_pp x_p = -b_p.  ``K`` a SciPy sparse matrix, ``potential_rows`` the
+    potential dofs (Dirichlet identity rows included), ``functional(x)`` the real functional C of a real x (explicit part included)."""
+    import scipy.sparse.linalg as spla
+    rows = np.asarray(potential_rows, dtype=np.int64)
+    Kpp = K.tocsr()[rows][:, rows].tocsc()
+    x = np.zeros(K.shape[0])
+    x[rows] = spla.splu(Kpp).solve(-np.asarray(b, dtype=np.float64)[rows])
+    return functional(x), x
+
+
+def pore_stern_terms(coords, wall_facets, model, stern, bc_dofs, u2d, x2d=None):
+    """(C, b) facet by facet over the wall (the Python statement of the Stern part of ``k_cband_functional`` and of
+    ``k_response_rhs<3, 9>``): C = dD/dp_M + (dD/du).x of the complex (or real) x, the explicit part g |f| / (3 lam) per free wall node
+    of a facet in the real part alone, and b = the Stern rows of dF/dp_M (ndof,).  ``x2d`` None: x = 0 (C = dD/dp_M).  g and g' at
+    the facet mean of eps(u), w_a = |f| (p_M / 3 - (sum p + p_a) / 12), the facet mass |f| (1 + delta_ab) / 12."""
+    from .stern import coupled_g
+    u2d = np.asarray(u2d, dtype=np.float64)
+    nf, ns = u2d.shape[1], u2d.shape[1] - 1
+    x2d = np.zeros(u2d.shape, dtype=np.complex128) if x2d is None else np.asarray(x2d, dtype=np.complex128).reshape(u2d.shape)
+    eps0, epsc = float(model.eps0), np.asarray(model.epsc, dtype=np.float64)[:ns]
+    bc = set(int(r) for r in bc_dofs)
+    X = np.asarray(coords, dtype=np.float64)[np.asarray(wall_facets, dtype=np.int64)]
+    areas = 0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)
+    pM, lam = float(stern.p_electrode), float(stern.lam)
+    C, b = 0j, np.zeros(u2d.size)
+    for nd, area in zip(np.asarray(wall_facets, dtype=np.int64), areas):
+        g, dg = coupled_g(stern.model, eps0 + float(epsc @ u2d[nd, :ns].mean(axis=0)), stern.eps_surface)
+        p = u2d[nd, ns]
+        se = [complex(epsc @ x2d[q, :ns].real, epsc @ x2d[q, :ns].imag) / 3.0 for q in nd]
+        for a in range(3):
+            if int(nd[a]) * nf + ns in bc:
+                continue
+            wa = area * (pM / 3.0 - (p.sum() + p[a]) / 12.0)
+            b[int(nd[a]) * nf + ns] += g * (area / 3.0) / lam
+            re, im = g * (area / 3.0) / lam, 0.0
+            for q in range(3):
+                mab = area * (2.0 if a == q else 1.0) / 12.0
+                re += facet_term(g, dg, lam, wa, mab, se[q].real, x2d[nd[q], ns].real)
+                im += facet_term(g, dg, lam, wa, mab, se[q].imag, x2d[nd[q], ns].imag)
+            C += complex(re, im)
+    return C, b
+
+
+def add_pore_impedance_arguments(p):
+    p.add_argument("--pore_impedance", action="store_true",
+                   help="(addition) impedance spectrum of the pore at the last state (pore_impedance.npz); needs --electrode_voltage")
+    p.add_argument("--freq_min", required=False, default=1e-2, type=float, help="(addition) lowest frequency of --pore_impedance [Hz]")
+    p.add_argument("--freq_max", required=False, default=1e8, type=float, help="(addition) highest frequency of --pore_impedance [Hz]")
+    p.add_argument("--freq_per_decade", required=False, default=10, type=int, help="(addition) points per decade of --pore_impedance")
+
+
+def pore_impedance_keywords(a):
+    """The keyword of a parsed command line (``add_pore_impedance_arguments``); empty without --pore_impedance."""
+    if not a.pore_impedance:
+        return {}
+    return {"pore_impedance": dict(freq_min=a.freq_min, freq_max=a.freq_max, per_decade=a.freq_per_decade)}
+
+
+def refuse_pore_impedance(kwargs, what, hint=""):
+    """ValueError where ``kwargs`` asks for the pore's impedance spectrum (``pore_impedance``) in a driver that has none."""
+    if kwargs.get("pore_impedance"):
+        raise ValueError("pore_impedance: the 3D frequency response is not available in %s%s" % (what, hint))
+
+
 # ---- keywords of the drivers -----------------------------------------------------------------------------------------------------
 def add_impedance_arguments(p):
     p.add_argument("--impedance", action="store_true",

@@ -23,6 +23,7 @@ from .problem import (Galvanostat, add_galvanostat_arguments, add_kinetics_argum
 from .solver import GMPNPSystem, column_medians, device_medians_and_minima
 from .timestep import DriverStepping, adaptive_keywords, add_adaptive_arguments
 from .polarisation import add_polarisation_arguments, polarisation_keywords
+from .impedance import add_pore_impedance_arguments, pore_impedance_keywords
 from .vtk import write_pvd
 
 SOLVER_PARAMETERS = {  # reference 3D:789-798
@@ -94,7 +95,14 @@ class PoreRun:
         ``polarisation`` = dict(v_end=X, v_step=Y[, params=(0, ...)]) (thermal voltages; with ``electrode_voltage``): ``write_outputs``
         walks the steady-state polarisation curve from the run's last state and potential (``polarisation()``)
         and adds ``polarisation.npz`` and the ``polarisation_*`` metadata keys.  Not with ``target_current``, ``dt_order`` 2,
-        ``partition`` or ``multilevel`` (ValueError, before anything touches the device)."""
+        ``partition`` or ``multilevel`` (ValueError, before anything touches the device).
+        ``pore_impedance`` = dict(freq_min=1e-2, freq_max=1e8, per_decade=10) [Hz] (with ``electrode_voltage``): ``write_outputs``
+        computes the impedance spectrum of the pore at the run's last state (``pore_impedance()`` does the same at
+        any time) and adds ``pore_impedance.npz`` (frequency, sigma, capacitance [F/m2], admittance [S/m2], impedance [Ohm m2], dI_CO,
+        dI_H2 [S/m2], residual; all per wall area) and the metadata keys ``pore_impedance_points``, ``pore_impedance_status``,
+        ``capacitance_low`` / ``capacitance_high``, ``capacitance_high_closed_form`` (the potential block alone), ``R_ct`` (None
+        without kinetics) and ``pore_impedance_last_step_change``.  Not with ``partition``, ``multilevel`` or the device glue; a
+        galvanostat is switched off for the call.  The keyword ``impedance`` is the 1D driver's and stays refused here."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
         from .impedance import refuse_impedance
@@ -111,6 +119,22 @@ class PoreRun:
             if multilevel:
                 raise ValueError("polarisation: the curve is not available with the geometric multilevel term")
             self.polarisation_par = check_polarisation(self.polarisation_par, kwargs, dt_order)
+        self.pore_impedance_par = kwargs.pop("pore_impedance", None) or None
+        if self.pore_impedance_par is not None:
+            from .impedance import frequency_grid
+            if kwargs.get("electrode_voltage") is None:
+                raise ValueError("pore_impedance: the frequency response needs an electrode potential (electrode_voltage)")
+            if partition:
+                raise ValueError("pore_impedance: the frequency response is not available in a partitioned solve")
+            if multilevel:
+                raise ValueError("pore_impedance: the frequency response is not available with the geometric multilevel term")
+            if glue != "host":
+                raise ValueError("pore_impedance: the frequency response runs with the host glue")
+            self.pore_impedance_par = dict(self.pore_impedance_par)
+            try:
+                frequency_grid(**self.pore_impedance_par)   # a bad grid is refused before anything touches the device
+            except ValueError as e:
+                raise ValueError("pore_" + str(e)) from None
         self.stern = pop_stern(kwargs, kwargs.get("L", 100.0e-9))
         self.kinetic_par = pop_kinetics(kwargs)
         self.target_current = pop_galvanostat(kwargs)
@@ -370,6 +394,63 @@ class PoreRun:
                 "polarisation_params": [int(q) for q in out["sensitivity_params"]],
                 "polarisation_sechenov_rounds": int(out["sechenov_rounds"].max())}
 
+    def pore_impedance(self, frequencies):
+        """The impedance spectrum of the pore at the run's CURRENT state and electrode potential, at ``frequencies`` [Hz], per wall
+        area (gmpnp_amd/impedance.py: ``pore_spectrum``; one ``gmpnp_frequency_response_3d`` call).  A
+        galvanostatic run switches its galvanostat off for the call (that keeps the potential it found) and on again with the same
+        target.  Refused where ``polarisation`` is: partitions, the multilevel term, the device glue."""
+        from . import impedance as imp
+        if self.stern is None:
+            raise ValueError("pore_impedance: the frequency response needs an electrode potential (electrode_voltage)")
+        if self.glue != "host" or self._levels is not None or self.rank is not None:
+            raise ValueError("pore_impedance: the frequency response runs on one unpartitioned handle without the multilevel term (host glue)")
+        f = np.atleast_1d(np.asarray(frequencies, dtype=np.float64))
+        if not imp.count_valid(f.size) or not np.all(np.isfinite(f)) or np.any(f < 0.0):
+            raise ValueError("pore_impedance: 1 ... %d finite frequencies >= 0" % imp.MAX_FREQUENCIES)
+        dev = self.sys.dev
+        if self.galvanostat is not None:
+            dev.set_galvanostat(None)
+        try:
+            res = dev.frequency_response_3d(imp.pore_sigma_from_frequency(self.pp, f))
+        finally:
+            if self.galvanostat is not None:
+                dev.set_galvanostat(self.galvanostat)
+        return imp.pore_spectrum(self.pp, self._eps_0(), self.wall_area(), f, res)
+
+    def _eps_0(self):
+        from .params import _load_yaml
+        return _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters_pore") + ".yaml"))["nat_const"]["eps_0"]
+
+    def pore_impedance_outputs(self, newpath):
+        """``pore_impedance.npz`` of the last state and the metadata keys that go with it.  ``capacitance_high_closed_form``: the
+        concentrations frozen, x_p solves the potential block of the device's own Jacobian (``impedance.potential_block_capacitance``)."""
+        from . import impedance as imp
+        sp = self.pore_impedance(imp.frequency_grid(**self.pore_impedance_par))
+        nr = sp["dI_dV"].shape[1]
+        zero = np.zeros(len(sp["frequency"]), dtype=complex)
+        np.savez(os.path.join(newpath, "pore_impedance.npz"), frequency=sp["frequency"], sigma=sp["sigma"], capacitance=sp["capacitance"],
+                 admittance=sp["admittance"], impedance=sp["impedance"], dI_CO=sp["dI_dV"][:, 0] if nr > 0 else zero,
+                 dI_H2=sp["dI_dV"][:, 1] if nr > 1 else zero, residual=sp["residual"])
+        eps_0 = self._eps_0()
+        dev, prob = self.sys.dev, self.problem
+        p_M = self.potentials[-1] if self.potentials else self.stern.p_electrode
+        stern = type(self.stern)(self.stern.model, p_M, self.stern.lam, self.stern.eps_surface)
+        nf = prob.nf
+        u2d = dev.get_state().reshape(-1, nf)
+        dev.assemble(True)   # (the potential block of J does not depend on inv_dt: the mass sits on the species rows)
+        K = dev.jacobian_csr()
+        bc = self.sys.problem.bc_dofs
+        _, b = imp.pore_stern_terms(prob.coords, prob.wall_facets, prob.model, stern, bc, u2d)
+        c_inf, _ = imp.potential_block_capacitance(K, b, np.arange(nf - 1, prob.ndof, nf),
+                                                   lambda x: imp.pore_stern_terms(prob.coords, prob.wall_facets, prob.model, stern, bc, u2d, x.reshape(-1, nf))[0].real)
+        c_inf = c_inf * eps_0 / self.pp.L / self.wall_area()
+        g_ct = -float(sp["dI_dV"][0].sum().real) if nr else 0.0
+        change = float(np.abs(self.history[-1] - self.history[-2]).max()) if len(self.history) > 1 else None
+        return {"pore_impedance_points": int(len(sp["frequency"])), "capacitance_low": float(sp["capacitance"][0].real),
+                "capacitance_high": float(sp["capacitance"][-1].real), "capacitance_high_closed_form": float(c_inf),
+                "R_ct": (1.0 / g_ct) if g_ct != 0.0 else None, "pore_impedance_last_step_change": change,
+                "pore_impedance_status": int(np.bitwise_or.reduce(sp["status"]))}
+
     def wall_area(self):
         X = self.problem.coords[self.problem.wall_facets]
         return float((0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)).sum())
@@ -470,6 +551,8 @@ class PoreRun:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
             self.stepping.save(newpath, metadata_dict)
+        if self.pore_impedance_par is not None:   # at the run's last state, before the polarisation curve moves the handle
+            metadata_dict.update(self.pore_impedance_outputs(newpath))
         if self.polarisation_par is not None:   # last: the handle leaves the run's operating point
             metadata_dict.update(self.polarisation_outputs(newpath))
         with open(newpath + "metadata.json", "w") as fh:
@@ -483,7 +566,7 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
              device_kwargs=None, glue="host", budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM", stern_length=4.0e-10,
              stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0, p_eq_H2=0.0, target_current=None, polarisation=None,
-             **adaptive):
+             pore_impedance=None, **adaptive):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
     geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
@@ -502,6 +585,8 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
         stern.update(target_current=target_current)
     if polarisation:   # (the polarisation curve of ``PoreRun``, after the last step)
         stern.update(polarisation=polarisation)
+    if pore_impedance:   # (the impedance spectrum of ``PoreRun``, at the last state)
+        stern.update(pore_impedance=pore_impedance)
     run = PoreRun(**stern, num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
                   device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
@@ -545,6 +630,7 @@ def build_parser():
     add_kinetics_arguments(p)   # (with --electrode_voltage; not with --partitions / --multilevel)
     add_polarisation_arguments(p)  # (with --electrode_voltage; not with --partitions / --multilevel / --target_current / --dt_order 2)
     add_galvanostat_arguments(p)   # (with --kinetics tafel; not with --partitions / --multilevel / --dt_order 2)
+    add_pore_impedance_arguments(p)   # (with --electrode_voltage; not with --partitions / --multilevel)
     return p
 
 
@@ -591,7 +677,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a), **polarisation_keywords(a), **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a), **polarisation_keywords(a), **pore_impedance_keywords(a), **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

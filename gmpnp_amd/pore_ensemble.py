@@ -16,7 +16,7 @@ import numpy as np
 from . import backend
 from .edl_ensemble import ADAPTIVE_REFUSAL, AdaptiveRounds, error_text
 from .pore3d import SOLVER_PARAMETERS, PoreRun
-from .impedance import refuse_impedance
+from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
 from .programme import refuse_programme
@@ -43,6 +43,7 @@ def plan_members(members, num_steps=None):
     full = []
     for k, m in enumerate(members):
         refuse_impedance(m, "an ensemble (member %d)" % k)
+        refuse_pore_impedance(m, "an ensemble (member %d)" % k)
         refuse_polarisation(m, "an ensemble (member %d)" % k)
         refuse_fit(m, "an ensemble (member %d)" % k)
         refuse_programme(m, "an ensemble (member %d)" % k)

@@ -27,7 +27,7 @@ from . import backend, timestep
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .model import Model
 from .params import _load_yaml, _reaction_tables, utilities_dir
-from .impedance import refuse_impedance
+from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
 from .programme import refuse_programme
@@ -144,6 +144,7 @@ class RxnDiffRun:
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history and the budget log as they were.  Off: nothing changes."""
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_pore_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")

@@ -25,7 +25,7 @@ from . import backend, timestep
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import pore_parameters, utilities_dir
 from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
-from .impedance import refuse_impedance
+from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
 from .programme import refuse_programme
@@ -65,6 +65,7 @@ class RxnPoreRun:
         (gmpnp_amd/timestep.py; not a reference feature): the step size is the error controller's, ``inv_dt = 1/h``; a rejected step
         leaves the clock, the history, the budget log and the CO2 Dirichlet value as they were.  Off: nothing changes."""
         refuse_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_pore_impedance(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")

@@ -55,12 +55,13 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
     (``num_steps`` is not used) and its summary gets ``stop_reason``, ``steps_accepted`` and ``steps_rejected``."""
     if adaptive.get("adaptive_dt") and ramp_steps > 0:
         raise ValueError("--adaptive_dt: the voltage ramp (--ramp_steps) counts fixed steps")
-    from .impedance import refuse_impedance
+    from .impedance import refuse_impedance, refuse_pore_impedance
     from .polarisation import refuse_polarisation
     from .fit import refuse_fit
     from .programme import refuse_programme
     from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
     refuse_impedance(adaptive, "the pore sweep")
+    refuse_pore_impedance(adaptive, "the pore sweep")
     refuse_polarisation(adaptive, "the pore sweep")
     refuse_fit(adaptive, "the pore sweep")
     refuse_programme(adaptive, "the pore sweep")
@@ -107,7 +108,7 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
 
 
 def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, write=False, as_published=False, ramp_steps=0,
-            one_stream=False, L=50e-9, device_kwargs=None, budget=False, electrode_voltage=None, kinetics=None, target_current=None, impedance=None):
+            one_stream=False, L=50e-9, device_kwargs=None, budget=False, electrode_voltage=None, kinetics=None, target_current=None, impedance=None, pore_impedance=None):
     """One pore run of ``num_steps`` time steps; returns a small summary dict (never raises for a diverged Newton).
 
     ``ramp_steps`` > 0 is a continuation the reference does not have: the wall potential Dirichlet value (bc3 of
@@ -115,9 +116,10 @@ def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, 
     Newton from the zero state diverges for |voltage_multiplier| >= 5 (as published) or > 1 (with the wall fluxes),
     in the CPU oracle exactly as on the GPU.  ``electrode_voltage`` (the Stern boundary condition of ``PoreRun``) is refused
     with ValueError: the sweep prescribes and ramps the wall potential itself; so is ``kinetics`` (the surface kinetics need it)."""
-    from .impedance import refuse_impedance
+    from .impedance import refuse_impedance, refuse_pore_impedance
     from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
     refuse_impedance({"impedance": impedance}, "the pore sweep")
+    refuse_pore_impedance({"pore_impedance": pore_impedance}, "the pore sweep")
     refuse_galvanostat({"target_current": target_current}, "the pore sweep")
     refuse_stern({"electrode_voltage": electrode_voltage}, "the pore sweep")
     refuse_kinetics({"kinetics": kinetics}, "the pore sweep")

@@ -637,6 +637,32 @@ typedef struct {
 int gmpnp_frequency_response(gmpnp_solver* s, int32_t n, const double* sigma /* [n] */, gmpnp_response_t* out /* [n] */,
                              double* x_out /* [n][n_dofs][2] in file order, or NULL */);
 
+/* ---- frequency response, 3D (the same response on the 3D pore: a complex block-banded LU) ------------------------------------------
+ * 3D handles with the Stern option on; arguments, records and semantics of gmpnp_frequency_response with the 3D terms of the
+ * galvanostat and of the tangent: K = J(u) at inv_dt = 0 with the Stern rows facet by facet, the kinetic rows and the Dirichlet
+ * identity rows; M = the consistent P1 tetrahedron mass (vol / 20 (1 + delta_ab), formed from the mesh as the Jacobian gather forms it,
+ * one double per node block) on the species rows that carry no Dirichlet value; b = dF/dp_M as gmpnp_galvanostat_terms returns it.
+ * C and dI_r are the tangent's facet-wise functionals applied to Re x and Im x separately, the explicit d/dp_M part in the real part
+ * alone; they are the sums over the wall (gmpnp_electrode_tangent's dD and dI of the p_M column at sigma = 0 and inv_dt = 0), a wall
+ * mean divides them by sum_I w_I.  (K + i sigma M) x = -b is solved by a complex block-banded LU in the elimination order of the real
+ * one (partial pivoting inside the 9 x 9 pivot blocks, key |re| + |im|), refined on the device by up to three rounds while the
+ * residual max |(K + i sigma M) x + b| is above 1e-10 max |b| and halves.  The band, n (2 b + 1) 81 (re, im) pairs per frequency, is
+ * storage of the response's own; frequencies go through the launches in chunks sized from gmpnp_options_t.band_lu_max_gb with one
+ * host synchronisation per chunk.  A frequency's result does not depend on n or on the chunking, two calls give equal bits, and
+ * afterwards F, the Jacobian, the real band LU, the status words and the validity flags are what they were, bit for bit.
+ * status: bit 256 = a pivot block was singular, bit 512 = a value that is not finite, per frequency.
+ * Refused (GMPNP_ERR_INVALID, the message names the frequency response): 1D handles (gmpnp_frequency_response), partition handles, a
+ * coarse level attached or serving as one, the Stern option off, the galvanostat on, Stern and kinetic options with different
+ * p_electrode, n outside 1 ... 4096, a sigma that is negative or not finite, a band of one frequency above band_lu_max_gb (the message
+ * gives its size).  eps <= 0 on the wall or a rate that is not finite: GMPNP_ERR_NUMERIC.  gmpnp_time_kernel(30) times every launch
+ * of the last chunk. */
+int gmpnp_frequency_response_3d(gmpnp_solver* s, int32_t n, const double* sigma /* [n] */, gmpnp_response_t* out /* [n] */,
+                                double* x_out /* [n][n_dofs][2] in file order, or NULL */);
+/* The shape of a 3D handle's block-banded LU: the node blocks n and the stored band width b (the pattern's band in the elimination
+ * order, at least 15: the substitution's panel).  The real factor takes n (2 b + 1) 81 doubles, the complex band of one frequency
+ * twice that.  Nothing is allocated or launched. */
+int gmpnp_band_lu_shape(gmpnp_solver* s, int32_t* n_blocks, int32_t* band);
+
 /* ---- electrode tangent (no reference counterpart: polarisation curves by continuation in the electrode potential) --------------------
  * 1D and 3D handles with the Stern option on.  With p_M and the other electrode parameters theta_k as parameters of F(u; theta) = 0, the
  * tangent z_k = du/dtheta_k at the handle's current u, p_M and model.inv_dt solves
@@ -830,7 +856,9 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * multi-column cyclic-reduction chain(s) of the last gmpnp_electrode_tangent call with extraction and application (needs such a call
  * and the Jacobian it left), 29 = the launches of one gmpnp_electrode_trace_append (k_stern_residual, k_kinetics_residual with the
  * kinetics on, k_electrode_record; needs an open trace, whose records, count, D_prev, Q and Q_D stay: the hook's launches write a slot
- * and accumulators of their own). */
+ * and accumulators of their own), 30 = every launch of one chunk of the 3D frequency response (scatter, k_cband_step per pivot, the
+ * solve and its refinement rounds, k_cband_functional on the frequencies of the last chunk of the last gmpnp_frequency_response_3d
+ * call, which it needs; it writes the response's own storage only). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
