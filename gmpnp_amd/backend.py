@@ -50,6 +50,8 @@ EXPORTS = [
     "gmpnp_parameter_advance", "gmpnp_get_electrode_options",
     "gmpnp_set_electrode_potential", "gmpnp_electrode_trace_open", "gmpnp_electrode_trace_append", "gmpnp_electrode_trace_read",
     "gmpnp_electrode_trace_close",
+    "gmpnp_sensitivity_open", "gmpnp_sensitivity_step", "gmpnp_sensitivity_read", "gmpnp_sensitivity_columns", "gmpnp_sensitivity_set_columns",
+    "gmpnp_sensitivity_close",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -157,6 +159,20 @@ ELECTRODE_RECORD_DTYPE = np.dtype([("t", "f8"), ("h", "f8"), ("p_M", "f8"), ("p_
                                    ("I", "f8", MAX_SURFACE_REACTIONS), ("Q", "f8", MAX_SURFACE_REACTIONS), ("Q_D", "f8"),
                                    ("u_boundary", "f8", MAX_SPECIES), ("status", "i4"), ("pad_", "i4")])
 ELECTRODE_RECORD_NONFINITE = 1    # bit of gmpnp_electrode_record_t.status
+
+
+class CSensitivityRecord(ctypes.Structure):
+    """ctypes image of ``gmpnp_sensitivity_record_t`` (include/gmpnp.h)."""
+    _fields_ = [("t", c_double), ("h", c_double), ("param", c_int32), ("pad0_", c_int32), ("dD", c_double), ("d_dD_dt", c_double),
+                ("dI", c_double * MAX_SURFACE_REACTIONS), ("dQ", c_double * MAX_SURFACE_REACTIONS), ("dQ_D", c_double),
+                ("dp_boundary", c_double), ("residual", c_double), ("status", c_int32), ("pad_", c_int32)]
+
+
+SENSITIVITY_RECORD_DTYPE = np.dtype([("t", "f8"), ("h", "f8"), ("param", "i4"), ("pad0_", "i4"), ("dD", "f8"), ("d_dD_dt", "f8"),
+                                     ("dI", "f8", MAX_SURFACE_REACTIONS), ("dQ", "f8", MAX_SURFACE_REACTIONS), ("dQ_D", "f8"),
+                                     ("dp_boundary", "f8"), ("residual", "f8"), ("status", "i4"), ("pad_", "i4")])
+SENSITIVITY_NONFINITE, SENSITIVITY_SINGULAR, SENSITIVITY_ASSEMBLY = 1, 2, 4   # bits of gmpnp_sensitivity_record_t.status
+SENSITIVITY_START = {"zero": 0, "steady": 1, "continue": 2}                  # gmpnp_sensitivity_open's start
 TANGENT_MAX_COLUMNS = 10          # GMPNP_TANGENT_MAX_COLUMNS
 RESPONSE_MAX_FREQUENCIES = 4096   # gmpnp_frequency_response: n in 1 ... 4096
 RESPONSE_SINGULAR, RESPONSE_NONFINITE = 256, 512   # bits of gmpnp_response_t.status
@@ -318,6 +334,12 @@ def load_library(path: str = None):
     lib.gmpnp_electrode_trace_append.argtypes = [c_void_p, c_double, c_double]
     lib.gmpnp_electrode_trace_read.argtypes = [c_void_p, c_int32, c_int32, POINTER(CElectrodeRecord)]
     lib.gmpnp_electrode_trace_close.argtypes = [c_void_p]
+    lib.gmpnp_sensitivity_open.argtypes = [c_void_p, c_int32, POINTER(c_int32), c_int32, c_int32]
+    lib.gmpnp_sensitivity_step.argtypes = [c_void_p, c_double, c_double]
+    lib.gmpnp_sensitivity_read.argtypes = [c_void_p, c_int32, c_int32, POINTER(CSensitivityRecord)]
+    lib.gmpnp_sensitivity_columns.argtypes = [c_void_p, c_int32, POINTER(c_double)]
+    lib.gmpnp_sensitivity_set_columns.argtypes = [c_void_p, POINTER(c_double)]
+    lib.gmpnp_sensitivity_close.argtypes = [c_void_p]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -824,6 +846,45 @@ class DeviceSolver:
     def electrode_trace_close(self):
         """``gmpnp_electrode_trace_close``."""
         self._check(self.lib.gmpnp_electrode_trace_close(self._h))
+
+    def sensitivity_open(self, params, start, capacity):
+        """``gmpnp_sensitivity_open``: the state sensitivities S of the parameter codes ``params`` (``polarisation.PARAM_*``) and a
+        record buffer of ``capacity`` steps.  ``start``: "zero" (S = 0), "steady" (S = the columns of a still-valid
+        ``electrode_tangent`` call) or "continue" (S and the accumulators stay, the count is reset), or the C value 0 / 1 / 2."""
+        pr = np.ascontiguousarray(params, dtype=np.int32).ravel()
+        code = SENSITIVITY_START[start] if isinstance(start, str) else int(start)
+        self._check(self.lib.gmpnp_sensitivity_open(self._h, int(pr.size), _iptr(pr), code, int(capacity)))
+        self._n_sensitivities = int(pr.size)
+
+    def sensitivity_step(self, t, h):
+        """``gmpnp_sensitivity_step``: the recursion of the accepted step of length ``h`` that ends at ``t`` with the current u and the
+        step's inv_dt, and one record per column, formed and stored on the device (no synchronisation, no copy)."""
+        self._check(self.lib.gmpnp_sensitivity_step(self._h, float(t), float(h)))
+
+    def sensitivity_read(self, first, n_steps) -> np.ndarray:
+        """``gmpnp_sensitivity_read``: the records of steps ``first`` ... ``first + n_steps - 1`` as a structured array
+        (``SENSITIVITY_RECORD_DTYPE``) of shape (n_steps, n columns)."""
+        n_steps, n = int(n_steps), getattr(self, "_n_sensitivities", 1)
+        out = (CSensitivityRecord * max(n_steps * n, 1))()
+        self._check(self.lib.gmpnp_sensitivity_read(self._h, int(first), n_steps, out))
+        return np.frombuffer(out, dtype=SENSITIVITY_RECORD_DTYPE, count=max(n_steps * n, 0)).copy().reshape(max(n_steps, 0), n)
+
+    def sensitivity_columns(self, which=0) -> np.ndarray:
+        """``gmpnp_sensitivity_columns``: S (``which`` = 0) or the right-hand sides of the last step (1), (n, ndof) in file order."""
+        out = np.empty((getattr(self, "_n_sensitivities", 1), self.ndof))
+        self._check(self.lib.gmpnp_sensitivity_columns(self._h, int(which), _dptr(out)))
+        return out
+
+    def sensitivity_set_columns(self, S):
+        """``gmpnp_sensitivity_set_columns``: S <- ``S`` (n, ndof) in file order (the tests' hook)."""
+        a = np.ascontiguousarray(S, dtype=np.float64)
+        if a.shape != (getattr(self, "_n_sensitivities", 1), self.ndof):
+            raise ValueError("sensitivities: S has the shape (n, ndof) of the open buffer")
+        self._check(self.lib.gmpnp_sensitivity_set_columns(self._h, _dptr(a)))
+
+    def sensitivity_close(self):
+        """``gmpnp_sensitivity_close``."""
+        self._check(self.lib.gmpnp_sensitivity_close(self._h))
 
     def set_supg(self, rho=None, w_index=None):
         """Nodal SUPG parameters (nv, ns) of the PNP stabilisation (reference 1D:597-722), or None to switch it off."""

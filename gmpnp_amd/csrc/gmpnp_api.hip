@@ -220,6 +220,21 @@ struct gmpnp_tracer {
   bool open = false;
 };
 
+// device side of the transient sensitivities (gmpnp_sensitivity.h), allocated by the first gmpnp_sensitivity_open: a handle that never
+// asks for it keeps the buffers and launches it had
+struct gmpnp_sensitizer {
+  DevBuf<double> S, S_hook;               // [n][ndof] internal order: the state sensitivities; gmpnp_time_kernel(31)'s own
+  DevBuf<double> c, Jz;                   // [10][ndof] the columns dF/dtheta_k of the step; J s_k
+  DevBuf<double> mass;                    // [3][nv] the species rows' mass entries (species_mass_1d)
+  DevBuf<double> store;                   // per level of the cyclic-reduction pyramid: b, bi, x with 8 columns, then with 2 columns
+  DevBuf<gmpnp_sensitivity_record_t> rec; // [capacity + 1][n]: the row behind the buffer is the hook's
+  DevBuf<ElectrodeAccum> acc;             // [2][10]: dD_prev, dQ, dQ_D per column; the hook's own
+  DevBuf<int32_t> status;                 // the word of the column launches
+  int n = 0, capacity = 0, count = 0;
+  bool open = false, stepped = false;     // stepped: a right-hand side has been formed since the open
+  int32_t param[GMPNP_TANGENT_MAX_COLUMNS] = {};
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -310,6 +325,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_band_responder> band_responder;
   std::unique_ptr<gmpnp_tangenter> tangenter;
   std::unique_ptr<gmpnp_tracer> tracer;
+  std::unique_ptr<gmpnp_sensitizer> sensitizer;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
   // (boundary_rebind); allocated by the first of them
   DevBuf<double> bnd_dyn;
@@ -389,6 +405,9 @@ inline void tangent_drop(gmpnp_solver* s) { if (s->tangenter) { s->tangenter->fr
 // gmpnp_trace.h: the launches of one gmpnp_electrode_trace_append into a slot and accumulators of the hook's own (gmpnp_time_kernel 29)
 bool trace_is_open(const gmpnp_solver* s);
 int trace_time_append(gmpnp_solver* s);
+// gmpnp_sensitivity.h: the launches of one gmpnp_sensitivity_step on a second S, a slot and accumulators of the hook's own (gmpnp_time_kernel 31)
+bool sensitivity_is_open(const gmpnp_solver* s);
+int sensitivity_time_step(gmpnp_solver* s);
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
@@ -2019,6 +2038,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (kernel == 28 && !tangent_has_chain(s)) return fail(GMPNP_ERR_INVALID, "kernel 28 is the multi-column chain of the electrode tangent: no call has been made on this Jacobian (gmpnp_electrode_tangent, 1D)");
   if (kernel == 29 && !trace_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 29 is one append of the electrode trace: no trace is open (gmpnp_electrode_trace_open)");
   if (kernel == 30 && !response_band_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 30 is one chunk of the 3D frequency response: no call has been made (gmpnp_frequency_response_3d), or the Stern option is off");
+  if (kernel == 31 && !sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 31 is one step of the transient sensitivities: no buffer is open (gmpnp_sensitivity_open)");
   if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
@@ -2063,6 +2083,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 28: r = tangent_time_chain(s); break;    // extraction, k_bcr_forward_cols / k_bcr_tail_cols / k_bcr_backward_cols, application
       case 29: r = trace_time_append(s); break;     // k_stern_residual + k_kinetics_residual (kinetics on) + k_electrode_record
       case 30: r = response_band_time_chunk(s); break;   // scatter, k_cband_step per pivot, the solve and three refinement rounds, k_cband_functional
+      case 31: r = sensitivity_time_step(s); break;      // assembly, columns, k_sens_rhs, chain(s), application, k_spmv_plain per column, k_sens_record
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -2188,4 +2209,5 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_response.h"
 #include "gmpnp_tangent.h"
 #include "gmpnp_trace.h"
+#include "gmpnp_sensitivity.h"
 #include "gmpnp_response_band.h"

@@ -336,20 +336,27 @@ int response_launch_chunk(gmpnp_solver* s, int nfreq) {
 int response_time_chunk(gmpnp_solver* s) { return response_launch_chunk(s, s->responder->last_chunk); }
 bool response_has_chunk(const gmpnp_solver* s) { return s->responder && s->responder->last_chunk > 0; }
 
+// the mass entries [3][nv] of a species row towards I - 1, I, I + 1 (k_jac_gather's Mab, summed over the vertex's two cells in element
+// order): the consistent P1 mass M of J = K + inv_dt M on the free species rows (gmpnp_sensitivity.h reads the same vector)
+std::vector<double> species_mass_1d(const gmpnp_solver* s) {
+  const int nv = s->t.nv;
+  std::vector<double> m((size_t)3 * nv, 0.0);
+  constexpr double MDEN = Lay<1, 7>::MDEN;
+  for (int I = 0; I + 1 < nv; ++I) {
+    const double vol = std::fabs(s->t.coords[(size_t)I + 1] - s->t.coords[(size_t)I]);   // (1D: one coordinate per vertex, internal = path order)
+    m[(size_t)2 * nv + I] += vol * MDEN;          // I -> I + 1
+    m[(size_t)I + 1] += vol * MDEN;               // I + 1 -> I
+    m[(size_t)nv + I] += vol * MDEN * 2.0; m[(size_t)nv + I + 1] += vol * MDEN * 2.0;
+  }
+  return m;
+}
+
 // K, b and the mass vector of the current state into the response's own storage; the handle's F, J and flags are put back
 int response_setup(gmpnp_solver* s) {
   gmpnp_responder* R = s->responder.get();
   const int nv = s->t.nv, nf = s->nf;
-  // the mass entries of a species row (k_jac_gather's Mab, summed over the vertex's two cells in element order)
   {
-    std::vector<double> m((size_t)3 * nv, 0.0);
-    constexpr double MDEN = Lay<1, 7>::MDEN;
-    for (int I = 0; I + 1 < nv; ++I) {
-      const double vol = std::fabs(s->t.coords[(size_t)I + 1] - s->t.coords[(size_t)I]);   // (1D: one coordinate per vertex, internal = path order)
-      m[(size_t)2 * nv + I] += vol * MDEN;          // I -> I + 1
-      m[(size_t)I + 1] += vol * MDEN;               // I + 1 -> I
-      m[(size_t)nv + I] += vol * MDEN * 2.0; m[(size_t)nv + I + 1] += vol * MDEN * 2.0;
-    }
+    const std::vector<double> m = species_mass_1d(s);
     HIP_TRY(hipMemcpy(R->mass.p, m.data(), m.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipStreamSynchronize(s->stream));

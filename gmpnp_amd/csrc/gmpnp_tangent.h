@@ -284,25 +284,14 @@ __global__ __launch_bounds__(kVecBlock) void k_tan_columns(const Ctx c, const Ki
   }
 }
 
+// the boundary sums of one column's functionals, each lane its nodes n = lane, lane + 256, ...: v[0] = dD, v[1 + r] = dI_r, then the
+// weighted sum of z's potential entry and the sum of the weights (k_tan_functional and gmpnp_sensitivity.h's k_sens_record add the lanes
+// with block_sum)
 template <int DIM, int NF>
-__global__ __launch_bounds__(kVecBlock) void k_tan_functional(const Ctx c, const KinTab kt, const SternTab st, const int kinetics, const TanTab t) {
+__device__ __forceinline__ void tan_functional_sums(const Ctx& c, const KinTab& kt, const SternTab& st, const int kinetics, const int param,
+                                                    const double* __restrict__ z, double (&v)[3 + GMPNP_MAX_SURFACE_REACTIONS]) {
   GMPNP_RULE_NO_CONTRACT
   constexpr int NS = NF - 1, K = 3 + GMPNP_MAX_SURFACE_REACTIONS, FN = SternFacet<DIM, NF>::FN;
-  __shared__ double lds[4 * K];
-  __shared__ double mx[2 * 4];
-  const int k = blockIdx.x;
-  const int param = t.param[k];
-  const double* z = t.z + (size_t)k * t.ndof;
-  const double* Jz = t.Jz + (size_t)k * t.ndof;
-  const double* col = t.c + (size_t)k * t.ndof;
-  double rmax = 0.0, bmax = 0.0;
-  bool wild = false;
-  for (int idx = threadIdx.x; idx < t.ndof; idx += kVecBlock) {
-    const double ci = col[idx], v = Jz[idx] + ci, zi = z[idx];
-    wild = wild || !rule_finite(v) || !rule_finite(zi);
-    rmax = fmax(rmax, fabs(v)); bmax = fmax(bmax, fabs(ci));
-  }
-  double v[K];
 #pragma unroll
   for (int q = 0; q < K; ++q) v[q] = 0.0;
   const gmpnp_model_t* m = c.model;
@@ -355,6 +344,28 @@ __global__ __launch_bounds__(kVecBlock) void k_tan_functional(const Ctx c, const
         }
     }
   }
+}
+
+template <int DIM, int NF>
+__global__ __launch_bounds__(kVecBlock) void k_tan_functional(const Ctx c, const KinTab kt, const SternTab st, const int kinetics, const TanTab t) {
+  GMPNP_RULE_NO_CONTRACT
+  constexpr int K = 3 + GMPNP_MAX_SURFACE_REACTIONS;
+  __shared__ double lds[4 * K];
+  __shared__ double mx[2 * 4];
+  const int k = blockIdx.x;
+  const int param = t.param[k];
+  const double* z = t.z + (size_t)k * t.ndof;
+  const double* Jz = t.Jz + (size_t)k * t.ndof;
+  const double* col = t.c + (size_t)k * t.ndof;
+  double rmax = 0.0, bmax = 0.0;
+  bool wild = false;
+  for (int idx = threadIdx.x; idx < t.ndof; idx += kVecBlock) {
+    const double ci = col[idx], v = Jz[idx] + ci, zi = z[idx];
+    wild = wild || !rule_finite(v) || !rule_finite(zi);
+    rmax = fmax(rmax, fabs(v)); bmax = fmax(bmax, fabs(ci));
+  }
+  double v[K];
+  tan_functional_sums<DIM, NF>(c, kt, st, kinetics, param, z, v);
   block_sum<K>(v, lds);
   const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
   double a = wild ? -1.0 : rmax, b = bmax;   // -1 marks a value that is not finite (every true maximum is >= 0)

@@ -26,7 +26,7 @@ import numpy as np
 from . import backend
 from .impedance import add_impedance_arguments, impedance_keywords
 from .polarisation import add_polarisation_arguments, polarisation_keywords
-from .fit import add_fit_arguments, fit_keywords
+from .fit import add_fit_arguments, fit_keywords, programme_fit_keywords
 from .programme import add_programme_arguments, programme_keywords
 from .mesh import read_dolfin_xml, resolve_mesh_path
 from .params import _load_yaml, edl_parameters, utilities_dir
@@ -122,6 +122,15 @@ class EDLRun:
         if self.programme_par is not None:
             from .programme import check_programme
             self.programme_par = check_programme(self.programme_par, kwargs, dt_order)
+        # ``fit_programme`` = dict(data=path[, params=(...)]) (with ``programme`` in fixed mode and ``kinetics``): ``write_outputs`` fits the
+        # named electrode parameters to the transient data of the file (time_s, i_CO and / or i_H2[, surface_charge, weight_*]; what
+        # ``programme.npz`` holds) over the programme, BEFORE the programme itself is marched with the fitted parameters (DESIGN.md
+        # section 5p; ``fit_programme()`` does the same at any time); it adds ``fit_programme.npz`` (``fit.npz``'s tables over time_s) and
+        # the metadata keys ``fit_programme_*``.  Not with ``fit`` or ``polarisation``, nor where the programme is refused.
+        self.fit_programme_par = kwargs.pop("fit_programme", None) or None
+        if self.fit_programme_par is not None:
+            from .fit import check_fit_programme
+            self.fit_programme_par = check_fit_programme(self.fit_programme_par, dict(kwargs, programme=self.programme_par), dt_order)
         self.programme_state = None   # the state a programme ended at (impedance_outputs reads it in the place of the history's last row)
         self.dt_tol, self.dt_bounds, self.max_steps = (dt_rtol, dt_atol), (dt_min, dt_max), max_steps
         self.fit_par = kwargs.pop("fit", None) or None
@@ -474,6 +483,60 @@ class EDLRun:
         np.savez(newpath + "/fit.npz", **out)
         return meta
 
+    def fit_programme(self, data, params=None, programme=None):
+        """Fits the electrode parameters ``params`` to the transient data ``data`` (a path, or a dict of the columns time_s, i_CO and /
+        or i_H2, optional surface_charge and weight_*) of the potential programme ``programme`` (default: the run's own keyword) in
+        fixed mode, by ``fit.LevenbergMarquardt`` over ``fit.TransientCurve``: every trial goes back to the start state, moves the
+        parameters with ``gmpnp_parameter_advance`` as predictor, re-converges the steady state at the start potential, takes the
+        tangent and marches with the sensitivities of section 5p.  The run must stand at its steady state.  Afterwards the run and
+        the handle stand at the start potential with the FITTED parameters at the steady state there, the run's inv_dt put back.
+        Returns the arrays of ``fit_programme.npz`` plus ``metadata`` and ``result``."""
+        from . import fit as ft
+        from . import programme as prg
+        if self.stern is None or self.kinetics is None:
+            raise ValueError("fit_programme: the fit needs an electrode potential and the surface kinetics (electrode_voltage, kinetics='tafel')")
+        if self.galvanostat is not None:
+            raise ValueError("fit_programme: not available with target_current (the galvanostat owns the potential)")
+        if self.supg:
+            raise ValueError("fit_programme: not available with stabilization Y")
+        par = programme if programme is not None else self.programme_par
+        if not par or par.get("steps_per_segment") is None:
+            raise ValueError("fit_programme: the fit needs a programme in fixed mode (steps_per_segment)")
+        par = prg.check_programme(par, dict(electrode_voltage=self.stern.p_electrode, kinetics=self.kinetics))
+        names = tuple(params or ft.DEFAULT_PARAMS)
+        codes = ft.param_codes(names)
+        table = ft.check_programme_data(ft.load_programme_data(data) if not isinstance(data, dict) else data, len(codes))
+        ep = self.ep
+        segs = prg.build(par, float(self.stern.p_electrode), ep.time_constant, ep.thermal_voltage)
+        n_seg = int(par["steps_per_segment"])
+        ft.match_times(table["time_s"], np.array(prg.fixed_step_times(segs, n_seg)) * ep.time_constant)   # refused before a trial runs
+        eps_0 = _load_yaml(os.path.join(utilities_dir(), self.kwargs.get("params_file", "parameters") + ".yaml"))["nat_const"]["eps_0"]
+        L_D = ep.L_D
+        system = ft.DeviceTransient(self, segs, n_seg, codes, eps_0 * ep.thermal_voltage / ep.L_n, lambda h: 1.0 / (h * L_D), ep.time_constant,
+                                    par.get("capacity") or 4096)
+        curve = ft.TransientCurve(system, table, len(codes))
+        inv_dt = float(self.sys.problem.model.inv_dt)
+        theta0 = ft.theta_of(system.kept["stern"], system.kept["kinetics"], codes)
+        try:
+            res = ft.LevenbergMarquardt(curve, [ft.is_log(c) for c in codes]).run(theta0)
+            res["theta"] = ft.theta_of(system.kept["stern"], system.kept["kinetics"], codes)   # the numbers the handle holds
+        finally:
+            system.finish(inv_dt)
+        rx = self.kinetics.reactions
+        self.kinetic_par = dict(self.kinetic_par, i0_CO=rx[0].k, i0_H2=rx[1].k, alpha_CO=rx[0].alpha, alpha_H2=rx[1].alpha)
+        out = ft.fit_arrays(names, codes, table, theta0, res, curve.kept["values"], ep.L_n, abscissa="time_s")
+        meta = ft.fit_metadata(names, out, res)
+        out["metadata"], out["result"] = {k.replace("fit_", "fit_programme_", 1): v for k, v in meta.items()}, res
+        return out
+
+    def fit_programme_outputs(self, newpath):
+        """``fit_programme.npz`` and the metadata keys that go with it (see ``__init__``)."""
+        out = self.fit_programme(**self.fit_programme_par)
+        meta = out.pop("metadata")
+        out.pop("result")
+        np.savez(newpath + "/fit_programme.npz", **out)
+        return meta
+
     def programme(self, verbose=False, **par):
         """Marches the electrode potential through the programme ``par`` (the ``programme`` keyword of ``__init__``) from the run's
         CURRENT state, on a clock of its own from 0 (gmpnp_amd/programme.py: ``run_programme`` over ``DeviceProgrammeOps``).  The
@@ -490,16 +553,32 @@ class EDLRun:
             raise ValueError("programme: not available with target_current (the galvanostat owns the potential)")
         if self.supg:
             raise ValueError("programme: not available with stabilization Y")
-        par = prg.check_programme(par, dict(electrode_voltage=self.stern.p_electrode))
+        par = prg.check_programme(par, dict(electrode_voltage=self.stern.p_electrode, kinetics=self.kinetics))
         ep = self.ep
         segs = prg.build(par, float(self.stern.p_electrode), ep.time_constant, ep.thermal_voltage)
         L_D = ep.L_D
-        ops = prg.DeviceProgrammeOps(self, self.solver_parameters, lambda h: 1.0 / (h * L_D), self.dt_tol, par.get("capacity") or 4096)
-        policy = TimeStepPolicy(h_min=float(self.dt_bounds[0]), h_max=math.inf if self.dt_bounds[1] is None else float(self.dt_bounds[1]))
         inv_dt = float(self.sys.problem.model.inv_dt)
+        names = tuple(par.get("sensitivities") or ())
+        codes, start = (prg.sensitivity_codes(names), par.get("sensitivity_start") or "steady") if names else (None, "zero")
+        try:
+            if names and start == "steady":   # S starts as the steady state's dependence on theta: the tangent at inv_dt = 0, still valid at the open
+                self.sys.set_time_step(0.0)
+                tan = self.sys.dev.electrode_tangent(codes)
+                if tan["status"].any():
+                    raise RuntimeError("programme: the steady tangent the sensitivities start from is not finite")
+            ops = prg.DeviceProgrammeOps(self, self.solver_parameters, lambda h: 1.0 / (h * L_D), self.dt_tol, par.get("capacity") or 4096,
+                                         sensitivities=codes, sensitivity_start=start)
+        except BaseException:
+            self.sys.set_time_step(inv_dt)
+            raise
+        policy = TimeStepPolicy(h_min=float(self.dt_bounds[0]), h_max=math.inf if self.dt_bounds[1] is None else float(self.dt_bounds[1]))
+        srec = None
         try:
             res = prg.run_programme(ops, segs, policy, dt_init=par.get("dt_init") or ep.dts[0], dt_restart=par.get("dt_restart"),
                                     steps_per_segment=par.get("steps_per_segment"), max_attempts=self.max_steps)
+            if names:
+                srec = ops.sensitivity_records()
+                self.sys.dev.sensitivity_close()
             rec = ops.records()
             last = self.sys.vertex_values()
         except BaseException:   # (a Newton failure in fixed mode, a library error): back to the last accepted state, no trace left open
@@ -528,12 +607,20 @@ class EDLRun:
                 "programme_potential_OHP": float(out["potential_OHP"][-1]) if len(rec) else None,
                 "programme_surface_charge": float(out["surface_charge"][-1]) if len(rec) else None}
         out.update(log=prg.log_arrays(res["log"]), states=[(k, t * ep.time_constant, v) for k, t, v in states], metadata=meta)
+        if names:
+            out["sensitivity"] = prg.sensitivity_arrays(ep, eps_0, srec, names, codes)
+            meta.update(programme_sensitivity_parameters=list(names), programme_sensitivity_start=start,
+                        programme_sensitivity_status=int(np.bitwise_or.reduce(srec["status"].ravel())) if srec.size else 0,
+                        programme_sensitivity_residual=float(srec["residual"].max()) if srec.size else 0.0)
         return out
 
     def programme_outputs(self, newpath):
         """``programme.npz``, ``programme_states.npz`` and the attempts for ``timestep_log.npz``; returns (metadata keys, log arrays)."""
         out = self.programme(**self.programme_par)
         meta, log, states = out.pop("metadata"), out.pop("log"), out.pop("states")
+        sens = out.pop("sensitivity", None)
+        if sens is not None:   # only with the option on
+            np.savez(newpath + "/programme_sensitivity.npz", **sens)
         np.savez(newpath + "/programme.npz", **out)
         np.savez(newpath + "/programme_states.npz", segment=np.array([k for k, _, _ in states], dtype=np.int64),
                  time_s=np.array([t for _, t, _ in states]), states=np.stack([v for _, _, v in states]), coor=self.mesh.coords)
@@ -555,6 +642,9 @@ class EDLRun:
         identifier = run_identifier(ep, k, self.stern, self.target_current)
         newpath = os.path.join(output_root(), ep.model_name, stamp + "_experiment", identifier)
         os.makedirs(newpath, exist_ok=True)
+        # the fit to transients starts every trial at the steady state of the run's potential: before the programme, which is then
+        # marched with the fitted parameters
+        fit_programme = self.fit_programme_outputs(newpath) if self.fit_programme_par is not None else None
         programme = self.programme_outputs(newpath) if self.programme_par is not None else None   # first: the metadata reports the state it ends at
         hist = np.stack(self.history)
         names = ["H", "OH", "HCO3", "CO32", "CO2", "cat", "p"]
@@ -626,6 +716,8 @@ class EDLRun:
             with_schedule = dict(np.load(log_path)) if os.path.exists(log_path) else {}
             np.savez(log_path, **with_schedule, **programme[1])
             metadata_dict["timestep_log"] = "timestep_log.npz"
+        if fit_programme is not None:
+            metadata_dict.update(fit_programme)
         if self.fit_par is not None:   # before the curve, which is then the fitted one; the handle ends at the run's operating point
             metadata_dict.update(self.fit_outputs(newpath))
         if self.polarisation_par is not None:   # last: the handle leaves the run's operating point
@@ -720,7 +812,7 @@ def main(argv=None):
                      H2_FE=a.H2_FE, mesh_structure=a.mesh_structure, current_OHP_ss=a.current_OHP_ss, L_n=a.L_n,
                      stabilization=a.stabilization, H_OHP=a.H_OHP, cation=a.cation, params_file=a.params_file,
                      dry_run=a.dry_run, num_steps=a.num_steps, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a),
-                     **impedance_keywords(a), **polarisation_keywords(a), **fit_keywords(a), **programme_keywords(a))
+                     **impedance_keywords(a), **polarisation_keywords(a), **fit_keywords(a), **programme_keywords(a), **programme_fit_keywords(a))
 
 
 if __name__ == "__main__":

@@ -435,14 +435,249 @@ class DeviceCurve:
         self.run.sys.set_time_step(inv_dt)
 
 
+# ---- fits to transients: the same rule over a marched programme ---------------------------------------------------
+TIME_TOL = 1.0e-9                             # a data time coincides with a step end to this relative difference
+PROGRAMME_DATA_KEYS = ("time_s",) + DATA_KEYS[1:]
+
+
+def load_programme_data(path):
+    """``load_data`` for transient data: ``time_s`` in the place of ``electrode_voltage`` (what ``programme.npz`` holds is accepted as
+    it is; its other keys are not read)."""
+    path = str(path)
+    if path.lower().endswith(".npz"):
+        with np.load(path) as z:
+            return {k: np.asarray(z[k], dtype=np.float64).ravel() for k in PROGRAMME_DATA_KEYS if k in z.files}
+    table = np.genfromtxt(path, delimiter=",", names=True, dtype=np.float64)
+    names = table.dtype.names or ()
+    if "time_s" not in names:
+        raise ValueError("fit_programme: a CSV needs a header row with time_s")
+    return {k: np.atleast_1d(table[k]).astype(np.float64) for k in names if k in PROGRAMME_DATA_KEYS}
+
+
+def check_programme_data(data, n_params):
+    """The refusals of transient data; returns a dict as ``check_data`` does, with ``time_s`` (n,) in the order given."""
+    if "time_s" not in data or not any(k in data for k in CURRENT_KEYS):
+        raise ValueError("fit_programme: the data hold time_s and i_CO and / or i_H2 (optional: surface_charge, weight_*)")
+    t = np.asarray(data["time_s"], dtype=np.float64).ravel()
+    out = {"quantities": tuple(k for k in CURRENT_KEYS + ("surface_charge",) if k in data), "time_s": t}
+    if t.size < 1 or not np.isfinite(t).all() or len(set(t.tolist())) != t.size:
+        raise ValueError("fit_programme: the times must be finite and distinct")
+    for k in out["quantities"]:
+        v = np.asarray(data[k], dtype=np.float64).ravel()
+        w = np.asarray(data.get("weight_" + k, np.ones(t.size)), dtype=np.float64).ravel()
+        if w.size == 1:
+            w = np.full(t.size, w[0])
+        if v.size != t.size or w.size != t.size:
+            raise ValueError("fit_programme: %s has %d values and %d weights for %d times" % (k, v.size, w.size, t.size))
+        if not (np.isfinite(v).all() and np.isfinite(w).all() and np.all(w >= 0.0)):
+            raise ValueError("fit_programme: %s and its weights must be finite, the weights >= 0" % k)
+        if k in CURRENT_KEYS and np.any(v <= 0.0):
+            raise ValueError("fit_programme: %s must be > 0 (the residual is that of ln I)" % k)
+        out[k], out["weight_" + k] = v, w
+    if "surface_charge" in out["quantities"] and not np.abs(out["surface_charge"]).max() > 0.0:
+        raise ValueError("fit_programme: surface_charge is zero everywhere")
+    if t.size * len(out["quantities"]) < int(n_params):
+        raise ValueError("fit_programme: %d residuals are fewer than the %d parameters" % (t.size * len(out["quantities"]), n_params))
+    return out
+
+
+def match_times(data_times, step_times):
+    """The index of the step that ends at every data time (both in seconds); ValueError names the first data time that coincides with
+    no step end to a relative ``TIME_TOL``."""
+    steps = np.asarray(step_times, dtype=np.float64)
+    idx = []
+    for t in np.asarray(data_times, dtype=np.float64):
+        j = int(np.argmin(np.abs(steps - t)))
+        if not abs(steps[j] - t) <= TIME_TOL * max(abs(t), abs(steps[j])):
+            raise ValueError("fit_programme: the data time %.17g s is not the end of a step of the programme (the nearest ends at %.17g s)" % (t, steps[j]))
+        idx.append(j)
+    return np.array(idx, dtype=np.int64)
+
+
+class TransientCurve:
+    """The evaluator of ``LevenbergMarquardt`` over a marched programme in fixed mode.  ``system`` supplies
+
+        start(delta) -> bool      from the kept start: the parameters moved by ``delta`` (the predictor of the state with them), the
+                                  steady state at the start potential re-converged, the tangent taken there; False: it failed
+        march() -> None | dict    the programme marched with sensitivities from that start: ``t`` (steps,) [s], the values ``i_CO``,
+                                  ``i_H2``, ``surface_charge`` (steps,) and ``slopes`` {quantity: (steps, n_params)}, ``newton``
+        keep()                    the last trial's start (parameters and state) becomes the kept one
+        newton                    the Newton iterations of the last start() and march(), also of a failed one
+
+    Residuals and rows come from ``residual_rows`` at the steps the data times coincide with (``match_times``).  A trial that is not
+    accepted leaves nothing behind: every trial begins at the kept start."""
+
+    def __init__(self, system, data, n_params):
+        self.system, self.data, self.n = system, data, int(n_params)
+        self.kept, self.last, self.failed_newton, self.index = None, None, 0, None
+
+    def evaluate(self, delta):
+        s = self.system
+        out = s.march() if s.start(delta) else None
+        if out is None:
+            self.failed_newton = int(s.newton)
+            return None
+        if self.index is None:
+            self.index = match_times(self.data["time_s"], out["t"])
+        r, J, values = [], [], []
+        for m, j in enumerate(self.index):
+            v = {k: float(out[k][j]) for k in CURRENT_KEYS + ("surface_charge",)}
+            if not (v["i_CO"] > 0.0 and v["i_H2"] > 0.0 and all(math.isfinite(x) for x in v.values())):
+                self.failed_newton = int(out["newton"])
+                return None
+            rr, JJ = residual_rows(self.data, m, v, {k: out["slopes"][k][j] for k in v})
+            r += rr
+            J += JJ
+            values.append(v)
+        return dict(r=np.array(r), J=np.array(J).reshape(len(r), self.n), newton=int(out["newton"]), values=values)
+
+    def trial(self, theta, delta):
+        if self.kept is not None and not np.any(delta):
+            self.last = self.kept
+            return self.kept
+        self.last = self.evaluate(np.asarray(delta, dtype=np.float64))
+        return self.last
+
+    def accept(self):
+        self.kept = self.last
+        self.system.keep()
+
+
+class DeviceTransient:
+    """``TransientCurve``'s system over a driver run (``EDLRun``) at the steady state of its start potential, and its own handle.
+    start(): ``set_state`` of the kept start, the kept options, ``electrode_tangent`` and ``parameter_advance(delta)`` at inv_dt = 0
+    (the predictor, with the run's ``step_fraction``), a Newton solve (``polarisation.NEWTON``) to the steady state of the moved
+    parameters, and the tangent there, which the sensitivities start from.  march(): ``run_programme`` in fixed mode over
+    ``DeviceProgrammeOps`` with the sensitivities of the fit's parameters."""
+
+    def __init__(self, run, segs, steps_per_segment, codes, sigma_unit, inv_dt_of_h, time_constant, capacity=4096):
+        from . import backend
+        self.run, self.dev, self.segs, self.steps, self.codes = run, run.sys.dev, segs, int(steps_per_segment), tuple(int(c) for c in codes)
+        self.sigma_unit, self.capacity, self.inv_dt_of_h, self.time_constant = float(sigma_unit), int(capacity), inv_dt_of_h, float(time_constant)
+        self.options = backend.newton_options(backend.with_step_fraction(pol.NEWTON, run.step_fraction), dim=1)
+        self.V0 = float(run.stern.p_electrode)
+        stern, kinetics = self.dev.electrode_options()
+        u = self.dev.get_state()
+        self.kept = dict(stern=stern, kinetics=kinetics, u=u)
+        self.pending, self.newton = None, 0
+
+    def set_options(self, stern, kinetics):
+        s, k = records_of(stern, kinetics, self.V0)
+        self.run.stern, self.run.kinetics = s, k
+        self.run.problem.stern, self.run.problem.kinetics = s, k
+        self.dev.set_stern(s)
+        self.dev.set_kinetics(k)
+
+    def start(self, delta):
+        from . import backend
+        k, run = self.kept, self.run
+        self.newton, self.pending = 0, None
+        stern, kinetics, ok = moved_options(k["stern"], k["kinetics"], run.problem.nf - 1, self.codes, delta)
+        if not ok:
+            return False
+        try:
+            run.sys.set_time_step(0.0)
+            self.dev.set_state(k["u"], k["u"])
+            self.set_options(k["stern"], k["kinetics"])
+            if np.any(delta):
+                self.dev.electrode_tangent(self.codes)
+                self.dev.parameter_advance(self.codes, delta, run.step_fraction)
+                stern, kinetics = self.dev.electrode_options()   # the numbers the library's own exp produced
+                s, kk = records_of(stern, kinetics, self.V0)
+                run.stern, run.kinetics, run.problem.stern, run.problem.kinetics = s, kk, s, kk
+            st = self.dev.newton_solve(self.options)
+            self.newton += st["iterations"]
+            u = self.dev.get_state()
+            self.dev.set_state(u, u)
+            if self.dev.electrode_tangent(self.codes)["status"].any():
+                return False
+        except backend.GmpnpError as e:
+            if e.code not in (backend.ERR_NOT_CONVERGED, backend.ERR_NUMERIC, backend.ERR_LINEAR):
+                raise
+            self.newton += (e.stats or {}).get("iterations", 0)
+            return False
+        self.pending = dict(stern=stern, kinetics=kinetics, u=u)
+        return True
+
+    def march(self):
+        from . import backend
+        from . import programme as prg
+        run, tc = self.run, self.time_constant
+        ops = prg.DeviceProgrammeOps(run, pol.NEWTON, self.inv_dt_of_h, capacity=self.capacity, sensitivities=self.codes, sensitivity_start="steady")
+        budget, run.budget = run.budget, None   # (a trial's steps are no rows of the run's budget log)
+        try:
+            prg.run_programme(ops, self.segs, steps_per_segment=self.steps)
+            srec = ops.sensitivity_records()
+            self.dev.sensitivity_close()
+            rec = ops.records()
+        except (RuntimeError, backend.GmpnpError) as e:
+            ops.abort()
+            self.newton += ops.newton_iterations
+            if isinstance(e, backend.GmpnpError) and e.code == backend.ERR_HIP:
+                raise
+            return None
+        finally:
+            run.budget = budget
+        self.newton += ops.newton_iterations
+        if rec["status"].any() or srec["status"].any():
+            return None
+        q = self.sigma_unit
+        return {"t": rec["t"] * tc, "i_CO": rec["I"][:, 0], "i_H2": rec["I"][:, 1], "surface_charge": q * rec["D"], "newton": self.newton,
+                "slopes": {"i_CO": srec["dI"][:, :, 0], "i_H2": srec["dI"][:, :, 1], "surface_charge": q * srec["dD"]}}
+
+    def keep(self):
+        self.kept = self.pending
+
+    def finish(self, inv_dt):
+        """The handle and the run at the start potential with the kept parameters, at the steady state there, ``inv_dt`` put back."""
+        k = self.kept
+        self.dev.set_state(k["u"], k["u"])
+        self.set_options(k["stern"], k["kinetics"])
+        self.run.sys.set_time_step(inv_dt)
+
+
+def programme_fit_keywords(a):
+    """The fit_programme keyword of a parsed command line; empty without --fit_programme_data."""
+    if getattr(a, "fit_programme_data", None) is None:
+        return {}
+    par = dict(data=a.fit_programme_data)
+    if a.fit_params is not None:
+        par["params"] = tuple(a.fit_params)
+    return {"fit_programme": par}
+
+
+def check_fit_programme(par, kwargs, dt_order=1):
+    """The refusals of a driver's ``fit_programme`` keyword, before anything touches the device; returns the checked dict."""
+    par = dict(par)
+    if set(par) - {"data", "params"} or "data" not in par:
+        raise ValueError("fit_programme: the keyword is dict(data=[, params=])")
+    if kwargs.get("fit") or kwargs.get("polarisation"):
+        raise ValueError("fit_programme: not in one run with fit or polarisation (each leaves the run at a potential of its own)")
+    prog = kwargs.get("programme")
+    if not prog:
+        raise ValueError("fit_programme: the fit to transients needs the programme the data were taken with (programme)")
+    if prog.get("steps_per_segment") is None:
+        raise ValueError("fit_programme: the programme runs in fixed mode (steps_per_segment)")
+    if prog.get("sensitivities"):
+        raise ValueError("fit_programme: the fit carries the sensitivities of its own parameters (leave the programme's sensitivities out)")
+    if kwargs.get("kinetics") is None:
+        raise ValueError("fit_programme: the fit needs the surface kinetics (kinetics='tafel')")
+    par["params"] = tuple(par.get("params") or DEFAULT_PARAMS)
+    try:
+        param_codes(par["params"])
+    except ValueError as e:
+        raise ValueError("fit_programme: %s" % e) from None
+    return par
+
+
 # ---- units and tables ------------------------------------------------------------------------------------------------------------------
 def physical_values(codes, theta, L_n):
     """i0 [A/m2], alpha and stern_length [m] from ln k_r, alpha_r and ln lam."""
     return np.array([math.exp(t) * (L_n if pol.param_kind(c) == 3 else 1.0) if is_log(c) else t for c, t in zip(codes, theta)], dtype=np.float64)
 
 
-def fit_arrays(names, codes, data, theta0, res, model_values, L_n):
-    """The arrays of ``fit.npz``."""
+def fit_arrays(names, codes, data, theta0, res, model_values, L_n, abscissa="electrode_voltage"):
+    """The arrays of ``fit.npz`` (``abscissa`` = "time_s": of ``fit_programme.npz``, the same tables over the data times)."""
     h = res["history"]
     out = {"names": np.array(names), "codes": np.asarray(codes, dtype=np.int32),
            "initial_values": physical_values(codes, theta0, L_n), "fitted_values": physical_values(codes, res["theta"], L_n),
@@ -451,7 +686,7 @@ def fit_arrays(names, codes, data, theta0, res, model_values, L_n):
            "singular_values": res["singular_values"], "residuals": res["residuals"], "quantities": np.array(data["quantities"]),
            "history_cost": np.array([x["cost"] for x in h]), "history_lambda": np.array([x["lam"] for x in h]),
            "history_accepted": np.array([x["accepted"] for x in h]), "history_newton_iterations": np.array([x["newton"] for x in h], dtype=np.int64),
-           "history_step": np.array([x["step"] for x in h]), "electrode_voltage": data["electrode_voltage"]}
+           "history_step": np.array([x["step"] for x in h]), abscissa: data[abscissa]}
     for k in data["quantities"]:
         out["data_" + k], out["weight_" + k], out["model_" + k] = data[k], data["weight_" + k], np.array([v[k] for v in model_values])
     return out
@@ -468,6 +703,9 @@ def fit_metadata(names, arrays, res):
 def add_fit_arguments(p):
     p.add_argument("--fit_data", required=False, default=None, type=str,
                    help="(addition) fit the electrode kinetics to the polarisation data of this .npz / .csv (electrode_voltage, i_CO, i_H2[, surface_charge]): fit.npz")
+    p.add_argument("--fit_programme_data", required=False, default=None, type=str, metavar="FILE",
+                   help="(addition) fit the electrode parameters (--fit_params) to the transient data of this .npz / .csv (time_s, i_CO, i_H2[, surface_charge]; "
+                        "what programme.npz holds) over --programme in fixed mode (--programme_steps_per_segment): fit_programme.npz")
     p.add_argument("--fit_params", required=False, default=None, nargs="+", type=str, help="(addition) the fitted parameters out of %s (default: %s)"
                    % (" ".join(PARAMETERS), " ".join(DEFAULT_PARAMS)))
 
@@ -475,7 +713,7 @@ def add_fit_arguments(p):
 def fit_keywords(a):
     """The fit keyword of a parsed command line (``add_fit_arguments``); empty without --fit_data."""
     if a.fit_data is None:
-        if a.fit_params is not None:
+        if a.fit_params is not None and getattr(a, "fit_programme_data", None) is None:
             raise ValueError("fit: --fit_params needs --fit_data")
         return {}
     par = dict(data=a.fit_data)

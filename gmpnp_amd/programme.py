@@ -177,6 +177,17 @@ def programme_fixed_step(seg, n):
     return (seg[1] - seg[0]) / n
 
 
+def fixed_step_times(segs, n):
+    """The step ends of ``run_programme``'s fixed mode, by its own arithmetic (t + h, the last step of a segment on t1 itself)."""
+    out = []
+    for seg in segs:
+        h, t = programme_fixed_step(seg, n), seg[0]
+        for j in range(n):
+            t = seg[1] if j == n - 1 else t + h
+            out.append(t)
+    return out
+
+
 def electrode_record_combine(acc, h, D, I):
     """The combine step of one electrode record (``gmpnp_electrode_trace_append``), every product, quotient and sum rounded on its own:
     ``acc`` = dict(D_prev, Q (4,), Q_D) is updated in place; returns dD_dt."""
@@ -319,7 +330,23 @@ def build(par, electrode_voltage, time_constant, thermal_voltage):
 
 PROGRAMME_FIELDS = {"pulse": ({"v_levels", "durations"}, {"cycles", "rise_time"}), "triangle": ({"v_vertex", "scan_rate"}, {"cycles"}),
                     "table": ({"time_s", "electrode_voltage"}, set())}
-COMMON_FIELDS = {"kind", "dt_init", "dt_restart", "steps_per_segment", "capacity"}
+COMMON_FIELDS = {"kind", "dt_init", "dt_restart", "steps_per_segment", "capacity", "sensitivities", "sensitivity_start"}
+
+
+def sensitivity_codes(names):
+    """The tangent's parameter codes of the names of ``fit.PARAMETERS`` plus "offset" (a potential offset of the whole waveform, code
+    0): no new codes.  ValueError for an unknown or repeated name, none or more than ten."""
+    from .fit import PARAMETERS
+    names = [str(n) for n in names]
+    known = dict(PARAMETERS, **{OFFSET: 0})
+    bad = [n for n in names if n not in known]
+    if bad:
+        raise ValueError("programme: unknown sensitivity parameter %s (known: %s)" % (bad[0], ", ".join(sorted(known))))
+    if len(set(names)) != len(names):
+        raise ValueError("programme: a sensitivity parameter is repeated")
+    if not 1 <= len(names) <= 10:
+        raise ValueError("programme: 1 ... 10 sensitivity parameters")
+    return [known[n] for n in names]
 
 
 def check_programme(par, kwargs, dt_order=1):
@@ -351,6 +378,15 @@ def check_programme(par, kwargs, dt_order=1):
         raise ValueError("programme: steps_per_segment must be at least 1")
     if par.get("capacity") is not None and int(par["capacity"]) < 1:
         raise ValueError("programme: capacity must be at least 1")
+    if par.get("sensitivities"):
+        codes = sensitivity_codes(par["sensitivities"])
+        if kwargs.get("kinetics") is None and any(16 <= c < 48 for c in codes):
+            raise ValueError("programme: the sensitivity to a kinetic parameter needs the surface kinetics (kinetics='tafel')")
+    if par.get("sensitivity_start") is not None:
+        if not par.get("sensitivities"):
+            raise ValueError("programme: sensitivity_start without sensitivities")
+        if par["sensitivity_start"] not in ("steady", "zero"):
+            raise ValueError("programme: sensitivity_start is 'steady' or 'zero'")
     build(par, float(kwargs["electrode_voltage"]), 1.0, 1.0)   # a waveform that is not valid is refused here (the units do not matter)
     return par
 
@@ -373,6 +409,11 @@ def add_programme_arguments(p):
     p.add_argument("--programme_file", required=False, default=None, type=str, help="(addition) CSV of --programme table: columns time_s, electrode_voltage")
     p.add_argument("--programme_dt_init", required=False, default=None, type=float, help="(addition) first step of the programme and after a jump (scaled time)")
     p.add_argument("--programme_steps_per_segment", required=False, default=None, type=int, help="(addition) fixed mode: equal steps per segment, no estimator")
+    p.add_argument("--programme_sensitivities", required=False, default=None, type=str, nargs="+", metavar="NAMES",
+                   help="(addition) carry the transient sensitivities to these parameters (i0_CO, i0_H2, alpha_CO, alpha_H2, stern_length, offset) "
+                        "through the programme (programme_sensitivity.npz)")
+    p.add_argument("--programme_sensitivity_start", required=False, default=None, choices=("steady", "zero"),
+                   help="(addition) the sensitivities start from the steady state's dependence on the parameters (default) or from zero")
 
 
 def load_table(path):
@@ -387,6 +428,8 @@ def load_table(path):
 def programme_keywords(a):
     """The programme keyword of a parsed command line (``add_programme_arguments``); empty without --programme."""
     if a.programme is None:
+        if getattr(a, "programme_sensitivities", None) or getattr(a, "programme_sensitivity_start", None):
+            raise ValueError("programme: --programme_sensitivities and --programme_sensitivity_start need --programme")
         return {}
     par = {"kind": a.programme}
     if a.programme == "pulse":
@@ -406,6 +449,10 @@ def programme_keywords(a):
         par["dt_init"] = a.programme_dt_init
     if a.programme_steps_per_segment is not None:
         par["steps_per_segment"] = a.programme_steps_per_segment
+    if getattr(a, "programme_sensitivities", None):
+        par["sensitivities"] = list(a.programme_sensitivities)
+    if getattr(a, "programme_sensitivity_start", None):
+        par["sensitivity_start"] = a.programme_sensitivity_start
     return {"programme": par}
 
 
@@ -417,7 +464,7 @@ class DeviceProgrammeOps:
     and the states at the breakpoints, not a state per step.  The accumulated charges go on across a drained buffer: the host adds
     what the records before held."""
 
-    def __init__(self, run, solver_parameters, inv_dt_of_h, tol=(1e-2, 1e-4), capacity=4096):
+    def __init__(self, run, solver_parameters, inv_dt_of_h, tol=(1e-2, 1e-4), capacity=4096, sensitivities=None, sensitivity_start="zero"):
         from . import backend
         self.backend = backend
         self.run, self.sys, self.dev = run, run.sys, run.sys.dev
@@ -425,8 +472,20 @@ class DeviceProgrammeOps:
         self.chunks, self.segments, self.states, self.count = [], [], [], 0
         self.base_Q, self.base_Q_D = np.zeros(MAX_SURFACE_REACTIONS), 0.0
         self.newton_iterations, self.residuals = 0, []   # residuals: the last Newton residual of every accepted step
-        self.dev.electrode_trace_open(self.capacity)
+        # the transient sensitivities (section 5p): parameter codes of the tangent; "steady" takes the columns of the tangent call the
+        # caller has just made at inv_dt = 0, "zero" starts from S = 0.  The device keeps dQ and dQ_D across a drained buffer.
+        self.sensitivities = None if sensitivities is None else [int(q) for q in sensitivities]
+        self.sensitivity_chunks = []
+        if sensitivity_start not in ("zero", "steady"):
+            raise ValueError("programme: sensitivity_start is 'steady' or 'zero'")
+        self.dev.electrode_trace_open(self.capacity)   # (launches the Stern term only: a steady tangent stays valid for the open below)
         self.D_first = self.dev.stern_displacement()   # the D_prev the trace starts from (the bits the open call took)
+        if self.sensitivities is not None:
+            try:
+                self.dev.sensitivity_open(self.sensitivities, sensitivity_start, self.capacity)
+            except BaseException:
+                self.dev.electrode_trace_close()
+                raise
 
     def set_potential(self, p):
         run = self.run
@@ -468,6 +527,8 @@ class DeviceProgrammeOps:
         if self.run.budget is not None:   # while u_n is the previous state and inv_dt the step's
             self.run.budget.take(self.sys)
         self.dev.electrode_trace_append(t, h)
+        if self.sensitivities is not None:   # accepted steps only: a rejected attempt never touches S
+            self.dev.sensitivity_step(t, h)
         self.residuals.append(float(self.sys.last_stats["residuals"][-1]))
         self.segments.append(int(seg))
         self.count += 1
@@ -490,16 +551,21 @@ class DeviceProgrammeOps:
             rec["Q_D"] = rec["Q_D"] + self.base_Q_D
             self.base_Q, self.base_Q_D = rec["Q"][-1].copy(), float(rec["Q_D"][-1])
             self.chunks.append(rec)
+            if self.sensitivities is not None:
+                self.sensitivity_chunks.append(self.dev.sensitivity_read(0, self.count))
             self.count = 0
         if reopen:
             self.dev.electrode_trace_open(self.capacity)
+            if self.sensitivities is not None:
+                self.dev.sensitivity_open(self.sensitivities, "continue", self.capacity)
 
     def abort(self):
         """After an exception inside the loop: the handle returns to the last accepted state (u <- u_n) and the trace is closed, so
         the run is left at the potential of the attempt that failed (``run.stern`` / ``run.kinetics`` and the handle agree) with no
         trace open.  The records written so far stay in ``chunks`` / on the device unread."""
         backend = self.backend
-        for call in (self.sys.time_reject, self.dev.electrode_trace_close):
+        calls = (self.sys.time_reject, self.dev.electrode_trace_close) + ((self.dev.sensitivity_close,) if self.sensitivities is not None else ())
+        for call in calls:
             try:
                 call()
             except backend.GmpnpError as e:
@@ -513,6 +579,16 @@ class DeviceProgrammeOps:
         self.dev.electrode_trace_close()
         return np.concatenate(self.chunks) if self.chunks else np.zeros(0, dtype=ELECTRODE_RECORD_DTYPE)
 
+    def sensitivity_records(self):
+        """Every sensitivity record so far, (steps, columns), in order (drains both buffers; the sensitivities stay open, with S on the
+        device, until ``sensitivity_close``)."""
+        from .backend import SENSITIVITY_RECORD_DTYPE
+        if self.sensitivities is None:
+            raise ValueError("programme: the run carries no sensitivities")
+        self.drain()
+        n = len(self.sensitivities)
+        return np.concatenate(self.sensitivity_chunks) if self.sensitivity_chunks else np.zeros((0, n), dtype=SENSITIVITY_RECORD_DTYPE)
+
 
 OUTPUT_KEYS = ("time_s", "electrode_voltage", "potential_OHP", "surface_charge", "i_CO", "i_H2", "i_charging", "i_total", "charge_CO",
                "charge_H2", "charge_double_layer", "FE_H2", "FE_H2_cycle", "OHP_H", "OHP_OH", "OHP_HCO3", "OHP_CO32", "OHP_CO2", "OHP_cat",
@@ -521,6 +597,31 @@ SPECIES_KEYS = ("OHP_H", "OHP_OH", "OHP_HCO3", "OHP_CO32", "OHP_CO2", "OHP_cat")
 METADATA_KEYS = ("programme_kind", "programme_cycles", "programme_segments", "programme_steps_accepted", "programme_steps_rejected",
                  "programme_stop_reason", "programme_t_reached", "programme_newton_iterations", "programme_charge_closure",
                  "programme_status", "programme_electrode_voltage", "programme_potential_OHP", "programme_surface_charge")
+
+
+SENSITIVITY_KEYS = ("d_i_CO", "d_i_H2", "d_surface_charge", "d_i_charging", "d_charge_CO", "d_charge_H2", "d_charge_double_layer",
+                    "d_potential_OHP")
+SENSITIVITY_METADATA_KEYS = ("programme_sensitivity_parameters", "programme_sensitivity_start", "programme_sensitivity_status",
+                             "programme_sensitivity_residual")
+OFFSET = "offset"   # the name of parameter code 0 in the drivers: a potential offset of the whole waveform
+
+
+def sensitivity_arrays(ep, eps_0, srec, names, codes):
+    """The arrays of ``programme_sensitivity.npz`` from the sensitivity records (steps, columns): time_s, parameters, status (steps,
+    columns) and, per quantity of ``SENSITIVITY_KEYS``, an array (steps, columns) in the units and signs of ``output_arrays``
+    (d_i_CO, d_i_H2 [A/m2], d_surface_charge [C/m2], d_i_charging [A/m2], the charges [C/m2], d_potential_OHP [V]) per unit of the
+    column's parameter: ln i0, alpha, ln stern_length, and volts for the offset (the library's column is per thermal voltage)."""
+    V_T, tc = ep.thermal_voltage, ep.time_constant
+    q = eps_0 * V_T / ep.L_n
+    per = np.array([1.0 / V_T if int(c) == 0 else 1.0 for c in codes])[None, :]
+    out = {"time_s": (srec["t"][:, 0] if len(srec) else np.zeros(0)) * tc, "parameters": np.array([str(n) for n in names]),
+           "status": srec["status"].astype(np.int64),
+           "d_i_CO": srec["dI"][:, :, 0] * per, "d_i_H2": srec["dI"][:, :, 1] * per, "d_surface_charge": q * srec["dD"] * per,
+           "d_i_charging": -q * srec["d_dD_dt"] / tc * per, "d_charge_CO": srec["dQ"][:, :, 0] * tc * per,
+           "d_charge_H2": srec["dQ"][:, :, 1] * tc * per, "d_charge_double_layer": -q * srec["dQ_D"] * per,
+           "d_potential_OHP": srec["dp_boundary"] * V_T * per}
+    assert set(out) == set(SENSITIVITY_KEYS) | {"time_s", "parameters", "status"}
+    return out
 
 
 def segment_cycles(segs, cycles):

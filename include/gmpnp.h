@@ -779,6 +779,65 @@ int gmpnp_electrode_trace_append(gmpnp_solver* s, double t, double h);
 int gmpnp_electrode_trace_read(gmpnp_solver* s, int32_t first, int32_t n, gmpnp_electrode_record_t* out /* [n] */);
 int gmpnp_electrode_trace_close(gmpnp_solver* s);
 
+/* ---- transient sensitivities (no reference counterpart: what a marched potential programme says about the electrode parameters;
+ * kernels: csrc/gmpnp_sensitivity.h) ---------------------------------------------------------------------------------------------------
+ * 1D handles.  With J = K + inv_dt M (M the consistent P1 mass on the free species rows) the backward-Euler time term is linear in u_n,
+ * dF/du_n = -inv_dt M, so the exact discrete forward sensitivity s_k = du/dtheta_k of a marched programme obeys, per accepted step,
+ *     J(u^{n+1}) s_k^{n+1} = -c_k(u^{n+1}) + inv_dt M s_k^n          (Dirichlet rows: 0)
+ * with the electrode tangent's columns c_k = dF/dtheta_k and its parameter codes (0 = p_M: an offset of the whole waveform, 16 + r =
+ * ln k_r, 32 + r = alpha_r, 48 = ln lam).  The buffers are per handle and allocated by the first gmpnp_sensitivity_open (a handle that
+ * never asks keeps the buffers and launches it had).
+ *   open(n, param, start, capacity)   n = 1 ... 10 columns and a record buffer of `capacity` steps x n columns.  start = 0: S = 0 (the
+ *                     state the march starts from does not depend on theta); start = 1: S = the columns of a still-valid
+ *                     gmpnp_electrode_tangent call that holds every param[k] with status 0 (made at inv_dt = 0 it is the steady state's
+ *                     dependence on theta; refused with a stale or missing tangent, as gmpnp_parameter_advance is); start = 2: S and
+ *                     the accumulators stay what they are and only the count is reset (the same n and param as the open before: a
+ *                     full buffer was read).  start 0 and 1 take the tangent's functional dD of S at the current u and options as
+ *                     dD_prev and zero dQ and dQ_D.  One synchronisation.
+ *   step(t, h)        once per accepted step, after its Newton solve, with model.inv_dt the step's; u_n is not read.  It enqueues its
+ *                     launches and returns: no host synchronisation, no copy.  F and J are assembled at the current u as
+ *                     gmpnp_electrode_tangent assembles them and the columns c_k are formed by its kernels; k_sens_rhs writes
+ *                     -c_k + inv_dt M s_k straight into level 0 of the multi-column cyclic reduction (at most 2 columns: one chain of
+ *                     2; otherwise a chain of 8 and, for columns 9 and 10, a chain of 2); the solution replaces S; k_sens_record (one
+ *                     workgroup, fixed order, no floating-point atomics) applies the tangent's functionals to S and the trace's combine
+ *                     step to the derivatives, every product, quotient and sum rounded on its own,
+ *                         d_dD_dt = (dD - dD_prev) / h     dQ[r] += h dI[r]     dQ_D += h d_dD_dt     dD_prev = dD
+ *                     and stores one record per column.  status: bit 1 = a value of the column that is not finite, bit 2 = the
+ *                     elimination met a singular pivot, bit 4 = the assembly reported eps <= 0 or a rate that is not finite.
+ *                     Afterwards u, u_n, the options and the electrode trace are untouched, F and J are those of the current u, a
+ *                     following gmpnp_newton_solve gives the bits of a handle that never made the call, and the tangent is dropped as
+ *                     after a tangent call.  A column's records and S do not depend on which other columns are carried; two runs give
+ *                     equal bits; from start = 0 the first step is gmpnp_electrode_tangent at that state and inv_dt, bit for bit.
+ *                     A full buffer is refused and nothing is overwritten: read the records and open with start = 2.
+ *   read(first, n_steps)   the records of steps first ... first + n_steps - 1, out[n_steps][n], one synchronisation and one copy
+ *   columns(which)    parity hook: which = 0 the sensitivities S, which = 1 the right-hand sides of the last step, out[n][n_dofs] in
+ *                     file order
+ *   close()           step, read, columns and hook 31 are refused until the next open (the buffers stay with the handle)
+ * Refused (GMPNP_ERR_INVALID, the message names the sensitivities): everything gmpnp_electrode_tangent refuses of a handle, 3D handles,
+ * n outside 1 ... 10, an unknown or repeated parameter, a kinetic parameter with the kinetics off or of a reaction >= n_reactions,
+ * capacity < 1, start outside 0 ... 2, start = 2 without an earlier open of the same columns, h <= 0 or not finite, t not finite, step /
+ * read / columns / close without an open buffer, a read outside the steps written. */
+typedef struct {
+  double t, h;                                /* the arguments of the step */
+  int32_t param;
+  int32_t pad0_;
+  double dD, d_dD_dt;
+  double dI[GMPNP_MAX_SURFACE_REACTIONS];
+  double dQ[GMPNP_MAX_SURFACE_REACTIONS];
+  double dQ_D;
+  double dp_boundary;
+  double residual;                            /* max |J s - rhs| / max |rhs| */
+  int32_t status;                             /* bits 1, 2, 4 */
+  int32_t pad_;
+} gmpnp_sensitivity_record_t;
+int gmpnp_sensitivity_open(gmpnp_solver* s, int32_t n, const int32_t* param /* [n] */, int32_t start, int32_t capacity);
+int gmpnp_sensitivity_step(gmpnp_solver* s, double t, double h);
+int gmpnp_sensitivity_read(gmpnp_solver* s, int32_t first, int32_t n_steps, gmpnp_sensitivity_record_t* out /* [n_steps][n] */);
+int gmpnp_sensitivity_columns(gmpnp_solver* s, int32_t which, double* out /* [n][n_dofs] in file order */);
+/* Parity hook's counterpart: S <- in (what the tests of the right-hand side and of the status word plant); dD_prev, dQ and dQ_D stay. */
+int gmpnp_sensitivity_set_columns(gmpnp_solver* s, const double* in /* [n][n_dofs] in file order */);
+int gmpnp_sensitivity_close(gmpnp_solver* s);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -858,7 +917,11 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * kinetics on, k_electrode_record; needs an open trace, whose records, count, D_prev, Q and Q_D stay: the hook's launches write a slot
  * and accumulators of their own), 30 = every launch of one chunk of the 3D frequency response (scatter, k_cband_step per pivot, the
  * solve and its refinement rounds, k_cband_functional on the frequencies of the last chunk of the last gmpnp_frequency_response_3d
- * call, which it needs; it writes the response's own storage only). */
+ * call, which it needs; it writes the response's own storage only), 31 = the launches of one gmpnp_sensitivity_step (assembly, columns,
+ * k_sens_rhs, the multi-column chain(s), application, k_spmv_plain per column, k_sens_record; needs an open sensitivity buffer, whose S,
+ * records, count and accumulators stay: the hook's launches work on a second S (allocated by the first hook call), a slot and
+ * accumulators of their own; like a step it reassembles F and J at the current u and drops the tangent, so a gmpnp_sensitivity_open with
+ * start = 1 needs a gmpnp_electrode_tangent call made after it). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
