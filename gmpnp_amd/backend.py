@@ -50,6 +50,7 @@ EXPORTS = [
     "gmpnp_parameter_advance", "gmpnp_get_electrode_options",
     "gmpnp_set_electrode_potential", "gmpnp_electrode_trace_open", "gmpnp_electrode_trace_append", "gmpnp_electrode_trace_read",
     "gmpnp_electrode_trace_close",
+    "gmpnp_wall_profile_open", "gmpnp_wall_profile_append", "gmpnp_wall_profile_read", "gmpnp_wall_profile_close",
     "gmpnp_sensitivity_open", "gmpnp_sensitivity_step", "gmpnp_sensitivity_read", "gmpnp_sensitivity_columns", "gmpnp_sensitivity_set_columns",
     "gmpnp_sensitivity_close",
 ]
@@ -159,6 +160,12 @@ ELECTRODE_RECORD_DTYPE = np.dtype([("t", "f8"), ("h", "f8"), ("p_M", "f8"), ("p_
                                    ("I", "f8", MAX_SURFACE_REACTIONS), ("Q", "f8", MAX_SURFACE_REACTIONS), ("Q_D", "f8"),
                                    ("u_boundary", "f8", MAX_SPECIES), ("status", "i4"), ("pad_", "i4")])
 ELECTRODE_RECORD_NONFINITE = 1    # bit of gmpnp_electrode_record_t.status
+# image of gmpnp_wall_profile_record_t (include/gmpnp.h "wall profile"): one element per (step, bin)
+WALL_PROFILE_RECORD_DTYPE = np.dtype([("t", "f8"), ("h", "f8"), ("z_lo", "f8"), ("z_hi", "f8"), ("area", "f8"), ("D", "f8"),
+                                      ("I", "f8", MAX_SURFACE_REACTIONS), ("Q", "f8", MAX_SURFACE_REACTIONS), ("p_mean", "f8"),
+                                      ("u_mean", "f8", MAX_SPECIES), ("count", "i4"), ("status", "i4")])
+WALL_PROFILE_MAX_BINS = 256       # GMPNP_WALL_PROFILE_MAX_BINS
+WALL_PROFILE_NONFINITE = 1        # bit of gmpnp_wall_profile_record_t.status
 
 
 class CSensitivityRecord(ctypes.Structure):
@@ -334,6 +341,10 @@ def load_library(path: str = None):
     lib.gmpnp_electrode_trace_append.argtypes = [c_void_p, c_double, c_double]
     lib.gmpnp_electrode_trace_read.argtypes = [c_void_p, c_int32, c_int32, POINTER(CElectrodeRecord)]
     lib.gmpnp_electrode_trace_close.argtypes = [c_void_p]
+    lib.gmpnp_wall_profile_open.argtypes = [c_void_p, c_int32, POINTER(c_double), c_int32]
+    lib.gmpnp_wall_profile_append.argtypes = [c_void_p, c_double, c_double]
+    lib.gmpnp_wall_profile_read.argtypes = [c_void_p, c_int32, c_int32, c_void_p]
+    lib.gmpnp_wall_profile_close.argtypes = [c_void_p]
     lib.gmpnp_sensitivity_open.argtypes = [c_void_p, c_int32, POINTER(c_int32), c_int32, c_int32]
     lib.gmpnp_sensitivity_step.argtypes = [c_void_p, c_double, c_double]
     lib.gmpnp_sensitivity_read.argtypes = [c_void_p, c_int32, c_int32, POINTER(CSensitivityRecord)]
@@ -846,6 +857,30 @@ class DeviceSolver:
     def electrode_trace_close(self):
         """``gmpnp_electrode_trace_close``."""
         self._check(self.lib.gmpnp_electrode_trace_close(self._h))
+
+    def wall_profile_open(self, edges, capacity):
+        """``gmpnp_wall_profile_open``: the wall of the 3D pore in ``len(edges) - 1`` axial bins with the edges ``edges`` (z, the mesh's
+        third coordinate in units of L; ``programme.wall_bin``) and a buffer of ``capacity`` steps; the charges of the bins start at 0."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+        self._check(self.lib.gmpnp_wall_profile_open(self._h, int(e.size) - 1, e.ctypes.data_as(POINTER(c_double)), int(capacity)))
+        self._wall_profile_bins = int(e.size) - 1
+
+    def wall_profile_append(self, t, h):
+        """``gmpnp_wall_profile_append``: the records of every bin for the step of length ``h`` that ends at ``t`` with the current u,
+        formed and stored on the device (no synchronisation, no copy)."""
+        self._check(self.lib.gmpnp_wall_profile_append(self._h, float(t), float(h)))
+
+    def wall_profile_read(self, first, n) -> np.ndarray:
+        """``gmpnp_wall_profile_read``: the records of steps ``first`` ... ``first + n - 1`` as a structured array (n, bins)
+        (``WALL_PROFILE_RECORD_DTYPE``)."""
+        n, nb = int(n), max(int(getattr(self, "_wall_profile_bins", 0)), 1)
+        out = np.zeros((max(n, 1), nb), dtype=WALL_PROFILE_RECORD_DTYPE)
+        self._check(self.lib.gmpnp_wall_profile_read(self._h, int(first), n, out.ctypes.data_as(c_void_p)))
+        return out[:max(n, 0)]
+
+    def wall_profile_close(self):
+        """``gmpnp_wall_profile_close``."""
+        self._check(self.lib.gmpnp_wall_profile_close(self._h))
 
     def sensitivity_open(self, params, start, capacity):
         """``gmpnp_sensitivity_open``: the state sensitivities S of the parameter codes ``params`` (``polarisation.PARAM_*``) and a

@@ -220,6 +220,19 @@ struct gmpnp_tracer {
   bool open = false;
 };
 
+// device side of the wall profile (gmpnp_wall_profile.h), allocated by the first gmpnp_wall_profile_open: a handle that never asks for it
+// keeps the buffers and launches it had
+struct gmpnp_wall_profiler {
+  DevBuf<gmpnp_wall_profile_record_t> rec;   // [capacity + 1][n_bins]: the row behind the buffer is gmpnp_time_kernel(32)'s
+  DevBuf<double> Q;                          // [2][n_bins][4]: the charges of the bins; the hook's own
+  DevBuf<double> w, edges;                   // [n_nodes] w_I of the Stern nodes; [n_bins + 1]
+  DevBuf<int32_t> bin_ptr, bin_pos;          // CSR over the bins of positions in the Stern node list, ascending inside a bin
+  DevBuf<int32_t> status;                    // the word of the Stern and kinetic launches of an append (not the solver's)
+  std::vector<double> h_edges;               // the edges of the lists the device holds
+  int n_bins = 0, capacity = 0, count = 0;
+  bool open = false;
+};
+
 // device side of the transient sensitivities (gmpnp_sensitivity.h), allocated by the first gmpnp_sensitivity_open: a handle that never
 // asks for it keeps the buffers and launches it had
 struct gmpnp_sensitizer {
@@ -326,6 +339,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_tangenter> tangenter;
   std::unique_ptr<gmpnp_tracer> tracer;
   std::unique_ptr<gmpnp_sensitizer> sensitizer;
+  std::unique_ptr<gmpnp_wall_profiler> wall_profiler;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
   // (boundary_rebind); allocated by the first of them
   DevBuf<double> bnd_dyn;
@@ -408,6 +422,9 @@ int trace_time_append(gmpnp_solver* s);
 // gmpnp_sensitivity.h: the launches of one gmpnp_sensitivity_step on a second S, a slot and accumulators of the hook's own (gmpnp_time_kernel 31)
 bool sensitivity_is_open(const gmpnp_solver* s);
 int sensitivity_time_step(gmpnp_solver* s);
+// gmpnp_wall_profile.h: the launches of one gmpnp_wall_profile_append into the row of slots and the charges of the hook's own (gmpnp_time_kernel 32)
+bool wall_profile_is_open(const gmpnp_solver* s);
+int wall_profile_time_append(gmpnp_solver* s);
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
@@ -2039,6 +2056,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (kernel == 29 && !trace_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 29 is one append of the electrode trace: no trace is open (gmpnp_electrode_trace_open)");
   if (kernel == 30 && !response_band_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 30 is one chunk of the 3D frequency response: no call has been made (gmpnp_frequency_response_3d), or the Stern option is off");
   if (kernel == 31 && !sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 31 is one step of the transient sensitivities: no buffer is open (gmpnp_sensitivity_open)");
+  if (kernel == 32 && !wall_profile_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 32 is one append of the wall profile: no profile is open (gmpnp_wall_profile_open)");
   if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
@@ -2084,6 +2102,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 29: r = trace_time_append(s); break;     // k_stern_residual + k_kinetics_residual (kinetics on) + k_electrode_record
       case 30: r = response_band_time_chunk(s); break;   // scatter, k_cband_step per pivot, the solve and three refinement rounds, k_cband_functional
       case 31: r = sensitivity_time_step(s); break;      // assembly, columns, k_sens_rhs, chain(s), application, k_spmv_plain per column, k_sens_record
+      case 32: r = wall_profile_time_append(s); break;   // k_stern_residual + k_kinetics_residual (kinetics on) + k_wall_profile
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -2211,3 +2230,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_trace.h"
 #include "gmpnp_sensitivity.h"
 #include "gmpnp_response_band.h"
+#include "gmpnp_wall_profile.h"

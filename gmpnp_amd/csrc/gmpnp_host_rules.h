@@ -471,6 +471,37 @@ GMPNP_RULE_HD inline double electrode_record_combine(ElectrodeAccum& a, double h
 }
 inline bool electrode_trace_step_valid(double t, double h) { return rule_finite(t) && rule_finite(h) && h > 0.0; }
 
+// ---- wall profile (include/gmpnp.h "wall profile"; kernel: gmpnp_wall_profile.h; gmpnp_amd/programme.py states the same in Python) ------
+// The wall of the 3D pore in n axial bins with the edges edges[0] < ... < edges[n] (z: the mesh's third coordinate, units of L).
+// wall_bin uses comparisons only, so the two statements agree bit for bit by construction: the bin of z is the largest b with
+// edges[b] <= z, z == edges[n] goes to bin n - 1, and z outside [edges[0], edges[n]] (or NaN) is bin -1 and belongs to no bin.
+constexpr int kWallProfileMaxBins = 256;
+inline int wall_bin(double z, const double* edges, int n) {
+  if (!(z >= edges[0]) || !(z <= edges[n])) return -1;
+  int b = 0;
+  for (int k = 1; k < n; ++k) if (edges[k] <= z) b = k;
+  return b;
+}
+inline bool wall_bins_valid(const double* edges, int n) {
+  if (n < 1 || n > kWallProfileMaxBins || !edges) return false;
+  for (int k = 0; k <= n; ++k) if (!rule_finite(edges[k])) return false;
+  for (int k = 0; k < n; ++k) if (!(edges[k] < edges[k + 1])) return false;
+  return true;
+}
+// n equal bins over [z_lo, z_hi]: every operation rounded on its own; the last edge is z_hi itself
+inline std::vector<double> uniform_edges(double z_lo, double z_hi, int n) {
+  GMPNP_RULE_NO_CONTRACT
+  std::vector<double> e((size_t)(n > 0 ? n : 0) + 1, z_hi);
+  for (int k = 0; k < n; ++k) e[k] = z_lo + (z_hi - z_lo) * ((double)k / (double)n);
+  return e;
+}
+// the charge statement of electrode_record_combine for one bin: Q_b[r] += h I_b[r], product and sum rounded on their own
+GMPNP_RULE_HD inline void wall_profile_charge(double (&Q)[GMPNP_MAX_SURFACE_REACTIONS], double h, const double (&I)[GMPNP_MAX_SURFACE_REACTIONS]) {
+  GMPNP_RULE_NO_CONTRACT
+  Q[0] = Q[0] + h * I[0]; Q[1] = Q[1] + h * I[1]; Q[2] = Q[2] + h * I[2]; Q[3] = Q[3] + h * I[3];
+}
+inline bool wall_profile_step_valid(double t, double h) { return electrode_trace_step_valid(t, h); }
+
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every
 // update.  A driver hands every residual norm (with the device status word of its evaluation) to first() / next() and does what
 // the verdict says; on `failed` and `limit` the error is (code, message).  Owns r0, steric_excursion, residuals[], n_residuals

@@ -118,6 +118,8 @@ class EDLRun:
         the run stands at the programme's last potential (``stern``, ``kinetics``, the metadata's ``electrode_voltage``), and
         ``impedance`` is taken there.  Not with ``target_current``, ``polarisation``, ``fit``, ``stabilization`` "Y", ``H_OHP`` or
         ``dt_order`` 2 (ValueError, before anything touches the device)."""
+        from .programme import refuse_pore_programme
+        refuse_pore_programme(kwargs, "the 1D driver", " (its electrode record is the profile: use programme)")
         self.programme_par = kwargs.pop("programme", None) or None
         if self.programme_par is not None:
             from .programme import check_programme

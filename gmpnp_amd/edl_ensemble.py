@@ -18,7 +18,7 @@ from .edl1d import EDLRun, run_identifier
 from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
-from .programme import refuse_programme
+from .programme import refuse_pore_programme, refuse_programme
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .params import edl_parameters
 from .timestep import member_adaptive_keywords, refuse_ensemble_order2
@@ -50,6 +50,7 @@ def plan_members(members, num_steps=None):
         refuse_polarisation(m, "an ensemble (member %d)" % k)
         refuse_fit(m, "an ensemble (member %d)" % k)
         refuse_programme(m, "an ensemble (member %d)" % k)
+        refuse_pore_programme(m, "an ensemble (member %d)" % k)
         refuse_galvanostat(m, "an ensemble (member %d)" % k)
         refuse_stern(m, "an ensemble (member %d)" % k)
         refuse_kinetics(m, "an ensemble (member %d)" % k)

@@ -23,7 +23,7 @@ from .edl1d import output_root
 from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
-from .programme import refuse_programme
+from .programme import refuse_pore_programme, refuse_programme
 from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
 from .edl_ensemble import EDLEnsemble, sweep_members
 from .timestep import adaptive_keywords, add_adaptive_arguments
@@ -59,6 +59,7 @@ def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget
         refuse_polarisation(m, "the ensemble sweep (member %d)" % k)
         refuse_fit(m, "the ensemble sweep (member %d)" % k)
         refuse_programme(m, "the ensemble sweep (member %d)" % k)
+        refuse_pore_programme(m, "the ensemble sweep (member %d)" % k)
         refuse_galvanostat(m, "the ensemble sweep (member %d)" % k)
         refuse_stern(m, "the ensemble sweep (member %d)" % k)
         refuse_kinetics(m, "the ensemble sweep (member %d)" % k)
@@ -67,6 +68,7 @@ def run_sweep(members, num_steps=None, device_id=0, stamp=None, log=None, budget
     refuse_polarisation(adaptive, "the ensemble sweep")
     refuse_fit(adaptive, "the ensemble sweep")
     refuse_programme(adaptive, "the ensemble sweep")
+    refuse_pore_programme(adaptive, "the ensemble sweep")
     refuse_galvanostat(adaptive, "the ensemble sweep")
     refuse_stern(adaptive, "the ensemble sweep")
     refuse_kinetics(adaptive, "the ensemble sweep")

@@ -24,6 +24,7 @@ from .solver import GMPNPSystem, column_medians, device_medians_and_minima
 from .timestep import DriverStepping, adaptive_keywords, add_adaptive_arguments
 from .polarisation import add_polarisation_arguments, polarisation_keywords
 from .impedance import add_pore_impedance_arguments, pore_impedance_keywords
+from .programme import add_pore_programme_arguments, pore_programme_keywords
 from .vtk import write_pvd
 
 SOLVER_PARAMETERS = {  # reference 3D:789-798
@@ -102,7 +103,19 @@ class PoreRun:
         dI_H2 [S/m2], residual; all per wall area) and the metadata keys ``pore_impedance_points``, ``pore_impedance_status``,
         ``capacitance_low`` / ``capacitance_high``, ``capacitance_high_closed_form`` (the potential block alone), ``R_ct`` (None
         without kinetics) and ``pore_impedance_last_step_change``.  Not with ``partition``, ``multilevel`` or the device glue; a
-        galvanostat is switched off for the call.  The keyword ``impedance`` is the 1D driver's and stays refused here."""
+        galvanostat is switched off for the call.  The keyword ``impedance`` is the 1D driver's and stays refused here.
+        ``pore_programme`` = dict(kind="pulse", v_levels=[A, B], durations=[s, s], cycles=n[, rise_time=s]) | dict(kind="triangle",
+        v_vertex=X, scan_rate=V/s, cycles=n) | dict(kind="table", time_s=[...], electrode_voltage=[...]), with ``bins`` (16: a count of
+        axial bins, uniform over the z range of the wall nodes, or explicit edges [m]) and ``dt_init``, ``steps_per_segment``,
+        ``capacity`` (with ``electrode_voltage``): ``write_outputs`` marches the electrode potential through the waveform from the run's
+        last state, after the schedule and before ``pore_impedance`` and ``polarisation``, on a clock of its own that starts at 0
+        (``pore_programme()`` does the same at any time).  Per accepted step the device forms one electrode record
+        and one wall-profile record per bin (``gmpnp_wall_profile_append``) without a copy of the state, and the lagged Sechenov update
+        of ``accept_solution`` is applied from the device's medians.  Adds ``pore_programme.npz`` (``programme.PORE_OUTPUT_KEYS``),
+        ``pore_programme_states.npz``, the attempts as ``pore_programme_*`` arrays of ``timestep_log.npz`` and the metadata keys
+        ``programme.PORE_METADATA_KEYS``; afterwards the run stands at the programme's last potential.  Order 1, no sensitivities; not
+        with ``target_current``, ``polarisation``, ``dt_order`` 2, ``partition``, ``multilevel`` or the device glue (ValueError, before
+        anything touches the device).  The keyword ``programme`` is the 1D driver's and stays refused here."""
         if glue not in ("host", "device"):
             raise ValueError("glue must be 'host' or 'device'")
         from .impedance import refuse_impedance
@@ -111,6 +124,10 @@ class PoreRun:
         from .programme import refuse_programme
         refuse_fit(kwargs, "the 3D pore driver (the library's parameter advance works there, the fit's host glue is 1D)")
         refuse_programme(kwargs, "the 3D pore driver (potential programmes are 1D)")
+        self.pore_programme_par = kwargs.pop("pore_programme", None) or None
+        if self.pore_programme_par is not None:   # (while kwargs still holds polarisation, target_current and electrode_voltage)
+            from .programme import check_pore_programme
+            self.pore_programme_par = check_pore_programme(self.pore_programme_par, kwargs, dt_order, partition, multilevel, glue)
         self.polarisation_par = kwargs.pop("polarisation", None) or None
         if self.polarisation_par is not None:
             from .polarisation import check_polarisation
@@ -162,6 +179,7 @@ class PoreRun:
         if self.stern is not None and multilevel:
             raise ValueError("electrode_voltage: the Stern boundary condition is not available with the geometric multilevel term")
         self.adaptive = bool(adaptive_dt)
+        self.dt_tol, self.dt_bounds, self.max_steps, self.dt_order = (dt_rtol, dt_atol), (dt_min, dt_max), max_steps, int(dt_order)
         if self.adaptive and partition:
             raise ValueError("adaptive_dt: adaptive time stepping is not available in a partitioned solve")
         self.step_fraction = float(step_fraction)
@@ -451,6 +469,88 @@ class PoreRun:
                 "R_ct": (1.0 / g_ct) if g_ct != 0.0 else None, "pore_impedance_last_step_change": change,
                 "pore_impedance_status": int(np.bitwise_or.reduce(sp["status"]))}
 
+    def wall_node_z(self):
+        """z (units of L) of the wall's nodes: what the bins of the wall profile sort."""
+        wall = np.unique(np.asarray(self.problem.wall_facets, dtype=np.int64))
+        return np.asarray(self.problem.coords, dtype=np.float64)[wall, 2]
+
+    def sechenov_glue(self):
+        """The lagged Sechenov update of ``accept_solution`` from the device's medians (no state is gathered) and the new Dirichlet
+        set: what an accepted step of ``pore_programme`` runs."""
+        meds, _ = device_medians_and_minima(self.sys, (1, 2, 3, 7), ())
+        self.co2_bc = self.pp.sechenov_co2_scaled(*meds)
+        self.sys.set_bcs(*pore_dirichlet(self.pp, self.bnd, self.co2_bc, stern=True))
+
+    def pore_programme(self, verbose=False, **par):
+        """Marches the electrode potential through the programme ``par`` (the ``pore_programme`` keyword of ``__init__``) from the
+        run's CURRENT state, on a clock of its own from 0 (gmpnp_amd/programme.py: ``run_programme`` over ``DeviceProgrammeOps`` with
+        the Sechenov glue behind every accepted step and the wall profile beside the trace).  Newton and the linear solver are the
+        run's own ``solver_parameters``, inv_dt = 1 / h, seconds are converted with ``pp.time_constant``
+        (``impedance.pore_sigma_from_frequency`` documents the relation), the tolerances and ``max_steps`` are the run's.  The run's
+        own inv_dt is put back afterwards; the run and the handle end at the programme's last potential.  Returns the arrays of
+        ``pore_programme.npz`` plus ``log``, ``states`` (segment, time_s, (nv, nf) values at the breakpoints and at the end) and
+        ``metadata`` (the ``pore_programme_*`` keys)."""
+        import math
+        from . import programme as prg
+        from .timestep import TimeStepPolicy
+        if self.stern is None:
+            raise ValueError("pore_programme: a potential programme needs an electrode potential (electrode_voltage)")
+        if self.galvanostat is not None:
+            raise ValueError("pore_programme: not available with target_current (the galvanostat owns the potential)")
+        if self.glue != "host" or self._levels is not None or self.rank is not None:
+            raise ValueError("pore_programme: the programme runs on one unpartitioned handle without the multilevel term (host glue)")
+        par = prg.check_pore_programme(par, dict(electrode_voltage=self.stern.p_electrode, kinetics=self.kinetics),
+                                       self.dt_order)
+        pp = self.pp
+        edges = prg.resolve_bins(par["bins"], self.wall_node_z(), pp.L)
+        segs = prg.build(par, float(self.stern.p_electrode), pp.time_constant, pp.thermal_voltage)
+        inv_dt = float(self.sys.problem.model.inv_dt)
+        policy = TimeStepPolicy(h_min=float(self.dt_bounds[0]), h_max=math.inf if self.dt_bounds[1] is None else float(self.dt_bounds[1]))
+        ops = prg.DeviceProgrammeOps(self, self.solver_parameters, lambda h: 1.0 / h, self.dt_tol, par.get("capacity") or 4096,
+                                     after_accept=self.sechenov_glue, profile_edges=edges)
+        try:
+            res = prg.run_programme(ops, segs, policy, dt_init=par.get("dt_init") or pp.dt, dt_restart=par.get("dt_restart"),
+                                    steps_per_segment=par.get("steps_per_segment"), max_attempts=self.max_steps)
+            rec = ops.records()
+            prof = ops.profile_records()
+            last = self.sys.vertex_values()
+        except BaseException:   # back to the last accepted state, no trace or profile left open
+            ops.abort()
+            raise
+        finally:
+            self.sys.set_time_step(inv_dt)
+        out = prg.pore_output_arrays(pp, self._eps_0(), self.wall_area(), rec, prof, ops.segments, segs, par.get("cycles", 1))
+        if verbose:
+            print("pore_programme %s: %d accepted steps, %d attempts, %s" % (par["kind"], len(rec), len(res["log"]), res["stop_reason"]))
+        states = list(ops.states)
+        t_last = res["times"][-1] if res["times"] else 0.0
+        if not states or states[-1][1] != t_last:   # the run ended between two breakpoints (max_steps, h_min): its last state is kept too
+            states.append((ops.segments[-1] if ops.segments else 0, t_last, last))
+        n = len(rec)
+        meta = {"pore_programme_kind": par["kind"], "pore_programme_cycles": int(par.get("cycles", 1)), "pore_programme_segments": len(segs),
+                "pore_programme_steps_accepted": int(n), "pore_programme_steps_rejected": int(len(res["log"]) - n),
+                "pore_programme_stop_reason": res["stop_reason"], "pore_programme_t_reached": float(t_last * pp.time_constant),
+                "pore_programme_newton_iterations": int(ops.newton_iterations),
+                "pore_programme_charge_closure": float(rec["Q_D"][-1] - (rec["D"][-1] - ops.D_first)) if n else 0.0,
+                "pore_programme_status": (int(np.bitwise_or.reduce(rec["status"])) | int(np.bitwise_or.reduce(prof["status"].ravel()))) if n else 0,
+                "pore_programme_electrode_voltage": float(self.stern.p_electrode),
+                "pore_programme_potential_OHP": float(out["potential_OHP"][-1]) if n else None,
+                "pore_programme_surface_charge": float(out["surface_charge"][-1]) if n else None,
+                "pore_programme_bins": int(len(edges) - 1)}
+        assert set(meta) == set(prg.PORE_METADATA_KEYS)
+        out.update(log=prg.log_arrays(res["log"]), states=[(k, t * pp.time_constant, v) for k, t, v in states], metadata=meta)
+        return out
+
+    def pore_programme_outputs(self, newpath):
+        """``pore_programme.npz``, ``pore_programme_states.npz`` and the attempts for ``timestep_log.npz``; returns (metadata keys, log
+        arrays)."""
+        out = self.pore_programme(**self.pore_programme_par)
+        meta, log, states = out.pop("metadata"), out.pop("log"), out.pop("states")
+        np.savez(os.path.join(newpath, "pore_programme.npz"), **out)
+        np.savez(os.path.join(newpath, "pore_programme_states.npz"), segment=np.array([k for k, _, _ in states], dtype=np.int64),
+                 time_s=np.array([t for _, t, _ in states]), states=np.stack([v for _, _, v in states]), coor=self.mesh.coords)
+        return meta, {"pore_programme_" + k: v for k, v in log.items()}
+
     def wall_area(self):
         X = self.problem.coords[self.problem.wall_facets]
         return float((0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)).sum())
@@ -539,6 +639,8 @@ class PoreRun:
             "num_steps_run": int(self.n)}
         if self.step_fraction:
             metadata_dict["step_fraction"] = self.step_fraction
+        # after the schedule, in front of everything that reads the handle: the metadata reports the state the programme ends at
+        programme = self.pore_programme_outputs(newpath) if self.pore_programme_par is not None else None
         if self.stern is not None:
             metadata_dict.update(self.stern_summary())
         if self.kinetics is not None:
@@ -551,6 +653,12 @@ class PoreRun:
             metadata_dict.update(self.budget.save(newpath))
         if self.stepper is not None:
             self.stepping.save(newpath, metadata_dict)
+        if programme is not None:
+            metadata_dict.update(programme[0])
+            log_path = os.path.join(newpath, "timestep_log.npz")
+            with_schedule = dict(np.load(log_path)) if os.path.exists(log_path) else {}
+            np.savez(log_path, **with_schedule, **programme[1])
+            metadata_dict["timestep_log"] = "timestep_log.npz"
         if self.pore_impedance_par is not None:   # at the run's last state, before the polarisation curve moves the handle
             metadata_dict.update(self.pore_impedance_outputs(newpath))
         if self.polarisation_par is not None:   # last: the handle leaves the run's operating point
@@ -566,7 +674,7 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
              roughness_factor=150.0, num_steps=None, as_published=False, verbose=True, refine=0, multilevel=False, partition=None,
              device_kwargs=None, glue="host", budget=False, step_fraction=0.0, electrode_voltage=None, stern_model="BDM", stern_length=4.0e-10,
              stern_eps_surface=6.0, kinetics=None, i0_CO=None, i0_H2=None, alpha_CO=0.5, alpha_H2=0.5, p_eq_CO=0.0, p_eq_H2=0.0, target_current=None, polarisation=None,
-             pore_impedance=None, **adaptive):
+             pore_impedance=None, pore_programme=None, **adaptive):
     """Same keyword surface as the reference's ``solveEDL`` (3D:96-113); returns the output directory.  Additions:
     ``num_steps``, ``as_published``, ``refine`` (uniform refinements of the mesh file), ``multilevel`` (with ``refine`` > 0: the
     geometric multilevel term of the preconditioner), ``partition`` / ``device_kwargs`` / ``glue`` / ``budget`` as ``PoreRun`` takes them (with
@@ -587,6 +695,8 @@ def solveEDL(concentration_elec=1.0, voltage_multiplier=None, H2_FE=0.05, curren
         stern.update(polarisation=polarisation)
     if pore_impedance:   # (the impedance spectrum of ``PoreRun``, at the last state)
         stern.update(pore_impedance=pore_impedance)
+    if pore_programme:   # (the potential programme of ``PoreRun``, after the last step)
+        stern.update(pore_programme=pore_programme)
     run = PoreRun(**stern, num_steps=num_steps, as_published=as_published, refine=refine, multilevel=multilevel, partition=partition,
                   device_kwargs=device_kwargs, glue=glue, budget=budget, step_fraction=step_fraction, **adaptive, concentration_elec=concentration_elec,
                   voltage_multiplier=voltage_multiplier, H2_FE=H2_FE, current_rough=current_rough, L=L, cation=cation,
@@ -631,6 +741,7 @@ def build_parser():
     add_polarisation_arguments(p)  # (with --electrode_voltage; not with --partitions / --multilevel / --target_current / --dt_order 2)
     add_galvanostat_arguments(p)   # (with --kinetics tafel; not with --partitions / --multilevel / --dt_order 2)
     add_pore_impedance_arguments(p)   # (with --electrode_voltage; not with --partitions / --multilevel)
+    add_pore_programme_arguments(p)   # (with --electrode_voltage; not with --partitions / --multilevel / --target_current / --polarisation / --dt_order 2)
     return p
 
 
@@ -677,7 +788,7 @@ def main(argv=None):
                         pore_geom_multiplier=a.pore_geom_multiplier,
                         electrolyte_flow_geom_multiplier=a.electrolyte_flow_geom_multiplier,
                         roughness_factor=a.roughness_factor, num_steps=a.num_steps, as_published=a.as_published, refine=a.refine,
-                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a), **polarisation_keywords(a), **pore_impedance_keywords(a), **extra)
+                        multilevel=a.multilevel, budget=a.budget, step_fraction=a.step_fraction, **adaptive_keywords(a), **stern_keywords(a), **kinetics_keywords(a), **galvanostat_keywords(a), **polarisation_keywords(a), **pore_impedance_keywords(a), **pore_programme_keywords(a), **extra)
     finally:
         if tdist is not None:
             tdist.barrier()

@@ -204,6 +204,83 @@ def fresh_accumulators(D):
     return {"D_prev": float(D), "Q": [0.0] * MAX_SURFACE_REACTIONS, "Q_D": 0.0}
 
 
+# ---- the wall profile's rule (csrc/gmpnp_host_rules.h "wall profile", statement for statement) -----------------------------------------------
+WALL_PROFILE_MAX_BINS = 256   # GMPNP_WALL_PROFILE_MAX_BINS
+
+
+def wall_bin(z, edges, n):
+    """The axial bin of ``z`` among the n + 1 ascending ``edges``, by comparisons only: the largest b with edges[b] <= z; z == edges[n]
+    goes to bin n - 1; z outside [edges[0], edges[n]] (or NaN) is bin -1 and belongs to no bin."""
+    if not z >= edges[0] or not z <= edges[n]:
+        return -1
+    b = 0
+    for k in range(1, n):
+        if edges[k] <= z:
+            b = k
+    return b
+
+
+def wall_bins_valid(edges, n):
+    if n < 1 or n > WALL_PROFILE_MAX_BINS or edges is None or len(edges) != n + 1:
+        return False
+    if not all(math.isfinite(float(e)) for e in edges):
+        return False
+    return all(edges[k] < edges[k + 1] for k in range(n))
+
+
+def uniform_edges(z_lo, z_hi, n):
+    """n equal bins over [z_lo, z_hi]: z_lo + (z_hi - z_lo) * (k / n), every operation rounded on its own; the last edge is z_hi."""
+    z_lo, z_hi = float(z_lo), float(z_hi)
+    return [z_lo + (z_hi - z_lo) * (float(k) / float(n)) for k in range(n)] + [z_hi]
+
+
+def wall_profile_charge(Q, h, I):
+    """The charge statement of ``electrode_record_combine`` for one bin: Q[r] + h I[r], product and sum rounded on their own."""
+    return [float(Q[r]) + float(h) * float(I[r]) for r in range(MAX_SURFACE_REACTIONS)]
+
+
+def wall_bin_lists(z, edges):
+    """The positions (ascending) of the values ``z`` in every bin of ``edges``: what ``gmpnp_wall_profile_open`` uploads as a CSR."""
+    n = len(edges) - 1
+    out = [[] for _ in range(n)]
+    for k, zk in enumerate(z):
+        b = wall_bin(float(zk), edges, n)
+        if b >= 0:
+            out[b].append(k)
+    return out
+
+
+def resolve_bins(bins, z_wall, L):
+    """The edges (units of L) of a driver's ``bins``: a count, uniform over the z range of the wall nodes ``z_wall`` (units of L), or
+    explicit edges in metres.  ValueError (``pore_programme``) where they are not valid or a bin holds no wall node."""
+    if np.ndim(bins) == 0:
+        check_bins(bins)
+        edges = uniform_edges(float(np.min(z_wall)), float(np.max(z_wall)), int(bins))
+    else:
+        edges = [float(e) / float(L) for e in bins]
+    n = len(edges) - 1
+    if not wall_bins_valid(edges, n):
+        raise ValueError("pore_programme: bins is a count 1 ... %d or finite, strictly ascending edges [m]" % WALL_PROFILE_MAX_BINS)
+    for b, members in enumerate(wall_bin_lists(z_wall, edges)):
+        if not members:
+            raise ValueError("pore_programme: bin %d of %d holds no node of the wall: ask for fewer bins" % (b, n))
+    return edges
+
+
+def check_bins(bins):
+    """The part of ``resolve_bins`` that needs no mesh (before anything touches the device)."""
+    bad = ValueError("pore_programme: bins is a count 1 ... %d or finite, strictly ascending edges [m]" % WALL_PROFILE_MAX_BINS)
+    if isinstance(bins, (bool, str)) or bins is None:
+        raise bad
+    if np.ndim(bins) == 0:
+        if not float(bins).is_integer() or not 1 <= int(bins) <= WALL_PROFILE_MAX_BINS:
+            raise bad
+        return
+    edges = [float(e) for e in np.asarray(bins, dtype=np.float64).ravel()]
+    if np.ndim(bins) != 1 or not wall_bins_valid(edges, len(edges) - 1):
+        raise bad
+
+
 # ---- the loop ------------------------------------------------------------------------------------------------------------------------------
 LOG_COLUMNS = ("t", "h", "accepted", "reason", "err", "newton", "segment", "potential", "restart")
 
@@ -464,12 +541,19 @@ class DeviceProgrammeOps:
     and the states at the breakpoints, not a state per step.  The accumulated charges go on across a drained buffer: the host adds
     what the records before held."""
 
-    def __init__(self, run, solver_parameters, inv_dt_of_h, tol=(1e-2, 1e-4), capacity=4096, sensitivities=None, sensitivity_start="zero"):
+    def __init__(self, run, solver_parameters, inv_dt_of_h, tol=(1e-2, 1e-4), capacity=4096, sensitivities=None, sensitivity_start="zero",
+                 after_accept=None, profile_edges=None):
+        """``after_accept`` (the pore driver's Sechenov glue; the 1D path passes none): called once per accepted step, in front of
+        ``time_accept``; a rejected attempt never reaches it.  ``profile_edges`` (3D handles): ``record`` also appends to the wall
+        profile with these edges and ``drain`` reads and reopens it with the trace; ``profile_records`` returns (steps, bins)."""
         from . import backend
         self.backend = backend
         self.run, self.sys, self.dev = run, run.sys, run.sys.dev
         self.solver_parameters, self.inv_dt_of_h, self.tol, self.capacity = solver_parameters, inv_dt_of_h, tol, int(capacity)
         self.chunks, self.segments, self.states, self.count = [], [], [], 0
+        self.after_accept = after_accept
+        self.profile_edges = None if profile_edges is None else [float(e) for e in profile_edges]
+        self.profile_chunks, self.profile_base_Q = [], None
         self.base_Q, self.base_Q_D = np.zeros(MAX_SURFACE_REACTIONS), 0.0
         self.newton_iterations, self.residuals = 0, []   # residuals: the last Newton residual of every accepted step
         # the transient sensitivities (section 5p): parameter codes of the tangent; "steady" takes the columns of the tangent call the
@@ -483,6 +567,12 @@ class DeviceProgrammeOps:
         if self.sensitivities is not None:
             try:
                 self.dev.sensitivity_open(self.sensitivities, sensitivity_start, self.capacity)
+            except BaseException:
+                self.dev.electrode_trace_close()
+                raise
+        if self.profile_edges is not None:
+            try:
+                self.dev.wall_profile_open(self.profile_edges, self.capacity)
             except BaseException:
                 self.dev.electrode_trace_close()
                 raise
@@ -527,6 +617,8 @@ class DeviceProgrammeOps:
         if self.run.budget is not None:   # while u_n is the previous state and inv_dt the step's
             self.run.budget.take(self.sys)
         self.dev.electrode_trace_append(t, h)
+        if self.profile_edges is not None:
+            self.dev.wall_profile_append(t, h)
         if self.sensitivities is not None:   # accepted steps only: a rejected attempt never touches S
             self.dev.sensitivity_step(t, h)
         self.residuals.append(float(self.sys.last_stats["residuals"][-1]))
@@ -536,6 +628,8 @@ class DeviceProgrammeOps:
             self.drain(reopen=True)
 
     def accept(self):
+        if self.after_accept is not None:
+            self.after_accept()
         self.sys.time_accept()
 
     def reject(self):
@@ -553,9 +647,17 @@ class DeviceProgrammeOps:
             self.chunks.append(rec)
             if self.sensitivities is not None:
                 self.sensitivity_chunks.append(self.dev.sensitivity_read(0, self.count))
+            if self.profile_edges is not None:   # the charges of the bins go on across a drained buffer, as the trace's do
+                prof = self.dev.wall_profile_read(0, self.count)
+                if self.profile_base_Q is not None:
+                    prof["Q"] = prof["Q"] + self.profile_base_Q
+                self.profile_base_Q = prof["Q"][-1].copy()
+                self.profile_chunks.append(prof)
             self.count = 0
         if reopen:
             self.dev.electrode_trace_open(self.capacity)
+            if self.profile_edges is not None:
+                self.dev.wall_profile_open(self.profile_edges, self.capacity)
             if self.sensitivities is not None:
                 self.dev.sensitivity_open(self.sensitivities, "continue", self.capacity)
 
@@ -565,6 +667,7 @@ class DeviceProgrammeOps:
         trace open.  The records written so far stay in ``chunks`` / on the device unread."""
         backend = self.backend
         calls = (self.sys.time_reject, self.dev.electrode_trace_close) + ((self.dev.sensitivity_close,) if self.sensitivities is not None else ())
+        calls = calls + ((self.dev.wall_profile_close,) if self.profile_edges is not None else ())
         for call in calls:
             try:
                 call()
@@ -578,6 +681,17 @@ class DeviceProgrammeOps:
         self.drain()
         self.dev.electrode_trace_close()
         return np.concatenate(self.chunks) if self.chunks else np.zeros(0, dtype=ELECTRODE_RECORD_DTYPE)
+
+    def profile_records(self):
+        """Every record of the wall profile so far, (steps, bins), in order (after ``records``, which drained both buffers; closes the
+        profile)."""
+        from .backend import WALL_PROFILE_RECORD_DTYPE
+        if self.profile_edges is None:
+            raise ValueError("programme: the run carries no wall profile")
+        self.drain()
+        self.dev.wall_profile_close()
+        n = len(self.profile_edges) - 1
+        return np.concatenate(self.profile_chunks) if self.profile_chunks else np.zeros((0, n), dtype=WALL_PROFILE_RECORD_DTYPE)
 
     def sensitivity_records(self):
         """Every sensitivity record so far, (steps, columns), in order (drains both buffers; the sensitivities stay open, with S on the
@@ -635,7 +749,7 @@ def segment_cycles(segs, cycles):
     return np.minimum(np.floor((mid - t0) / period).astype(np.int64), cycles - 1)
 
 
-def output_arrays(ep, eps_0, rec, segments, segs, cycles):
+def output_arrays(ep, eps_0, rec, segments, segs, cycles, species_index=(0, 1, 2, 3, 4, 5)):
     """The arrays of ``programme.npz`` (``OUTPUT_KEYS``) from the records of the trace.  The OHP is one point, so the integrated rates are
     current densities: i_CO, i_H2 [A/m2], their charges [C/m2] = Q_r x time_constant.  surface_charge [C/m2] = eps_0 V_T / L_n x D is
     the charge ON THE ELECTRODE (negative for a cathode); i_charging = -d(surface_charge)/dt [A/m2] is cathodic-positive like the
@@ -661,7 +775,135 @@ def output_arrays(ep, eps_0, rec, segments, segs, cycles):
     out = {"time_s": rec["t"] * tc, "electrode_voltage": rec["p_M"].copy(), "potential_OHP": rec["p_boundary"] * V_T, "surface_charge": q * rec["D"],
            "i_CO": i_CO, "i_H2": i_H2, "i_charging": i_ch, "i_total": tot + i_ch, "charge_CO": rec["Q"][:, 0] * tc, "charge_H2": rec["Q"][:, 1] * tc,
            "charge_double_layer": -q * rec["Q_D"], "FE_H2": fe, "FE_H2_cycle": fe_cycle, "segment": seg, "status": rec["status"].astype(np.int64)}
-    for j, key in enumerate(SPECIES_KEYS):
+    for j, key in zip(species_index, SPECIES_KEYS):   # (the 1D model's species order; the pore driver passes its own)
         out[key] = rec["u_boundary"][:, j].copy()
     assert set(out) == set(OUTPUT_KEYS) and all(len(out[k]) == n for k in OUTPUT_KEYS if k != "FE_H2_cycle")
+    return out
+
+
+# ---- potential programmes in the 3D pore: the keyword ``pore_programme`` of ``PoreRun`` ------------------------------
+PORE_SPECIES_INDEX = (0, 1, 2, 3, 4, 7)   # H, OH, HCO3, CO32, CO2, cat among the pore model's eight species (``SPECIES_KEYS``' order)
+PROFILE_GEOMETRY_KEYS = ("z_lo_m", "z_hi_m", "bin_area_m2")
+PROFILE_KEYS = ("profile_i_CO", "profile_i_H2", "profile_FE_H2", "profile_surface_charge", "profile_potential_OHP", "profile_CO2",
+                "profile_H", "profile_charge_CO", "profile_charge_H2", "profile_status")
+PORE_OUTPUT_KEYS = OUTPUT_KEYS + PROFILE_GEOMETRY_KEYS + PROFILE_KEYS
+PORE_METADATA_KEYS = tuple("pore_" + k for k in METADATA_KEYS) + ("pore_programme_bins",)
+PORE_COMMON_FIELDS = {"kind", "dt_init", "dt_restart", "steps_per_segment", "capacity", "bins"}
+
+
+def check_pore_programme(par, kwargs, dt_order=1, partition=None, multilevel=False, glue="host"):
+    """The refusals of the pore driver's ``pore_programme`` keyword, before anything touches the device; returns the checked dict
+    (``bins`` defaults to 16).  The waveform is ``check_programme``'s; order 1 only and no sensitivities."""
+    par = dict(par)
+    if set(par) & {"sensitivities", "sensitivity_start"}:
+        raise ValueError("pore_programme: the transient sensitivities are 1D (programme)")
+    if kwargs.get("programme"):
+        raise ValueError("pore_programme: not in one run with programme (which the 3D pore driver refuses)")
+    if partition:
+        raise ValueError("pore_programme: not available in a partitioned solve")
+    if multilevel:
+        raise ValueError("pore_programme: not available with the geometric multilevel term")
+    if glue != "host":
+        raise ValueError("pore_programme: the programme runs with the host glue")
+    bins = par.pop("bins", 16)
+    check_bins(bins)
+    try:
+        par = check_programme(par, kwargs, dt_order)
+    except ValueError as e:
+        raise ValueError("pore_" + str(e)) from None
+    par["bins"] = bins
+    return par
+
+
+def refuse_pore_programme(kwargs, what, hint=""):
+    """ValueError where ``kwargs`` asks for a potential programme of the pore (``pore_programme``) in a driver that has none."""
+    if kwargs.get("pore_programme"):
+        raise ValueError("pore_programme: potential programmes with a wall profile are not available in %s%s" % (what, hint))
+
+
+def add_pore_programme_arguments(p):
+    """The pore parser's flags.  None of them begins with --programme: argparse would take --programme for an abbreviation."""
+    p.add_argument("--pore_programme", required=False, default=None, choices=KINDS,
+                   help="(addition) potential programme after the run's own schedule, from its last state, with the wall resolved along "
+                        "the axis (pore_programme.npz)")
+    p.add_argument("--v_levels", required=False, default=None, type=float, nargs="+", help="(addition) levels of --pore_programme pulse [thermal voltages]")
+    p.add_argument("--durations", required=False, default=None, type=float, nargs="+", help="(addition) hold times of --pore_programme pulse [s]")
+    p.add_argument("--cycles", required=False, default=1, type=int, help="(addition) cycles of --pore_programme pulse / triangle")
+    p.add_argument("--rise_time", required=False, default=0.0, type=float, help="(addition) ramp in place of each jump of --pore_programme pulse [s]")
+    p.add_argument("--v_vertex", required=False, default=None, type=float, help="(addition) vertex potential of --pore_programme triangle [thermal voltages]")
+    p.add_argument("--scan_rate", required=False, default=None, type=float, help="(addition) scan rate of --pore_programme triangle [V/s]")
+    p.add_argument("--pore_programme_file", required=False, default=None, type=str,
+                   help="(addition) CSV of --pore_programme table: columns time_s, electrode_voltage")
+    p.add_argument("--pore_programme_dt_init", required=False, default=None, type=float,
+                   help="(addition) first step of the programme and after a jump (scaled time)")
+    p.add_argument("--pore_programme_steps_per_segment", required=False, default=None, type=int,
+                   help="(addition) fixed mode: equal steps per segment, no estimator")
+    p.add_argument("--pore_programme_bins", required=False, default=None, type=int, help="(addition) axial bins of the wall profile (default 16)")
+
+
+def pore_programme_keywords(a):
+    """The ``pore_programme`` keyword of a parsed command line (``add_pore_programme_arguments``); empty without --pore_programme."""
+    kind = a.pore_programme
+    if kind is None:
+        return {}
+    par = {"kind": kind}
+    if kind == "pulse":
+        if a.v_levels is None or a.durations is None:
+            raise ValueError("pore_programme: --pore_programme pulse needs --v_levels and --durations")
+        par.update(v_levels=list(a.v_levels), durations=list(a.durations), cycles=a.cycles, rise_time=a.rise_time)
+    elif kind == "triangle":
+        if a.v_vertex is None or a.scan_rate is None:
+            raise ValueError("pore_programme: --pore_programme triangle needs --v_vertex and --scan_rate")
+        par.update(v_vertex=a.v_vertex, scan_rate=a.scan_rate, cycles=a.cycles)
+    else:
+        if a.pore_programme_file is None:
+            raise ValueError("pore_programme: --pore_programme table needs --pore_programme_file")
+        t, v = load_table(a.pore_programme_file)
+        par.update(time_s=t, electrode_voltage=v)
+    if a.pore_programme_dt_init is not None:
+        par["dt_init"] = a.pore_programme_dt_init
+    if a.pore_programme_steps_per_segment is not None:
+        par["steps_per_segment"] = a.pore_programme_steps_per_segment
+    if a.pore_programme_bins is not None:
+        par["bins"] = a.pore_programme_bins
+    return {"pore_programme": par}
+
+
+def wall_mean_records(rec, wall_area):
+    """The records of the trace with the integrated quantities (D, dD_dt, I, Q, Q_D) divided by the wall area (scaled units): what
+    ``output_arrays`` turns into wall means."""
+    out = rec.copy()
+    for key in ("D", "dD_dt", "I", "Q", "Q_D"):
+        out[key] = rec[key] / float(wall_area)
+    return out
+
+
+def pore_output_arrays(pp, eps_0, wall_area, rec, prof, segments, segs, cycles):
+    """The arrays of ``pore_programme.npz`` (``PORE_OUTPUT_KEYS``).  ``OUTPUT_KEYS`` as wall means: the currents [A/m2] and charges
+    [C/m2] divided by the wall area (scaled, sum_I w_I), surface_charge = eps_0 V_T / L x D / wall area as ``polarisation.curve_arrays``
+    has it for 3D.  From the profile records ``prof`` (steps, bins), every quantity divided by the bin's OWN area: z_lo_m, z_hi_m [m],
+    bin_area_m2 [m2] (bins,); profile_i_CO, profile_i_H2 [A/m2], profile_FE_H2, profile_surface_charge [C/m2],
+    profile_potential_OHP [V], profile_CO2 and profile_H (scaled concentrations, as arrays_unscaled.npz holds them),
+    profile_charge_CO, profile_charge_H2 [C/m2] and profile_status, each (steps, bins)."""
+    from types import SimpleNamespace
+    ep = SimpleNamespace(thermal_voltage=pp.thermal_voltage, time_constant=pp.time_constant, L_n=pp.L)
+    out = output_arrays(ep, eps_0, wall_mean_records(rec, wall_area), segments, segs, cycles, species_index=PORE_SPECIES_INDEX)
+    V_T, tc, L = pp.thermal_voltage, pp.time_constant, pp.L
+    q = eps_0 * V_T / L
+    nb = prof.shape[1]
+    if len(prof):
+        area = prof["area"]
+        out.update(z_lo_m=prof["z_lo"][0] * L, z_hi_m=prof["z_hi"][0] * L, bin_area_m2=area[0] * L * L)
+    else:
+        area = np.ones((0, nb))
+        out.update(z_lo_m=np.full(nb, np.nan), z_hi_m=np.full(nb, np.nan), bin_area_m2=np.full(nb, np.nan))
+    i_CO, i_H2 = prof["I"][:, :, 0] / area, prof["I"][:, :, 1] / area
+    tot = i_CO + i_H2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fe = np.where(tot != 0.0, i_H2 / tot, np.nan)
+    out.update(profile_i_CO=i_CO, profile_i_H2=i_H2, profile_FE_H2=fe, profile_surface_charge=q * prof["D"] / area,
+               profile_potential_OHP=prof["p_mean"] * V_T, profile_CO2=prof["u_mean"][:, :, 4].copy(), profile_H=prof["u_mean"][:, :, 0].copy(),
+               profile_charge_CO=prof["Q"][:, :, 0] * tc / area, profile_charge_H2=prof["Q"][:, :, 1] * tc / area,
+               profile_status=prof["status"].astype(np.int64))
+    assert set(out) == set(PORE_OUTPUT_KEYS)
     return out

@@ -30,7 +30,7 @@ from .params import _load_yaml, _reaction_tables, utilities_dir
 from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
-from .programme import refuse_programme
+from .programme import refuse_pore_programme, refuse_programme
 from .problem import edl_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem
 
@@ -148,6 +148,7 @@ class RxnDiffRun:
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_pore_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")

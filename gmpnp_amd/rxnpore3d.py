@@ -28,7 +28,7 @@ from .pore3d import SOLVER_PARAMETERS, output_root, scale_conc_time
 from .impedance import refuse_impedance, refuse_pore_impedance
 from .polarisation import refuse_polarisation
 from .fit import refuse_fit
-from .programme import refuse_programme
+from .programme import refuse_pore_programme, refuse_programme
 from .problem import GALVANOSTAT_KEYWORDS, KINETICS_KEYWORDS, pore_dirichlet, pore_problem, refuse_galvanostat, refuse_kinetics, refuse_stern
 from .solver import GMPNPSystem, column_medians
 from .vtk import write_pvd
@@ -69,6 +69,7 @@ class RxnPoreRun:
         refuse_polarisation(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_fit(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")
+        refuse_pore_programme(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_galvanostat(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_stern(kwargs, "the reaction-diffusion drivers (they solve no potential)")
         refuse_kinetics(kwargs, "the reaction-diffusion drivers (they solve no potential)")
@@ -212,12 +213,16 @@ def solveEDL(concentration_elec=1.0, H2_FE=0.05, current_rough=3000.0, L=100.0e-
         run.sys.close()
 
 
+PORE_PROGRAMME_FLAGS = {"--pore_programme", "--v_levels", "--durations", "--cycles", "--rise_time", "--v_vertex", "--scan_rate", "--pore_programme_file",
+                        "--pore_programme_dt_init", "--pore_programme_steps_per_segment", "--pore_programme_bins"}
+
+
 def build_parser():
     from .pore3d import build_parser as pore_parser
     p = pore_parser()  # same flags as the MPNP pore script ...
     for act in list(p._actions):
         if ({"--voltage_multiplier", "--as_published", "--electrode_voltage", "--stern_model", "--stern_length", "--stern_eps_surface"}
-                | {"--" + k for k in KINETICS_KEYWORDS + GALVANOSTAT_KEYWORDS} | {"--polarisation", "--v_end", "--v_step"}) & set(act.option_strings):
+                | {"--" + k for k in KINETICS_KEYWORDS + GALVANOSTAT_KEYWORDS} | {"--polarisation", "--v_end", "--v_step"} | PORE_PROGRAMME_FLAGS) & set(act.option_strings):
             p._remove_action(act)  # ... minus the voltage (reference :788-942 has none)
             for s in act.option_strings:
                 p._option_string_actions.pop(s, None)

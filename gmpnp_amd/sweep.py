@@ -58,13 +58,14 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
     from .impedance import refuse_impedance, refuse_pore_impedance
     from .polarisation import refuse_polarisation
     from .fit import refuse_fit
-    from .programme import refuse_programme
+    from .programme import refuse_pore_programme, refuse_programme
     from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
     refuse_impedance(adaptive, "the pore sweep")
     refuse_pore_impedance(adaptive, "the pore sweep")
     refuse_polarisation(adaptive, "the pore sweep")
     refuse_fit(adaptive, "the pore sweep")
     refuse_programme(adaptive, "the pore sweep")
+    refuse_pore_programme(adaptive, "the pore sweep")
     refuse_galvanostat(adaptive, "the pore sweep")
     refuse_stern(adaptive, "the pore sweep")
     refuse_kinetics(adaptive, "the pore sweep")
@@ -108,7 +109,7 @@ def run_group(radius_nm, voltages, num_steps, concentration_elec=0.5, device_id=
 
 
 def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, write=False, as_published=False, ramp_steps=0,
-            one_stream=False, L=50e-9, device_kwargs=None, budget=False, electrode_voltage=None, kinetics=None, target_current=None, impedance=None, pore_impedance=None):
+            one_stream=False, L=50e-9, device_kwargs=None, budget=False, electrode_voltage=None, kinetics=None, target_current=None, impedance=None, pore_impedance=None, pore_programme=None):
     """One pore run of ``num_steps`` time steps; returns a small summary dict (never raises for a diverged Newton).
 
     ``ramp_steps`` > 0 is a continuation the reference does not have: the wall potential Dirichlet value (bc3 of
@@ -120,6 +121,8 @@ def run_job(radius_nm, voltage, num_steps, concentration_elec=0.5, device_id=0, 
     from .problem import refuse_galvanostat, refuse_kinetics, refuse_stern
     refuse_impedance({"impedance": impedance}, "the pore sweep")
     refuse_pore_impedance({"pore_impedance": pore_impedance}, "the pore sweep")
+    from .programme import refuse_pore_programme
+    refuse_pore_programme({"pore_programme": pore_programme}, "the pore sweep")
     refuse_galvanostat({"target_current": target_current}, "the pore sweep")
     refuse_stern({"electrode_voltage": electrode_voltage}, "the pore sweep")
     refuse_kinetics({"kinetics": kinetics}, "the pore sweep")

@@ -779,6 +779,49 @@ int gmpnp_electrode_trace_append(gmpnp_solver* s, double t, double h);
 int gmpnp_electrode_trace_read(gmpnp_solver* s, int32_t first, int32_t n, gmpnp_electrode_record_t* out /* [n] */);
 int gmpnp_electrode_trace_close(gmpnp_solver* s);
 
+/* ---- wall profile (no reference counterpart: the electrode record resolved along the axis of the 3D pore; rule: "wall profile" in
+ * csrc/gmpnp_host_rules.h and gmpnp_amd/programme.py; kernel: csrc/gmpnp_wall_profile.h) ---------------------------------------------
+ * 3D handles.  The nodes of the Stern boundary (the wall) are sorted into n_bins axial bins by their z, the mesh's third coordinate in
+ * units of L: edges[n_bins + 1] finite and strictly ascending, the bin of z the largest b with edges[b] <= z, z == edges[n_bins] in
+ * the last bin, z outside the edges in no bin (wall_bin of the rule; a node on an interior edge is counted once).  The profile is a
+ * per-handle buffer of capacity x n_bins records that the device fills, n_bins per accepted time step, allocated by the first
+ * gmpnp_wall_profile_open (a handle that never asks keeps the buffers and launches it had).
+ *   open(n_bins, edges, capacity)   sorts the nodes, uploads the lists, allocates capacity x n_bins slots, resets the count and zeroes
+ *                     the charges Q of every bin (one synchronisation).  A bin without a node is refused and the message names it:
+ *                     ask for fewer bins.
+ *   append(t, h)      k_stern_residual, k_kinetics_residual (kinetics on) and k_wall_profile (one workgroup per bin) at the current
+ *                     u, which writes the step's n_bins slots: no host synchronisation and no copy.  Over the nodes I of bin b, in the
+ *                     statements and the order of gmpnp_electrode_trace_append's record, with w_I the wall weights:
+ *                         area = sum_I w_I     D = sum_I (Stern term of the potential row)     I[r] = sum_I w_I rate_r (0 with the
+ *                         kinetics off)       p_mean = sum_I w_I p_I / area     u_mean[f] = sum_I w_I u_{I,f} / area
+ *                         Q[r] += h I[r]      (product and sum rounded on their own; the device keeps Q per bin)
+ *                     With one bin over the whole wall D and I are the bits of gmpnp_electrode_record_t.  status bit 1: a value of the
+ *                     bin's record is not finite (the other bins are not touched).  No floating-point atomics: two profiles of one
+ *                     sequence of states give equal bits.  A full buffer is refused and nothing is overwritten.
+ *   read(first, n)    the records of steps first ... first + n - 1, out[n][n_bins], one synchronisation and one copy
+ *   close()           append, read and hook 32 are refused until the next open (the buffers stay with the handle)
+ * Refused (GMPNP_ERR_INVALID, the message names the wall profile): 1D handles (the electrode record is their profile), the Stern option
+ * off, partition handles, a multilevel coarse level attached or the handle serving as one, the galvanostat on, n_bins outside
+ * 1 ... 256 or edges that are not finite and strictly ascending, a bin without a node, capacity < 1, h <= 0 or not finite, t not
+ * finite, append / read / close without an open profile, a read outside the steps written, a full buffer. */
+#define GMPNP_WALL_PROFILE_MAX_BINS 256
+typedef struct {
+  double t, h;                                /* the arguments of the append */
+  double z_lo, z_hi;                          /* the bin's edges */
+  double area;                                /* sum of the wall weights of the bin's nodes (scaled units) */
+  double D;
+  double I[GMPNP_MAX_SURFACE_REACTIONS];
+  double Q[GMPNP_MAX_SURFACE_REACTIONS];
+  double p_mean;
+  double u_mean[GMPNP_MAX_SPECIES];
+  int32_t count;                              /* nodes of the bin */
+  int32_t status;                             /* bit 1: a value that is not finite */
+} gmpnp_wall_profile_record_t;
+int gmpnp_wall_profile_open(gmpnp_solver* s, int32_t n_bins, const double* edges /* [n_bins + 1] */, int32_t capacity);
+int gmpnp_wall_profile_append(gmpnp_solver* s, double t, double h);
+int gmpnp_wall_profile_read(gmpnp_solver* s, int32_t first, int32_t n, gmpnp_wall_profile_record_t* out /* [n][n_bins] */);
+int gmpnp_wall_profile_close(gmpnp_solver* s);
+
 /* ---- transient sensitivities (no reference counterpart: what a marched potential programme says about the electrode parameters;
  * kernels: csrc/gmpnp_sensitivity.h) ---------------------------------------------------------------------------------------------------
  * 1D handles.  With J = K + inv_dt M (M the consistent P1 mass on the free species rows) the backward-Euler time term is linear in u_n,
@@ -921,7 +964,9 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * k_sens_rhs, the multi-column chain(s), application, k_spmv_plain per column, k_sens_record; needs an open sensitivity buffer, whose S,
  * records, count and accumulators stay: the hook's launches work on a second S (allocated by the first hook call), a slot and
  * accumulators of their own; like a step it reassembles F and J at the current u and drops the tangent, so a gmpnp_sensitivity_open with
- * start = 1 needs a gmpnp_electrode_tangent call made after it). */
+ * start = 1 needs a gmpnp_electrode_tangent call made after it), 32 = the launches of one gmpnp_wall_profile_append (k_stern_residual,
+ * k_kinetics_residual with the kinetics on, k_wall_profile; needs an open wall profile, whose records, count and charges stay: the
+ * hook's launches write the row of slots behind the buffer and charges of their own). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
