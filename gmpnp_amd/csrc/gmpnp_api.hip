@@ -174,7 +174,8 @@ struct gmpnp_responder {
 };
 
 // device side of gmpnp_frequency_response_3d (gmpnp_response_band.h), allocated by the first call: a handle that never asks for it keeps
-// the buffers and launches it had.  The complex band is storage of the response's own; the handle's real BandLU is not touched.
+// the buffers and launches it had.  The complex band is storage of the response's own (a BandView<BandComplex> of gmpnp_band_lu.h's
+// kernels, one member per frequency); the handle's real band (gmpnp_solver::lu) is not touched.
 namespace gmpnp { struct CBandState; }
 struct gmpnp_band_responder {
   DevBuf<double> mass, rhs, kvals;     // [nb] mass per node block; b = dF/dp_M (internal order); the SELL values of K = J at inv_dt = 0
@@ -298,7 +299,7 @@ struct gmpnp_solver {
   // block-tridiagonal direct solver (1D): cyclic-reduction pyramid
   std::vector<TriLevel> tri; DevBuf<double> tri_store; DevBuf<int32_t> tri_kpos; bool tri_ok = false;
   // block-banded LU (3D): direct solver / fallback of the Krylov solve; storage is allocated on first use
-  DevBuf<double> lu_band, lu_dinv, lu_y, lu_part; DevBuf<int32_t> lu_pos, lu_node; BandLU lu{}; bool lu_ready = false;
+  DevBuf<double> lu_band, lu_dinv, lu_y, lu_part; DevBuf<int32_t> lu_pos, lu_node; BandView<BandReal> lu{}; bool lu_ready = false;
   // asynchronous coarse refresh: the Galerkin product + inverse of THIS iteration's matrix run on a side stream while
   // BiCGStab uses the inverse built from the previous iteration's matrix; adopted at the next set-up (double buffer)
   hipStream_t stream2 = nullptr; hipEvent_t ev_mat = nullptr, ev_chain = nullptr, ev_jac = nullptr, ev_dots = nullptr;
@@ -1183,8 +1184,46 @@ int band_prepare(gmpnp_solver* s) {
   HIP_TRY(s->lu_dinv.alloc((size_t)n * NF * NF)); HIP_TRY(s->lu_y.alloc((size_t)n * NF));
   HIP_TRY(s->lu_pos.upload(t.lu_pos)); HIP_TRY(s->lu_node.upload(t.lu_node));
   HIP_TRY(s->lu_part.alloc((size_t)kBandPanel * kBandChunks * NF));
-  s->lu = BandLU{s->lu_band.p, s->lu_dinv.p, s->lu_pos.p, s->lu_node.p, n, b};
+  BandView<BandReal>& lu = s->lu;   // a batch of one (BandReal::kBatched is false): no strides, every launch is live
+  lu = BandView<BandReal>{};
+  lu.band = s->lu_band.p; lu.dinv = s->lu_dinv.p; lu.lu_pos = s->lu_pos.p; lu.lu_node = s->lu_node.p; lu.n = n; lu.b = b;
+  lu.status = s->status.p; lu.status_bit = 2;
   s->lu_ready = true;
+  return GMPNP_OK;
+}
+
+// The launch chains of gmpnp_band_lu.h's kernels for a batch of m bands (the Newton path: 1; the 3D frequency response: a chunk of
+// frequencies): S is BandReal or BandComplex.
+// the factorisation of bands already scattered: D_0^-1, then one launch per pivot block
+template <int NF, class S>
+int band_launch_factor(hipStream_t stream, const BandView<S>& lu, int m) {
+  constexpr int G = kBandThreads / (NF * NF);
+  hipLaunchKernelGGL((k_band_step<NF, S>), dim3(1, 1, m), dim3(kBandThreads), 0, stream, lu, -1);
+  for (int k = 0; k + 1 < lu.n; ++k) {
+    const int w = std::min(lu.b, lu.n - 1 - k);
+    hipLaunchKernelGGL((k_band_step<NF, S>), dim3(grid_for(w, S::kColChunk), grid_for(w, G) + 1, m), dim3(kBandThreads), 0, stream, lu, k);
+  }
+  HIP_TRY(hipGetLastError());
+  return GMPNP_OK;
+}
+// one substitution of every live member: rhs -> x (both internal order); y [m][n NF] and part [m][kBandPanel][kBandChunks][NF] are its workspace
+template <int NF, class S>
+int band_launch_substitute(hipStream_t stream, const BandView<S>& lu, int m, const typename S::Store* rhs, typename S::Store* y,
+                           typename S::Store* part, typename S::Store* x) {
+  using T = typename S::Store;
+  const int n = lu.n, P = kBandPanel;
+  hipLaunchKernelGGL((k_band_gather<NF, S>), dim3(grid_for(n * NF, 256), m), dim3(256), 0, stream, lu, rhs, y);
+  for (int K0 = 0; K0 < n; K0 += P) {   // forward: panels in elimination order
+    const int K1 = std::min(K0 + P, n);
+    hipLaunchKernelGGL((k_band_panel<NF, S, true>), dim3(K1 - K0, kBandChunks, m), dim3(NF * kWave), 0, stream, lu, (const T*)y, part, K0, K1);
+    hipLaunchKernelGGL((k_band_tri<NF, S, true>), dim3(m), dim3(NF * kWave), 0, stream, lu, y, (const T*)part, x, K0, K1);
+  }
+  for (int K0 = ((n - 1) / P) * P; K0 >= 0; K0 -= P) {   // backward: the same panels in reverse
+    const int K1 = std::min(K0 + P, n);
+    hipLaunchKernelGGL((k_band_panel<NF, S, false>), dim3(K1 - K0, kBandChunks, m), dim3(NF * kWave), 0, stream, lu, (const T*)y, part, K0, K1);
+    hipLaunchKernelGGL((k_band_tri<NF, S, false>), dim3(m), dim3(NF * kWave), 0, stream, lu, y, (const T*)part, x, K0, K1);
+  }
+  HIP_TRY(hipGetLastError());
   return GMPNP_OK;
 }
 
@@ -1192,42 +1231,36 @@ int band_prepare(gmpnp_solver* s) {
 template <int NF>
 int band_factor(gmpnp_solver* s) {
   int rc = band_prepare<NF>(s); if (rc) return rc;
-  const BandLU& lu = s->lu;
-  constexpr int G = kBandThreads / (NF * NF);
-  HIP_TRY(hipMemsetAsync(lu.band, 0, s->lu_band.n * sizeof(double), s->stream));
-  hipLaunchKernelGGL((k_band_scatter<NF>), dim3(s->t.nslices), dim3(64), 0, s->stream, s->c, lu);
-  hipLaunchKernelGGL((k_band_step<NF>), dim3(1, 1), dim3(kBandThreads), 0, s->stream, lu, -1, s->status.p);
-  for (int k = 0; k + 1 < lu.n; ++k) {
-    const int w = std::min(lu.b, lu.n - 1 - k);
-    hipLaunchKernelGGL((k_band_step<NF>), dim3(grid_for(w, kBandColChunk), grid_for(w, G) + 1), dim3(kBandThreads), 0, s->stream, lu, k, s->status.p);
-  }
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(s->lu.band, 0, s->lu_band.n * sizeof(double), s->stream));
+  hipLaunchKernelGGL((k_band_scatter<NF>), dim3(s->t.nslices), dim3(64), 0, s->stream, s->c, s->lu);
+  rc = band_launch_factor<NF>(s->stream, s->lu, 1); if (rc) return rc;
   s->direct_solves++;
   return GMPNP_OK;
 }
 
 template <int NF>
 int band_substitute(gmpnp_solver* s, const double* rhs, double* x) {
-  const BandLU& lu = s->lu;
-  const int n = lu.n, P = kBandPanel;
-  double* y = s->lu_y.p; double* part = s->lu_part.p;
-  hipLaunchKernelGGL((k_band_gather<NF>), dim3((n * NF + 255) / 256), dim3(256), 0, s->stream, lu, rhs, y);
-  for (int K0 = 0; K0 < n; K0 += P) {   // forward: panels in elimination order
-    const int K1 = std::min(K0 + P, n);
-    hipLaunchKernelGGL((k_band_panel<NF, true>), dim3(K1 - K0, kBandChunks), dim3(NF * kWave), 0, s->stream, lu, (const double*)y, part, K0, K1);
-    hipLaunchKernelGGL((k_band_tri<NF, true>), dim3(1), dim3(NF * kWave), 0, s->stream, lu, y, (const double*)part, x, K0, K1);
+  return band_launch_substitute<NF>(s->stream, s->lu, 1, rhs, s->lu_y.p, s->lu_part.p, x);
+}
+
+// One solve with the factorisation the stream holds: rhs in kb, x in kx, checked with the true residual kr = b - J kx and refined by
+// band_refine_again (gmpnp_host_rules.h) against `tol` (the pivoting is restricted to the node blocks).  *rn = the last ||b - J x||;
+// the verdict on it is the caller's.
+template <int NF>
+int band_refined_substitute(gmpnp_solver* s, double tol, double* rn) {
+  int rc = band_substitute<NF>(s, s->kb.p, s->kx.p); if (rc) return rc;
+  rc = true_residual<NF>(s, rn); if (rc) return rc;
+  double best = 0.0;
+  for (int round = 0; band_refine_again(round, rule_finite(*rn), *rn, best, tol); ++round) {
+    best = *rn;
+    rc = band_substitute<NF>(s, s->kr.p, s->ks.p); if (rc) return rc;
+    hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, (const double*)s->ks.p, 1.0, (int)s->ndof);
+    rc = true_residual<NF>(s, rn); if (rc) return rc;
   }
-  for (int K0 = ((n - 1) / P) * P; K0 >= 0; K0 -= P) {   // backward: the same panels in reverse
-    const int K1 = std::min(K0 + P, n);
-    hipLaunchKernelGGL((k_band_panel<NF, false>), dim3(K1 - K0, kBandChunks), dim3(NF * kWave), 0, s->stream, lu, (const double*)y, part, K0, K1);
-    hipLaunchKernelGGL((k_band_tri<NF, false>), dim3(1), dim3(NF * kWave), 0, s->stream, lu, y, (const double*)part, x, K0, K1);
-  }
-  HIP_TRY(hipGetLastError());
   return GMPNP_OK;
 }
 
-// Direct solve of J dx = b with b in kb: dx in kx, checked and refined with the true residual (the pivoting is
-// restricted to the node blocks).  stats->residual_norm = ||b - J dx||.
+// Direct solve of J dx = b with b in kb: dx in kx, checked and refined with the true residual.  stats->residual_norm = ||b - J dx||.
 // `as_direct` (the Newton loop): an answer that is finite but misses the tolerance is RETURNED, not refused — the reference's
 // MUMPS / UMFPACK hand back whatever the factorisation gives (3D:792), and it is Newton's own residual test that judges the step;
 // st->converged = 0 says so.  The parity hook gmpnp_linear_solve keeps the strict verdict.
@@ -1235,18 +1268,10 @@ template <int NF>
 int band_solve(gmpnp_solver* s, double bnorm, double rtol, double atol, gmpnp_linear_stats_t* st, bool as_direct = false) {
   const double tol = std::max(rtol * bnorm, atol);
   int rc = band_factor<NF>(s); if (rc) return rc;
-  rc = band_substitute<NF>(s, s->kb.p, s->kx.p); if (rc) return rc;
-  double rn = 0.0, best = 0.0;
-  rc = true_residual<NF>(s, &rn); if (rc) return rc;   // kr = b - J kx
+  double rn = 0.0;
+  rc = band_refined_substitute<NF>(s, tol, &rn); if (rc) return rc;
   HIP_TRY(hipMemcpy(s->h_status, s->status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
   if (*s->h_status & 2) return fail(GMPNP_ERR_LINEAR, "block-banded LU: singular pivot block");
-  for (int round = 0; round < 3 && rn == rn && rn > tol; ++round) {   // iterative refinement
-    best = rn;
-    rc = band_substitute<NF>(s, s->kr.p, s->ks.p); if (rc) return rc;
-    hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, (const double*)s->ks.p, 1.0, (int)s->ndof);
-    rc = true_residual<NF>(s, &rn); if (rc) return rc;
-    if (!(rn < 0.5 * best)) break;   // attainable accuracy reached
-  }
   if (st) { st->converged = (rn == rn && rn <= 1e3 * tol) ? 1 : 0; st->residual_norm = rn; st->rhs_norm = bnorm; }
   if (as_direct && rn == rn && !std::isinf(rn)) return GMPNP_OK;
   if (!(rn == rn) || rn > 1e3 * tol) {
@@ -2100,7 +2125,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 27: r = response_time_chunk(s); break;   // k_response_solve + k_response_functional on the last chunk's frequencies
       case 28: r = tangent_time_chain(s); break;    // extraction, k_bcr_forward_cols / k_bcr_tail_cols / k_bcr_backward_cols, application
       case 29: r = trace_time_append(s); break;     // k_stern_residual + k_kinetics_residual (kinetics on) + k_electrode_record
-      case 30: r = response_band_time_chunk(s); break;   // scatter, k_cband_step per pivot, the solve and three refinement rounds, k_cband_functional
+      case 30: r = response_band_time_chunk(s); break;   // k_cband_scatter, k_band_step<9, BandComplex> per pivot, the solve and three refinement rounds, k_cband_functional
       case 31: r = sensitivity_time_step(s); break;      // assembly, columns, k_sens_rhs, chain(s), application, k_spmv_plain per column, k_sens_record
       case 32: r = wall_profile_time_append(s); break;   // k_stern_residual + k_kinetics_residual (kinetics on) + k_wall_profile
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");

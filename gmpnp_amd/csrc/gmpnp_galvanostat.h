@@ -212,24 +212,6 @@ int galvanostat_launch_potential(gmpnp_solver* s, int slot, int which_report, bo
   return GMPNP_OK;
 }
 
-// one 3D solve with the factorisation the stream holds: rhs in kb (||rhs|| = bnorm), x in kx, refined by band_solve's rule
-template <int NF>
-int galvanostat_band_substitute(gmpnp_solver* s, double bnorm, double rtol, double atol) {
-  const double tol = std::max(rtol * bnorm, atol);
-  int rc = band_substitute<NF>(s, s->kb.p, s->kx.p); if (rc) return rc;
-  double rn = 0.0, best = 0.0;
-  rc = true_residual<NF>(s, &rn); if (rc) return rc;   // kr = b - J kx
-  for (int round = 0; round < 3 && rn == rn && rn > tol; ++round) {
-    best = rn;
-    rc = band_substitute<NF>(s, s->kr.p, s->ks.p); if (rc) return rc;
-    hipLaunchKernelGGL(k_axpy, dim3(grid_for(s->ndof, 256)), dim3(256), 0, s->stream, s->kx.p, (const double*)s->ks.p, 1.0, (int)s->ndof);
-    rc = true_residual<NF>(s, &rn); if (rc) return rc;
-    if (!(rn < 0.5 * best)) break;   // attainable accuracy reached
-  }
-  if (!(rn == rn) || std::isinf(rn)) return fail(GMPNP_ERR_LINEAR, "galvanostat: block-banded LU: the residual of a solve is not finite");
-  return GMPNP_OK;
-}
-
 // y = J^-1 F and z = J^-1 b with the Jacobian the stream holds (||F|| = r)
 template <int DIM, int NF>
 int galvanostat_solves(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_newton_stats_t& st, double r) {
@@ -243,7 +225,10 @@ int galvanostat_solves(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_n
   } else {
     HIP_TRY(hipMemcpyAsync(s->kb.p, s->F.p, bytes, hipMemcpyDeviceToDevice, s->stream));
     int rc = band_factor<NF>(s); if (rc) return rc;
-    rc = galvanostat_band_substitute<NF>(s, r, o.krylov_relative_tolerance, o.krylov_absolute_tolerance); if (rc) return rc;
+    const char* wild = "galvanostat: block-banded LU: the residual of a solve is not finite";
+    double rn = 0.0;
+    rc = band_refined_substitute<NF>(s, std::max(o.krylov_relative_tolerance * r, o.krylov_absolute_tolerance), &rn); if (rc) return rc;
+    if (!rule_finite(rn)) return fail(GMPNP_ERR_LINEAR, wild);
     HIP_TRY(hipMemcpy(s->h_status, s->status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (*s->h_status & 2) return fail(GMPNP_ERR_LINEAR, "galvanostat: block-banded LU: singular pivot block");
     HIP_TRY(hipMemcpyAsync(G->y.p, s->kx.p, bytes, hipMemcpyDeviceToDevice, s->stream));
@@ -253,7 +238,8 @@ int galvanostat_solves(gmpnp_solver* s, const gmpnp_newton_options_t& o, gmpnp_n
                        s->c.part_f, (int)s->ndof);
     HIP_TRY(hipStreamSynchronize(s->stream));
     const double bn = std::sqrt(sum_partials(s, 0));
-    rc = galvanostat_band_substitute<NF>(s, bn, o.krylov_relative_tolerance, o.krylov_absolute_tolerance); if (rc) return rc;
+    rc = band_refined_substitute<NF>(s, std::max(o.krylov_relative_tolerance * bn, o.krylov_absolute_tolerance), &rn); if (rc) return rc;
+    if (!rule_finite(rn)) return fail(GMPNP_ERR_LINEAR, wild);
     HIP_TRY(hipMemcpyAsync(G->z.p, s->kx.p, bytes, hipMemcpyDeviceToDevice, s->stream));
     st.direct_solves++; s->x0.left(false);
     return GMPNP_OK;

@@ -223,6 +223,16 @@ inline bool response_block_inverse(const Cx* A, Cx* inv, int* pivot_row) {
   return bad;
 }
 
+// ---- refinement of a block-banded LU solve (gmpnp_api.hip: band_refined_substitute; gmpnp_response_band.h: k_cband_judge) --------------
+// The pivoting of the band LU is restricted to the node blocks, so every answer is checked with the true residual and refined.  `round`
+// counts the refinements already made (0: the plain solve), rn is the residual of the present answer, best the one of the answer before
+// (round > 0).  Another round is made while the residual is finite, above the tolerance and, after a refinement, at least halved
+// (otherwise the attainable accuracy is reached); three rounds at the most.
+GMPNP_RULE_HD inline bool band_refine_again(int round, bool finite, double rn, double best, double tol) {
+  if (!finite || round >= 3 || !(rn > tol)) return false;
+  return round == 0 || rn < 0.5 * best;
+}
+
 // ---- electrode tangent and polarisation curves (include/gmpnp.h "electrode tangent"; kernels: gmpnp_tangent.h) ----------------------
 // The tangent z = du/dtheta of F(u; theta) = 0 solves J z = -dF/dtheta.  Parameter codes: 0 = p_M, 16 + r = ln k_r, 32 + r = alpha_r,
 // 48 = ln lam; kinds 0 ... 3 in that order, -1 = unknown.  The explicit derivatives at a boundary node, per unit weight:

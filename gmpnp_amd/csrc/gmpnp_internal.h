@@ -237,16 +237,6 @@ struct Topology {
   int lu_band = 0;                        // max |lu_pos[I] - lu_pos[J]| over the blocks of the pattern
 };
 
-// Block-banded LU of the Jacobian in the elimination order above (direct fallback of the 3D Krylov solve).
-// Block (p, q), |p - q| <= b, lives at band[(p * (2b+1) + (q - p + b)) * NF*NF], row major.
-struct BandLU {
-  double* band;           // [n][2b+1][NF][NF]
-  double* dinv;           // [n][NF][NF] inverses of the pivot blocks
-  const int32_t* lu_pos;  // [nv] internal node -> position
-  const int32_t* lu_node; // [nv] position -> internal node
-  int32_t n, b;
-};
-
 // Builds every table above; returns an error message or "" on success.
 std::string build_topology(const gmpnp_mesh_t& mesh, int nf, int n_aggregates_requested, Topology& t,
                            const gmpnp_partition_t* part = nullptr);

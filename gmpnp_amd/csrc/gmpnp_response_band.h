@@ -5,40 +5,31 @@
 //     (K + i sigma M) x = -b        K = J(u) at inv_dt = 0,  M = the consistent P1 mass on the free species rows,  b = dF/dp_M
 //     C(sigma) = dD/dp_M + (dD/du).x        dI_r(sigma) = dI_r/dp_M + (dI_r/du).x
 // K, M and b are real and the same for every frequency; a spectrum is n independent complex block-banded systems, and a chunk of them
-// goes through ONE chain of launches: the frequency is the last grid dimension of every kernel below.
+// goes through ONE chain of launches: the frequency is the last grid dimension of every kernel below, and the batch member of
+// gmpnp_band_lu.h's kernels, which do the elimination and the substitution on (re, im) pairs (policy BandComplex; the launch chains
+// are gmpnp_api.hip's band_launch_factor / band_launch_substitute, the ones of the real solver).  What is the response's own:
 //
 //   set-up (once per call)   gmpnp_response.h's sequence: model.inv_dt = 0 on the device, residual + Jacobian gather, k_galv_rhs /
 //                     k_response_rhs for b, the SELL values of K copied into the response's OWN storage, k_cband_mass (one double per
 //                     node block from the element records' volumes, vol MDEN (1 + delta_ab) as the gather forms it), then the model
 //                     back and the residual (and the gather, where the handle held a valid Jacobian) again.
 //   k_cband_scatter   SELL values of K -> complex band, plus i sigma m_pq on the (i, i) entries of block (p, q) for free species rows i
-//   k_cband_step      pivot k: A_pq -= A_pk (D_k^-1 A_kq) over the window, D_k^-1 A_kq staged in LDS, every global operand requested
-//                     before the first barrier; one extra workgroup per frequency: D_{k+1}^-1 by group16_inverse_cx (Gauss-Jordan,
-//                     partial pivoting inside the block, key |re| + |im|).  The band holds (re, im) pairs: a lane moves 16 bytes.
-//   k_cband_gather / k_cband_panel / k_cband_tri   substitution in panels of 16 block rows, partial sums added in fixed order
-//   k_cband_init / k_cband_axpy / k_cband_residual / k_cband_judge   refinement by band_solve's rule WITHOUT the host: the complex
-//                     residual -(K + i sigma M) x - b from the real SELL values and the mass, its maximum per frequency, and a
-//                     per-frequency `live` word: up to three rounds while the residual is above 1e-10 max |b| and halves.  The
-//                     launches of a round are always made; the workgroups of a frequency that is done leave at once.
+//   k_cband_init / k_cband_axpy / k_cband_residual / k_cband_judge   refinement WITHOUT the host: the complex residual
+//                     -(K + i sigma M) x - b from the real SELL values and the mass, its maximum per frequency, and a per-frequency
+//                     `live` word (the band kernels' BandView::live): band_refine_again (gmpnp_host_rules.h, the real solver's rule)
+//                     against 1e-10 max |b|.  The launches of a round are always made; the workgroups of a frequency that is done
+//                     leave at once.
 //   k_cband_functional   one workgroup per frequency: C and dI_r from the boundary nodes (k_tan_functional's node and facet terms on
 //                     Re x and Im x, block_sum in fixed order), the residual and the status word.
 // No floating-point atomics, no grid barriers, no spins; a frequency's workgroups read and write that frequency's storage alone, so its
-// bits do not depend on n or on the chunk.  Status bit 256: a pivot block was singular; 512: a value that is not finite.
+// bits do not depend on n or on the chunk.  Status bit 256: a pivot block was singular (the pivot workgroups' BandView::status_bit, one
+// word per frequency); 512: a value that is not finite.
 // One host synchronisation per chunk.  Included at the end of gmpnp_api.hip.
 #pragma once
 
 namespace gmpnp {
 
-constexpr int kCBandColChunk = 8;   // pivot-row blocks one workgroup multiplies by D_k^-1 and keeps in LDS (10.4 KB; the real kernel takes 16, which here would double the operand registers)
-
-struct CBand {
-  double2* band;          // [nfreq][n][2b+1][NF][NF] (re, im)
-  double2* dinv;          // [nfreq][n][NF][NF]
-  const int32_t* lu_pos;  // [nv] internal node -> position
-  const int32_t* lu_node; // [nv] position -> internal node
-  int32_t n, b;
-  size_t fstride;         // band entries per frequency
-};
+using CBand = BandView<BandComplex>;   // band [nfreq][n][2b+1][NF][NF], dinv [nfreq][n][NF][NF]: (re, im) pairs
 
 // what the refinement keeps per frequency
 struct CBandState {
@@ -54,25 +45,11 @@ struct CBandVec {
   double2* x;              // [nfreq][ndof] internal order
   double2* r;              // [nfreq][ndof] residual -(K + i sigma M) x - b (the first right-hand side: -b)
   double2* dx;             // [nfreq][ndof] what a substitution leaves
-  double2* y;              // [nfreq][ndof] elimination order
-  double2* part;           // [nfreq][kBandPanel][kBandChunks][NF]
   double* rmax;            // [nfreq][nslices] max |r| per slice, -1: a value that is not finite
   CBandState* st;          // [nfreq]
   int32_t* fstat;          // [nfreq] bit 256 from the pivot workgroups
   RespOut* out;            // [nfreq]
 };
-
-__device__ __forceinline__ Cx cx_ld(const double2* p) { const double2 v = *p; return Cx{v.x, v.y}; }
-__device__ __forceinline__ void cx_st(double2* p, Cx v) { *p = make_double2(v.re, v.im); }
-// acc - a b, contraction allowed: the elimination's update
-__device__ __forceinline__ Cx cx_nmac(Cx acc, Cx a, Cx b) { return Cx{acc.re - a.re * b.re + a.im * b.im, acc.im - a.re * b.im - a.im * b.re}; }
-__device__ __forceinline__ Cx cx_mac(Cx acc, Cx a, Cx b) { return Cx{acc.re + a.re * b.re - a.im * b.im, acc.im + a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ Cx cx_shfl16(Cx v, int src) { return Cx{__shfl(v.re, src, 16), __shfl(v.im, src, 16)}; }
-
-template <int NF>
-__device__ __forceinline__ double2* cband_at(const CBand& lu, int f, int p, int q) {
-  return lu.band + (size_t)f * lu.fstride + ((size_t)p * (2 * lu.b + 1) + (size_t)(q - p + lu.b)) * (NF * NF);
-}
 
 // mass[k] of node block k: the gather's Mab summed over the block's element contributions in list order
 template <int DIM, int NF>
@@ -104,260 +81,10 @@ __global__ __launch_bounds__(64) void k_cband_scatter(const Ctx c, const CBand l
     const int blk = c.sell_blk[rec];
     if (blk < 0) continue;
     const int q = lu.lu_pos[c.sell_cols[rec] & 0xffffff];
-    double2* dst = cband_at<NF>(lu, f, p, q) + i * NF;
+    double2* dst = band_at<NF>(lu, f, p, q) + i * NF;
     const double im = sg * v.mass[blk];
 #pragma unroll
     for (int j = 0; j < NF; ++j) dst[j] = make_double2(val[(size_t)(kp * NF + j) * kWave], j == i ? im : 0.0);
-  }
-}
-
-// group16_inverse on complex rows: lane r (< NF) of a 16-lane group holds row r of [A | I]; response_block_inverse is its statement
-template <int NF>
-__device__ inline bool group16_inverse_cx(Cx (&row)[2 * NF], int r) {
-  GMPNP_RULE_NO_CONTRACT
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < NF; ++k) {
-    double v = (r < NF && r >= k) ? response_pivot_key(row[k]) : -1.0; int idx = r;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-      const double ov = __shfl_xor(v, o, 16); const int oi = __shfl_xor(idx, o, 16);
-      if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    bad |= !(v > 0.0);
-    const Cx ip = cx_inv(cx_shfl16(row[k], idx));
-    const Cx oldk_k = cx_shfl16(row[k], k);
-    const Cx f = cx_mul((r == idx) ? oldk_k : row[k], ip);
-#pragma unroll
-    for (int j = k + 1; j < 2 * NF; ++j) {
-      const Cx from_p = cx_shfl16(row[j], idx), from_k = cx_shfl16(row[j], k);
-      const Cx mine = (r == idx) ? from_k : row[j];
-      row[j] = (r == k) ? cx_mul(from_p, ip) : cx_sub(mine, cx_mul(f, from_p));
-    }
-    row[k] = Cx{(r == k) ? 1.0 : 0.0, 0.0};
-  }
-  return bad;
-}
-
-// grid (ceil(w / QC), 1 + ceil(w / G), nfreq), w = min(b, n-1-k); k = -1: grid (1, 1, nfreq).  k_band_step's layout: the first grid
-// row is the pivot workgroup of block (k+1, k+1).
-template <int NF>
-__global__ __launch_bounds__(kBandThreads) void k_cband_step(const CBand lu, const int k, int32_t* fstat) {
-  constexpr int BB = NF * NF, G = kBandThreads / BB, QC = kCBandColChunk;
-  __shared__ double2 sU[QC * BB];
-  __shared__ double2 sD[BB];
-  const int f = blockIdx.z;
-  const int t = threadIdx.x, g = t / BB, e = t - g * BB, i = e / NF, j = e - i * NF;
-  double2* dinv = lu.dinv + (size_t)f * lu.n * BB;
-  if (blockIdx.y == 0) {
-    if (blockIdx.x != 0) return;
-    Cx entry{0.0, 0.0};
-    if (k >= 0) {
-      const int tc = min(t, BB - 1), ic = tc / NF, jc = tc - ic * NF;
-      Cx a9[NF], l9[NF];
-      const double2* Ak = cband_at<NF>(lu, f, k, k + 1);
-      const double2* Lp = cband_at<NF>(lu, f, k + 1, k) + ic * NF;
-#pragma unroll
-      for (int m = 0; m < NF; ++m) { a9[m] = cx_ld(Ak + m * NF + jc); l9[m] = cx_ld(Lp + m); }
-      double2* Cd = cband_at<NF>(lu, f, k + 1, k + 1) + tc;
-      Cx acc = cx_ld(Cd);
-      if (t < BB) sD[t] = dinv[(size_t)k * BB + t];
-      __syncthreads();
-      Cx u{0.0, 0.0};   // same operation order as the window update below
-#pragma unroll
-      for (int ll = 0; ll < NF; ++ll) u = cx_mac(u, cx_ld(sD + ic * NF + ll), a9[ll]);
-      if (t < BB) cx_st(sU + t, u);
-      __syncthreads();
-#pragma unroll
-      for (int m = 0; m < NF; ++m) acc = cx_nmac(acc, l9[m], cx_ld(sU + m * NF + jc));
-      if (t < BB) cx_st(Cd, acc);
-      entry = acc;
-    } else if (t < BB) {
-      entry = cx_ld(cband_at<NF>(lu, f, 0, 0) + t);
-    }
-    if (k + 1 >= lu.n) return;
-    if (t < BB) cx_st(sD + t, entry);
-    __syncthreads();
-    if (t < kWave) {   // wave 0: its four 16-lane groups all do the same work, group 0 writes
-      const int r = t & 15;
-      Cx row[2 * NF];
-#pragma unroll
-      for (int jj = 0; jj < NF; ++jj) {
-        row[jj] = (r < NF) ? cx_ld(sD + (r < NF ? r : 0) * NF + jj) : Cx{0.0, 0.0};
-        row[NF + jj] = Cx{(jj == r) ? 1.0 : 0.0, 0.0};
-      }
-      const bool bad = group16_inverse_cx<NF>(row, r);
-      if (t < NF) {
-        double2* o = dinv + ((size_t)(k + 1) * NF + t) * NF;
-#pragma unroll
-        for (int jj = 0; jj < NF; ++jj) cx_st(o + jj, row[NF + jj]);
-      }
-      if (t == 0 && bad) atomicOr(fstat + f, kResponseSingular);
-    }
-    return;
-  }
-  const int w = min(lu.b, lu.n - 1 - k);
-  const int q0 = k + 1 + blockIdx.x * QC, p = k + 1 + ((int)blockIdx.y - 1) * G + g;
-  const int nq = min(QC, k + w + 1 - q0);
-  constexpr int UP = (QC * BB + kBandThreads - 1) / kBandThreads;   // U' entries per thread
-  const bool act = g < G && p <= k + w;
-  const int pc = min(p, k + w);
-  const double2 dk = dinv[(size_t)k * BB + min(t, BB - 1)];
-  const double2* Ak = cband_at<NF>(lu, f, k, q0);
-  Cx a[UP][NF];
-#pragma unroll
-  for (int u = 0; u < UP; ++u) {
-    const int idx = min(t + u * kBandThreads, nq * BB - 1), qq = idx / BB, ee = idx - qq * BB, jj = ee % NF;
-#pragma unroll
-    for (int l = 0; l < NF; ++l) a[u][l] = cx_ld(Ak + (size_t)qq * BB + l * NF + jj);
-  }
-  const double2* Lp = cband_at<NF>(lu, f, pc, k) + i * NF;
-  Cx l[NF];
-#pragma unroll
-  for (int m = 0; m < NF; ++m) l[m] = cx_ld(Lp + m);
-  double2* C = cband_at<NF>(lu, f, pc, q0) + e;
-  Cx cv[QC];
-#pragma unroll
-  for (int qq = 0; qq < QC; ++qq) cv[qq] = cx_ld(C + (size_t)min(qq, nq - 1) * BB);
-  if (t < BB) sD[t] = dk;
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < UP; ++u) {
-    const int idx = t + u * kBandThreads;
-    const int ic = min(idx, nq * BB - 1), qq = ic / BB, ee = ic - qq * BB, m = ee / NF;
-    Cx acc{0.0, 0.0};
-#pragma unroll
-    for (int ll = 0; ll < NF; ++ll) acc = cx_mac(acc, cx_ld(sD + m * NF + ll), a[u][ll]);
-    if (idx < nq * BB) cx_st(sU + idx, acc);
-  }
-  __syncthreads();
-  if (act) {
-    const bool pivot_block = (p == k + 1 && q0 == k + 1);   // (k+1, k+1) belongs to the pivot workgroup
-#pragma unroll
-    for (int qq = 0; qq < QC; ++qq) {
-      Cx acc = cv[qq];
-#pragma unroll
-      for (int m = 0; m < NF; ++m) acc = cx_nmac(acc, l[m], cx_ld(sU + min(qq, nq - 1) * BB + m * NF + j));
-      if (qq < nq && !(pivot_block && qq == 0)) cx_st(C + (size_t)qq * BB, acc);
-    }
-  }
-}
-
-// ---- substitution: gmpnp_band_lu.h's panels on complex vectors, the frequency in the last grid dimension ------------------------------
-// grid (ceil(n NF / 256), nfreq): y = src in elimination order
-template <int NF>
-__global__ __launch_bounds__(256) void k_cband_gather(const CBand lu, const CBandVec v) {
-  const int f = blockIdx.y;
-  if (!v.st[f].live) return;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= lu.n * NF) return;
-  const int k = idx / NF;
-  v.y[(size_t)f * v.ndof + idx] = v.r[(size_t)f * v.ndof + (size_t)lu.lu_node[k] * NF + (idx - k * NF)];
-}
-
-// grid (K1 - K0, kBandChunks, nfreq)
-template <int NF, bool FWD>
-__global__ __launch_bounds__(NF * kWave) void k_cband_panel(const CBand lu, const CBandVec v, const int K0, const int K1) {
-  constexpr int U = kBandDotBatch / 2, BB = NF * NF;
-  const int f = blockIdx.z;
-  if (!v.st[f].live) return;
-  const int t = threadIdx.x, wv = t / kWave, lane = t - wv * kWave;
-  const int kk = blockIdx.x, ch = blockIdx.y, k = K0 + kk;
-  const int q_lo = FWD ? max(0, k - lu.b) : K1, q_hi = FWD ? K0 : min(k + lu.b, lu.n - 1) + 1;
-  const int nblk = max(q_hi - q_lo, 0), per = (nblk + kBandChunks - 1) / kBandChunks;
-  const int c_lo = q_lo + ch * per, c_hi = min(c_lo + per, q_hi);
-  const int count = max(c_hi - c_lo, 0) * NF, last = max(count - 1, 0);
-  Cx acc{0.0, 0.0};
-  if (count > 0) {   // uniform per workgroup
-    const double2* row = cband_at<NF>(lu, f, k, c_lo) + wv * NF;
-    const double2* yv = v.y + (size_t)f * v.ndof + (size_t)c_lo * NF;
-    for (int base = 0; base < count; base += U * kWave) {
-      Cx w[U], z[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int idx = min(base + u * kWave + lane, last), qo = idx / NF, jj = idx - qo * NF;
-        w[u] = cx_ld(row + (size_t)qo * BB + jj); z[u] = cx_ld(yv + idx);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (base + u * kWave + lane < count) acc = cx_mac(acc, w[u], z[u]);
-    }
-  }
-  acc.re = wave_sum(acc.re); acc.im = wave_sum(acc.im);
-  if (lane == kWave - 1) cx_st(v.part + (((size_t)f * kBandPanel + kk) * kBandChunks + ch) * NF + wv, acc);
-}
-
-// grid (nfreq); np = K1 - K0 <= kBandPanel block rows.  The in-panel entries of block row s + 1 are requested while row s is solved.
-template <int NF, bool FWD>
-__global__ __launch_bounds__(NF * kWave) void k_cband_tri(const CBand lu, const CBandVec v, const int K0, const int K1) {
-  constexpr int P = kBandPanel, BB = NF * NF, UM = ((P - 1) * NF + kWave - 1) / kWave;
-  __shared__ double2 yp[P * NF];   // the panel's solution blocks
-  __shared__ double2 dl[P * BB];   // D_k^-1
-  __shared__ double2 rh[P * NF];   // forward: rhs_k - outside sum; backward: outside sum
-  __shared__ double2 yk[P * NF];   // backward: y_k
-  __shared__ double2 st[NF];
-  const int f = blockIdx.x;
-  if (!v.st[f].live) return;
-  const int t = threadIdx.x, wv = t / kWave, lane = t - wv * kWave;
-  const int np = K1 - K0;
-  double2* y = v.y + (size_t)f * v.ndof;
-  const double2* part = v.part + (size_t)f * kBandPanel * kBandChunks * NF;
-  auto load_row = [&](int s, Cx (&w)[UM]) {   // the s in-panel blocks of the row solved at step s (s >= 1)
-    const int sc = min(s, np - 1), k = FWD ? K0 + sc : K1 - 1 - sc;
-    const double2* row = (FWD ? cband_at<NF>(lu, f, k, K0) : cband_at<NF>(lu, f, k, min(k + 1, lu.n - 1))) + wv * NF;
-    const int last = max(sc * NF - 1, 0);
-#pragma unroll
-    for (int u = 0; u < UM; ++u) {
-      const int idx = min(u * kWave + lane, last), qo = idx / NF, jj = idx - qo * NF;
-      w[u] = (np > 1) ? cx_ld(row + (size_t)qo * BB + jj) : Cx{0.0, 0.0};
-    }
-  };
-  Cx vn[UM];
-#pragma unroll
-  for (int u = 0; u < UM; ++u) vn[u] = Cx{0.0, 0.0};
-  for (int idx = t; idx < np * BB; idx += NF * kWave) dl[idx] = lu.dinv[((size_t)f * lu.n + K0) * BB + idx];
-  if (t < np * NF) {
-    const int kk = t / NF;
-    Cx sacc{0.0, 0.0};
-#pragma unroll
-    for (int c = 0; c < kBandChunks; ++c) sacc = cx_add(sacc, cx_ld(part + ((size_t)kk * kBandChunks + c) * NF + (t - kk * NF)));
-    const Cx yv = cx_ld(y + (size_t)K0 * NF + t);
-    cx_st(rh + t, FWD ? cx_sub(yv, sacc) : sacc);
-    if (!FWD) cx_st(yk + t, yv);
-  }
-  __syncthreads();
-  for (int s = 0; s < np; ++s) {
-    Cx vc[UM];
-#pragma unroll
-    for (int u = 0; u < UM; ++u) vc[u] = vn[u];
-    if (s + 1 < np) load_row(s + 1, vn);
-    const int kk = FWD ? s : np - 1 - s;
-    const double2* ys = yp + (FWD ? 0 : (kk + 1) * NF);   // entry (qo, j) of the in-panel row meets ys[qo * NF + j]
-    Cx acc{0.0, 0.0};
-    if (s > 0) {
-#pragma unroll
-      for (int u = 0; u < UM; ++u) {
-        const int raw = u * kWave + lane;
-        if (raw < s * NF) acc = cx_mac(acc, vc[u], cx_ld(ys + raw));
-      }
-      acc.re = wave_sum(acc.re); acc.im = wave_sum(acc.im);
-    }
-    if (lane == kWave - 1) { const Cx h = cx_ld(rh + kk * NF + wv); cx_st(st + wv, FWD ? cx_sub(h, acc) : cx_add(h, acc)); }
-    __syncthreads();
-    if (t < NF) {
-      Cx r{0.0, 0.0};
-#pragma unroll
-      for (int m = 0; m < NF; ++m) r = cx_mac(r, cx_ld(dl + kk * BB + t * NF + m), cx_ld(st + m));
-      if (!FWD) r = cx_sub(cx_ld(yk + kk * NF + t), r);
-      cx_st(yp + kk * NF + t, r);
-    }
-    __syncthreads();
-  }
-  if (t < np * NF) {
-    const int kk = t / NF;
-    const double2 r = yp[t];
-    y[(size_t)K0 * NF + t] = r;
-    if (!FWD) v.dx[(size_t)f * v.ndof + (size_t)lu.lu_node[K0 + kk] * NF + (t - kk * NF)] = r;
   }
 }
 
@@ -435,7 +162,7 @@ __global__ __launch_bounds__(64) void k_cband_residual(const Ctx c, const CBandV
   if (lane == 0) v.rmax[(size_t)f * v.nslices + s] = mod;
 }
 
-// grid (nfreq), one wave: band_solve's rule on the residual of the x just formed.  Round 0 is the plain solve.
+// grid (nfreq), one wave: band_refine_again on the residual of the x just formed.  Round 0 is the plain solve.
 __global__ __launch_bounds__(kWave) void k_cband_judge(const CBandVec v, const int round) {
   const int f = blockIdx.x;
   CBandState st = v.st[f];
@@ -451,10 +178,8 @@ __global__ __launch_bounds__(kWave) void k_cband_judge(const CBandVec v, const i
     mod = (mod < 0.0 || m2 < 0.0) ? -1.0 : fmax(mod, m2);
   }
   if (threadIdx.x != 0) return;
-  const double tol = 1e-10 * st.bmax;
   const bool fin = mod >= 0.0;
-  bool live = fin && mod > tol && round < 3;
-  if (round > 0 && !(fin && mod < 0.5 * st.best)) live = false;   // attainable accuracy reached
+  const bool live = band_refine_again(round, fin, mod, st.best, 1e-10 * st.bmax);
   st.rn = fin ? mod : __longlong_as_double(0x7ff8000000000000ll);
   st.best = st.rn; st.live = live ? 1 : 0; st.rounds = round;
   v.st[f] = st;
@@ -542,42 +267,30 @@ __global__ __launch_bounds__(kVecBlock) void k_cband_functional(const Ctx c, con
 
 namespace {
 
+// the chunk's bands as gmpnp_band_lu.h's batch: one member per frequency, its `live` word in the refinement's state, its pivot word in fstat
 CBand cband_tab(gmpnp_solver* s) {
   gmpnp_band_responder* R = s->band_responder.get();
-  return CBand{R->band.p, R->dinv.p, R->pos.p, R->node.p, R->n, R->b, (size_t)R->n * (2 * R->b + 1) * 81};
+  CBand lu{};
+  lu.band = R->band.p; lu.dinv = R->dinv.p; lu.lu_pos = R->pos.p; lu.lu_node = R->node.p; lu.n = R->n; lu.b = R->b;
+  lu.band_stride = (size_t)R->n * (2 * R->b + 1) * 81; lu.dinv_stride = (size_t)R->n * 81;
+  lu.vec_stride = (size_t)s->ndof; lu.part_stride = (size_t)kBandPanel * kBandChunks * 9;
+  lu.live = &R->st.p->live; lu.live_stride = (int32_t)(sizeof(CBandState) / sizeof(int32_t));
+  lu.status = R->fstat.p; lu.status_stride = 1; lu.status_bit = kResponseSingular;
+  return lu;
 }
 CBandVec cband_vec(gmpnp_solver* s) {
   gmpnp_band_responder* R = s->band_responder.get();
   CBandVec v{};
   v.ndof = (int32_t)s->ndof; v.nslices = s->t.nslices;
   v.sigma = R->sigma.p; v.mass = R->mass.p; v.b = R->rhs.p;
-  v.x = R->x.p; v.r = R->r.p; v.dx = R->dx.p; v.y = R->y.p; v.part = R->part.p; v.rmax = R->rmax.p;
+  v.x = R->x.p; v.r = R->r.p; v.dx = R->dx.p; v.rmax = R->rmax.p;
   v.st = R->st.p; v.fstat = R->fstat.p; v.out = R->out.p;
   return v;
 }
 
-// one substitution of every live frequency of the chunk: r -> dx
-int cband_substitute(gmpnp_solver* s, const CBand& lu, const CBandVec& v, int m) {
-  constexpr int NF = 9;
-  const int n = lu.n, P = kBandPanel;
-  hipLaunchKernelGGL((k_cband_gather<NF>), dim3(grid_for(n * NF, 256), m), dim3(256), 0, s->stream, lu, v);
-  for (int K0 = 0; K0 < n; K0 += P) {
-    const int K1 = std::min(K0 + P, n);
-    hipLaunchKernelGGL((k_cband_panel<NF, true>), dim3(K1 - K0, kBandChunks, m), dim3(NF * kWave), 0, s->stream, lu, v, K0, K1);
-    hipLaunchKernelGGL((k_cband_tri<NF, true>), dim3(m), dim3(NF * kWave), 0, s->stream, lu, v, K0, K1);
-  }
-  for (int K0 = ((n - 1) / P) * P; K0 >= 0; K0 -= P) {
-    const int K1 = std::min(K0 + P, n);
-    hipLaunchKernelGGL((k_cband_panel<NF, false>), dim3(K1 - K0, kBandChunks, m), dim3(NF * kWave), 0, s->stream, lu, v, K0, K1);
-    hipLaunchKernelGGL((k_cband_tri<NF, false>), dim3(m), dim3(NF * kWave), 0, s->stream, lu, v, K0, K1);
-  }
-  HIP_TRY(hipGetLastError());
-  return GMPNP_OK;
-}
-
 // every launch of one chunk whose sigma the device holds: scatter, factorisation, solve, three rounds of refinement, functionals
 int cband_launch_chunk(gmpnp_solver* s, int m) {
-  constexpr int NF = 9, G = kBandThreads / (NF * NF);
+  constexpr int NF = 9;
   gmpnp_band_responder* R = s->band_responder.get();
   const CBand lu = cband_tab(s);
   const CBandVec v = cband_vec(s);
@@ -587,18 +300,13 @@ int cband_launch_chunk(gmpnp_solver* s, int m) {
   const int kin = kinetics_on(s) ? 1 : 0;
   KinTab kt{};
   if (kin) kt = kinetics_tab(s, R->status.p);
-  HIP_TRY(hipMemsetAsync(lu.band, 0, (size_t)m * lu.fstride * sizeof(double2), s->stream));
+  HIP_TRY(hipMemsetAsync(lu.band, 0, (size_t)m * lu.band_stride * sizeof(double2), s->stream));
   HIP_TRY(hipMemsetAsync(R->fstat.p, 0, (size_t)m * sizeof(int32_t), s->stream));
   hipLaunchKernelGGL((k_cband_scatter<NF>), dim3(s->t.nslices, m), dim3(64), 0, s->stream, ck, lu, v);
   hipLaunchKernelGGL(k_cband_init, dim3(m), dim3(kVecBlock), 0, s->stream, v);
-  hipLaunchKernelGGL((k_cband_step<NF>), dim3(1, 1, m), dim3(kBandThreads), 0, s->stream, lu, -1, R->fstat.p);
-  for (int k = 0; k + 1 < lu.n; ++k) {
-    const int w = std::min(lu.b, lu.n - 1 - k);
-    hipLaunchKernelGGL((k_cband_step<NF>), dim3(grid_for(w, kCBandColChunk), grid_for(w, G) + 1, m), dim3(kBandThreads), 0, s->stream, lu, k, R->fstat.p);
-  }
-  HIP_TRY(hipGetLastError());
+  int rc = band_launch_factor<NF>(s->stream, lu, m); if (rc) return rc;
   for (int round = 0; round <= 3; ++round) {
-    int rc = cband_substitute(s, lu, v, m); if (rc) return rc;
+    rc = band_launch_substitute<NF>(s->stream, lu, m, (const double2*)v.r, R->y.p, R->part.p, v.dx); if (rc) return rc;   // every live frequency: r -> dx
     hipLaunchKernelGGL(k_cband_axpy, dim3(grid_for((int)s->ndof, kVecBlock), m), dim3(kVecBlock), 0, s->stream, v);
     hipLaunchKernelGGL((k_cband_residual<NF>), dim3(s->t.nslices, m), dim3(64), 0, s->stream, ck, v);
     hipLaunchKernelGGL(k_cband_judge, dim3(m), dim3(kWave), 0, s->stream, v, round);

@@ -555,8 +555,8 @@ int tangent_time_chain(gmpnp_solver* s) {
 }
 bool tangent_has_chain(const gmpnp_solver* s) { return s->tangenter && s->tangenter->last_n > 0 && s->dim == 1 && s->jacobian_valid; }
 
-// 3D: one band-LU factorisation of the Jacobian the stream holds and n substitutions, each refined by band_solve's rule
-// (galvanostat_band_substitute); the storage of the factorisation is band_prepare's, under its memory cap
+// 3D: one band-LU factorisation of the Jacobian the stream holds and n substitutions, each refined (band_refined_substitute);
+// the storage of the factorisation is band_prepare's, under its memory cap
 template <int NF>
 int tangent_band_solves(gmpnp_solver* s, int n) {
   gmpnp_tangenter* T = s->tangenter.get();
@@ -569,7 +569,9 @@ int tangent_band_solves(gmpnp_solver* s, int n) {
                        s->c.part_f, (int)ndof);
     HIP_TRY(hipStreamSynchronize(s->stream));
     const double bn = std::sqrt(sum_partials(s, 0));
-    rc = galvanostat_band_substitute<NF>(s, bn, 1e-10, 0.0); if (rc) return rc;
+    double rn = 0.0;
+    rc = band_refined_substitute<NF>(s, std::max(1e-10 * bn, 0.0), &rn); if (rc) return rc;
+    if (!rule_finite(rn)) return fail(GMPNP_ERR_LINEAR, "galvanostat: block-banded LU: the residual of a solve is not finite");   // (the text this refusal has always had)
     HIP_TRY(hipMemcpyAsync(T->z.p + k * ndof, s->kx.p, bytes, hipMemcpyDeviceToDevice, s->stream));
   }
   return GMPNP_OK;

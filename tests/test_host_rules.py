@@ -35,6 +35,7 @@ BITS = {1: "1 - sum_j a_j u_j <= 0 at a quadrature point; ", 2: "singular diagon
 #   gburst n  (event a b c d)*n                                       0 predicted(a, b, c)  1 first(a, b)  2 record(a, b, c, d)  3 solve_done(a)
 #   x0 n  (event a scale)*n                                           0 ready(a, scale)  1 left(a)
 #   options dim  <the 16 int32 fields of gmpnp_options_t in order>  band_lu_max_gb
+#   refine round finite rn best tol                                   band_refine_again: 1 = another refinement round of a band LU solve
 DRIVER = r"""
 #include <cstdio>
 #include <iostream>
@@ -158,6 +159,9 @@ int main() {
       if (!err.empty()) printf("ERR %s\n", err.c_str());
       else printf("OK %d %d %d %d %d %d %d %d %d %.17g\n", s.coarse_async, s.coarse_lag, s.warm_async, s.warm_start, s.host_poll, s.burst_iters,
                   s.phase_timing ? 1 : 0, s.direct_fallback, s.strict_steric, s.lu_max_gb);
+    } else if (cmd == "refine") {
+      const int round = (int)num(); const bool finite = num() != 0.0; const double rn = num(), best = num(), tol = num();
+      printf("%d\n", band_refine_again(round, finite, rn, best, tol) ? 1 : 0);
     }
   }
   return 0;
@@ -676,3 +680,32 @@ def test_resolve_options(rules):
                 assert len(errs) == 1 and line[4:] == errs[0], (dim, o, line)
             seen.add(line[4:])
     assert seen == {T_NEGATIVE, T_FORM, T_RANGE, T_STORES}
+
+
+def test_band_refinement_rule(rules):
+    """band_refine_again, the one continue/stop rule of the block-banded LU's refinement (the host's band_refined_substitute and the
+    frequency response's k_cband_judge), against its restatement: another round while the residual is finite, above the tolerance and
+    (after a refinement) less than half the one before; three rounds at the most.  Rounds 0-3 with residuals that halve, that do not,
+    that equal the tolerance, NaN and Inf, and the device's finiteness flag down on an ordinary number."""
+    nan, inf = float("nan"), float("inf")
+
+    def again(rnd, finite, rn, best, tol):
+        if not finite or rnd >= 3 or not rn > tol:
+            return False
+        return rnd == 0 or rn < 0.5 * best
+
+    tol = 1e-10
+    cases = []
+    for rnd in range(4):
+        for best in (1e-3, 1e-8):
+            for rn in (0.4999 * best, 0.5 * best, 0.5001 * best, best, 2.0 * best, tol, tol * (1 + 2.0 ** -52), 0.5 * tol, 0.0, nan, inf):
+                cases.append((rnd, int(np.isfinite(rn)), rn, best, tol))
+            cases.append((rnd, 0, 0.1 * best, best, tol))
+    answers = rules(["refine %d %d %r %r %r" % c for c in cases])
+    assert [int(a) for a in answers] == [int(again(*c)) for c in cases]
+    assert not any(int(a) for c, a in zip(cases, answers) if not c[1])   # NaN, Inf, the flag down: never another round
+    # by hand: the plain solve refines whatever came before; halving goes on, not halving stops; the fourth judgement stops; rn = tol stops
+    hand = [((0, 1, 2e-3, 1e-3, tol), 1), ((1, 1, 0.4e-3, 1e-3, tol), 1), ((2, 1, 0.5e-3, 1e-3, tol), 0), ((2, 1, 0.6e-3, 1e-3, tol), 0),
+            ((3, 1, 0.4e-3, 1e-3, tol), 0), ((0, 1, tol, 1e-3, tol), 0), ((0, 1, tol * (1 + 2.0 ** -52), 1e-3, tol), 1), ((0, 0, inf, 0.0, tol), 0),
+            ((0, 0, nan, 0.0, tol), 0), ((1, 0, inf, 1e-3, tol), 0)]
+    assert [int(a) for a in rules(["refine %d %d %r %r %r" % c for c, _ in hand])] == [w for _, w in hand]
