@@ -53,6 +53,8 @@ EXPORTS = [
     "gmpnp_wall_profile_open", "gmpnp_wall_profile_append", "gmpnp_wall_profile_read", "gmpnp_wall_profile_close",
     "gmpnp_sensitivity_open", "gmpnp_sensitivity_step", "gmpnp_sensitivity_read", "gmpnp_sensitivity_columns", "gmpnp_sensitivity_set_columns",
     "gmpnp_sensitivity_close",
+    "gmpnp_cycle_open", "gmpnp_cycle_begin", "gmpnp_cycle_end", "gmpnp_cycle_mix", "gmpnp_cycle_restart", "gmpnp_cycle_vectors",
+    "gmpnp_cycle_close",
 ]
 # columns of a species-budget table (gmpnp_budget_column, include/gmpnp.h): per field
 #   storage + reaction + wall + exit + point = dirichlet + closure
@@ -183,6 +185,15 @@ SENSITIVITY_START = {"zero": 0, "steady": 1, "continue": 2}                  # g
 TANGENT_MAX_COLUMNS = 10          # GMPNP_TANGENT_MAX_COLUMNS
 RESPONSE_MAX_FREQUENCIES = 4096   # gmpnp_frequency_response: n in 1 ... 4096
 RESPONSE_SINGULAR, RESPONSE_NONFINITE = 256, 512   # bits of gmpnp_response_t.status
+
+
+CYCLE_MAX_DEPTH = 8               # GMPNP_CYCLE_MAX_DEPTH
+
+
+class CCycleReport(ctypes.Structure):
+    """ctypes image of ``gmpnp_cycle_report_t`` (include/gmpnp.h, periodic steady state)."""
+    _fields_ = [("err", c_double), ("err_max", c_double), ("worst_dof", c_int64), ("n_free", c_int64), ("nonfinite", c_int32),
+                ("window", c_int32), ("A", c_double * (CYCLE_MAX_DEPTH * CYCLE_MAX_DEPTH)), ("b", c_double * CYCLE_MAX_DEPTH)]
 
 
 class CLinearStats(ctypes.Structure):
@@ -351,6 +362,13 @@ def load_library(path: str = None):
     lib.gmpnp_sensitivity_columns.argtypes = [c_void_p, c_int32, POINTER(c_double)]
     lib.gmpnp_sensitivity_set_columns.argtypes = [c_void_p, POINTER(c_double)]
     lib.gmpnp_sensitivity_close.argtypes = [c_void_p]
+    lib.gmpnp_cycle_open.argtypes = [c_void_p, c_int32, POINTER(CTimeTol)]
+    lib.gmpnp_cycle_begin.argtypes = [c_void_p]
+    lib.gmpnp_cycle_end.argtypes = [c_void_p, POINTER(CCycleReport)]
+    lib.gmpnp_cycle_mix.argtypes = [c_void_p, c_int32, POINTER(c_double), c_double, POINTER(c_double)]
+    lib.gmpnp_cycle_restart.argtypes = [c_void_p]
+    lib.gmpnp_cycle_vectors.argtypes = [c_void_p, c_int32, POINTER(c_double)]
+    lib.gmpnp_cycle_close.argtypes = [c_void_p]
     lib.gmpnp_step_limit.argtypes = [c_void_p, POINTER(c_double), c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     if path is None:
         _lib = lib
@@ -857,6 +875,53 @@ class DeviceSolver:
     def electrode_trace_close(self):
         """``gmpnp_electrode_trace_close``."""
         self._check(self.lib.gmpnp_electrode_trace_close(self._h))
+
+    # periodic steady state: the accelerated cycle map (include/gmpnp.h "periodic steady state", gmpnp_amd/periodic.py)
+    def cycle_open(self, depth, rtol, atol):
+        """``gmpnp_cycle_open``: a window of at most ``depth`` + 1 pairs (1 <= depth <= 8) and the weights w = atol_f + rtol |u_n| of
+        the CURRENT u_n (``atol``: a scalar or one value per field)."""
+        tol = CTimeTol()
+        _fill_time_tol(tol, self.nf, rtol, atol)
+        self._check(self.lib.gmpnp_cycle_open(self._h, int(depth), byref(tol)))
+
+    def cycle_begin(self):
+        """``gmpnp_cycle_begin``: x_k <- u_n."""
+        self._check(self.lib.gmpnp_cycle_begin(self._h))
+
+    def cycle_end(self):
+        """``gmpnp_cycle_end``: g_k <- u_n; the report as a dict: err, err_max, worst_dof (file order, -1: none), n_free, nonfinite,
+        window (pairs, m + 1) and the normal system of the window's m differences, A (m, m) and b (m,)."""
+        r = CCycleReport()
+        self._check(self.lib.gmpnp_cycle_end(self._h, byref(r)))
+        m = max(int(r.window) - 1, 0)
+        A = np.array(r.A[:]).reshape(CYCLE_MAX_DEPTH, CYCLE_MAX_DEPTH)[:m, :m].copy()
+        return {"err": r.err, "err_max": r.err_max, "worst_dof": int(r.worst_dof), "n_free": int(r.n_free), "nonfinite": bool(r.nonfinite),
+                "window": int(r.window), "A": A, "b": np.array(r.b[:m])}
+
+    def cycle_mix(self, gamma, tau: float = 0.0) -> float:
+        """``gmpnp_cycle_mix``: u = u_n <- g_k + alpha (sum_j gamma_j g_j - g_k) on the free rows, g_k on the Dirichlet rows; returns
+        alpha (1 with ``tau`` = 0, else the step limiter's factor).  Afterwards the handle is where ``set_state(u, u)`` leaves it."""
+        g = np.ascontiguousarray(gamma, dtype=np.float64).ravel()
+        alpha = c_double()
+        self._check(self.lib.gmpnp_cycle_mix(self._h, int(g.size), _dptr(g), float(tau), byref(alpha)))
+        return alpha.value
+
+    def cycle_restart(self):
+        """``gmpnp_cycle_restart``: empties the window."""
+        self._check(self.lib.gmpnp_cycle_restart(self._h))
+
+    def cycle_vectors(self, which, window=None):
+        """``gmpnp_cycle_vectors`` (parity hook, file order): ``which`` = "x" or "g": (``window``, ndof) in window order (``window``: the
+        pairs held, as the last report said); "w": the weights (ndof,)."""
+        code = {"x": 0, "g": 1, "w": 2}[which]
+        out = np.empty(self.ndof if code == 2 else (int(window), self.ndof))
+        if out.size:
+            self._check(self.lib.gmpnp_cycle_vectors(self._h, code, _dptr(out)))
+        return out
+
+    def cycle_close(self):
+        """``gmpnp_cycle_close``."""
+        self._check(self.lib.gmpnp_cycle_close(self._h))
 
     def wall_profile_open(self, edges, capacity):
         """``gmpnp_wall_profile_open``: the wall of the 3D pore in ``len(edges) - 1`` axial bins with the edges ``edges`` (z, the mesh's

@@ -249,6 +249,22 @@ struct gmpnp_sensitizer {
   int32_t param[GMPNP_TANGENT_MAX_COLUMNS] = {};
 };
 
+// device side of the accelerated cycle map (gmpnp_cycle.h), allocated by the first gmpnp_cycle_open: a handle that never asks for it
+// keeps the buffers and launches it had
+namespace gmpnp { struct CycleReport; }
+struct gmpnp_cycler {
+  DevBuf<double> X, G, w;                 // [depth + 1][ndof] ring of the pairs (x_j, g_j), internal order; the frozen weights
+  DevBuf<double> part, part_max, alpha;   // workgroup partials of the residual; the mix's step factor
+  DevBuf<int32_t> part_dof, part_bad;
+  int depth = 0, cap = 0, nblk = 0;
+  int start = 0, window = 0;              // pair j of the window (oldest first) sits in slot (start + j) % cap
+  bool open = false, begun = false, ended = false;   // begun: x_k is written; ended: a report is out and no mix has used it
+  bool report_bad = false;                // the last report met a NaN / Inf: gmpnp_cycle_mix is refused
+  gmpnp::CycleReport* h_report = nullptr;   // pinned: what k_cycle_reduce writes
+  gmpnp::CycleReport* d_report = nullptr;   // ... its device address
+  ~gmpnp_cycler() { if (h_report) (void)hipHostFree(h_report); }
+};
+
 struct gmpnp_solver {
   Topology t;
   gmpnp_model_t model{};
@@ -341,6 +357,7 @@ struct gmpnp_solver {
   std::unique_ptr<gmpnp_tracer> tracer;
   std::unique_ptr<gmpnp_sensitizer> sensitizer;
   std::unique_ptr<gmpnp_wall_profiler> wall_profiler;
+  std::unique_ptr<gmpnp_cycler> cycler;
   // bndF + the Stern term (potential rows) + the kinetic term (species rows): what Ctx::bndF points at while either option is on
   // (boundary_rebind); allocated by the first of them
   DevBuf<double> bnd_dyn;
@@ -426,6 +443,11 @@ int sensitivity_time_step(gmpnp_solver* s);
 // gmpnp_wall_profile.h: the launches of one gmpnp_wall_profile_append into the row of slots and the charges of the hook's own (gmpnp_time_kernel 32)
 bool wall_profile_is_open(const gmpnp_solver* s);
 int wall_profile_time_append(gmpnp_solver* s);
+// gmpnp_cycle.h: residual + reduce + mix on the window of an open cycle, between a bracket that keeps u and u_n (gmpnp_time_kernel 33)
+bool cycle_has_window(const gmpnp_solver* s);
+int cycle_time_launch(gmpnp_solver* s);
+int cycle_kernel_begin(gmpnp_solver* s, DevBuf<double>& keep);
+int cycle_kernel_end(gmpnp_solver* s, DevBuf<double>& keep);
 
 // Either option on: bnd_dyn <- bndF (which restores the rows of an option just switched off; the kernels of the options that are on
 // rewrite theirs in front of every residual gather) and the context reads bnd_dyn.  Both off: the context reads the constant bndF.
@@ -2082,6 +2104,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   if (kernel == 30 && !response_band_has_chunk(s)) return fail(GMPNP_ERR_INVALID, "kernel 30 is one chunk of the 3D frequency response: no call has been made (gmpnp_frequency_response_3d), or the Stern option is off");
   if (kernel == 31 && !sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 31 is one step of the transient sensitivities: no buffer is open (gmpnp_sensitivity_open)");
   if (kernel == 32 && !wall_profile_is_open(s)) return fail(GMPNP_ERR_INVALID, "kernel 32 is one append of the wall profile: no profile is open (gmpnp_wall_profile_open)");
+  if (kernel == 33 && !cycle_has_window(s)) return fail(GMPNP_ERR_INVALID, "kernel 33 is the cycle residual and mix: no cycle is open with a pair in its window (gmpnp_cycle_open, gmpnp_cycle_end)");
   if ((kernel == 0 || kernel == 18 || kernel == 24 || kernel == 25 || kernel == 26) && !s->jacobian_valid)
     return fail(GMPNP_ERR_INVALID, "no Jacobian assembled for the current state");
   HIP_TRY(hipSetDevice(s->opts.device_id));
@@ -2128,6 +2151,7 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
       case 30: r = response_band_time_chunk(s); break;   // k_cband_scatter, k_band_step<9, BandComplex> per pivot, the solve and three refinement rounds, k_cband_functional
       case 31: r = sensitivity_time_step(s); break;      // assembly, columns, k_sens_rhs, chain(s), application, k_spmv_plain per column, k_sens_record
       case 32: r = wall_profile_time_append(s); break;   // k_stern_residual + k_kinetics_residual (kinetics on) + k_wall_profile
+      case 33: r = cycle_time_launch(s); break;          // k_cycle_residual + k_cycle_reduce + k_cycle_mix (direction) + k_step_limit + k_cycle_mix (apply)
       default: return fail(GMPNP_ERR_INVALID, "unknown kernel id");
     }
     return r;
@@ -2144,9 +2168,10 @@ int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double*
   DevBuf<double> keep;   // kernel 22 shifts u into u_n: u_n and u_nm1 are put back behind the launches
   if (kernel == 22) { rc = time_kernel_begin(s, keep); if (rc) return rc; }
   if (kernel == 23) { rc = time_kernel_begin2(s, keep); if (rc) return rc; }
+  if (kernel == 33) { rc = cycle_kernel_begin(s, keep); if (rc) return rc; }   // the mix writes u and u_n
   // kernel 22: whatever happens between the bracket's two halves, u_n and u_nm1 are put back (g_err keeps the first message)
-  auto restore = [&](int code) { if (kernel != 22 && kernel != 23) return code; const std::string msg = g_err;
-                                 const int rc2 = kernel == 22 ? time_kernel_end(s, keep) : time_kernel_end2(s, keep);
+  auto restore = [&](int code) { if (kernel != 22 && kernel != 23 && kernel != 33) return code; const std::string msg = g_err;
+                                 const int rc2 = kernel == 22 ? time_kernel_end(s, keep) : kernel == 23 ? time_kernel_end2(s, keep) : cycle_kernel_end(s, keep);
                                  if (code) { g_err = msg; return code; } return rc2; };
   rc = one(); if (rc) return restore(rc);  // warm
   float ms = 0.f;
@@ -2256,3 +2281,4 @@ int gmpnp_spmv_profile(gmpnp_solver* s, int64_t* n_sampled, double* mean_us, int
 #include "gmpnp_sensitivity.h"
 #include "gmpnp_response_band.h"
 #include "gmpnp_wall_profile.h"
+#include "gmpnp_cycle.h"

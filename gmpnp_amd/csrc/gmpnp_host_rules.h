@@ -899,4 +899,95 @@ inline std::string build_level_tables(const std::vector<int32_t>& fine_perm, con
   return std::string();
 }
 
+// ---- periodic steady state (include/gmpnp.h "periodic steady state"; kernels: gmpnp_cycle.h; gmpnp_amd/periodic.py states both rules
+// in Python, operation for operation) ---------------------------------------------------------------------------------------------------
+// anderson_weights: the mixing weights of a window of m + 1 pairs from its normal system A theta = b (A[i * lda + j] = <d_i, d_j>_W,
+// b_i = <d_i, r_k>_W, i, j < m; column 0 is the oldest difference).  Cholesky A = L L^T of the columns lo ... m - 1, lo = 0 first; where
+// a squared pivot is below 1e-12 x the largest diagonal entry of those columns or is not finite, a theta is not finite, or the weights
+// do not sum to 1 within 1e-12 (what gmpnp_cycle_mix asks), the oldest column is dropped (lo + 1) and the elimination starts again;
+// m - lo = 0 columns give gamma = (0, ..., 0, 1), the plain iteration.  With x_{k+1} = g_k - sum_j theta_j (g_{j+1} - g_j):
+//     gamma_lo = theta_lo      gamma_i = theta_i - theta_{i-1} (lo < i < m)      gamma_m = 1 - theta_{m-1}      gamma_i = 0 (i < lo)
+// Every product, quotient and sum is rounded on its own.  Returns the number of dropped columns; gamma has m + 1 entries.
+constexpr int kCycleRuleDepth = GMPNP_CYCLE_MAX_DEPTH;
+constexpr double kCyclePivotFloor = 1.0e-12, kCycleSumSlack = 1.0e-12;
+
+inline bool cycle_gamma_valid(int n, const double* gamma) {
+  GMPNP_RULE_NO_CONTRACT
+  if (n < 1 || n > kCycleRuleDepth + 1 || !gamma) return false;
+  double sum = 0.0;
+  for (int j = 0; j < n; ++j) {
+    if (!rule_finite(gamma[j])) return false;
+    sum = sum + gamma[j];
+  }
+  const double off = sum - 1.0;
+  return (off < 0.0 ? -off : off) <= kCycleSumSlack;
+}
+
+inline int anderson_weights(int m, const double* A, int lda, const double* b, double* gamma) {
+  GMPNP_RULE_NO_CONTRACT
+  if (m < 0) m = 0;
+  if (m > kCycleRuleDepth) m = kCycleRuleDepth;
+  for (int lo = 0; lo < m; ++lo) {
+    const int n = m - lo;
+    double L[kCycleRuleDepth][kCycleRuleDepth] = {}, y[kCycleRuleDepth] = {}, th[kCycleRuleDepth] = {};
+    double top = 0.0;
+    bool ok = true;
+    for (int i = 0; i < n; ++i) {
+      const double d = A[(lo + i) * lda + (lo + i)];
+      if (!rule_finite(d)) ok = false;
+      else if (d > top) top = d;
+    }
+    for (int j = 0; j < n && ok; ++j) {
+      double piv = A[(lo + j) * lda + (lo + j)];
+      for (int k = 0; k < j; ++k) piv = piv - L[j][k] * L[j][k];
+      if (!rule_finite(piv) || !(piv >= kCyclePivotFloor * top) || !(piv > 0.0)) { ok = false; break; }
+      L[j][j] = std::sqrt(piv);
+      for (int i = j + 1; i < n; ++i) {
+        double v = A[(lo + j) * lda + (lo + i)];   // the upper triangle
+        for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
+        L[i][j] = v / L[j][j];
+      }
+    }
+    if (!ok) continue;
+    for (int i = 0; i < n; ++i) {
+      double v = b[lo + i];
+      for (int k = 0; k < i; ++k) v = v - L[i][k] * y[k];
+      y[i] = v / L[i][i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+      double v = y[i];
+      for (int k = i + 1; k < n; ++k) v = v - L[k][i] * th[k];
+      th[i] = v / L[i][i];
+      if (!rule_finite(th[i])) ok = false;
+    }
+    if (!ok) continue;
+    for (int i = 0; i < lo; ++i) gamma[i] = 0.0;
+    gamma[lo] = th[0];
+    for (int i = 1; i < n; ++i) gamma[lo + i] = th[i] - th[i - 1];
+    gamma[m] = 1.0 - th[n - 1];
+    if (cycle_gamma_valid(m + 1, gamma)) return lo;
+  }
+  for (int i = 0; i < m; ++i) gamma[i] = 0.0;
+  gamma[m] = 1.0;
+  return m;
+}
+
+// cycle_verdict: what the residual history err[0 .. n - 1] of n marched cycles means.  Converged at err <= tol_cycle; give_up once
+// max_cycles cycles are marched; restart (empty the window and go on from g_k) where the residual grew by more than `growth` over the
+// cycle before, is not finite, or the report / the mix met a non-finite value (`nonfinite`); growth is a safeguard, not a tuned constant.
+enum CycleVerdict : int32_t { cycle_continue = 0, cycle_converged = 1, cycle_restart = 2, cycle_give_up = 3 };
+struct CyclePolicy { double tol_cycle = 1.0; int max_cycles = 50; double growth = 10.0; };
+
+inline CycleVerdict cycle_verdict(const double* err, int n, bool nonfinite, const CyclePolicy& p) {
+  GMPNP_RULE_NO_CONTRACT
+  if (n < 1) return cycle_continue;
+  const double e = err[n - 1];
+  const bool bad = nonfinite || !rule_finite(e);
+  if (!bad && e <= p.tol_cycle) return cycle_converged;
+  if (n >= p.max_cycles) return cycle_give_up;
+  if (bad) return cycle_restart;
+  if (n >= 2 && rule_finite(err[n - 2]) && e > p.growth * err[n - 2]) return cycle_restart;
+  return cycle_continue;
+}
+
 }  // namespace gmpnp

@@ -547,6 +547,7 @@ class EDLRun:
         closed and the run stands at the potential of the failed attempt; the exception goes on to the caller.  Returns
         the arrays of ``programme.npz`` plus ``log`` (the attempts, by column), ``states`` (segment, time_s, (nv, nf) values at the
         breakpoints) and ``metadata`` (the ``programme_*`` keys)."""
+        from . import periodic as prd
         from . import programme as prg
         from .timestep import TimeStepPolicy
         if self.stern is None:
@@ -568,16 +569,23 @@ class EDLRun:
                 tan = self.sys.dev.electrode_tangent(codes)
                 if tan["status"].any():
                     raise RuntimeError("programme: the steady tangent the sensitivities start from is not finite")
+            # ``periodic``: the limit cycle of ONE period in the place of a march (gmpnp_amd/periodic.py, section 5r)
+            periodic = par.get("periodic")
+            periodic = None if periodic is None or periodic is False else prd.check_periodic(periodic, par)
             ops = prg.DeviceProgrammeOps(self, self.solver_parameters, lambda h: 1.0 / (h * L_D), self.dt_tol, par.get("capacity") or 4096,
-                                         sensitivities=codes, sensitivity_start=start)
+                                         sensitivities=codes, sensitivity_start=start, cycle_tol=periodic[1:] if periodic else (1e-2, 1e-4))
         except BaseException:
             self.sys.set_time_step(inv_dt)
             raise
         policy = TimeStepPolicy(h_min=float(self.dt_bounds[0]), h_max=math.inf if self.dt_bounds[1] is None else float(self.dt_bounds[1]))
-        srec = None
+        srec, search = None, None
         try:
-            res = prg.run_programme(ops, segs, policy, dt_init=par.get("dt_init") or ep.dts[0], dt_restart=par.get("dt_restart"),
-                                    steps_per_segment=par.get("steps_per_segment"), max_attempts=self.max_steps)
+            if periodic:
+                search = prd.run_periodic(ops, segs, periodic[0], par["steps_per_segment"])
+                res = search["record"]   # the converged period, marched once more with records (not converged: the last marched period)
+            else:
+                res = prg.run_programme(ops, segs, policy, dt_init=par.get("dt_init") or ep.dts[0], dt_restart=par.get("dt_restart"),
+                                        steps_per_segment=par.get("steps_per_segment"), max_attempts=self.max_steps)
             if names:
                 srec = ops.sensitivity_records()
                 self.sys.dev.sensitivity_close()
@@ -609,6 +617,9 @@ class EDLRun:
                 "programme_potential_OHP": float(out["potential_OHP"][-1]) if len(rec) else None,
                 "programme_surface_charge": float(out["surface_charge"][-1]) if len(rec) else None}
         out.update(log=prg.log_arrays(res["log"]), states=[(k, t * ep.time_constant, v) for k, t, v in states], metadata=meta)
+        if search is not None:   # only with the option on: the history of the search and the state the recorded period starts from
+            out["periodic"] = dict(prd.history_arrays(search["history"]), state=search["state"])
+            meta.update(prd.metadata(search))
         if names:
             out["sensitivity"] = prg.sensitivity_arrays(ep, eps_0, srec, names, codes)
             meta.update(programme_sensitivity_parameters=list(names), programme_sensitivity_start=start,
@@ -623,6 +634,9 @@ class EDLRun:
         sens = out.pop("sensitivity", None)
         if sens is not None:   # only with the option on
             np.savez(newpath + "/programme_sensitivity.npz", **sens)
+        search = out.pop("periodic", None)
+        if search is not None:   # only with the option on: programme.npz is then the recorded period of the limit cycle
+            np.savez(newpath + "/programme_periodic.npz", **search)
         np.savez(newpath + "/programme.npz", **out)
         np.savez(newpath + "/programme_states.npz", segment=np.array([k for k, _, _ in states], dtype=np.int64),
                  time_s=np.array([t for _, t, _ in states]), states=np.stack([v for _, _, v in states]), coor=self.mesh.coords)

@@ -660,6 +660,8 @@ def check_fit_programme(par, kwargs, dt_order=1):
         raise ValueError("fit_programme: the programme runs in fixed mode (steps_per_segment)")
     if prog.get("sensitivities"):
         raise ValueError("fit_programme: the fit carries the sensitivities of its own parameters (leave the programme's sensitivities out)")
+    if prog.get("periodic") is not None and prog.get("periodic") is not False:
+        raise ValueError("fit_programme: not with a periodic programme (the data are the transient of a march, not the limit cycle)")
     if kwargs.get("kinetics") is None:
         raise ValueError("fit_programme: the fit needs the surface kinetics (kinetics='tafel')")
     par["params"] = tuple(par.get("params") or DEFAULT_PARAMS)

@@ -407,7 +407,7 @@ def build(par, electrode_voltage, time_constant, thermal_voltage):
 
 PROGRAMME_FIELDS = {"pulse": ({"v_levels", "durations"}, {"cycles", "rise_time"}), "triangle": ({"v_vertex", "scan_rate"}, {"cycles"}),
                     "table": ({"time_s", "electrode_voltage"}, set())}
-COMMON_FIELDS = {"kind", "dt_init", "dt_restart", "steps_per_segment", "capacity", "sensitivities", "sensitivity_start"}
+COMMON_FIELDS = {"kind", "dt_init", "dt_restart", "steps_per_segment", "capacity", "sensitivities", "sensitivity_start", "periodic"}
 
 
 def sensitivity_codes(names):
@@ -464,6 +464,9 @@ def check_programme(par, kwargs, dt_order=1):
             raise ValueError("programme: sensitivity_start without sensitivities")
         if par["sensitivity_start"] not in ("steady", "zero"):
             raise ValueError("programme: sensitivity_start is 'steady' or 'zero'")
+    if par.get("periodic") is not None and par.get("periodic") is not False:   # the limit cycle in the place of a march (section 5r)
+        from .periodic import check_periodic
+        check_periodic(par["periodic"], par)
     build(par, float(kwargs["electrode_voltage"]), 1.0, 1.0)   # a waveform that is not valid is refused here (the units do not matter)
     return par
 
@@ -491,6 +494,12 @@ def add_programme_arguments(p):
                         "through the programme (programme_sensitivity.npz)")
     p.add_argument("--programme_sensitivity_start", required=False, default=None, choices=("steady", "zero"),
                    help="(addition) the sensitivities start from the steady state's dependence on the parameters (default) or from zero")
+    p.add_argument("--programme_periodic", required=False, default=False, action="store_true",
+                   help="(addition) look for the limit cycle of ONE period of the waveform by Anderson acceleration of the cycle map "
+                        "(needs --programme_steps_per_segment; programme.npz holds the converged period, programme_periodic.npz the search)")
+    p.add_argument("--periodic_tol", required=False, default=None, type=float, help="(addition) the cycle is converged at a weighted residual <= this (default 1)")
+    p.add_argument("--periodic_depth", required=False, default=None, type=int, help="(addition) differences of a full Anderson window, 1 ... 8 (default 4)")
+    p.add_argument("--periodic_max_cycles", required=False, default=None, type=int, help="(addition) cycles marched at the most (default 50)")
 
 
 def load_table(path):
@@ -504,9 +513,14 @@ def load_table(path):
 
 def programme_keywords(a):
     """The programme keyword of a parsed command line (``add_programme_arguments``); empty without --programme."""
+    periodic = {k: getattr(a, "periodic_" + k) for k in ("tol", "depth", "max_cycles") if getattr(a, "periodic_" + k, None) is not None}
+    if periodic and not getattr(a, "programme_periodic", False):
+        raise ValueError("programme: --periodic_tol, --periodic_depth and --periodic_max_cycles need --programme_periodic")
     if a.programme is None:
         if getattr(a, "programme_sensitivities", None) or getattr(a, "programme_sensitivity_start", None):
             raise ValueError("programme: --programme_sensitivities and --programme_sensitivity_start need --programme")
+        if getattr(a, "programme_periodic", False):
+            raise ValueError("programme: --programme_periodic needs --programme")
         return {}
     par = {"kind": a.programme}
     if a.programme == "pulse":
@@ -530,6 +544,8 @@ def programme_keywords(a):
         par["sensitivities"] = list(a.programme_sensitivities)
     if getattr(a, "programme_sensitivity_start", None):
         par["sensitivity_start"] = a.programme_sensitivity_start
+    if getattr(a, "programme_periodic", False):
+        par["periodic"] = periodic
     return {"programme": par}
 
 
@@ -542,12 +558,14 @@ class DeviceProgrammeOps:
     what the records before held."""
 
     def __init__(self, run, solver_parameters, inv_dt_of_h, tol=(1e-2, 1e-4), capacity=4096, sensitivities=None, sensitivity_start="zero",
-                 after_accept=None, profile_edges=None):
+                 after_accept=None, profile_edges=None, cycle_tol=(1e-2, 1e-4)):
         """``after_accept`` (the pore driver's Sechenov glue; the 1D path passes none): called once per accepted step, in front of
         ``time_accept``; a rejected attempt never reaches it.  ``profile_edges`` (3D handles): ``record`` also appends to the wall
-        profile with these edges and ``drain`` reads and reopens it with the trace; ``profile_records`` returns (steps, bins)."""
+        profile with these edges and ``drain`` reads and reopens it with the trace; ``profile_records`` returns (steps, bins).
+        ``cycle_tol`` = (rtol, atol) of the weights of the accelerated cycle map (``cycle_open``; section 5r)."""
         from . import backend
         self.backend = backend
+        self.cycle_tol, self.cycle_is_open = (float(cycle_tol[0]), float(cycle_tol[1])), False
         self.run, self.sys, self.dev = run, run.sys, run.sys.dev
         self.solver_parameters, self.inv_dt_of_h, self.tol, self.capacity = solver_parameters, inv_dt_of_h, tol, int(capacity)
         self.chunks, self.segments, self.states, self.count = [], [], [], 0
@@ -660,6 +678,56 @@ class DeviceProgrammeOps:
                 self.dev.wall_profile_open(self.profile_edges, self.capacity)
             if self.sensitivities is not None:
                 self.dev.sensitivity_open(self.sensitivities, "continue", self.capacity)
+
+    # ---- the accelerated cycle map (``periodic.run_periodic``; section 5r) ----
+    def cycle_open(self, depth):
+        if self.sensitivities is not None or self.profile_edges is not None:
+            raise ValueError("programme: periodic runs carry neither sensitivities nor a wall profile")
+        self.dev.cycle_open(depth, *self.cycle_tol)
+        self.cycle_is_open = True
+
+    def cycle_close(self):
+        if self.cycle_is_open:
+            self.cycle_is_open = False
+            self.dev.cycle_close()
+
+    def cycle_begin(self):
+        self.dev.cycle_begin()
+
+    def cycle_end(self):
+        return self.dev.cycle_end()
+
+    def _fresh_records(self, between=None):
+        """Drops every record and breakpoint state taken so far and opens the trace again at the state ``between`` leaves (the mix, which
+        the library refuses under an open trace): D_prev is that state's D and the charges start at 0."""
+        self.count = 0
+        self.dev.electrode_trace_close()
+        try:
+            return between() if between is not None else None
+        finally:
+            self.dev.electrode_trace_open(self.capacity)
+            self.D_first = self.dev.stern_displacement()
+            self.chunks, self.segments, self.states, self.residuals = [], [], [], []
+            self.base_Q, self.base_Q_D = np.zeros(MAX_SURFACE_REACTIONS), 0.0
+
+    def cycle_mix(self, gamma, tau):
+        backend = self.backend
+
+        def mix():
+            try:
+                return self.dev.cycle_mix(gamma, tau)
+            except backend.GmpnpError as e:   # a value of the direction that is not finite: nothing was applied
+                if e.code != backend.ERR_NUMERIC:
+                    raise
+                return math.nan
+        return self._fresh_records(mix)
+
+    def cycle_restart(self):
+        self.dev.cycle_restart()
+        self._fresh_records()
+
+    def state(self):
+        return self.sys.vertex_values()
 
     def abort(self):
         """After an exception inside the loop: the handle returns to the last accepted state (u <- u_n) and the trace is closed, so
@@ -797,6 +865,8 @@ def check_pore_programme(par, kwargs, dt_order=1, partition=None, multilevel=Fal
     par = dict(par)
     if set(par) & {"sensitivities", "sensitivity_start"}:
         raise ValueError("pore_programme: the transient sensitivities are 1D (programme)")
+    if "periodic" in par:   # (the lagged Sechenov Dirichlet value would be part of the cycle map's state)
+        raise ValueError("pore_programme: periodic (the limit cycle by the accelerated cycle map) is 1D (programme)")
     if kwargs.get("programme"):
         raise ValueError("pore_programme: not in one run with programme (which the 3D pore driver refuses)")
     if partition:

@@ -881,6 +881,61 @@ int gmpnp_sensitivity_columns(gmpnp_solver* s, int32_t which, double* out /* [n]
 int gmpnp_sensitivity_set_columns(gmpnp_solver* s, const double* in /* [n][n_dofs] in file order */);
 int gmpnp_sensitivity_close(gmpnp_solver* s);
 
+/* ---- periodic steady state: the accelerated cycle map (no reference counterpart: the limit cycle of a potential programme; kernels:
+ * csrc/gmpnp_cycle.h; rules: anderson_weights and cycle_verdict of csrc/gmpnp_host_rules.h; driver: gmpnp_amd/periodic.py; DESIGN.md
+ * section 5r) ----------------------------------------------------------------------------------------------------------------------------
+ * The cycle map Phi takes u_n at the start of one period of a waveform, marched with fixed steps, to u_n at its end.  The handle keeps a
+ * window of at most depth + 1 pairs (x_j, g_j = Phi(x_j)), oldest first, k the newest, and one weight vector.  With r_j = g_j - x_j and
+ * d_j = r_{j+1} - r_j, Anderson acceleration (type II, beta = 1) takes theta = argmin |r_k - sum_j theta_j d_j|_W and goes on from
+ * x_{k+1} = g_k - sum_j theta_j (g_{j+1} - g_j) = sum_j gamma_j g_j, sum_j gamma_j = 1.  The device forms the residual norm and the
+ * normal system, the host solves it (anderson_weights) and the device mixes the stored states.
+ *   open(depth, tol)  depth 1 ... 8; allocates depth + 1 pairs of n_dofs doubles and the weights, frozen HERE from the current u_n:
+ *                     w = atol_f + rtol |u_n| per dof.  Empties the window.  One synchronisation.
+ *   begin()           x_k <- u_n (a device copy); the oldest pair leaves a full window
+ *   end(report)       g_k <- u_n, the pair enters the window; over the dofs that carry no Dirichlet value (a Dirichlet dof's change
+ *                     over a cycle is boundary data):
+ *                         err = sqrt(sum (r_k / w)^2 / n_free)     err_max = max |r_k / w| at worst_dof (ties: the smaller dof of
+ *                         the handle's internal order)             A_ij = sum (d_i / w)(d_j / w)     b_i = sum (d_i / w)(r_k / w)
+ *                     for i, j < window - 1, zero behind; the differences are formed first and then the products (a Gram matrix of
+ *                     the r_j would cancel where successive residuals agree to several digits).  A NaN / Inf anywhere in a stored
+ *                     vector of the window or in the weights (u_n was not finite at the open) sets nonfinite and makes err and
+ *                     err_max NaN; the status stays GMPNP_OK, and a mix behind such a report is refused (with tau = 0 no pass of
+ *                     the mix would notice the value on its way into u and u_n): restart, or open again.  Fixed-order
+ *                     reductions, no atomics: two calls on one window return the same bits.  One synchronisation.
+ *   mix(n, gamma, tau, alpha_out)   n = the window of the last report, every gamma finite, |sum gamma - 1| <= 1e-12 (summed left to
+ *                     right).  Free rows: u = u_n <- g_k + alpha (sum_j gamma_j g_j - g_k), the sum over j in window order from
+ *                     gamma_0 g_0, every product and sum rounded on its own; Dirichlet rows: g_k.  alpha = 1 with tau = 0, otherwise
+ *                     the fraction-to-boundary factor of gmpnp_step_limit for the correction dx = -(sum_j gamma_j g_j - g_k) at the
+ *                     state g_k (the same kernel and rule).  A NaN / Inf in that direction: nothing is applied, alpha = NaN,
+ *                     GMPNP_ERR_NUMERIC.  Afterwards the handle is where gmpnp_set_state(u, u) leaves it: no history levels, the
+ *                     state marked as set from outside, Jacobian and preconditioner invalid, the tangent dropped, the time term
+ *                     reading u_n.  A second mix needs another end.
+ *   restart()         empties the window (the weights stay)
+ *   vectors(which, out)   parity hook, file order: which = 0 the x_j, 1 the g_j ([window][n_dofs], window order), 2 the weights
+ *   close()           every call but open is refused until the next open (the buffers stay with the handle)
+ * Everything is allocated by the first open: a handle that never calls it keeps the buffers and launches it had.  Refused
+ * (GMPNP_ERR_INVALID, the message names the cycle): partition handles, a coarse level attached or the handle serving as one, the
+ * galvanostat on, order-2 time stepping (p_M, u_nm1 would be part of the map's state), depth outside 1 ... 8, a tolerance
+ * gmpnp_time_error would refuse, any call but open without an open cycle, end without begin, mix before end or behind a report with nonfinite set, a wrong n, a gamma that is
+ * not finite or does not sum to 1, tau outside {0} and (0, 1), and at mix an open electrode trace, sensitivity session or wall profile
+ * (close them and open them again behind the mix: their accumulators then start at the mixed state). */
+#define GMPNP_CYCLE_MAX_DEPTH 8
+typedef struct {
+  double err, err_max;
+  int64_t worst_dof;                                             /* file order (vertex*n_fields+field), -1: none */
+  int64_t n_free;
+  int32_t nonfinite, window;                                     /* window: pairs held, this one included */
+  double A[GMPNP_CYCLE_MAX_DEPTH * GMPNP_CYCLE_MAX_DEPTH];       /* row-major, both triangles filled from the upper one */
+  double b[GMPNP_CYCLE_MAX_DEPTH];
+} gmpnp_cycle_report_t;
+int gmpnp_cycle_open(gmpnp_solver* s, int32_t depth, const gmpnp_time_tol_t* tol);
+int gmpnp_cycle_begin(gmpnp_solver* s);
+int gmpnp_cycle_end(gmpnp_solver* s, gmpnp_cycle_report_t* report);
+int gmpnp_cycle_mix(gmpnp_solver* s, int32_t n, const double* gamma /* [n] */, double tau, double* alpha_out /* or NULL */);
+int gmpnp_cycle_restart(gmpnp_solver* s);
+int gmpnp_cycle_vectors(gmpnp_solver* s, int32_t which, double* out);
+int gmpnp_cycle_close(gmpnp_solver* s);
+
 /* ---- ensemble of problems (no reference counterpart: the reference solves one problem per run; a voltage x cation x
  * concentration sweep of 1D/MPNP_CO2ER_EDL.py or 3D/MPNP_CO2ER_pore.py is many separate runs) ------------------------------------
  * n = 1 ... 64 handles the caller made with gmpnp_create on the SAME mesh (same vertices, cells and vertex order) and device,
@@ -966,7 +1021,10 @@ int gmpnp_ensemble_time_advance(gmpnp_ensemble* e, const int32_t* action /* [n]:
  * accumulators of their own; like a step it reassembles F and J at the current u and drops the tangent, so a gmpnp_sensitivity_open with
  * start = 1 needs a gmpnp_electrode_tangent call made after it), 32 = the launches of one gmpnp_wall_profile_append (k_stern_residual,
  * k_kinetics_residual with the kinetics on, k_wall_profile; needs an open wall profile, whose records, count and charges stay: the
- * hook's launches write the row of slots behind the buffer and charges of their own). */
+ * hook's launches write the row of slots behind the buffer and charges of their own), 33 = the launches of one cycle residual and
+ * one mix (k_cycle_residual, k_cycle_reduce, then k_cycle_mix's direction pass, k_step_limit and k_cycle_mix's apply pass with
+ * gamma = the newest pair alone and tau = 0.9; needs an open cycle with at least one pair behind a gmpnp_cycle_end; u and u_n are put
+ * back, the window, the history and the handle's flags stay). */
 int gmpnp_time_kernel(gmpnp_solver* s, int32_t kernel, int32_t launches, double* avg_us);
 /* Fused BiCGStab half-iterations (SpMV + vector updates) timed with HIP events since the last call (opts.profile_every):
  * n_sampled = half-iterations inside the timed bursts (each a run of back-to-back launches, all of them before the end of
