@@ -855,6 +855,14 @@ class DeviceSolver:
         one call (the bits ``set_stern`` followed by ``set_kinetics`` with that value leave)."""
         self._check(self.lib.gmpnp_set_electrode_potential(self._h, float(p)))
 
+    def _read_records(self, call, dtype, first, n, width=None):
+        """Rows ``first`` ... ``first + n - 1`` of a record stream by its read call, as a structured array of ``dtype``: (n,), or
+        (n, width) where a row holds ``width`` records."""
+        n, w = int(n), 1 if width is None else max(int(width), 1)
+        out = np.zeros((max(n, 1), w), dtype=dtype)
+        self._check(call(self._h, int(first), n, out.ctypes.data_as(call.argtypes[3])))
+        return out[:max(n, 0), 0] if width is None else out[:max(n, 0)]
+
     def electrode_trace_open(self, capacity):
         """``gmpnp_electrode_trace_open``: a trace of ``capacity`` records; D at the current u becomes D_prev, Q and Q_D start at 0."""
         self._check(self.lib.gmpnp_electrode_trace_open(self._h, int(capacity)))
@@ -867,10 +875,7 @@ class DeviceSolver:
     def electrode_trace_read(self, first, n) -> np.ndarray:
         """``gmpnp_electrode_trace_read``: records ``first`` ... ``first + n - 1`` as a structured array (``ELECTRODE_RECORD_DTYPE``;
         I and Q hold ``MAX_SURFACE_REACTIONS`` entries, u_boundary ``MAX_SPECIES``)."""
-        n = int(n)
-        out = (CElectrodeRecord * max(n, 1))()
-        self._check(self.lib.gmpnp_electrode_trace_read(self._h, int(first), n, out))
-        return np.frombuffer(out, dtype=ELECTRODE_RECORD_DTYPE, count=max(n, 0)).copy()
+        return self._read_records(self.lib.gmpnp_electrode_trace_read, ELECTRODE_RECORD_DTYPE, first, n)
 
     def electrode_trace_close(self):
         """``gmpnp_electrode_trace_close``."""
@@ -938,10 +943,7 @@ class DeviceSolver:
     def wall_profile_read(self, first, n) -> np.ndarray:
         """``gmpnp_wall_profile_read``: the records of steps ``first`` ... ``first + n - 1`` as a structured array (n, bins)
         (``WALL_PROFILE_RECORD_DTYPE``)."""
-        n, nb = int(n), max(int(getattr(self, "_wall_profile_bins", 0)), 1)
-        out = np.zeros((max(n, 1), nb), dtype=WALL_PROFILE_RECORD_DTYPE)
-        self._check(self.lib.gmpnp_wall_profile_read(self._h, int(first), n, out.ctypes.data_as(c_void_p)))
-        return out[:max(n, 0)]
+        return self._read_records(self.lib.gmpnp_wall_profile_read, WALL_PROFILE_RECORD_DTYPE, first, n, getattr(self, "_wall_profile_bins", 0))
 
     def wall_profile_close(self):
         """``gmpnp_wall_profile_close``."""
@@ -964,10 +966,7 @@ class DeviceSolver:
     def sensitivity_read(self, first, n_steps) -> np.ndarray:
         """``gmpnp_sensitivity_read``: the records of steps ``first`` ... ``first + n_steps - 1`` as a structured array
         (``SENSITIVITY_RECORD_DTYPE``) of shape (n_steps, n columns)."""
-        n_steps, n = int(n_steps), getattr(self, "_n_sensitivities", 1)
-        out = (CSensitivityRecord * max(n_steps * n, 1))()
-        self._check(self.lib.gmpnp_sensitivity_read(self._h, int(first), n_steps, out))
-        return np.frombuffer(out, dtype=SENSITIVITY_RECORD_DTYPE, count=max(n_steps * n, 0)).copy().reshape(max(n_steps, 0), n)
+        return self._read_records(self.lib.gmpnp_sensitivity_read, SENSITIVITY_RECORD_DTYPE, first, n_steps, getattr(self, "_n_sensitivities", 1))
 
     def sensitivity_columns(self, which=0) -> np.ndarray:
         """``gmpnp_sensitivity_columns``: S (``which`` = 0) or the right-hand sides of the last step (1), (n, ndof) in file order."""

@@ -55,6 +55,48 @@ struct DevBuf {
   }
 };
 
+// The nouns of a record stream's messages: "<prefix>: no <what> is open (<open_call>)", "... the buffer is full (read the records and
+// <reopen>)", "... the <rows> asked for have not been written".
+struct RecordNouns {
+  const char *prefix, *what, *open_call, *rows, *reopen;
+  std::string say(const std::string& tail) const { return std::string(prefix) + ": " + tail; }
+  std::string not_open() const { return say(std::string("no ") + what + " is open (" + open_call + ")"); }
+};
+
+// A device buffer of per-step records (rule: gmpnp_host_rules.h "record streams"): [capacity + 1][width] records, appended to without
+// host synchronisation and read in chunks.  The row behind the buffer is the timing hook's (gmpnp_time_kernel 29 / 31 / 32).
+template <class Rec>
+struct RecordStream {
+  const RecordNouns& nouns;
+  DevBuf<Rec> rec;
+  int width = 0, capacity = 0, count = 0;   // width: records per step
+  bool open = false;
+  explicit RecordStream(const RecordNouns& n) : nouns(n) {}
+  // an empty buffer of `cap` rows of `w` records: allocated again only where either changed
+  int reserve(int cap, int w, hipStream_t stream) {
+    if (capacity != cap || width != w) {
+      HIP_TRY(hipStreamSynchronize(stream));
+      capacity = 0;   // (alloc frees the old buffer first: an allocation that fails leaves no capacity a later open could take for a buffer)
+      HIP_TRY(rec.alloc(record_rows(cap) * (size_t)w));
+      capacity = cap; width = w;
+    }
+    count = 0;
+    return GMPNP_OK;
+  }
+  Rec* row(int slot) const { return rec.p + (size_t)slot * width; }
+  Rec* hook_row() const { return row(capacity); }
+  bool full() const { return !record_can_append(count, capacity); }
+  int refuse_full() const { return fail(GMPNP_ERR_INVALID, nouns.say(std::string("the buffer is full (read the records and ") + nouns.reopen + ")")); }
+  int read(int32_t first, int32_t n, Rec* out, hipStream_t stream) const {
+    if (!record_range_valid(first, n, count))
+      return fail(GMPNP_ERR_INVALID, nouns.say(std::string("the ") + nouns.rows + " asked for have not been written"));
+    HIP_TRY(hipMemcpyAsync(out, row(first), (size_t)n * width * sizeof(Rec), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return GMPNP_OK;
+  }
+  void close() { open = false; }
+};
+
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -212,40 +254,40 @@ struct gmpnp_tangenter {
 
 // device side of the electrode trace (gmpnp_trace.h), allocated by the first gmpnp_electrode_trace_open: a handle that never asks for it
 // keeps the buffers and launches it had
+constexpr RecordNouns kTraceNouns{"electrode trace", "trace", "gmpnp_electrode_trace_open", "records", "open the trace again"};
 struct gmpnp_tracer {
-  DevBuf<gmpnp_electrode_record_t> rec;   // [capacity + 1]: the slot behind the buffer is gmpnp_time_kernel(29)'s
+  RecordStream<gmpnp_electrode_record_t> rec{kTraceNouns};   // one record per step
   DevBuf<ElectrodeAccum> acc;             // [2]: D_prev, Q, Q_D of the trace; the hook's own
   DevBuf<double> w;                       // [n_nodes] w_I of the Stern nodes (read while the kinetics, which hold the same, are off)
   DevBuf<int32_t> status;                 // the word of the Stern and kinetic launches of an open / append (not the solver's)
-  int capacity = 0, count = 0;
-  bool open = false;
 };
 
 // device side of the wall profile (gmpnp_wall_profile.h), allocated by the first gmpnp_wall_profile_open: a handle that never asks for it
 // keeps the buffers and launches it had
+constexpr RecordNouns kWallProfileNouns{"wall profile", "profile", "gmpnp_wall_profile_open", "records", "open the profile again"};
 struct gmpnp_wall_profiler {
-  DevBuf<gmpnp_wall_profile_record_t> rec;   // [capacity + 1][n_bins]: the row behind the buffer is gmpnp_time_kernel(32)'s
+  RecordStream<gmpnp_wall_profile_record_t> rec{kWallProfileNouns};   // n_bins records per step
   DevBuf<double> Q;                          // [2][n_bins][4]: the charges of the bins; the hook's own
   DevBuf<double> w, edges;                   // [n_nodes] w_I of the Stern nodes; [n_bins + 1]
   DevBuf<int32_t> bin_ptr, bin_pos;          // CSR over the bins of positions in the Stern node list, ascending inside a bin
   DevBuf<int32_t> status;                    // the word of the Stern and kinetic launches of an append (not the solver's)
   std::vector<double> h_edges;               // the edges of the lists the device holds
-  int n_bins = 0, capacity = 0, count = 0;
-  bool open = false;
+  int n_bins = 0;                            // of the lists the device holds (0: none a later open could take for valid)
 };
 
 // device side of the transient sensitivities (gmpnp_sensitivity.h), allocated by the first gmpnp_sensitivity_open: a handle that never
 // asks for it keeps the buffers and launches it had
+constexpr RecordNouns kSensNouns{"sensitivities", "buffer", "gmpnp_sensitivity_open", "steps", "open again with start = 2"};
 struct gmpnp_sensitizer {
   DevBuf<double> S, S_hook;               // [n][ndof] internal order: the state sensitivities; gmpnp_time_kernel(31)'s own
   DevBuf<double> c, Jz;                   // [10][ndof] the columns dF/dtheta_k of the step; J s_k
   DevBuf<double> mass;                    // [3][nv] the species rows' mass entries (species_mass_1d)
   DevBuf<double> store;                   // per level of the cyclic-reduction pyramid: b, bi, x with 8 columns, then with 2 columns
-  DevBuf<gmpnp_sensitivity_record_t> rec; // [capacity + 1][n]: the row behind the buffer is the hook's
+  RecordStream<gmpnp_sensitivity_record_t> rec{kSensNouns};   // n records per step
   DevBuf<ElectrodeAccum> acc;             // [2][10]: dD_prev, dQ, dQ_D per column; the hook's own
   DevBuf<int32_t> status;                 // the word of the column launches
-  int n = 0, capacity = 0, count = 0;
-  bool open = false, stepped = false;     // stepped: a right-hand side has been formed since the open
+  int n = 0;
+  bool stepped = false;                   // a right-hand side has been formed since the open
   int32_t param[GMPNP_TANGENT_MAX_COLUMNS] = {};
 };
 

@@ -479,7 +479,16 @@ GMPNP_RULE_HD inline double electrode_record_combine(ElectrodeAccum& a, double h
   a.D_prev = D;
   return dD_dt;
 }
-inline bool electrode_trace_step_valid(double t, double h) { return rule_finite(t) && rule_finite(h) && h > 0.0; }
+
+// ---- record streams (RecordStream in gmpnp_api.hip: the electrode trace, the wall profile, the transient sensitivities) ------------------
+// A buffer of `capacity` rows, one per accepted step, written without host synchronisation and read in chunks.  One more row stands
+// behind the buffer for the timing hooks of gmpnp_time_kernel, which so never write a row that can be read.
+inline size_t record_rows(int capacity) { return (size_t)capacity + 1; }
+// rows first ... first + n - 1 have been written (the sum in 64 bits: first + n cannot wrap)
+inline bool record_range_valid(int32_t first, int32_t n, int count) { return first >= 0 && n >= 1 && (int64_t)first + n <= count; }
+inline bool record_can_append(int count, int capacity) { return count < capacity; }
+// the step of length h that ends at t
+inline bool record_step_valid(double t, double h) { return rule_finite(t) && rule_finite(h) && h > 0.0; }
 
 // ---- wall profile (include/gmpnp.h "wall profile"; kernel: gmpnp_wall_profile.h; gmpnp_amd/programme.py states the same in Python) ------
 // The wall of the 3D pore in n axial bins with the edges edges[0] < ... < edges[n] (z: the mesh's third coordinate, units of L).
@@ -510,7 +519,6 @@ GMPNP_RULE_HD inline void wall_profile_charge(double (&Q)[GMPNP_MAX_SURFACE_REAC
   GMPNP_RULE_NO_CONTRACT
   Q[0] = Q[0] + h * I[0]; Q[1] = Q[1] + h * I[1]; Q[2] = Q[2] + h * I[2]; Q[3] = Q[3] + h * I[3];
 }
-inline bool wall_profile_step_valid(double t, double h) { return electrode_trace_step_valid(t, h); }
 
 // [3P] dolfin::NewtonSolver, criterion "residual": r / r0 < rtol || r < atol, tested BEFORE the first iteration and after every
 // update.  A driver hands every residual norm (with the device status word of its evaluation) to first() / next() and does what

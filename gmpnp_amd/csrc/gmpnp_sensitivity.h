@@ -21,6 +21,8 @@
 //                     synchronisation, no copy, no floating-point atomics; the sums are picked out of the register array with constant
 //                     indices.  `init`: gmpnp_sensitivity_open's launch, which only takes dD as dD_prev and zeroes dQ and dQ_D.
 // A column's numbers never meet another column's: its records and S do not depend on which other columns are carried.
+// The records' buffer is a RecordStream of width n (gmpnp_api.hip; rule: gmpnp_host_rules.h "record streams"), as the electrode trace's
+// and the wall profile's are; the refusal of a handle goes through tangent_refusal.
 // Included at the end of gmpnp_api.hip.
 #pragma once
 
@@ -184,19 +186,19 @@ int sens_solve_chain(gmpnp_solver* s, double* S, const std::vector<TriCols>& cl,
   return GMPNP_OK;
 }
 
-SensTab sens_tab(gmpnp_solver* s, const SensLevels& L, const double* S, int row, int which) {
+SensTab sens_tab(gmpnp_solver* s, const SensLevels& L, const double* S, gmpnp_sensitivity_record_t* rec, int which) {
   gmpnp_sensitizer* Z = s->sensitizer.get();
   SensTab t{};
   t.n = Z->n; t.ndof = (int32_t)s->ndof; t.nv = s->t.nv;
   for (int k = 0; k < Z->n; ++k) t.param[k] = Z->param[k];
   t.S = S; t.Jz = Z->Jz.p; t.b8 = L.c8[0].b; t.b2 = L.c2[0].b;
-  t.rec = Z->rec.p + (size_t)row * Z->n; t.acc = Z->acc.p + (size_t)which * kTangentMaxColumns;
+  t.rec = rec; t.acc = Z->acc.p + (size_t)which * kTangentMaxColumns;
   t.word = s->status.p; t.own = Z->status.p;
   return t;
 }
 
-// the launches of one step on the sensitivities `S`, into row `row` of the records with the accumulators acc[which]: nothing waits
-int sens_launch(gmpnp_solver* s, double t, double h, double* S, int row, int which) {
+// the launches of one step on the sensitivities `S`, into the row `rec` of the records with the accumulators acc[which]: nothing waits
+int sens_launch(gmpnp_solver* s, double t, double h, double* S, gmpnp_sensitivity_record_t* rec, int which) {
   constexpr int DIM = 1, NF = 7;
   gmpnp_sensitizer* Z = s->sensitizer.get();
   const size_t ndof = (size_t)s->ndof;
@@ -242,7 +244,7 @@ int sens_launch(gmpnp_solver* s, double t, double h, double* S, int row, int whi
   for (int k = 0; k < n; ++k)
     hipLaunchKernelGGL((k_spmv_plain<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c, (const double*)(S + (size_t)k * ndof),
                        Z->Jz.p + (size_t)k * ndof);
-  SensTab t_ = sens_tab(s, L, S, row, which);
+  SensTab t_ = sens_tab(s, L, S, rec, which);
   t_.t = t; t_.h = h; t_.init = 0;
   hipLaunchKernelGGL((k_sens_record<DIM, NF>), dim3(1), dim3(kVecBlock), 0, s->stream, s->c, kt, st, kin, t_);
   HIP_TRY(hipGetLastError());
@@ -250,16 +252,14 @@ int sens_launch(gmpnp_solver* s, double t, double h, double* S, int row, int whi
   return GMPNP_OK;
 }
 
-bool sensitivity_is_open(const gmpnp_solver* s) { return s->sensitizer && s->sensitizer->open; }
+bool sensitivity_is_open(const gmpnp_solver* s) { return s->sensitizer && s->sensitizer->rec.open; }
 
 // gmpnp_time_kernel 31: the second S, the row behind the buffer and the second set of accumulators, so the march stays what it was
 int sensitivity_time_step(gmpnp_solver* s) {
   if (const char* why = sens_refusal(s)) return fail(GMPNP_ERR_INVALID, std::string("sensitivities: ") + why);
   if (!s->sensitizer->S_hook.p) HIP_TRY(s->sensitizer->S_hook.alloc((size_t)kTangentMaxColumns * s->ndof));   // (zeroed)
-  return sens_launch(s, 0.0, 1.0, s->sensitizer->S_hook.p, s->sensitizer->capacity, 1);
+  return sens_launch(s, 0.0, 1.0, s->sensitizer->S_hook.p, s->sensitizer->rec.hook_row(), 1);
 }
-
-const char* const kSensNotOpen = "sensitivities: no buffer is open (gmpnp_sensitivity_open)";
 
 }  // namespace
 
@@ -312,15 +312,10 @@ int gmpnp_sensitivity_open(gmpnp_solver* s, int32_t n, const int32_t* param, int
     s->sensitizer = std::move(N);
     Z = s->sensitizer.get();
   }
-  Z->open = false;
+  Z->rec.close();
   HIP_TRY(hipStreamSynchronize(s->stream));
-  if (Z->capacity != capacity || Z->n != n) {
-    Z->capacity = 0;   // (alloc frees the old buffer first: an allocation that fails leaves no capacity a later open could take for a buffer)
-    HIP_TRY(Z->rec.alloc(((size_t)capacity + 1) * n));
-    Z->capacity = capacity;
-  }
-  Z->count = 0;
-  if (start == 2) { Z->open = true; return GMPNP_OK; }
+  if (int rc = Z->rec.reserve(capacity, n, s->stream)) return rc;
+  if (start == 2) { Z->rec.open = true; return GMPNP_OK; }
   Z->n = n;
   for (int k = 0; k < n; ++k) Z->param[k] = param[k];
   Z->stepped = false;
@@ -337,46 +332,42 @@ int gmpnp_sensitivity_open(gmpnp_solver* s, int32_t n, const int32_t* param, int
     const SternTab st = stern_tab(s, Z->status.p);
     KinTab kt{};
     if (kin) kt = kinetics_tab(s, Z->status.p);
-    SensTab t_ = sens_tab(s, sens_levels(s), Z->S.p, 0, 0);
+    SensTab t_ = sens_tab(s, sens_levels(s), Z->S.p, Z->rec.row(0), 0);
     t_.t = 0.0; t_.h = 1.0; t_.init = 1;
     hipLaunchKernelGGL((k_sens_record<1, 7>), dim3(1), dim3(kVecBlock), 0, s->stream, s->c, kt, st, kin, t_);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
-  Z->open = true;
+  Z->rec.open = true;
   return GMPNP_OK;
 }
 
 int gmpnp_sensitivity_step(gmpnp_solver* s, double t, double h) {
   if (!s) return fail(GMPNP_ERR_INVALID, "sensitivities: NULL argument");
   if (const char* why = sens_refusal(s)) return fail(GMPNP_ERR_INVALID, std::string("sensitivities: ") + why);
-  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNotOpen);
-  if (!electrode_trace_step_valid(t, h)) return fail(GMPNP_ERR_INVALID, "sensitivities: t finite, h finite and > 0");
+  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNouns.not_open());
+  if (!record_step_valid(t, h)) return fail(GMPNP_ERR_INVALID, "sensitivities: t finite, h finite and > 0");
   gmpnp_sensitizer* Z = s->sensitizer.get();
   const int nr = kinetics_on(s) ? s->kineticist->opt.n_reactions : 0;
   for (int k = 0; k < Z->n; ++k)
     if (!tangent_param_valid(Z->param[k], nr)) return fail(GMPNP_ERR_INVALID, "sensitivities: a kinetic parameter of the open buffer names a reaction the kinetics no longer hold");
-  if (Z->count >= Z->capacity) return fail(GMPNP_ERR_INVALID, "sensitivities: the buffer is full (read the records and open again with start = 2)");
+  if (Z->rec.full()) return Z->rec.refuse_full();
   HIP_TRY(hipSetDevice(s->opts.device_id));
-  int rc = sens_launch(s, t, h, Z->S.p, Z->count, 0); if (rc) return rc;
-  Z->count += 1;
+  int rc = sens_launch(s, t, h, Z->S.p, Z->rec.row(Z->rec.count), 0); if (rc) return rc;
+  Z->rec.count += 1;
   return GMPNP_OK;
 }
 
 int gmpnp_sensitivity_read(gmpnp_solver* s, int32_t first, int32_t n_steps, gmpnp_sensitivity_record_t* out) {
   if (!s || !out) return fail(GMPNP_ERR_INVALID, "sensitivities: NULL argument");
-  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNotOpen);
-  gmpnp_sensitizer* Z = s->sensitizer.get();
-  if (first < 0 || n_steps < 1 || (int64_t)first + n_steps > Z->count) return fail(GMPNP_ERR_INVALID, "sensitivities: the steps asked for have not been written");
+  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNouns.not_open());
   HIP_TRY(hipSetDevice(s->opts.device_id));
-  HIP_TRY(hipMemcpyAsync(out, Z->rec.p + (size_t)first * Z->n, (size_t)n_steps * Z->n * sizeof(gmpnp_sensitivity_record_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return GMPNP_OK;
+  return s->sensitizer->rec.read(first, n_steps, out, s->stream);
 }
 
 int gmpnp_sensitivity_columns(gmpnp_solver* s, int32_t which, double* out) {
   if (!s || !out) return fail(GMPNP_ERR_INVALID, "sensitivities: NULL argument");
-  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNotOpen);
+  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNouns.not_open());
   if (which != 0 && which != 1) return fail(GMPNP_ERR_INVALID, "sensitivities: which is 0 (S) or 1 (the right-hand sides of the last step)");
   gmpnp_sensitizer* Z = s->sensitizer.get();
   if (which == 1 && !Z->stepped) return fail(GMPNP_ERR_INVALID, "sensitivities: no step has been made since the buffer was opened");
@@ -400,7 +391,7 @@ int gmpnp_sensitivity_columns(gmpnp_solver* s, int32_t which, double* out) {
 
 int gmpnp_sensitivity_set_columns(gmpnp_solver* s, const double* in) {
   if (!s || !in) return fail(GMPNP_ERR_INVALID, "sensitivities: NULL argument");
-  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNotOpen);
+  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNouns.not_open());
   gmpnp_sensitizer* Z = s->sensitizer.get();
   HIP_TRY(hipSetDevice(s->opts.device_id));
   for (int k = 0; k < Z->n; ++k) { int rc = upload_vec(s, in + (size_t)k * s->ndof, Z->S.p + (size_t)k * s->ndof); if (rc) return rc; }
@@ -409,8 +400,8 @@ int gmpnp_sensitivity_set_columns(gmpnp_solver* s, const double* in) {
 
 int gmpnp_sensitivity_close(gmpnp_solver* s) {
   if (!s) return fail(GMPNP_ERR_INVALID, "sensitivities: NULL argument");
-  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNotOpen);
-  s->sensitizer->open = false;
+  if (!sensitivity_is_open(s)) return fail(GMPNP_ERR_INVALID, kSensNouns.not_open());
+  s->sensitizer->rec.close();
   return GMPNP_OK;
 }
 

@@ -1,21 +1,77 @@
 // Potential programmes on the device: gmpnp_set_electrode_potential and the electrode trace (include/gmpnp.h "potential programmes"),
-// rule in gmpnp_host_rules.h (electrode_record_combine).
+// rule in gmpnp_host_rules.h (electrode_record_combine).  Also the one home of what the trace and the wall profile (gmpnp_wall_profile.h)
+// share: the boundary sum of a record on the device, the refusals and the weights of the Stern nodes on the host.
 //
-//   k_electrode_record   one workgroup, fixed order, behind k_stern_residual (and k_kinetics_residual) at the current u.  Over the
-//                        nodes of the Stern boundary, ascending (the list of SternTab, which is the kinetics' list too):
-//                            D        the sum of k_stern_sum: bnd_dyn - bndF on the potential rows
-//                            I[r]     the sum of k_kinetics_sum: w_I rate_r straight from u (kinetics on)
-//                            means    sum_I w_I u_{I,f} and sum_I w_I
-//                        each lane adds its nodes n = lane, lane + 256, ... in the statements of those two kernels and block_sum adds
-//                        the lanes component by component, so D and I carry the bits gmpnp_stern_displacement and
-//                        gmpnp_kinetics_currents return.  Lane 0 applies electrode_record_combine to the accumulators the device
-//                        keeps (D_prev, Q, Q_D) and writes the record's slot: no host synchronisation, no copy, no floating-point
-//                        atomics.  The sums are picked out of the register array with constant indices (unrolled loops).
+//   boundary_record_sums    over entries of the Stern boundary's node list (the list of SternTab, which is the kinetics' list too), ascending:
+//                               v[0]        D: the sum of k_stern_sum, bnd_dyn - bndF on the potential rows
+//                               v[1 + r]    I[r]: the sum of k_kinetics_sum, w_I rate_r straight from u (kinetics on)
+//                               v[U0 + f]   sum_I w_I u_{I,f}
+//                               v[W0]       sum_I w_I
+//                           each lane adds its entries e0 + lane, e0 + lane + 256, ... in the statements of those two kernels; block_sum
+//                           then adds the lanes component by component, so D and I carry the bits gmpnp_stern_displacement and
+//                           gmpnp_kinetics_currents return, whichever kernel asks.  `pos` names the entries' positions in the node list
+//                           (nullptr: entry e is position e).
+//   boundary_record_means   the means of the potential and of the species over the summed weight, 0 beyond the species, and whether all
+//                           of them are finite.
+//   k_electrode_record      one workgroup, fixed order, behind k_stern_residual (and k_kinetics_residual) at the current u, over the whole
+//                           list.  Lane 0 applies electrode_record_combine to the accumulators the device keeps (D_prev, Q, Q_D) and
+//                           writes the record's slot: no host synchronisation, no copy, no floating-point atomics.
+// The sums are picked out of the register array with constant indices (unrolled loops): a dynamic index would put v[] into scratch.
 // The weights are the kinetics' own array while that option is on, otherwise the trace's copy (boundary_weights, gmpnp_kinetics.h).
 // Included at the end of gmpnp_api.hip.
 #pragma once
 
 namespace gmpnp {
+
+template <int NF>
+struct BoundarySums {
+  static constexpr int NS = NF - 1, R = GMPNP_MAX_SURFACE_REACTIONS, U0 = 1 + R, W0 = U0 + NF, K = W0 + 1;
+};
+
+template <int NF>
+__device__ __forceinline__ void boundary_record_sums(const Ctx& c, const SternTab& st, const KinTab& kt, const double* w, int kinetics, int e0, int e1,
+                                                     const int32_t* pos, double (&v)[BoundarySums<NF>::K]) {
+  using B = BoundarySums<NF>;
+  constexpr int NS = B::NS, R = B::R;
+#pragma unroll
+  for (int k = 0; k < B::K; ++k) v[k] = 0.0;
+  for (int e = e0 + (int)threadIdx.x; e < e1; e += kVecBlock) {
+    const int n = pos ? pos[e] : e;
+    const size_t row0 = (size_t)st.node[n] * NF;
+    v[0] += st.bnd_dyn[row0 + NS] - st.bndF[row0 + NS];
+    double uu[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) uu[j] = c.u[row0 + j];
+    const double wn = w[n];
+    if (kinetics) {
+      KinRate Rr[R];
+      kinetics_rates<NF>(kt, uu, Rr);
+#pragma unroll
+      for (int r = 0; r < R; ++r) v[1 + r] += wn * Rr[r].rate;
+    }
+#pragma unroll
+    for (int j = 0; j < NF; ++j) v[B::U0 + j] += wn * uu[j];
+    v[B::W0] += wn;
+  }
+}
+
+// lane 0, behind block_sum: the means and whether every one of them is finite
+struct BoundaryMeans { double p, u[GMPNP_MAX_SPECIES]; bool ok; };
+template <int NF>
+__device__ __forceinline__ BoundaryMeans boundary_record_means(const double (&v)[BoundarySums<NF>::K]) {
+  using B = BoundarySums<NF>;
+  constexpr int NS = B::NS;
+  const double ws = v[B::W0];
+  BoundaryMeans m;
+  m.p = v[B::U0 + NS] / ws;
+  m.ok = rule_finite(m.p);
+#pragma unroll
+  for (int j = 0; j < GMPNP_MAX_SPECIES; ++j) {
+    m.u[j] = j < NS ? v[B::U0 + (j < NS ? j : 0)] / ws : 0.0;
+    m.ok = m.ok && rule_finite(m.u[j]);
+  }
+  return m;
+}
 
 struct TraceTab {
   const double* w;                  // [n_nodes] w_I of the Stern nodes
@@ -27,28 +83,10 @@ struct TraceTab {
 
 template <int DIM, int NF>
 __global__ __launch_bounds__(kVecBlock) void k_electrode_record(const Ctx c, const SternTab st, const KinTab kt, const TraceTab tr) {
-  constexpr int NS = NF - 1, R = GMPNP_MAX_SURFACE_REACTIONS, U0 = 1 + R, W0 = U0 + NF, K = W0 + 1;
+  constexpr int R = GMPNP_MAX_SURFACE_REACTIONS, K = BoundarySums<NF>::K;
   __shared__ double lds[4 * K];
   double v[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = 0.0;
-  for (int n = threadIdx.x; n < st.n_nodes; n += kVecBlock) {
-    const size_t row0 = (size_t)st.node[n] * NF;
-    v[0] += st.bnd_dyn[row0 + NS] - st.bndF[row0 + NS];
-    double uu[NF];
-#pragma unroll
-    for (int j = 0; j < NF; ++j) uu[j] = c.u[row0 + j];
-    const double w = tr.w[n];
-    if (tr.kinetics) {
-      KinRate Rr[R];
-      kinetics_rates<NF>(kt, uu, Rr);
-#pragma unroll
-      for (int r = 0; r < R; ++r) v[1 + r] += w * Rr[r].rate;
-    }
-#pragma unroll
-    for (int j = 0; j < NF; ++j) v[U0 + j] += w * uu[j];
-    v[W0] += w;
-  }
+  boundary_record_sums<NF>(c, st, kt, tr.w, tr.kinetics, 0, st.n_nodes, nullptr, v);
   block_sum<K>(v, lds);
   if (threadIdx.x != 0) return;
   ElectrodeAccum a = *tr.acc;
@@ -56,20 +94,16 @@ __global__ __launch_bounds__(kVecBlock) void k_electrode_record(const Ctx c, con
   const double dD_dt = electrode_record_combine(a, tr.h, v[0], I);
   *tr.acc = a;
   gmpnp_electrode_record_t* o = tr.rec;
-  const double ws = v[W0];
   bool ok = rule_finite(tr.t) && rule_finite(tr.h) && rule_finite(tr.p_M) && rule_finite(v[0]) && rule_finite(dD_dt) && rule_finite(a.Q_D);
   o->t = tr.t; o->h = tr.h; o->p_M = tr.p_M;
-  const double pb = v[U0 + NS] / ws;
-  o->p_boundary = pb; ok = ok && rule_finite(pb);
   o->D = v[0]; o->dD_dt = dD_dt;
 #pragma unroll
   for (int r = 0; r < R; ++r) { o->I[r] = I[r]; o->Q[r] = a.Q[r]; ok = ok && rule_finite(I[r]) && rule_finite(a.Q[r]); }
   o->Q_D = a.Q_D;
+  const BoundaryMeans m = boundary_record_means<NF>(v);
+  o->p_boundary = m.p; ok = ok && m.ok;
 #pragma unroll
-  for (int j = 0; j < GMPNP_MAX_SPECIES; ++j) {
-    const double m = j < NS ? v[U0 + (j < NS ? j : 0)] / ws : 0.0;
-    o->u_boundary[j] = m; ok = ok && rule_finite(m);
-  }
+  for (int j = 0; j < GMPNP_MAX_SPECIES; ++j) o->u_boundary[j] = m.u[j];
   o->status = ok ? 0 : 1; o->pad_ = 0;
 }
 
@@ -77,27 +111,27 @@ __global__ __launch_bounds__(kVecBlock) void k_electrode_record(const Ctx c, con
 
 namespace {
 
-const char* trace_refusal(const gmpnp_solver* s) {
-  if (!stern_on(s)) return "electrode trace: the Stern boundary condition is off (gmpnp_set_stern)";
-  if (s->partitioned) return "electrode trace: partition handles and groups are not supported";
-  if (s->ml_coarse || s->ml_is_coarse) return "electrode trace: not with a multilevel coarse level attached";
-  if (galvanostat_on(s)) return "electrode trace: the galvanostat is on (gmpnp_set_galvanostat): the potential is its unknown";
-  return nullptr;
+// refuses a handle that keeps no records of its Stern boundary (the trace, the wall profile)
+int boundary_record_refuse(const gmpnp_solver* s, const RecordNouns& w) {
+  const char* why = !stern_on(s) ? "the Stern boundary condition is off (gmpnp_set_stern)"
+                    : s->partitioned ? "partition handles and groups are not supported"
+                    : (s->ml_coarse || s->ml_is_coarse) ? "not with a multilevel coarse level attached"
+                    : galvanostat_on(s) ? "the galvanostat is on (gmpnp_set_galvanostat): the potential is its unknown" : nullptr;
+  return why ? fail(GMPNP_ERR_INVALID, w.say(why)) : GMPNP_OK;
 }
 
-// w_I of the Stern nodes in ascending internal order: the kinetics' weights, for a handle whose kinetics are off
-int trace_build_weights(gmpnp_solver* s, gmpnp_tracer* T) {
-  std::vector<double> wv, w;
+// w_I of the Stern nodes in ascending internal order (the kinetics' weights, for a handle whose kinetics are off) and, with `z`, their
+// third coordinates
+void stern_node_weights(const gmpnp_solver* s, std::vector<double>& w, std::vector<double>* z) {
+  std::vector<double> wv;
   std::vector<uint8_t> on;
   boundary_weights(s, wv, on);
-  for (int I = 0; I < s->t.nv; ++I) if (on[I]) w.push_back(wv[I]);
-  if ((int)w.size() != s->sterner->n_nodes) return fail(GMPNP_ERR_INVALID, "electrode trace: the Stern boundary's node list does not match its weights");
-  HIP_TRY(T->w.upload(w));
-  return GMPNP_OK;
+  for (int I = 0; I < s->t.nv; ++I)
+    if (on[I]) { w.push_back(wv[I]); if (z) z->push_back(s->t.coords[(size_t)I * 3 + 2]); }
 }
 
-// the launches of one append into slot `slot` with the accumulators acc[which]
-int trace_launch(gmpnp_solver* s, double t, double h, int slot, int which) {
+// the launches of one append into the row `rec` with the accumulators acc[which]
+int trace_launch(gmpnp_solver* s, double t, double h, gmpnp_electrode_record_t* rec, int which) {
   gmpnp_tracer* T = s->tracer.get();
   int rc = stern_launch_residual(s, T->status.p); if (rc) return rc;   // (the trace's own word: the solver's stays what it was)
   const bool kin = kinetics_on(s);
@@ -106,20 +140,19 @@ int trace_launch(gmpnp_solver* s, double t, double h, int slot, int which) {
   const KinTab kt = kin ? kinetics_tab(s, T->status.p) : KinTab{};
   TraceTab tr{};
   tr.w = kin ? s->kineticist->w.p : T->w.p;
-  tr.rec = T->rec.p + slot; tr.acc = T->acc.p + which;
+  tr.rec = rec; tr.acc = T->acc.p + which;
   tr.t = t; tr.h = h; tr.p_M = s->sterner->opt.p_electrode; tr.kinetics = kin ? 1 : 0;
   GMPNP_DISPATCH(s, hipLaunchKernelGGL((k_electrode_record<DIM, NF>), dim3(1), dim3(kVecBlock), 0, s->stream, s->c, st, kt, tr));
   HIP_TRY(hipGetLastError());
   return GMPNP_OK;
 }
 
-bool trace_is_open(const gmpnp_solver* s) { return s->tracer && s->tracer->open; }
+bool trace_is_open(const gmpnp_solver* s) { return s->tracer && s->tracer->rec.open; }
 
-// gmpnp_time_kernel 29: the slot behind the buffer and the second set of accumulators, so the trace stays what it was
+// gmpnp_time_kernel 29: the row behind the buffer and the second set of accumulators, so the trace stays what it was
 int trace_time_append(gmpnp_solver* s) {
-  const char* why = trace_refusal(s);
-  if (why) return fail(GMPNP_ERR_INVALID, why);
-  return trace_launch(s, 0.0, 1.0, s->tracer->capacity, 1);
+  if (int rc = boundary_record_refuse(s, kTraceNouns)) return rc;
+  return trace_launch(s, 0.0, 1.0, s->tracer->rec.hook_row(), 1);
 }
 
 }  // namespace
@@ -145,64 +178,55 @@ int gmpnp_set_electrode_potential(gmpnp_solver* s, double p) {
 
 int gmpnp_electrode_trace_open(gmpnp_solver* s, int32_t capacity) {
   if (!s) return fail(GMPNP_ERR_INVALID, "electrode trace: NULL argument");
-  const char* why = trace_refusal(s);
-  if (why) return fail(GMPNP_ERR_INVALID, why);
+  if (int rc = boundary_record_refuse(s, kTraceNouns)) return rc;
   if (capacity < 1) return fail(GMPNP_ERR_INVALID, "electrode trace: capacity must be at least 1");
   HIP_TRY(hipSetDevice(s->opts.device_id));
   if (!s->tracer) {
     std::unique_ptr<gmpnp_tracer> T(new gmpnp_tracer);
-    int rc = trace_build_weights(s, T.get()); if (rc) return rc;
+    std::vector<double> w;
+    stern_node_weights(s, w, nullptr);
+    if ((int)w.size() != s->sterner->n_nodes) return fail(GMPNP_ERR_INVALID, "electrode trace: the Stern boundary's node list does not match its weights");
+    HIP_TRY(T->w.upload(w));
     HIP_TRY(T->acc.alloc(2)); HIP_TRY(T->status.alloc(1));
     s->tracer = std::move(T);
   }
   gmpnp_tracer* T = s->tracer.get();
-  T->open = false;
-  if (T->capacity != capacity) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    T->capacity = 0;   // (alloc frees the old buffer first: an allocation that fails leaves no capacity a later open could take for a buffer)
-    HIP_TRY(T->rec.alloc((size_t)capacity + 1));
-    T->capacity = capacity;
-  }
-  T->count = 0;
+  T->rec.close();
+  int rc = T->rec.reserve(capacity, 1, s->stream); if (rc) return rc;
   // D_prev = D at the current u; Q = Q_D = 0
-  int rc = stern_launch_residual(s, T->status.p); if (rc) return rc;
+  rc = stern_launch_residual(s, T->status.p); if (rc) return rc;
   rc = stern_launch_sum(s, nullptr); if (rc) return rc;
   HIP_TRY(hipMemsetAsync(T->acc.p, 0, 2 * sizeof(ElectrodeAccum), s->stream));
   HIP_TRY(hipMemcpyAsync(&T->acc.p[0].D_prev, s->sterner->sum.p, sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  T->open = true;
+  T->rec.open = true;
   return GMPNP_OK;
 }
 
 int gmpnp_electrode_trace_append(gmpnp_solver* s, double t, double h) {
   if (!s) return fail(GMPNP_ERR_INVALID, "electrode trace: NULL argument");
-  const char* why = trace_refusal(s);
-  if (why) return fail(GMPNP_ERR_INVALID, why);
-  if (!trace_is_open(s)) return fail(GMPNP_ERR_INVALID, "electrode trace: no trace is open (gmpnp_electrode_trace_open)");
-  if (!electrode_trace_step_valid(t, h)) return fail(GMPNP_ERR_INVALID, "electrode trace: t finite, h finite and > 0");
+  if (int rc = boundary_record_refuse(s, kTraceNouns)) return rc;
+  if (!trace_is_open(s)) return fail(GMPNP_ERR_INVALID, kTraceNouns.not_open());
+  if (!record_step_valid(t, h)) return fail(GMPNP_ERR_INVALID, "electrode trace: t finite, h finite and > 0");
   gmpnp_tracer* T = s->tracer.get();
-  if (T->count >= T->capacity) return fail(GMPNP_ERR_INVALID, "electrode trace: the buffer is full (read the records and open the trace again)");
+  if (T->rec.full()) return T->rec.refuse_full();
   HIP_TRY(hipSetDevice(s->opts.device_id));
-  int rc = trace_launch(s, t, h, T->count, 0); if (rc) return rc;
-  T->count += 1;
+  int rc = trace_launch(s, t, h, T->rec.row(T->rec.count), 0); if (rc) return rc;
+  T->rec.count += 1;
   return GMPNP_OK;
 }
 
 int gmpnp_electrode_trace_read(gmpnp_solver* s, int32_t first, int32_t n, gmpnp_electrode_record_t* out) {
   if (!s || !out) return fail(GMPNP_ERR_INVALID, "electrode trace: NULL argument");
-  if (!trace_is_open(s)) return fail(GMPNP_ERR_INVALID, "electrode trace: no trace is open (gmpnp_electrode_trace_open)");
-  gmpnp_tracer* T = s->tracer.get();
-  if (first < 0 || n < 1 || (int64_t)first + n > T->count) return fail(GMPNP_ERR_INVALID, "electrode trace: the records asked for have not been written");
+  if (!trace_is_open(s)) return fail(GMPNP_ERR_INVALID, kTraceNouns.not_open());
   HIP_TRY(hipSetDevice(s->opts.device_id));
-  HIP_TRY(hipMemcpyAsync(out, T->rec.p + first, (size_t)n * sizeof(gmpnp_electrode_record_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return GMPNP_OK;
+  return s->tracer->rec.read(first, n, out, s->stream);
 }
 
 int gmpnp_electrode_trace_close(gmpnp_solver* s) {
   if (!s) return fail(GMPNP_ERR_INVALID, "electrode trace: NULL argument");
-  if (!trace_is_open(s)) return fail(GMPNP_ERR_INVALID, "electrode trace: no trace is open (gmpnp_electrode_trace_open)");
-  s->tracer->open = false;
+  if (!trace_is_open(s)) return fail(GMPNP_ERR_INVALID, kTraceNouns.not_open());
+  s->tracer->rec.close();
   return GMPNP_OK;
 }
 

@@ -550,12 +550,39 @@ def programme_keywords(a):
 
 
 # ---- the operations of a device handle and the outputs of the 1D driver ------------------------------------------------------------------
+class RecordStream:
+    """One device buffer of per-step records behind ``DeviceProgrammeOps``: ``calls`` = the handle's bound (open, append, read, close),
+    the list its chunks go to, the array that stands for no record, the arguments in front of the capacity at the first open and at an
+    open behind a drained buffer, and ``carry``: the fields whose sums start at 0 with every open, each with the field it sums.  Behind
+    a drained buffer the host goes on with the device's own statement, sum <- sum + h * rate (``electrode_record_combine``,
+    ``wall_profile_charge``: product and sum rounded on their own, one record after the other), from the last sum of the chunk before,
+    so the records are those of a buffer that was never drained, bit for bit.  (The chunk's sums added to the carried one as a whole
+    round differently from its second record on.)"""
+
+    def __init__(self, calls, chunks, empty, args=(), reopen_args=None, carry=None):
+        self.open, self.append, self.read, self.close = calls
+        self.chunks, self.empty, self.carry, self.base = chunks, empty, carry or {}, {}
+        self.args, self.reopen_args = args, args if reopen_args is None else reopen_args
+
+    def drain(self, count):
+        rec = self.read(0, count)
+        for f, rate in self.carry.items():
+            if f in self.base:
+                h = rec["h"].reshape(rec["h"].shape + (1,) * (rec[rate].ndim - rec["h"].ndim))
+                rec[f] = np.add.accumulate(np.concatenate([self.base[f][None], h * rec[rate]]))[1:]   # (accumulate: strictly in order)
+            self.base[f] = rec[f][-1].copy()
+        self.chunks.append(rec)
+
+    def records(self):
+        return np.concatenate(self.chunks) if self.chunks else self.empty
+
+
 class DeviceProgrammeOps:
     """What ``run_programme`` asks of a system, over a driver run (``EDLRun``: its ``sys``, ``stern``, ``kinetics``, ``budget``) and its
     device handle.  Per accepted step one ``electrode_trace_append`` (no synchronisation, no copy) and, with ``budget``, one row of the
     budget log; the trace is read when its ``capacity`` records are written and at the end (``drain``), so the host keeps the records
-    and the states at the breakpoints, not a state per step.  The accumulated charges go on across a drained buffer: the host adds
-    what the records before held."""
+    and the states at the breakpoints, not a state per step.  The accumulated charges go on across a drained buffer: the host continues
+    the device's sums from what the records before held (``RecordStream``)."""
 
     def __init__(self, run, solver_parameters, inv_dt_of_h, tol=(1e-2, 1e-4), capacity=4096, sensitivities=None, sensitivity_start="zero",
                  after_accept=None, profile_edges=None, cycle_tol=(1e-2, 1e-4)):
@@ -568,32 +595,37 @@ class DeviceProgrammeOps:
         self.cycle_tol, self.cycle_is_open = (float(cycle_tol[0]), float(cycle_tol[1])), False
         self.run, self.sys, self.dev = run, run.sys, run.sys.dev
         self.solver_parameters, self.inv_dt_of_h, self.tol, self.capacity = solver_parameters, inv_dt_of_h, tol, int(capacity)
-        self.chunks, self.segments, self.states, self.count = [], [], [], 0
+        self.chunks, self.profile_chunks, self.sensitivity_chunks, self.segments, self.states, self.count = [], [], [], [], [], 0
         self.after_accept = after_accept
         self.profile_edges = None if profile_edges is None else [float(e) for e in profile_edges]
-        self.profile_chunks, self.profile_base_Q = [], None
-        self.base_Q, self.base_Q_D = np.zeros(MAX_SURFACE_REACTIONS), 0.0
         self.newton_iterations, self.residuals = 0, []   # residuals: the last Newton residual of every accepted step
         # the transient sensitivities (section 5p): parameter codes of the tangent; "steady" takes the columns of the tangent call the
         # caller has just made at inv_dt = 0, "zero" starts from S = 0.  The device keeps dQ and dQ_D across a drained buffer.
         self.sensitivities = None if sensitivities is None else [int(q) for q in sensitivities]
-        self.sensitivity_chunks = []
         if sensitivity_start not in ("zero", "steady"):
             raise ValueError("programme: sensitivity_start is 'steady' or 'zero'")
-        self.dev.electrode_trace_open(self.capacity)   # (launches the Stern term only: a steady tangent stays valid for the open below)
-        self.D_first = self.dev.stern_displacement()   # the D_prev the trace starts from (the bits the open call took)
-        if self.sensitivities is not None:
+        dev = self.dev
+        self.trace = RecordStream((dev.electrode_trace_open, dev.electrode_trace_append, dev.electrode_trace_read, dev.electrode_trace_close),
+                                  self.chunks, np.zeros(0, backend.ELECTRODE_RECORD_DTYPE), carry={"Q": "I", "Q_D": "dD_dt"})
+        self.sensitivity = None if sensitivities is None else RecordStream(
+            (dev.sensitivity_open, dev.sensitivity_step, dev.sensitivity_read, dev.sensitivity_close), self.sensitivity_chunks,
+            np.zeros((0, len(self.sensitivities)), backend.SENSITIVITY_RECORD_DTYPE), (self.sensitivities, sensitivity_start), (self.sensitivities, "continue"))
+        self.profile = None if profile_edges is None else RecordStream(   # (the bins' charges go on across a drained buffer, as the trace's do)
+            (dev.wall_profile_open, dev.wall_profile_append, dev.wall_profile_read, dev.wall_profile_close), self.profile_chunks,
+            np.zeros((0, len(self.profile_edges) - 1), backend.WALL_PROFILE_RECORD_DTYPE), (self.profile_edges,), carry={"Q": "I"})
+        self.trace.open(self.capacity)   # (launches the Stern term only: a steady tangent stays valid for the sensitivities' open below)
+        self.D_first = dev.stern_displacement()   # the D_prev the trace starts from (the bits the open call took)
+        self.streams = [self.trace]
+        for st in filter(None, (self.sensitivity, self.profile)):
             try:
-                self.dev.sensitivity_open(self.sensitivities, sensitivity_start, self.capacity)
+                st.open(*st.args, self.capacity)
             except BaseException:
-                self.dev.electrode_trace_close()
+                for done in self.streams:
+                    done.close()
                 raise
-        if self.profile_edges is not None:
-            try:
-                self.dev.wall_profile_open(self.profile_edges, self.capacity)
-            except BaseException:
-                self.dev.electrode_trace_close()
-                raise
+            self.streams.append(st)
+        # appended to in this order (accepted steps only: a rejected attempt never touches S)
+        self.streams.sort(key=(self.trace, self.profile, self.sensitivity).index)
 
     def set_potential(self, p):
         run = self.run
@@ -634,11 +666,8 @@ class DeviceProgrammeOps:
     def record(self, t, h, seg, p):
         if self.run.budget is not None:   # while u_n is the previous state and inv_dt the step's
             self.run.budget.take(self.sys)
-        self.dev.electrode_trace_append(t, h)
-        if self.profile_edges is not None:
-            self.dev.wall_profile_append(t, h)
-        if self.sensitivities is not None:   # accepted steps only: a rejected attempt never touches S
-            self.dev.sensitivity_step(t, h)
+        for st in self.streams:
+            st.append(t, h)
         self.residuals.append(float(self.sys.last_stats["residuals"][-1]))
         self.segments.append(int(seg))
         self.count += 1
@@ -658,26 +687,12 @@ class DeviceProgrammeOps:
 
     def drain(self, reopen=False):
         if self.count:
-            rec = self.dev.electrode_trace_read(0, self.count)
-            rec["Q"] = rec["Q"] + self.base_Q
-            rec["Q_D"] = rec["Q_D"] + self.base_Q_D
-            self.base_Q, self.base_Q_D = rec["Q"][-1].copy(), float(rec["Q_D"][-1])
-            self.chunks.append(rec)
-            if self.sensitivities is not None:
-                self.sensitivity_chunks.append(self.dev.sensitivity_read(0, self.count))
-            if self.profile_edges is not None:   # the charges of the bins go on across a drained buffer, as the trace's do
-                prof = self.dev.wall_profile_read(0, self.count)
-                if self.profile_base_Q is not None:
-                    prof["Q"] = prof["Q"] + self.profile_base_Q
-                self.profile_base_Q = prof["Q"][-1].copy()
-                self.profile_chunks.append(prof)
+            for st in self.streams:
+                st.drain(self.count)
             self.count = 0
         if reopen:
-            self.dev.electrode_trace_open(self.capacity)
-            if self.profile_edges is not None:
-                self.dev.wall_profile_open(self.profile_edges, self.capacity)
-            if self.sensitivities is not None:
-                self.dev.sensitivity_open(self.sensitivities, "continue", self.capacity)
+            for st in self.streams:
+                st.open(*st.reopen_args, self.capacity)
 
     # ---- the accelerated cycle map (``periodic.run_periodic``; section 5r) ----
     def cycle_open(self, depth):
@@ -707,8 +722,8 @@ class DeviceProgrammeOps:
         finally:
             self.dev.electrode_trace_open(self.capacity)
             self.D_first = self.dev.stern_displacement()
-            self.chunks, self.segments, self.states, self.residuals = [], [], [], []
-            self.base_Q, self.base_Q_D = np.zeros(MAX_SURFACE_REACTIONS), 0.0
+            self.chunks.clear()
+            self.trace.base, self.segments, self.states, self.residuals = {}, [], [], []
 
     def cycle_mix(self, gamma, tau):
         backend = self.backend
@@ -734,9 +749,7 @@ class DeviceProgrammeOps:
         the run is left at the potential of the attempt that failed (``run.stern`` / ``run.kinetics`` and the handle agree) with no
         trace open.  The records written so far stay in ``chunks`` / on the device unread."""
         backend = self.backend
-        calls = (self.sys.time_reject, self.dev.electrode_trace_close) + ((self.dev.sensitivity_close,) if self.sensitivities is not None else ())
-        calls = calls + ((self.dev.wall_profile_close,) if self.profile_edges is not None else ())
-        for call in calls:
+        for call in [self.sys.time_reject] + [st.close for st in self.streams]:
             try:
                 call()
             except backend.GmpnpError as e:
@@ -745,31 +758,26 @@ class DeviceProgrammeOps:
 
     def records(self):
         """Every record so far, in order (drains the trace and closes it)."""
-        from .backend import ELECTRODE_RECORD_DTYPE
         self.drain()
-        self.dev.electrode_trace_close()
-        return np.concatenate(self.chunks) if self.chunks else np.zeros(0, dtype=ELECTRODE_RECORD_DTYPE)
+        self.trace.close()
+        return self.trace.records()
 
     def profile_records(self):
         """Every record of the wall profile so far, (steps, bins), in order (after ``records``, which drained both buffers; closes the
         profile)."""
-        from .backend import WALL_PROFILE_RECORD_DTYPE
-        if self.profile_edges is None:
+        if not self.profile:
             raise ValueError("programme: the run carries no wall profile")
         self.drain()
-        self.dev.wall_profile_close()
-        n = len(self.profile_edges) - 1
-        return np.concatenate(self.profile_chunks) if self.profile_chunks else np.zeros((0, n), dtype=WALL_PROFILE_RECORD_DTYPE)
+        self.profile.close()
+        return self.profile.records()
 
     def sensitivity_records(self):
         """Every sensitivity record so far, (steps, columns), in order (drains both buffers; the sensitivities stay open, with S on the
         device, until ``sensitivity_close``)."""
-        from .backend import SENSITIVITY_RECORD_DTYPE
-        if self.sensitivities is None:
+        if not self.sensitivity:
             raise ValueError("programme: the run carries no sensitivities")
         self.drain()
-        n = len(self.sensitivities)
-        return np.concatenate(self.sensitivity_chunks) if self.sensitivity_chunks else np.zeros((0, n), dtype=SENSITIVITY_RECORD_DTYPE)
+        return self.sensitivity.records()
 
 
 OUTPUT_KEYS = ("time_s", "electrode_voltage", "potential_OHP", "surface_charge", "i_CO", "i_H2", "i_charging", "i_total", "charge_CO",

@@ -36,6 +36,7 @@ BITS = {1: "1 - sum_j a_j u_j <= 0 at a quadrature point; ", 2: "singular diagon
 #   x0 n  (event a scale)*n                                           0 ready(a, scale)  1 left(a)
 #   options dim  <the 16 int32 fields of gmpnp_options_t in order>  band_lu_max_gb
 #   refine round finite rn best tol                                   band_refine_again: 1 = another refinement round of a band LU solve
+#   records first n count capacity t h                                record_range_valid, record_can_append, record_step_valid, record_rows
 DRIVER = r"""
 #include <cstdio>
 #include <iostream>
@@ -162,6 +163,11 @@ int main() {
     } else if (cmd == "refine") {
       const int round = (int)num(); const bool finite = num() != 0.0; const double rn = num(), best = num(), tol = num();
       printf("%d\n", band_refine_again(round, finite, rn, best, tol) ? 1 : 0);
+    } else if (cmd == "records") {
+      const int32_t first = (int32_t)num(), n = (int32_t)num(); const int count = (int)num(), capacity = (int)num();
+      const double t = num(), h = num();
+      printf("%d %d %d %zu\n", record_range_valid(first, n, count) ? 1 : 0, record_can_append(count, capacity) ? 1 : 0,
+             record_step_valid(t, h) ? 1 : 0, record_rows(capacity));
     }
   }
   return 0;
@@ -393,6 +399,28 @@ def test_level_tables_refusals(rules):
     ]
     for (_, want), line in zip(asks, rules([a for a, _ in asks])):
         assert line == "ERR " + want, line
+
+
+# ---- record streams: what RecordStream (gmpnp_api.hip) asks before it reads, appends or allocates -------------------------------------
+def records_want(first, n, count, capacity, t, h):
+    """The Python restatement: Python's integers do not wrap, so first + n is the sum the rule forms in 64 bits."""
+    finite = not (np.isnan(t) or np.isinf(t) or np.isnan(h) or np.isinf(h))
+    return "%d %d %d %d" % (first >= 0 and n >= 1 and first + n <= count, count < capacity, finite and h > 0.0, capacity + 1)
+
+
+def test_record_stream_rules(rules):
+    big = 2 ** 31 - 1
+    cases = [(first, n, count, 4, 1.0, 0.5) for count in (0, 3) for first in (-1, 0, 1, 2, 3) for n in (-1, 0, 1, 2, 3, 4)]
+    cases += [(0, 3, 3, 4, 1.0, 0.5), (1, 2, 3, 4, 1.0, 0.5), (1, 3, 3, 4, 1.0, 0.5), (0, 4, 3, 4, 1.0, 0.5)]     # first + n == count, count + 1
+    cases += [(big, big, 3, 4, 1.0, 0.5), (big, big, big, big, 1.0, 0.5), (big, 1, big, big, 1.0, 0.5)]        # a 32-bit sum would wrap to -2
+    cases += [(0, 1, count, 4, 1.0, 0.5) for count in (0, 3, 4, 5)]                                            # capacity - 1, capacity, beyond
+    cases += [(0, 1, 1, 4, t, h) for t, h in ((np.nan, 1.0), (np.inf, 1.0), (-np.inf, 1.0), (1.0, np.nan), (1.0, np.inf), (1.0, -np.inf),
+                                               (1.0, 0.0), (1.0, -0.0), (1.0, -1.0), (0.0, 1e-300), (-3.0, 1.0))]
+    got = rules(["records %d %d %d %d %r %r" % c for c in cases])
+    for c, line in zip(cases, got):
+        assert line == records_want(*c), (c, line)
+    assert records_want(big, big, 3, 4, 1.0, 0.5).startswith("0 ") and records_want(0, 1, 3, 4, 1.0, 0.5) == "1 1 1 5"
+    assert records_want(0, 1, 4, 4, 1.0, 0.5).split()[1] == "0" and records_want(0, 1, 1, 4, 1.0, 0.0).split()[2] == "0"
 
 
 def test_header_reaches_no_hip_include():
