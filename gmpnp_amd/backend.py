@@ -27,7 +27,7 @@ EXPORTS = [
     "gmpnp_version", "gmpnp_build_id", "gmpnp_last_error", "gmpnp_create", "gmpnp_destroy", "gmpnp_set_model",
     "gmpnp_set_dirichlet", "gmpnp_set_state", "gmpnp_get_state", "gmpnp_assign_previous",
     "gmpnp_newton_solve", "gmpnp_n_fields", "gmpnp_n_dofs", "gmpnp_n_blocks", "gmpnp_jacobian_nnz",
-    "gmpnp_n_aggregates", "gmpnp_krylov_launches_per_iteration", "gmpnp_assemble", "gmpnp_get_jacobian_csr", "gmpnp_spmv", "gmpnp_linear_solve",
+    "gmpnp_n_aggregates", "gmpnp_krylov_launches_per_iteration", "gmpnp_assemble", "gmpnp_get_jacobian_csr", "gmpnp_spmv", "gmpnp_spmv_scaled", "gmpnp_linear_solve",
     "gmpnp_time_kernel", "gmpnp_spmv_profile", "gmpnp_event_overhead",
     "gmpnp_set_supg",
     "gmpnp_create_partition", "gmpnp_comm_unique_id", "gmpnp_comm_create", "gmpnp_comm_selftest", "gmpnp_comm_destroy", "gmpnp_group_create", "gmpnp_group_create_hosted",
@@ -276,6 +276,7 @@ def load_library(path: str = None):
     lib.gmpnp_assemble.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     lib.gmpnp_get_jacobian_csr.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_double)]
     lib.gmpnp_spmv.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
+    lib.gmpnp_spmv_scaled.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
     lib.gmpnp_linear_solve.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), c_int32, c_double, c_double,
                                        c_int32, POINTER(CLinearStats)]
     lib.gmpnp_set_supg.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
@@ -639,6 +640,13 @@ class DeviceSolver:
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.empty(self.ndof)
         self._check(self.lib.gmpnp_spmv(self._h, _dptr(x), _dptr(y)))
+        return y
+
+    def spmv_scaled(self, x):
+        """As x with the column-scaled Jacobian of the last preconditioner set-up, read as the Krylov kernels read it."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.empty(self.ndof)
+        self._check(self.lib.gmpnp_spmv_scaled(self._h, _dptr(x), _dptr(y)))
         return y
 
     def linear_solve(self, b, linear_solver=LINEAR_TWOLEVEL, rtol=1e-10, atol=0.0, max_iterations=10000):

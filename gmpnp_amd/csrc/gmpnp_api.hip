@@ -1679,6 +1679,8 @@ static int create_impl(const gmpnp_mesh_t* mesh, const gmpnp_model_t* model, con
   HIP_TRY(s->n2e_ptr.upload(t.n2e_ptr)); HIP_TRY(s->n2e.upload(t.n2e));
   HIP_TRY(s->rowptr.upload(t.rowptr)); HIP_TRY(s->cols.upload(t.cols));
   HIP_TRY(s->cptr.upload(t.cptr)); HIP_TRY(s->contrib.upload(t.contrib));
+  // vals_s keeps its columns in pairs (value_pair_offset): a pair is 16-byte aligned because every slice starts at an even value
+  for (int q = 0; q <= t.nslices; ++q) if (t.slice_off[q] & 1) return fail(GMPNP_ERR_INVALID, "internal: a slice of the value arrays starts at an odd offset");
   { const size_t pad = (size_t)kRowPad * nf * kWave;  // the Krylov kernels preload unconditionally past short slices
     HIP_TRY(s->vals.alloc((size_t)t.slice_off[t.nslices], true, pad)); HIP_TRY(s->vals_s.alloc((size_t)t.slice_off[t.nslices], true, pad)); }
   HIP_TRY(s->slice_off.upload(t.slice_off)); HIP_TRY(s->slice_colbase.upload(t.slice_colbase));
@@ -2056,6 +2058,17 @@ int gmpnp_spmv(gmpnp_solver* s, const double* x, double* y) {
   return download_vec(s, s->kt.p, y);
 }
 
+int gmpnp_spmv_scaled(gmpnp_solver* s, const double* x, double* y) {
+  if (!s || !x || !y) return fail(GMPNP_ERR_INVALID, "NULL argument");
+  if (!s->jacobian_valid || !s->precond_valid) return fail(GMPNP_ERR_INVALID, "no preconditioner set up for the current Jacobian (a linear or Newton solve sets it up)");
+  HIP_TRY(hipSetDevice(s->opts.device_id));
+  int rc = upload_vec(s, x, s->kx.p); if (rc) return rc;
+  GMPNP_DISPATCH(s, hipLaunchKernelGGL((k_spmv_scaled<NF>), dim3(s->t.own_ntiles), dim3(kKrylovThreads), 0, s->stream, s->c,
+                                       (const double*)s->kx.p, s->kt.p));
+  HIP_TRY(hipGetLastError());
+  return download_vec(s, s->kt.p, y);
+}
+
 int gmpnp_linear_solve(gmpnp_solver* s, const double* b, double* x, int32_t mode, double rtol, double atol,
                        int32_t maxit, gmpnp_linear_stats_t* stats) {
   if (!s || !b || !x) return fail(GMPNP_ERR_INVALID, "NULL argument");
@@ -2269,7 +2282,7 @@ int gmpnp_debug_read(gmpnp_solver* s, int which, double* out, int64_t n) {
   const double* src = nullptr; int64_t cap = 0;
   switch (which) {
     case 0: src = s->krhat.p; cap = s->ndof; break;
-    case 1: src = s->vals_s.p; cap = (int64_t)s->vals_s.n; break;
+    case 1: src = s->vals_s.p; cap = (int64_t)s->vals_s.n; break;   // raw: inside a block position the pair layout of value_pair_offset, not [j][lane]
     case 2: src = s->Dinv.p; cap = (int64_t)s->Dinv.n; break;
     case 3: src = s->c.Aci; cap = (int64_t)s->Aci.n; break;
     case 4: src = s->c.vals; cap = (int64_t)s->vals.n; break;

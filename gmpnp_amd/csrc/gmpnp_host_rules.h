@@ -998,4 +998,18 @@ inline CycleVerdict cycle_verdict(const double* err, int n, bool nonfinite, cons
   return cycle_continue;
 }
 
+// ---- value layout of the column-scaled matrix (vals_s; kernels: TileRows, scale_columns_body, coarse_rows_body) ----------------------
+// One block position of a slice holds nf x 64 doubles: entry (j, lane) is column j of the block row that lane `lane` of the slice's
+// wave owns.  vals keeps them [j][lane] (value_plain_offset).  vals_s keeps the columns in PAIRS: [j / 2][lane][j & 1] for the nf / 2
+// pairs, then [lane] for the last column of an odd nf, so that a lane moves two neighbouring columns with one 16-byte request
+// (nf = 9: four of 16 bytes and one of 8 instead of nine of 8).  A position is nf x 64 doubles either way; position stride, slice
+// offsets and padding are those of vals, and both are even, so every pair is 16-byte aligned (asserted at create).  The writer
+// (scale_columns_body) and every reader of vals_s take their offsets from here and nowhere else.
+constexpr int kValueLanes = 64;
+GMPNP_RULE_HD constexpr int value_plain_offset(int /*nf*/, int j, int lane) { return j * kValueLanes + lane; }
+GMPNP_RULE_HD constexpr int value_pair_offset(int nf, int j, int lane) {
+  return (j | 1) < nf ? (j >> 1) * 2 * kValueLanes + 2 * lane + (j & 1)   // member j & 1 of pair j / 2
+                      : (nf - 1) * kValueLanes + lane;                    // the single last column of an odd nf
+}
+
 }  // namespace gmpnp

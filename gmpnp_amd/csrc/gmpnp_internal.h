@@ -41,6 +41,10 @@ constexpr int kSlicePad = 16;       // per-(slice,kpos) column-index record leng
 constexpr int kRowPreMax = GMPNP_ROW_PRELOAD_B > GMPNP_ROW_PRELOAD_A ? (GMPNP_ROW_PRELOAD_B > GMPNP_ROW_PRELOAD ? GMPNP_ROW_PRELOAD_B : GMPNP_ROW_PRELOAD)
                                                                      : (GMPNP_ROW_PRELOAD_A > GMPNP_ROW_PRELOAD ? GMPNP_ROW_PRELOAD_A : GMPNP_ROW_PRELOAD);
 constexpr int kRowPad = GMPNP_KRYLOV_WAVES * kRowPreMax;  // block positions of zero padding behind the last slice
+#ifndef GMPNP_VALUE_PAIRS
+#define GMPNP_VALUE_PAIRS 1  // vals_s keeps the columns of a block position in pairs (value_pair_offset, gmpnp_host_rules.h): 16-byte requests in the tile kernels; 0 = the layout of vals everywhere (A/B builds only)
+#endif
+constexpr bool kValuePairs = GMPNP_VALUE_PAIRS != 0;
 #ifndef GMPNP_NEWTON_CHAIN_DEFAULT
 #define GMPNP_NEWTON_CHAIN_DEFAULT 2  // Newton's launch chain between two solves: 0 serial, 1 Jacobian gather beside the convergence test, 2 also the folded launches (GMPNP_NEWTON_CHAIN in the environment overrides)
 #endif

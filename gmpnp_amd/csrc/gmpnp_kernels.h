@@ -13,6 +13,7 @@
 // Reference mathematics: 3D/MPNP_CO2ER_pore.py:505-769, 1D/MPNP_CO2ER_EDL.py:383-595.
 #pragma once
 #include "gmpnp_internal.h"
+#include "gmpnp_host_rules.h"   // value_pair_offset: where vals_s keeps entry (j, lane) of a block position
 
 namespace gmpnp {
 
@@ -255,6 +256,23 @@ __device__ __forceinline__ void block_inverse_body(const Ctx& c) {
 template <int NF>
 __global__ __launch_bounds__(64) void k_block_inverse(const Ctx c) { block_inverse_body<NF>(c); }
 
+// This lane's NF values of one block position of vals_s (`pos`: its first value): the pair layout of value_pair_offset, two
+// neighbouring columns per 16-byte request; with GMPNP_VALUE_PAIRS = 0 the layout of vals.
+template <int NF>
+__device__ __forceinline__ void fetch_scaled(const double* __restrict__ pos, int lane, double (&a)[NF]) {
+  if (kValuePairs) {
+#pragma unroll
+    for (int m = 0; m < NF / 2; ++m) {
+      const double2 v = *reinterpret_cast<const double2*>(pos + value_pair_offset(NF, 2 * m, lane));
+      a[2 * m] = v.x; a[2 * m + 1] = v.y;
+    }
+    if (NF & 1) a[NF - 1] = pos[value_pair_offset(NF, NF - 1, lane)];
+  } else {
+#pragma unroll
+    for (int j = 0; j < NF; ++j) a[j] = pos[value_plain_offset(NF, j, lane)];
+  }
+}
+
 template <int NF>
 __device__ __forceinline__ void coarse_rows_body(const Ctx& c) {
   constexpr int S = kWave / NF;
@@ -268,16 +286,16 @@ __device__ __forceinline__ void coarse_rows_body(const Ctx& c) {
 #pragma unroll
     for (int j = 0; j < NF; ++j) acc[q][j] = 0.0;
   const int cb = c.slice_colbase[s], mx = c.slice_colbase[s + 1] - cb;
-  const double* base = c.vals_s + c.slice_off[s] + lane;  // the coarse operator is built from the column-scaled matrix
+  const double* base = c.vals_s + c.slice_off[s];  // the coarse operator is built from the column-scaled matrix
   for (int kp = 0; kp < mx; ++kp) {
     const int slot = c.sell_aggslot[(size_t)(cb + kp) * kSlicePad + Iloc];
     if (slot == 255) continue;
+    double v[NF];
+    fetch_scaled<NF>(base + (size_t)kp * NF * kWave, lane, v);
 #pragma unroll
-    for (int j = 0; j < NF; ++j) {
-      const double v = base[(size_t)(kp * NF + j) * kWave];
+    for (int j = 0; j < NF; ++j)
 #pragma unroll
-      for (int q = 0; q < kMaxRowAggs; ++q) acc[q][j] += (q == slot) ? v : 0.0;
-    }
+      for (int q = 0; q < kMaxRowAggs; ++q) acc[q][j] += (q == slot) ? v[j] : 0.0;
   }
   double* o = c.AP + (size_t)(I * NF + i) * kMaxRowAggs * NF;
 #pragma unroll
@@ -643,14 +661,26 @@ __device__ __forceinline__ double ld_off(const double* __restrict__ base, unsign
 // Matrix part shared by the tile kernels: the wave's first PRE blocks are requested up front, x comes from LDS.
 // The preload is unconditional (vals / sell_lcol carry kRowPad block positions of zero padding behind the last
 // slice, positions past a short slice's end just read into the next slice) and masked afterwards.
-template <int NF, int PRE_ = GMPNP_ROW_PRELOAD>
+// PAIRED: `vals` is vals_s in its pair layout (fetch_scaled) — two neighbouring columns per 16-byte request, NF / 2 of them
+// and one of 8 bytes per block position instead of NF of 8; the products are formed in the order j = 0 .. NF - 1 either way.
+template <int NF, int PRE_ = GMPNP_ROW_PRELOAD, bool PAIRED = false>
 struct TileRows {
   static constexpr int PRE = PRE_;
   double av[PRE][NF];
   int lc[PRE];
   int Iloc, i, cb, mx, w, row;
   bool active;
-  const double* base;
+  const double* base;   // first value of the slice, + lane unless PAIRED
+
+  // this lane's NF values of block position kp
+  __device__ __forceinline__ void fetch(int kp, double (&a)[NF]) const {
+    if (PAIRED) {
+      fetch_scaled<NF>(base + (size_t)kp * NF * kWave, threadIdx.x & 63, a);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NF; ++j) a[j] = base[(size_t)(kp * NF + j) * kWave];
+    }
+  }
 
   __device__ inline void load(const Ctx& c, const double* __restrict__ vals, const TileRec& rec) {
     const int lane = threadIdx.x & 63;
@@ -658,7 +688,7 @@ struct TileRows {
     Iloc = lane / NF; i = lane - Iloc * NF;
     active = Iloc < rec.nn;
     row = active ? (rec.node0 + Iloc) * NF + i : 0;
-    cb = rec.colbase; mx = active ? rec.mx : 0; base = vals + rec.slice_off + lane;
+    cb = rec.colbase; mx = active ? rec.mx : 0; base = vals + rec.slice_off + (PAIRED ? 0 : lane);
     const int il = min(Iloc, kSlicePad - 1);
     // Positions past the slice's last block are clamped onto it: the request repeats a line another wave of this tile asks
     // for anyway instead of pulling a line of the NEXT slice through the fabric (every launch re-reads its bytes from the
@@ -672,9 +702,7 @@ struct TileRows {
     }
 #pragma unroll
     for (int u = 0; u < PRE; ++u) {
-      const int kp = min(w + u * kKrylovWaves, last);
-#pragma unroll
-      for (int j = 0; j < NF; ++j) av[u][j] = base[(size_t)(kp * NF + j) * kWave];
+      fetch(min(w + u * kKrylovWaves, last), av[u]);
     }
   }
 
@@ -690,9 +718,10 @@ struct TileRows {
     if (active) {
       for (int kp = w + PRE * kKrylovWaves; kp < mx; kp += kKrylovWaves) {  // rows with more than PRE*8 blocks
         const double* xv = xs + c.sell_lcol[(size_t)(cb + kp) * kSlicePad + Iloc] * NF;
-        const double* ap = base + (size_t)kp * NF * kWave;
+        double a[NF];
+        fetch(kp, a);
 #pragma unroll
-        for (int j = 0; j < NF; ++j) acc += ap[(size_t)j * kWave] * xv[j];
+        for (int j = 0; j < NF; ++j) acc += a[j] * xv[j];
       }
     }
     return acc;
@@ -1068,7 +1097,7 @@ __device__ __forceinline__ void bicg_a_body(const Ctx& c, const int k, const int
   TileCoarse<NF> tcs;
   tcs.load_index(c, tile);
   if (!FUSED) tcs.template load_values<false>(c);
-  TileRows<NF, (FUSED ? GMPNP_ROW_PRELOAD_A : GMPNP_ROW_PRELOAD)> rows;
+  TileRows<NF, (FUSED ? GMPNP_ROW_PRELOAD_A : GMPNP_ROW_PRELOAD), kValuePairs> rows;
   rows.load(c, c.vals_s, rec);
   const int nst = rec.ncols * NF;
   double st_s[kStagePre], st_t[kStagePre], st_p[kStagePre], st_v[kStagePre];
@@ -1246,7 +1275,7 @@ __device__ __forceinline__ void bicg_b_body(const Ctx& c, const int k, const int
   TileCoarse<NF> tcs;
   tcs.load_index(c, tile);
   if (!FUSED) tcs.template load_values<false>(c);
-  TileRows<NF, (FUSED ? GMPNP_ROW_PRELOAD_B : GMPNP_ROW_PRELOAD)> rows;
+  TileRows<NF, (FUSED ? GMPNP_ROW_PRELOAD_B : GMPNP_ROW_PRELOAD), kValuePairs> rows;
   rows.load(c, c.vals_s, rec);
   const int nst = rec.ncols * NF;
   double st_r[kStagePre], st_v[kStagePre];
@@ -1427,7 +1456,8 @@ __global__ __launch_bounds__(kKrylovThreads, 6) void k_half_b(const Ctx c, const
 }
 
 // Plain y = A x with the UNSCALED matrix (parity hook, partitioned driver); same tiling as the Krylov kernels.
-template <int NF, bool RES>
+// SCALED (parity hook of the layout, gmpnp_spmv_scaled): y = As x with vals_s, read the way the Krylov kernels read it.
+template <int NF, bool RES, bool SCALED = false>
 __device__ __forceinline__ void spmv_plain_body(const Ctx& c, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ out) {
   constexpr int NW = kKrylovWaves;
   __shared__ double red[kSlicesPerTile * NW][64];
@@ -1440,8 +1470,8 @@ __device__ __forceinline__ void spmv_plain_body(const Ctx& c, const double* __re
     const int cl = q / NF, f = q - cl * NF;
     xs[q] = x[(size_t)c.tile_cols[c0 + cl] * NF + f];
   }
-  TileRows<NF> rows;
-  rows.load(c, c.vals, rec);
+  TileRows<NF, GMPNP_ROW_PRELOAD, SCALED && kValuePairs> rows;
+  rows.load(c, SCALED ? c.vals_s : c.vals, rec);
   __syncthreads();
   red[wv][lane] = rows.dot(c, xs);
   __syncthreads();
@@ -1454,6 +1484,10 @@ __device__ __forceinline__ void spmv_plain_body(const Ctx& c, const double* __re
 template <int NF>
 __global__ __launch_bounds__(kKrylovThreads) void k_spmv_plain(const Ctx c, const double* __restrict__ x, double* __restrict__ out) {
   spmv_plain_body<NF, false>(c, x, nullptr, out);
+}
+template <int NF>
+__global__ __launch_bounds__(kKrylovThreads) void k_spmv_scaled(const Ctx c, const double* __restrict__ x, double* __restrict__ out) {
+  spmv_plain_body<NF, false, true>(c, x, nullptr, out);
 }
 // out = b - A x in one launch (the smoothing steps of the multilevel term, gmpnp_multilevel.h)
 template <int NF>
@@ -1471,7 +1505,7 @@ __device__ __forceinline__ void scale_columns_body(const Ctx& c) {
   const int Iloc = lane / NF;
   if (Iloc >= c.slice_nn[s]) return;
   const size_t rec = (size_t)(c.slice_colbase[s] + kpos) * kSlicePad + Iloc;
-  const size_t off = c.slice_off[s] + (size_t)kpos * NF * kWave + lane;
+  const size_t pos = c.slice_off[s] + (size_t)kpos * NF * kWave, off = pos + lane;
   if (c.sell_blk[rec] < 0) return;  // padding stays zero in vals_s as well
   const double* d = c.Dinv + (size_t)(c.sell_cols[rec] & 0xFFFFFF) * NF * NF;
   double a[NF], o[NF];
@@ -1483,8 +1517,15 @@ __device__ __forceinline__ void scale_columns_body(const Ctx& c) {
   for (int mI = 0; mI < NF; ++mI)
 #pragma unroll
     for (int j = 0; j < NF; ++j) o[j] += a[mI] * d[mI * NF + j];
+  if (kValuePairs) {   // the one writer of vals_s: columns in pairs, 16 bytes per store (value_pair_offset)
 #pragma unroll
-  for (int j = 0; j < NF; ++j) c.vals_s[off + (size_t)j * kWave] = o[j];
+    for (int m = 0; m < NF / 2; ++m)
+      *reinterpret_cast<double2*>(c.vals_s + pos + value_pair_offset(NF, 2 * m, lane)) = make_double2(o[2 * m], o[2 * m + 1]);
+    if (NF & 1) c.vals_s[pos + value_pair_offset(NF, NF - 1, lane)] = o[NF - 1];
+  } else {
+#pragma unroll
+    for (int j = 0; j < NF; ++j) c.vals_s[pos + value_plain_offset(NF, j, lane)] = o[j];
+  }
 }
 template <int NF>
 __global__ __launch_bounds__(kVecBlock) void k_scale_columns(const Ctx c) { scale_columns_body<NF>(c); }

@@ -331,6 +331,8 @@ int gmpnp_assemble(gmpnp_solver* s, int32_t want_jacobian, double* F_out, double
 int gmpnp_get_jacobian_csr(gmpnp_solver* s, int32_t* indptr, int32_t* indices, double* data);
 /* y = J x with the current device Jacobian. */
 int gmpnp_spmv(gmpnp_solver* s, const double* x, double* y);
+/* y = As x with the column-scaled Jacobian As = J blockdiag(J_II)^-1 of the last preconditioner set-up, read as the Krylov kernels read it (needs a set-up: a linear or Newton solve on this Jacobian). */
+int gmpnp_spmv_scaled(gmpnp_solver* s, const double* x, double* y);
 /* Solve J x = b with the current device Jacobian (preconditioner is rebuilt). */
 int gmpnp_linear_solve(gmpnp_solver* s, const double* b, double* x, int32_t linear_solver, double rtol,
                        double atol, int32_t max_iterations, gmpnp_linear_stats_t* stats);
